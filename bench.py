@@ -22,6 +22,13 @@ batch + D2H of the results, pinned memory, three batches in flight) is timed sep
 `config.pcie_inclusive_reads_per_s` -- it is never `value`.  Steps cycle through `--read-sets` distinct read sets so that no
 step replays the previous step's batch (the model kernel's memo table sees new keys, as in a real run).
 
+A plain run sets up, warms up, times the steps and prints the line: `value`, `ms_per_step`, the roofline figures of the timed
+launches (HIP events around every kernel of the timed steps) and the summary counters of the last step.  Everything that takes
+runs of its own -- the host-buffer (PCIe) leg, the gzip-column leg, the step timed again without kernel events, the chip's
+gather roof and the CPU baseline -- runs only with `--full` (`--no-pcie` and `--no-cpu-baseline` then drop single legs).
+`--dump-outputs DIR` writes the per-read results of the last timed step as DIR/<name>.npy (float32 where exact, float64 for
+the probabilities; a fixed, seeded sample of the reads when they would take more than 64 MiB).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -75,6 +82,11 @@ def main():
     ap.add_argument("--read-sets", type=int, default=3, help="distinct synthetic read sets the steps cycle through")
     ap.add_argument("--launch-check", action="store_true",
                     help="rehearse the launch / rendezvous / timing-reduction plumbing only (no GPU work; CPU test of --gpus N)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the informational legs: host-buffer (PCIe) leg, gzip column on the device, steps without kernel "
+                         "events, gather roof, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the per-read results of the last timed step as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -305,12 +317,14 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:  # before anything else is submitted: the result pointers stay valid until the third-next submit
+        dump_outputs(args.dump_outputs, api, local, res, n_reads, ncat)
 
     # Sub-millisecond steps (BASELINE configs[4]'s small batches): the HIP events that bracket every kernel for the roofline figures cost a
     # measurable part of such a step, so the same steps are run once more on a stream WITHOUT those events and that time is reported
     # beside ms_per_step (never instead of it).
     ms_no_events = None
-    if elapsed / max(1, args.steps) < 2e-3 and not rows_mode and not sparse_mode:
+    if args.full and elapsed / max(1, args.steps) < 2e-3 and not rows_mode and not sparse_mode:
         plain = api.Stream(index, n_reads, max_bases, profile=False)
         plain.set_model(api.default_model(ncat, 0, paired=paired))
         def plain_steps(k):
@@ -351,7 +365,7 @@ def main():
     flags = api.device_download(local, res.flags, n_reads, np.uint8)
 
     pcie_rate = None
-    if not args.no_pcie and world == 1 and not paired and not rows_mode and not sparse_mode:
+    if args.full and not args.no_pcie and world == 1 and not paired and not rows_mode and not sparse_mode:
         # host-buffer entry: packed batch in PINNED host memory (chn_host_alloc), three batches in flight, so the upload of batch
         # i+2 (copy stream) runs under the probe kernel of batch i+1 while batch i's count / model+call kernels finish beside it;
         # results are downloaded in stream and come back into ordinary numpy arrays
@@ -385,7 +399,7 @@ def main():
     # informational (never `value`): the same device-resident batches with the gzip `compression` column ALSO computed on the device (deflate
     # pass + tree arithmetic per read, src/utils.cpp:114-124) -- what the drop-in binary asks of the GPU per batch
     gzip_rate = None
-    if not args.no_pcie and world == 1 and not paired and not rows_mode and not sparse_mode and Lmax <= 61440:
+    if args.full and not args.no_pcie and world == 1 and not paired and not rows_mode and not sparse_mode and Lmax <= 61440:
         reads = last_reads
         k_gz = 3
 
@@ -404,7 +418,7 @@ def main():
 
     # what the chip gives the bare probe pattern on this index, measured now (a few ms): the honest ceiling of the probe kernel
     gather_roof = None
-    if not rows_mode and not sparse_mode:
+    if args.full and not rows_mode and not sparse_mode:
         k1_rate = (fetches / (k1_ms / max(k1_n, 1) * 1e-3)) if k1_ms > 0 else 0.0
         roof = {pol: index.gather_roof(nt=(pol == "nt")) for pol in ("default", "nt")}
         best = max(roof.values())
@@ -461,7 +475,7 @@ def main():
         }
         if rehearsal:
             out["rehearsal"] = True  # ranks share GPUs / gloo backend: plumbing check only, never a scaling figure
-        if world == 1 and not args.no_cpu_baseline and not rows_mode and not sparse_mode and not paired:
+        if args.full and world == 1 and not args.no_cpu_baseline and not rows_mode and not sparse_mode and not paired:
             out["cpu_baseline"] = cpu_baseline(api, index, last_reads, res, n_reads, args, local, categories, b2c)
     stream.destroy()
     if stream_b is not None:
@@ -554,6 +568,36 @@ def pmc_traffic(workload, n_reads, read_len):
             return {"traffic_bytes": d["traffic_bytes"],
                     "source": "%s (measured at commit %s, %s)" % (os.path.relpath(f, ROOT), doc.get("commit", "unrecorded"), doc.get("date", "undated"))}
     return None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, api, device, res, n_reads, ncat):
+    """What chn_batch_wait hands a caller for the last timed batch (chn_result, include/charon_hip.h), one .npy per field: integer
+    fields as float32 (exact: every value is below 2^24, checked), the probabilities as float64.  If the whole batch would take more
+    than DUMP_LIMIT_BYTES, the same fixed, seeded sample of reads is taken from every field and its read indices are written too."""
+    fields = {"num_hashes": (res.num_hashes, np.uint32, 1), "counts": (res.counts, np.uint32, ncat),
+              "unique_counts": (res.unique_counts, np.uint32, ncat), "probabilities": (res.probabilities, np.float64, ncat),
+              "call": (res.call, np.uint8, 1), "confidence": (res.confidence, np.uint8, 1), "flags": (res.flags, np.uint8, 1)}
+    per_read = sum(w * (8 if dt == np.float64 else 4) for _, dt, w in fields.values())
+    rows = None
+    if n_reads * per_read > DUMP_LIMIT_BYTES - 4096:
+        n_keep = (DUMP_LIMIT_BYTES - 4096) // (per_read + 8)
+        rows = np.sort(np.random.default_rng(20261016).choice(n_reads, n_keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, (ptr, dt, w) in fields.items():
+        a = api.device_download(device, ptr, n_reads * w * np.dtype(dt).itemsize, dt)
+        a = a.reshape(n_reads, w) if w > 1 else a
+        if rows is not None:
+            a = a[rows]
+        if dt != np.float64:
+            if a.size and int(a.max()) >= (1 << 24):
+                raise SystemExit("bench.py: %s holds values float32 cannot hold exactly" % name)
+            a = a.astype(np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    if rows is not None:
+        np.save(os.path.join(out_dir, "read_index.npy"), rows.astype(np.float64))
 
 
 def cpu_baseline(api, index, reads, res, n_reads, args, device, categories, b2c):

@@ -1,10 +1,12 @@
 """bench.py's contract, on the toy workload: one JSON line with the fields the driver reads, a roofline object for the dominant kernel
-and a cpu_baseline object whose sample was checked against the GPU rows -- so that a change to the bench cannot silently drop a field."""
+and (with --full) a cpu_baseline object whose sample was checked against the GPU rows -- so that a change to the bench cannot silently
+drop a field; a plain run is the timed steps alone, and --dump-outputs writes what its last step computed."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from tests import util
@@ -22,7 +24,7 @@ def _bench(*args, base=("--workload", "small", "--steps", "3", "--warmup", "1"))
 
 
 def test_bench_line_has_the_contract_fields():
-    d = _bench()
+    d = _bench("--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
               "roofline", "cpu_baseline"):
         assert k in d, k
@@ -63,7 +65,7 @@ def test_bench_row_sharded_modes_run_at_one_rank():
 
 def test_bench_small_paired_batches_report_the_step_without_kernel_events():
     """BASELINE configs[4] at the CLI's batch size: paired 2 x 150 b reads, 8 192 pairs per batch, call_category over 8 categories"""
-    d = _bench(base=("--workload", "cfg5", "--reads-per-step", "8192", "--steps", "40", "--warmup", "5", "--no-cpu-baseline", "--no-pcie"))
+    d = _bench(base=("--workload", "cfg5", "--reads-per-step", "8192", "--steps", "40", "--warmup", "5", "--no-cpu-baseline", "--no-pcie", "--full"))
     assert d["config"]["reads_per_step_per_gpu"] == 8192 and d["unit"] in ("pairs/s", "reads/s")
     ne = d["config"]["ms_per_step_without_kernel_events"]
     assert ne is not None and 0 < ne <= d["ms_per_step"] * 1.25
@@ -86,3 +88,31 @@ def test_two_ranks_drive_the_sharded_hip_paths_under_a_real_collective():
         assert d["config"]["summary_counts"] == want, (mode, d["config"]["summary_counts"], want)
         assert d["scaling"] == ("strong" if mode == "rows-dense" else "weak")
         assert d["value"] > 0 and d["config"]["row_log_reruns"] == 0
+
+
+def test_plain_run_is_the_timed_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full the line carries the headline fields and none of the legs that take runs of their own; --dump-outputs writes the
+    per-read results of the last timed step, identical from run to run (seeded inputs), and they add up to the line's summary counters."""
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    lines = [_bench("--dump-outputs", str(p), base=("--workload", "small", "--steps", "4", "--warmup", "1")) for p in dirs]
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "reads/s" and d["dtype"] == "u64" and "cpu_baseline" not in d
+    c = d["config"]
+    assert c["pcie_inclusive_reads_per_s"] is None and c["with_gzip_column_on_device_reads_per_s"] is None
+    assert c["ms_per_step_without_kernel_events"] is None and d["roofline"]["gather_roof"] is None
+    assert abs(d["value"] - c["reads_per_step_per_gpu"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    n, total = c["reads_per_step_per_gpu"], 0
+    shapes = {"num_hashes": (n,), "counts": (n, 2), "unique_counts": (n, 2), "probabilities": (n, 2), "call": (n,), "confidence": (n,),
+              "flags": (n,)}
+    for name, shape in shapes.items():
+        a, b = np.load(dirs[0] / (name + ".npy")), np.load(dirs[1] / (name + ".npy"))
+        assert a.shape == shape and a.dtype == (np.float64 if name == "probabilities" else np.float32), name
+        assert np.array_equal(a, b, equal_nan=True), name
+        total += os.path.getsize(dirs[0] / (name + ".npy"))
+    assert total <= 64 << 20 and not (dirs[0] / "read_index.npy").exists()
+    call, nh = np.load(dirs[0] / "call.npy"), np.load(dirs[0] / "num_hashes.npy")
+    assert {k: int(v) for k, v in c["summary_counts"].items()} == {"human": int((call == 0).sum()), "microbial": int((call == 1).sum()),
+                                                                     "unclassified": int((call == 255).sum())}
+    assert (np.load(dirs[0] / "counts.npy") <= nh[:, None]).all()

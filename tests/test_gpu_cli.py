@@ -46,18 +46,38 @@ def assert_same_tsv(got, want, prob_tol=1e-6):
                     assert abs(float(xs[4]) - float(ys[4])) <= prob_tol, (a, b)
 
 
+def relocated_cfg1_index(tmp_path):
+    """cfg1.idx records its two reference FASTAs (filepath_to_bin) by the absolute paths make_golden.py gave them.  A copy whose
+    cereal strings (u64 length, then the bytes) name this checkout's tests/golden files instead, so that the loader's self-check
+    (v) has the files wherever the repository lives."""
+    import struct
+    data = open(os.path.join(G, "cfg1.idx"), "rb").read()
+    for name in ("my.fasta", "cfg1_host.fasta"):
+        at = data.find(("/tests/golden/" + name).encode())
+        assert at > 0, name
+        end = at + len("/tests/golden/") + len(name)
+        start = next(s for s in range(end - len(name), 8, -1) if struct.unpack("<Q", data[s - 8:s])[0] == end - s)
+        new = os.path.join(G, name).encode()
+        data = data[:start - 8] + struct.pack("<Q", len(new)) + new + data[end:]
+    path = tmp_path / "cfg1_here.idx"
+    path.write_bytes(data)
+    return str(path)
+
+
 def test_cli_golden_cfg1(tmp_path):
     assert os.path.exists(EXE), "host front end not built"
     fq = os.path.join(G, "cfg1_reads.fastq.gz")
-    rc, out, err = run_cli(["--db", os.path.join(G, "cfg1.idx"), fq], str(tmp_path))
+    rc, out, err = run_cli(["--db", relocated_cfg1_index(tmp_path), fq], str(tmp_path))
     assert rc == 0, err
     assert_same_tsv(out, open(os.path.join(G, "cfg1_expected.tsv")).read())
     assert out.split("\n")[0].split("\t")[1] == "r1"  # r0 is dropped (no --extract)
     # loader self-check (v): the index records the reference FASTA paths; when they are readable their minimisers are probed
     log = open(tmp_path / "charon.log").read()
-    if all(os.path.exists(p) for p in ("/root/repo/tests/golden/my.fasta", "/root/repo/tests/golden/cfg1_host.fasta")):
-        assert "self-check: minimisers of 2 reference file(s) all found" in log
+    assert "self-check: minimisers of 2 reference file(s) all found" in log
     assert "self-check FAILED" not in log and "self-check FAILED" not in err
+    # the committed index itself (its reference paths need not exist here): the same rows
+    rc, out1, err = run_cli(["--db", os.path.join(G, "cfg1.idx"), fq], str(tmp_path))
+    assert rc == 0 and out1 == out, err
     # small GPU batches, more host threads: identical rows
     rc, out2, err = run_cli(["--db", os.path.join(G, "cfg1.idx"), "-t", "4", fq], str(tmp_path), {"CHARON_BATCH_READS": "37"})
     assert rc == 0 and out2 == out
@@ -308,12 +328,13 @@ def test_cli_rejects_corrupted_index_payload(tmp_path):
     loader's self-checks (ones in m_high vs elements of m_low, bits beyond m_size or in technical bins >= num_bins, distinct bits
     after decode), never classified with"""
     fq = os.path.join(G, "cfg1_reads.fastq.gz")
-    src = open(os.path.join(G, "cfg1.idx"), "rb").read()
+    src = open(relocated_cfg1_index(tmp_path), "rb").read()  # reference paths of this checkout: the reference-file self-check runs
+    shift = len(src) - os.path.getsize(os.path.join(G, "cfg1.idx"))  # (longer or shorter paths in the header)
     n = os.path.getsize(os.path.join(G, "cfg1_no_select.idx"))  # the same file up to the end of m_high
     outcomes = []
     for where, mask in ((n - 9, 0xFF), (n - 2000, 0x10), (n // 2, 0x01), (n // 2 + 777, 0x80)):
         b = bytearray(src)
-        b[where] ^= mask
+        b[where + shift] ^= mask
         p = tmp_path / "bad.idx"
         p.write_bytes(bytes(b))
         rc, out, err = run_cli(["--db", str(p), fq], str(tmp_path))

@@ -11,7 +11,7 @@ mkdir -p $OUT
 cd /tmp
 # 1. per-kernel time (rocprofv3 --kernel-trace --stats) of the bench command, with the bench line the same run printed
 for wl in 39g cfg2 cfg5; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_$wl -- python3 $ROOT/bench.py --workload $wl --steps 8 --warmup 2 --no-cpu-baseline --no-pcie > $OUT/bench_$wl.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_$wl -- python3 $ROOT/bench.py --full --workload $wl --steps 8 --warmup 2 --no-cpu-baseline --no-pcie > $OUT/bench_$wl.log 2>&1
   cp $(find /tmp/p_$wl -name '*kernel_stats.csv' | head -1) $OUT/kernel_stats_$wl.csv
   grep '^{' $OUT/bench_$wl.log | tail -1 > $OUT/bench_under_profiler_$wl.json
 done
@@ -48,13 +48,13 @@ cd $ROOT
 ./tools/gather_alloc_bench 1.1 >> $OUT/gather_alloc_microbench.txt 2>&1
 # 4. small batches (BASELINE config 5: launch collapse): paired 2 x 150 b, 8 192 and 65 536 pairs per batch
 for n in 8192 65536; do
-  python3 bench.py --workload cfg5 --reads-per-step $n --steps 200 --warmup 20 --no-cpu-baseline --no-pcie > $OUT/bench_cfg5_$n.json 2>/dev/null
+  python3 bench.py --full --workload cfg5 --reads-per-step $n --steps 200 --warmup 20 --no-cpu-baseline --no-pcie > $OUT/bench_cfg5_$n.json 2>/dev/null
 done
 # 5. other workload shapes + the default line with the CPU baseline
-python3 bench.py --workload 39g --steps 6 --warmup 2 --no-cpu-baseline --read-len 500 --read-len-max 50000 > $OUT/bench_mixed.json 2>/dev/null
+python3 bench.py --full --workload 39g --steps 6 --warmup 2 --no-cpu-baseline --read-len 500 --read-len-max 50000 > $OUT/bench_mixed.json 2>/dev/null
 python3 bench.py --workload 39g --shard rows --steps 6 --warmup 2 --no-cpu-baseline > $OUT/bench_rows_sparse.json 2>/dev/null
 python3 bench.py --workload 39g --shard rows-dense --steps 4 --warmup 1 --no-cpu-baseline > $OUT/bench_rows_dense.json 2>/dev/null
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_default.json 2>$OUT/bench_default.err
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_default.json 2>$OUT/bench_default.err
 python3 - $OUT <<'PY'
 import json, sys, glob, os
 for f in sorted(glob.glob(sys.argv[1] + "/bench_*.json")):

@@ -1,15 +1,17 @@
-# every bench line quoted in DESIGN.md section 5 (1 x MI355X); writes gpurun_out/final/*.json
+# every bench line quoted in DESIGN.md section 5 (1 x MI355X), with the informational legs (--full); writes OUTDIR/*.json
+# usage: bash tools/run_all_benches.sh OUTDIR
 set -e
-mkdir -p gpurun_out/final
-python bench.py > gpurun_out/final/default_39g.json
-python bench.py --workload cfg2 --no-cpu-baseline > gpurun_out/final/cfg2.json
-python bench.py --workload cfg5 --no-cpu-baseline > gpurun_out/final/cfg5.json
-python bench.py --workload 39g --read-len 500 --read-len-max 50000 --steps 5 --warmup 1 --no-cpu-baseline > gpurun_out/final/mixed.json
-python bench.py --workload 39g --read-len 300 --reads-per-step 8388608 --steps 5 --warmup 1 --no-cpu-baseline > gpurun_out/final/short300.json
-python bench.py --workload 39g --shard rows --steps 3 --warmup 1 --no-cpu-baseline > gpurun_out/final/rows.json
-python bench.py --workload 39g --pcie --steps 5 --warmup 1 --no-cpu-baseline > gpurun_out/final/pcie.json
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 5 --warmup 1 --no-cpu-baseline > gpurun_out/final/torchrun_n1.json
-for f in gpurun_out/final/*.json; do python - $f <<'PY'
+O=${1:?usage: bash tools/run_all_benches.sh OUTDIR}
+mkdir -p $O
+python bench.py --full > $O/default_39g.json
+python bench.py --full --workload cfg2 --no-cpu-baseline > $O/cfg2.json
+python bench.py --full --workload cfg5 --no-cpu-baseline > $O/cfg5.json
+python bench.py --full --workload 39g --read-len 500 --read-len-max 50000 --steps 5 --warmup 1 --no-cpu-baseline > $O/mixed.json
+python bench.py --full --workload 39g --read-len 300 --reads-per-step 8388608 --steps 5 --warmup 1 --no-cpu-baseline > $O/short300.json
+python bench.py --full --workload 39g --shard rows --steps 3 --warmup 1 --no-cpu-baseline > $O/rows.json
+python bench.py --full --workload 39g --steps 5 --warmup 1 --no-cpu-baseline > $O/pcie.json
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 5 --warmup 1 --full --no-cpu-baseline > $O/torchrun_n1.json
+for f in $O/*.json; do python - $f <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().split("\n")[-1])
 r=d["roofline"]; c=d["config"]
