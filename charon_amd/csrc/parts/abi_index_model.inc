@@ -160,6 +160,9 @@ struct chn_stream {
     int inflight = 0;  // batches submitted and not yet waited for (FIFO)
     HostModel model;
     K3Args k3;
+    // chn_classify_counts(_raw): inputs and outputs of k_model_call on the caller's counts.  A set of its own (allocated on first use,
+    // max_reads rows): a batch slot's buffers may hold device-resident results the caller still reads
+    struct CountsBufs { DevBuf num_hashes, counts, unique, len1, mq, comp, prob, call, conf, flags; } cc;
     // profiling
     double prof_ms[4] = {0, 0, 0, 0};
     uint64_t prof_n[4] = {0, 0, 0, 0};

@@ -272,39 +272,53 @@ extern "C" int chn_batch_wait(chn_stream *s, chn_result *r) {
     return CHN_OK;
 }
 
-extern "C" int chn_classify_counts(chn_stream *s, uint64_t n, const uint32_t *num_hashes, const uint32_t *counts,
-                                   const uint32_t *unique_counts, const uint32_t *lengths, const float *mean_quality,
-                                   const float *compression, double *probabilities, uint8_t *call, uint8_t *confidence) {
-    if (!s || !num_hashes || !counts || !unique_counts || !lengths || !probabilities || !call || !confidence)
+extern "C" int chn_classify_counts_raw(chn_stream *s, uint64_t n, const uint32_t *num_hashes, const uint32_t *counts,
+                                       const uint32_t *unique_counts, const uint32_t *lengths, const float *mean_quality,
+                                       const float *compression, double *probabilities, uint8_t *call, uint8_t *confidence,
+                                       uint8_t *flags) {
+    if (!s || !num_hashes || !counts || !unique_counts || !lengths || !probabilities || !call || !confidence || !flags)
         return fail(CHN_E_INVALID, "chn_classify_counts: null argument");
     if (!s->model.set) return fail(CHN_E_STATE, "chn_classify_counts: no model set");
     if (s->inflight) return fail(CHN_E_STATE, "chn_classify_counts: a batch is in flight");
-    Slot &sl = s->slot[0];
     if (n == 0) return CHN_OK;
     if (n > s->cfg.max_reads) return fail(CHN_E_CAPACITY, "chn_classify_counts: more reads than the stream's max_reads");
     HIPCHK(hipSetDevice(s->idx->d.device));
-    const uint64_t C = s->idx->d.num_categories;
+    const uint64_t C = s->idx->d.num_categories, m = s->cfg.max_reads;
+    chn_stream::CountsBufs &b = s->cc;  // never a batch slot's buffers (device-resident results of waited batches live there)
     int rc;
-    if ((rc = upload(sl.d_len1, lengths, n * 4, s->stream))) return rc;
-    if (mean_quality && (rc = upload(sl.d_mq, mean_quality, n * 4, s->stream))) return rc;
-    if (compression && (rc = upload(sl.d_comp, compression, n * 4, s->stream))) return rc;
-    HIPCHK(hipMemcpyAsync(sl.d_num_hashes.p, num_hashes, n * 4, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipMemcpyAsync(sl.d_counts.p, counts, n * C * 4, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipMemcpyAsync(sl.d_unique.p, unique_counts, n * C * 4, hipMemcpyHostToDevice, s->stream));
+    if ((rc = b.num_hashes.ensure(m * 4)) || (rc = b.counts.ensure(m * C * 4)) || (rc = b.unique.ensure(m * C * 4)) ||
+        (rc = b.prob.ensure(m * C * 8)) || (rc = b.call.ensure(m)) || (rc = b.conf.ensure(m)) || (rc = b.flags.ensure(m)))
+        return rc;
+    if ((rc = upload(b.len1, lengths, n * 4, s->stream, m * 4))) return rc;
+    if (mean_quality && (rc = upload(b.mq, mean_quality, n * 4, s->stream, m * 4))) return rc;
+    if (compression && (rc = upload(b.comp, compression, n * 4, s->stream, m * 4))) return rc;
+    HIPCHK(hipMemcpyAsync(b.num_hashes.p, num_hashes, n * 4, hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipMemcpyAsync(b.counts.p, counts, n * C * 4, hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipMemcpyAsync(b.unique.p, unique_counts, n * C * 4, hipMemcpyHostToDevice, s->stream));
     K3Args k3 = s->k3;
-    k3.num_hashes = sl.d_num_hashes.as<uint32_t>(); k3.counts = sl.d_counts.as<uint32_t>(); k3.unique = sl.d_unique.as<uint32_t>();
-    k3.len1 = sl.d_len1.as<uint32_t>(); k3.len2 = nullptr;
-    k3.mean_quality = mean_quality ? sl.d_mq.as<float>() : nullptr; k3.compression = compression ? sl.d_comp.as<float>() : nullptr;
-    k3.prob = sl.d_prob.as<double>(); k3.call = sl.d_call.as<uint8_t>(); k3.conf = sl.d_conf.as<uint8_t>(); k3.flags = sl.d_flags.as<uint8_t>();
+    k3.num_hashes = b.num_hashes.as<uint32_t>(); k3.counts = b.counts.as<uint32_t>(); k3.unique = b.unique.as<uint32_t>();
+    k3.len1 = b.len1.as<uint32_t>(); k3.len2 = nullptr;
+    k3.mean_quality = mean_quality ? b.mq.as<float>() : nullptr; k3.compression = compression ? b.comp.as<float>() : nullptr;
+    k3.prob = b.prob.as<double>(); k3.call = b.call.as<uint8_t>(); k3.conf = b.conf.as<uint8_t>(); k3.flags = b.flags.as<uint8_t>();
     k3.n_reads = (uint32_t)n;
     hipLaunchKernelGGL(k_model_call, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s->stream, k3);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s->stream));
-    HIPCHK(hipMemcpy(probabilities, sl.d_prob.p, n * C * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(call, sl.d_call.p, n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(confidence, sl.d_conf.p, n, hipMemcpyDeviceToHost));
-    std::vector<uint8_t> flags(n);
-    HIPCHK(hipMemcpy(flags.data(), sl.d_flags.p, n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(probabilities, b.prob.p, n * C * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(call, b.call.p, n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(confidence, b.conf.p, n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(flags, b.flags.p, n, hipMemcpyDeviceToHost));
+    return CHN_OK;
+}
+
+extern "C" int chn_classify_counts(chn_stream *s, uint64_t n, const uint32_t *num_hashes, const uint32_t *counts,
+                                   const uint32_t *unique_counts, const uint32_t *lengths, const float *mean_quality,
+                                   const float *compression, double *probabilities, uint8_t *call, uint8_t *confidence) {
+    std::vector<uint8_t> flags(std::max<uint64_t>(n, 1));
+    int rc = chn_classify_counts_raw(s, n, num_hashes, counts, unique_counts, lengths, mean_quality, compression, probabilities, call,
+                                     confidence, flags.data());
+    if (rc) return rc;
+    const uint64_t C = s->idx->d.num_categories;
     std::vector<double> p(C);
     const bool all = s->model.dist != CHN_DIST_KDE;  // gamma / beta: always the float path of the reference (see chn_batch_wait)
     for (uint64_t i = 0; i < n; ++i)

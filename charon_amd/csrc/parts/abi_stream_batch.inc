@@ -109,7 +109,9 @@ extern "C" int chn_stream_destroy(chn_stream *s) {
         for (DevBuf *b : bufs) b->release();
         sl.lb.release();
     }
-    DevBuf *bufs[] = {&s->d_hist, &s->d_model, &s->d_list, &s->d_cbase, &s->d_memo, &s->d_shx_cnt, &s->d_gzscratch};
+    DevBuf *bufs[] = {&s->d_hist, &s->d_model, &s->d_list, &s->d_cbase, &s->d_memo, &s->d_shx_cnt, &s->d_gzscratch,
+                      &s->cc.num_hashes, &s->cc.counts, &s->cc.unique, &s->cc.len1, &s->cc.mq, &s->cc.comp, &s->cc.prob, &s->cc.call,
+                      &s->cc.conf, &s->cc.flags};
     for (DevBuf *b : bufs) b->release();
     s->big.release();
     s->shx.release();

@@ -211,7 +211,7 @@ typedef struct chn_batch {
  * double log-density while the reference evaluates them in float: device-resident probabilities then agree to ~1e-5 only).
  * chn_batch_wait does that itself for host batches with host result buffers -- for gamma / beta it re-evaluates every read in float --;
  * with on_device results the flags are only reported and NOTHING is re-evaluated: a caller that needs the reference's `call` on
- * flagged reads runs chn_classify_counts on their counts. */
+ * flagged reads runs chn_classify_counts on their counts (which leaves the device-resident results in place). */
 typedef struct chn_result {
     uint32_t struct_size;
     uint32_t on_device;        /* 0: pointers below are host buffers to fill; 1: receive device pointers */
@@ -245,10 +245,21 @@ int chn_stream_sync(chn_stream *s);
 /* Model + call only (k_model_call) on per-read counts the caller already holds -- used for reads that the
  * Result state machine cached while the KDE models were still training (include/result.hpp:139-151,181-198)
  * and that must be classified with the models as they are later.  All pointers are HOST arrays; outputs as in
- * chn_result.  Replaces ReadEntry::dehost / ReadEntry::classify (include/read_entry.hpp:281-291). */
+ * chn_result.  Replaces ReadEntry::dehost / ReadEntry::classify (include/read_entry.hpp:281-291).
+ * The rows are re-evaluated on the host exactly as chn_batch_wait does for host batches: every flagged row, every
+ * row with num_hashes == 0 and, for gamma / beta models, every row.  No batch may be in flight.  The call stages its
+ * inputs and outputs in device buffers of the stream's own (allocated on first use, max_reads rows): device-resident
+ * results of earlier batches stay valid, so a caller with on_device results may run it on the counts of flagged reads. */
 int chn_classify_counts(chn_stream *s, uint64_t n_reads, const uint32_t *num_hashes, const uint32_t *counts,
                         const uint32_t *unique_counts, const uint32_t *lengths, const float *mean_quality,
                         const float *compression, double *probabilities, uint8_t *call, uint8_t *confidence);
+/* The same launch without the host re-evaluation: probabilities, call, confidence and flags exactly as k_model_call
+ * wrote them -- the values a device-resident batch returns for the same counts.  Same buffers and rules as
+ * chn_classify_counts; `flags` [n_reads] as chn_result.flags. */
+int chn_classify_counts_raw(chn_stream *s, uint64_t n_reads, const uint32_t *num_hashes, const uint32_t *counts,
+                            const uint32_t *unique_counts, const uint32_t *lengths, const float *mean_quality,
+                            const float *compression, double *probabilities, uint8_t *call, uint8_t *confidence,
+                            uint8_t *flags);
 
 /* ---- row-sharded ("hash-bin" sharded) mode, dense exchange (the checker of the sparse exchange below) -----------
  * For an index too large for one GPU: rank r creates a chn_index with row_begin/row_end = its slice and a stream on it.

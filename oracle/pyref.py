@@ -218,6 +218,176 @@ def call_host(unique, uprops, probs, host, mean_q, length, compression, conf_thr
     return 255, conf
 
 
+# ---- vectorised, float-exact restatement of Model::prob and the two calls (tests of k_model_call) --------------------------
+# Every float step is taken in the reference's order and precision (include/classify_stats.hpp:242-252,370-389;
+# include/read_entry.hpp:157-269).  The parametric densities are the contract the device states: log-density evaluated
+# exactly (mpmath, 40 digits), rounded once to float.
+SQRT_2PI = math.sqrt(2 * 3.141592653589793238463)
+F32_MIN_NORMAL = 2.0 ** -126
+
+
+def unique_props(uq, nh):
+    """float(unique) / float(num_hashes) in float32 (include/read_entry.hpp:140-150)"""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.asarray(uq, np.float64).astype(np.float32) / np.asarray(nh, np.float64).astype(np.float32)
+
+
+def kde_prob_vec(x, data, h):
+    """KDEParams::prob at every x: t = (x - xi) / h in float32, K(t) = exp in double rounded to float32, the float32 sum
+    taken in DATA order, divided by h * float(n)"""
+    x = np.asarray(x, np.float32)
+    h = np.float32(h)
+    total = np.zeros(x.shape, np.float32)
+    with np.errstate(all="ignore"):
+        for xi in np.asarray(data, np.float32):
+            t = ((x - xi) / h).astype(np.float64)
+            total = total + (np.exp(-(t * t) / 2) / SQRT_2PI).astype(np.float32)
+        return total / np.float32(h * np.float32(len(data)))
+
+
+def dexp_vec(x, rate=300.0):
+    """stats::dexp(x, rate) = exp(log(rate) - rate x): the argument in float32, exp correctly rounded to float32 (NaN -> NaN,
+    x < 0 -> 0)"""
+    x = np.asarray(x, np.float32)
+    rate = np.float32(rate)
+    with np.errstate(all="ignore"):
+        arg = np.float32(math.log(rate)) - rate * x
+        out = np.exp(arg.astype(np.float64)).astype(np.float32)
+    out[x < 0] = 0
+    out[np.isnan(x)] = np.nan
+    return out
+
+
+def _round_f32(v):
+    """an mpmath value rounded ONCE to the nearest float32 (subnormals and overflow included)"""
+    import mpmath as mp
+    if mp.isnan(v):
+        return np.float32(np.nan)
+    if mp.isinf(v) or v == 0:
+        return np.float32(float(v))
+    if abs(v) < mp.mpf(2) ** -126:  # fixed point at the subnormal spacing
+        return np.float32(float(mp.nint(v * mp.mpf(2) ** 149) * mp.mpf(2) ** -149))
+    with mp.workprec(24):
+        r = +v
+    return np.float32(float(r))  # exact in double; > FLT_MAX rounds to inf
+
+
+def dgamma(x, shape, scale):
+    """stats::dgamma(x, shape, scale) with dgamma_dev's boundary cases; interior: exp(log-density) exact, rounded once"""
+    x, shape, scale = np.float32(x), np.float32(shape), np.float32(scale)
+    if np.isnan(x) or np.isnan(shape) or np.isnan(scale) or shape < 0 or scale < 0:
+        return np.float32(np.nan)
+    if x < 0:
+        return np.float32(0)
+    if x == 0:
+        return np.float32(np.inf) if shape < 1 else (np.float32(0) if shape > 1 else np.float32(1) / scale)
+    if np.isinf(x):
+        return np.float32(0)
+    return _round_f32(dgamma_mp(x, shape, scale))
+
+
+def dgamma_mp(x, shape, scale):
+    """the interior gamma density (x > 0, shape and scale > 0) at 40 digits, an mpmath value"""
+    import mpmath as mp
+    with mp.workdps(40):
+        k, th, xd = mp.mpf(float(shape)), mp.mpf(float(scale)), mp.mpf(float(x))
+        return mp.exp(-mp.loggamma(k) - k * mp.log(th) + (k - 1) * mp.log(xd) - xd / th)
+
+
+def dbeta(x, a, b):
+    """stats::dbeta(x, a, b) with dbeta_dev's boundary cases; interior: exp(log-density) exact, rounded once"""
+    x, a, b = np.float32(x), np.float32(a), np.float32(b)
+    inf = np.float32(np.inf)
+    if np.isnan(x) or np.isnan(a) or np.isnan(b) or a < 0 or b < 0:
+        return np.float32(np.nan)
+    if x < 0 or x > 1:
+        return np.float32(0)
+    if a == 0 and b == 0:
+        return inf if x in (0, 1) else np.float32(0)
+    if a == 0 or (np.isinf(b) and not np.isinf(a)):
+        return inf if x == 0 else np.float32(0)
+    if b == 0 or (np.isinf(a) and not np.isinf(b)):
+        return inf if x == 1 else np.float32(0)
+    if np.isinf(a) and np.isinf(b):
+        return inf if x == 0.5 else np.float32(0)
+    if x == 0:
+        return inf if a < 1 else (np.float32(0) if a > 1 else b)
+    if x == 1:
+        return inf if b < 1 else (np.float32(0) if b > 1 else a)
+    return _round_f32(dbeta_mp(x, a, b))
+
+
+def dbeta_mp(x, a, b):
+    """the interior beta density (0 < x < 1, finite a and b > 0) at 40 digits, an mpmath value"""
+    import mpmath as mp
+    with mp.workdps(40):
+        ad, bd, xd = mp.mpf(float(a)), mp.mpf(float(b)), mp.mpf(float(x))
+        return mp.exp(-(mp.loggamma(ad) + mp.loggamma(bd) - mp.loggamma(ad + bd)) + (ad - 1) * mp.log(xd) + (bd - 1) * mp.log(1 - xd))
+
+
+def model_prob_vec(x, p_pos, p_neg, rate=300.0):
+    """Model::prob(x).pos from the two float32 densities: the x == 1 override, total = (p_err + p_pos) + p_neg in float32,
+    p_pos / total in float32 (returned as float64, what probabilities_ holds)"""
+    x = np.asarray(x, np.float32)
+    p_pos = np.array(p_pos, np.float32, copy=True).reshape(x.shape)
+    p_neg = np.asarray(p_neg, np.float32).reshape(x.shape)
+    p_pos[x == 1] = 1
+    with np.errstate(all="ignore"):
+        total = (dexp_vec(x, rate) + p_pos) + p_neg
+        return (p_pos / total).astype(np.float64)
+
+
+def kde_model_prob(x, pos, neg, h_pos=0.1, h_neg=0.001, rate=300.0):
+    return model_prob_vec(x, kde_prob_vec(x, pos, h_pos), kde_prob_vec(x, neg, h_neg), rate)
+
+
+def dist_model_prob(x, dist, pos_params, neg_params, rate=300.0):
+    """gamma (shape, loc, scale) or beta (alpha, beta, -) model at every x (scalar densities, call it on distinct x only)"""
+    x = np.asarray(x, np.float32)
+    if dist == "gamma":
+        f = lambda v, q: dgamma(np.float32(v - np.float32(q[1])), q[0], q[2])
+    else:
+        f = lambda v, q: dbeta(v, q[0], q[1])
+    with np.errstate(all="ignore"):
+        pp = np.array([f(v, pos_params) for v in x.ravel()], np.float32)
+        pn = np.array([f(v, neg_params) for v in x.ravel()], np.float32)
+    return model_prob_vec(x.ravel(), pp, pn, rate).reshape(x.shape)
+
+
+def call_category(unique, counts, probs, num_hashes, mean_q, length, compression, conf_thr=7, min_q=15.0, min_len=80,
+                  min_comp=0.0, min_pd=0.04, min_hits=0):
+    """ReadEntry::call_category (include/read_entry.hpp:157-216) -> (call, confidence); conf_thr as an int8 or its uint8 bits"""
+    u = [int(v) for v in unique]
+    first, second = 0, 1
+    if u[second] > u[first]:
+        first, second = second, first
+    for i in range(2, len(u)):
+        if u[i] > u[second]:
+            second = i
+            if u[second] > u[first]:
+                first, second = second, first
+    raw = (u[first] - u[second]) & 0xFFFFFFFF
+    conf = 255 if raw > 255 else raw
+    thr = conf_thr - 256 if conf_thr >= 128 else conf_thr  # int8 narrowing
+    f = np.float32
+    if f(mean_q) < f(min_q) or length < min_len or f(compression) < f(min_comp):
+        return 255, conf
+    pf, ps = float(probs[first]), float(probs[second])
+    call = 255
+    if ps == 0 and pf > 0:
+        call = first
+    elif conf > thr and pf > ps:
+        call = first
+    fc, sc = int(counts[first]), int(counts[second])
+    if sc > fc or ((fc - sc) & 0xFFFFFFFF) < min_hits:
+        call = 255
+    with np.errstate(all="ignore"):
+        fp, sp = f(fc) / f(num_hashes), f(sc) / f(num_hashes)
+        if sp > fp or f(fp - sp) < f(min_pd):
+            call = 255
+    return call, conf
+
+
 def gzip_ratio(seq):
     """get_compression_ratio (src/utils.cpp:114-124) with gzip-hpp's deflate parameters"""
     c = zlib.compressobj(-1, zlib.DEFLATED, 31, 8, zlib.Z_DEFAULT_STRATEGY)

@@ -121,3 +121,23 @@ def free_synth_reads(api, rd, device=0):
 def assert_same_results(a, b, keys=("num_hashes", "counts", "unique", "call", "conf", "probs")):
     for key in keys:
         assert np.array_equal(a[key], b[key], equal_nan=True) if key == "probs" else np.array_equal(a[key], b[key]), key
+
+
+def kde_tables(seed=71):
+    """synthetic KDE datasets of the model tests (tests/test_model_ref_cpu.py, tests/test_gpu_model_call.py), in the order the
+    kernel must iterate them: name -> float32 array.  'trained' is unsorted with values of many magnitudes, so its float sum
+    depends on the order of the terms."""
+    r = rng(seed)
+    t = {"n0": np.zeros(0, np.float32), "n1": np.float32([0.05])}
+    t["n63_dup"] = np.sort(np.round(r.uniform(0.0, 0.3, 63), 2)).astype(np.float32)  # many duplicates
+    v = r.uniform(0.0, 1.0, 64).astype(np.float32)
+    v[[5, 40]] = np.inf
+    v[17] = -np.inf
+    t["n64_inf"] = v
+    v = r.uniform(0.0, 0.2, 65).astype(np.float32)
+    v[31] = np.nan
+    t["n65_nan"] = v
+    t["trained"] = np.concatenate([r.lognormal(-3.0, 1.5, 600), r.uniform(0.0, 0.02, 400)]).astype(np.float32)
+    r.shuffle(t["trained"])
+    t["n4097"] = r.beta(2.0, 12.0, 4097).astype(np.float32)
+    return t
