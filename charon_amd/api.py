@@ -66,7 +66,7 @@ EXPORTS = ["chn_index_create", "chn_index_upload_rows", "chn_index_device_words"
            "chn_model_set", "chn_batch_submit", "chn_batch_wait", "chn_stream_sync", "chn_classify_counts", "chn_classify_counts_raw", "chn_stream_profile",
            "chn_stream_last_batch_bytes", "chn_synth_genomes", "chn_synth_fill_index", "chn_synth_plant", "chn_synth_reads",
            "chn_device_free", "chn_device_download", "chn_device_malloc", "chn_device_upload", "chn_host_alloc", "chn_host_free", "chn_shard_minimise",
-           "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_index_bin_popcounts", "chn_index_gather_roof", "chn_last_error", "chn_version"]
+           "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_last_error", "chn_version"]
 
 _L.chn_last_error.restype = C.c_char_p
 _L.chn_version.restype = C.c_char_p
@@ -111,6 +111,8 @@ _L.chn_index_emplace.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
 _L.chn_index_decode_ef.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64,
                                    C.POINTER(C.c_uint64)]
 _L.chn_index_bin_popcounts.argtypes = [C.c_void_p, C.c_void_p]
+_L.chn_index_replicate.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
+_L.chn_device_count.argtypes = [C.POINTER(C.c_int)]
 _L.chn_device_download.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64]
 
 
@@ -209,6 +211,17 @@ class Index:
         out = np.zeros(self.desc.technical_bins, np.uint64)
         _chk(_L.chn_index_bin_popcounts(self.h, out.ctypes.data))
         return out
+
+    def replicate(self, device):
+        """an independent copy of this index on `device` (chn_index_replicate: the copy is queued; this index must stay alive and
+        unwritten until a call on the replica that waits for it -- bin_popcounts, download, ... -- has returned)"""
+        h = C.c_void_p()
+        _chk(_L.chn_index_replicate(self.h, device, C.byref(h)))
+        rep = Index.__new__(Index)
+        rep.desc = IndexDesc.from_buffer_copy(self.desc)
+        rep.desc.device = device
+        rep.h = h
+        return rep
 
     def emplace(self, values, bin_index):
         values = np.ascontiguousarray(values, dtype=np.uint64)
@@ -454,6 +467,12 @@ def synth_reads(device, seed, dev_genomes, n_genomes, genome_len, n_reads, len_m
     _chk(_L.chn_synth_reads(device, seed, dev_genomes, n_genomes, genome_len, first_read_id, n_reads, len_min, len_max, sub_rate,
                             random_fraction, mean_quality, C.byref(out)))
     return out
+
+
+def device_count():
+    n = C.c_int()
+    _chk(_L.chn_device_count(C.byref(n)))
+    return n.value
 
 
 def pinned_array(shape, dtype):

@@ -79,6 +79,7 @@ bool g_gzip_emulator = true;
 #include "bz2_stream.inc"
 #include "fastx_reader.inc"
 #include "result.inc"
+#include "ordered_merge.inc"
 #include "dehost.inc"
 #include "index_builder.inc"
 
@@ -270,6 +271,12 @@ int main(int argc, char **argv) {
             return 0;
         } catch (std::exception &e) { std::cerr << "charon: " << e.what() << std::endl; return 1; }
     }
+    if (sub == "_ordered_merge") {  // hidden diagnostic: the ordered merge of CHARON_DEVICES under producer threads (no GPU involved)
+        if (argc < 5) return 2;
+        const int threads = std::atoi(argv[2]);
+        if (threads < 1 || threads > 256) return 2;
+        return ordered_merge_selftest(threads, std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10));
+    }
     if (sub == "_records") {  // hidden diagnostic: dump what the block reader sees (no GPU involved)
         try {
             if (argc < 3) return 2;
@@ -318,6 +325,11 @@ int main(int argc, char **argv) {
     } catch (ParseError &e) {
         std::cerr << e.what() << "\nRun with --help for more information.\n";
         return 105;  // CLI11 parse errors exit non-zero through CLI11_PARSE (src/main.cpp:63)
+    }
+    if (const char *e = std::getenv("CHARON_DEVICES")) {
+        // checked before the index file is opened and before any HIP call
+        const std::string err = std::getenv("CHARON_DEVICE") ? std::string("cannot be set together with CHARON_DEVICE") : parse_device_list(e, opt);
+        if (!err.empty()) { std::cerr << "charon: CHARON_DEVICES: " << err << std::endl; return 1; }
     }
     try {
         dehost_main(opt);  // the reference's subcommand callback discards dehost_main's return value (src/dehost_main.cpp:311)

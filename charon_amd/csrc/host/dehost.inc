@@ -453,6 +453,27 @@ int dehost_main(DehostArguments &opt) {
     chn_index *index = nullptr;
     const double t_meta = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
     warm.join();
+    // CHARON_DEVICES: one index replica per entry; replica 0 is the index decoded from the file, the others are device copies of it
+    std::vector<int> devices(1, opt.device);
+    if (opt.devices_all || !opt.devices.empty()) {
+        int count = 0;
+        CHN_CHECK(chn_device_count(&count));
+        if (opt.devices_all) {
+            devices.clear();
+            for (int i = 0; i < count && i < 64; ++i) devices.push_back(i);
+            if (devices.empty()) throw std::runtime_error("CHARON_DEVICES=all: no device is visible");
+        } else {
+            devices = opt.devices;
+            for (int dv : devices)
+                if (dv >= count) throw std::runtime_error("CHARON_DEVICES: device " + std::to_string(dv) + " is not below the device count " + std::to_string(count));
+        }
+        d.device = devices[0];
+    }
+    {
+        std::string list;
+        for (int dv : devices) list += (list.empty() ? "" : ",") + std::to_string(dv);
+        g_log.info("replicas: " + std::to_string(devices.size()) + " (devices " + list + ")");
+    }
     CHN_CHECK(chn_index_create(&d, &index));
     const double t_hip = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
     {
@@ -478,10 +499,29 @@ int dehost_main(DehostArguments &opt) {
                        std::to_string((uint64_t)expect) + " for its " + std::to_string(it->second) + " hashes");
     }
 
+    // the other replicas: queued device copies of replica 0, each checked against the set bits per bin the loader counted
+    const size_t n_rep = devices.size();
+    std::vector<chn_index *> rep_index(n_rep, nullptr);
+    std::vector<chn_stream *> rep_stream(n_rep, nullptr);
+    struct ReplicaObjects {  // destroyed whatever way this function is left (streams first: they wait for their batches)
+        std::vector<chn_index *> &idx; std::vector<chn_stream *> &st;
+        ~ReplicaObjects() { for (size_t r = 1; r < st.size(); ++r) chn_stream_destroy(st[r]); for (size_t r = 1; r < idx.size(); ++r) chn_index_destroy(idx[r]); }
+    } replica_objects{rep_index, rep_stream};
+    rep_index[0] = index;
+    for (size_t r = 1; r < n_rep; ++r) CHN_CHECK(chn_index_replicate(index, devices[r], &rep_index[r]));
+    for (size_t r = 1; r < n_rep; ++r) {
+        std::vector<uint64_t> bits(meta.technical_bins, 0);
+        CHN_CHECK(chn_index_bin_popcounts(rep_index[r], bits.data()));
+        if (bits != file.bits_per_bin)
+            throw std::runtime_error("replica " + std::to_string(r) + " (device " + std::to_string(devices[r]) + "): its set bits per bin differ from the decoded index");
+    }
+
     chn_stream_cfg cfg;
     cfg.struct_size = sizeof cfg; cfg.flags = 0; cfg.max_reads = opt.batch_reads; cfg.max_bases = opt.batch_bases;
     chn_stream *stream = nullptr;
     CHN_CHECK(chn_stream_create(index, &cfg, &stream));
+    rep_stream[0] = stream;
+    for (size_t r = 1; r < n_rep; ++r) CHN_CHECK(chn_stream_create(rep_index[r], &cfg, &rep_stream[r]));
     chn_model model;
     // call_category for paired dehost and for every classify run (include/read_entry.hpp:281-285), call_host otherwise
     CHN_CHECK(chn_model_default(&model, d.num_categories, host_index, (opt.is_paired || opt.classify_mode) ? 1 : 0));
@@ -516,6 +556,7 @@ int dehost_main(DehostArguments &opt) {
         std::shared_ptr<HostBatch> parent;  // owns the slabs the record views point into
         HostBatch sub;
         uint32_t version = 0;
+        uint64_t seq = 0;  // replica mode: position in input order (the ordered merge releases flights by it)
         // what chn_batch_wait fills (per flight: the rows of batch i are written by another thread while batch i + 1 is waited for)
         std::vector<uint32_t> nh, cnt, unq;
         std::vector<double> prob;
@@ -542,7 +583,7 @@ int dehost_main(DehostArguments &opt) {
     // chn_batch_wait + rows.  Fast path (models final, nothing to extract -- i.e. every plain `charon dehost` run after its
     // first read): rows are formatted in parallel straight from the result arrays into one buffer per thread and emitted in
     // order; no per-read objects.  Otherwise the reference's add_read state machine, read by read.
-    auto finish_wait = [&](Flight &fl) {
+    auto finish_wait = [&](Flight &fl, chn_stream *st, double &acc_wait) {
         HostBatch &sub = fl.sub;
         std::vector<uint32_t> &nh = fl.nh, &cnt = fl.cnt, &unq = fl.unq, &gz_sizes = fl.gz_sizes;
         std::vector<double> &prob = fl.prob;
@@ -557,8 +598,8 @@ int dehost_main(DehostArguments &opt) {
         const bool tallied = sub.gz_gpu_len != 0;
         if (tallied) { gz_sizes.resize(n); rs.gzip_sizes = gz_sizes.data(); }
         double tt = now();
-        CHN_CHECK(chn_batch_wait(stream, &rs));
-        t_wait += now() - tt;
+        CHN_CHECK(chn_batch_wait(st, &rs));
+        acc_wait += now() - tt;
     };
     auto finish_rows = [&](Flight &fl) {
         HostBatch &sub = fl.sub;
@@ -724,8 +765,8 @@ int dehost_main(DehostArguments &opt) {
             if (w.t.joinable()) w.t.join();
         }
     } writer_join{writer};
-    auto retire = [&](std::unique_ptr<Flight> &f) {
-        finish_wait(*f);
+    // a waited flight on to its rows: the row writer's queue, or here behind everything handed over before
+    auto hand_on = [&](std::unique_ptr<Flight> &f) {
         const bool hand_over = use_row_writer && !opt.run_extract && result.models_final() && result.current_model_version() == f->version;
         if (!hand_over) {  // the reference's read-by-read state machine: here, behind everything handed over before
             if (writer.t.joinable()) writer_drain();
@@ -740,8 +781,137 @@ int dehost_main(DehostArguments &opt) {
         writer.q.push_back(std::move(f));
         writer.cv.notify_all();
     };
+    auto retire = [&](std::unique_ptr<Flight> &f) {
+        finish_wait(*f, stream, t_wait);
+        hand_on(f);
+    };
+    auto fill_batch = [&](Flight &fl, chn_batch &bt) {
+        HostBatch &sub = fl.sub;
+        std::memset(&bt, 0, sizeof bt);
+        bt.struct_size = sizeof bt; bt.on_device = 0; bt.n_reads = sub.keep.size(); bt.n_bases = sub.n_bases;
+        bt.bases2 = sub.bases.data(); bt.nmask = sub.any_n ? sub.nmask.data() : nullptr;
+        bt.seg1_offset = sub.off1.data(); bt.seg1_length = sub.len1.data();
+        bt.seg2_offset = opt.is_paired ? sub.off2.data() : nullptr; bt.seg2_length = opt.is_paired ? sub.len2.data() : nullptr;
+        bt.mean_quality = sub.mq.data(); bt.compression = sub.comp.data();
+        bt.gzip_tallies = sub.gz_gpu_len;  // > 0: the call kernel leaves the compression gate to finish()
+        bt.gzip_output = CHN_GZIP_SIZES;   // deflate pass and tree arithmetic on the device: four bytes per read come back
+    };
+
+    // Replica mode, once the models are final (before that every batch runs on replica 0, retired one by one: the models may change with
+    // every read).  The main thread reads, splits and packs as before and deals the packed batches round-robin, numbered in input order;
+    // each replica's thread submits them on its own stream and waits for them, and the ordered merge hands them back to the row writer
+    // strictly in input order.  One replica (CHARON_DEVICES unset) is the same loop with N = 1.
+    static const size_t kMaxOutstanding = 3;  // flights per replica between dealing and release (the writer holds two more)
+    struct Replica {
+        size_t index = 0;
+        int device = 0;
+        chn_stream *stream = nullptr;
+        uint32_t model_version = 0;   // the models on its stream (every flight it submits must have been packed for them)
+        std::mutex m;
+        std::condition_variable cv;
+        std::deque<std::unique_ptr<Flight>> in;  // dealt, not yet submitted
+        uint64_t need = 0;            // flights up to this sequence number are wanted back (need_set: any)
+        bool need_set = false, closing = false, stop = false;
+        size_t outstanding = 0;       // main thread: dealt and not yet released by the merge
+        uint64_t batches = 0, reads = 0;
+        double t_submit = 0, t_wait = 0;
+        std::thread t;
+    };
+    std::vector<std::unique_ptr<Replica>> reps;
+    for (size_t r = 0; r < n_rep; ++r) {
+        reps.emplace_back(new Replica());
+        reps[r]->index = r; reps[r]->device = devices[r]; reps[r]->stream = rep_stream[r];
+    }
+    OrderedMerge<std::unique_ptr<Flight>> merge;
+    bool dealing = false;  // the replica threads run
+    uint64_t next_seq = 0;
+    auto replica_body = [&](Replica &rp) {
+        std::deque<std::unique_ptr<Flight>> flying;  // submitted, oldest first
+        try {
+            for (;;) {
+                std::unique_ptr<Flight> f;
+                {
+                    std::unique_lock<std::mutex> lk(rp.m);
+                    auto wait_oldest = [&] {
+                        return !flying.empty() && (rp.closing || flying.size() >= kMaxOutstanding || (rp.need_set && flying.front()->seq <= rp.need));
+                    };
+                    rp.cv.wait(lk, [&] { return rp.stop || (!rp.in.empty() && flying.size() < kMaxOutstanding) || wait_oldest() || (rp.closing && rp.in.empty()); });
+                    if (rp.stop) break;
+                    if (!rp.in.empty() && flying.size() < kMaxOutstanding) {
+                        f = std::move(rp.in.front());
+                        rp.in.pop_front();
+                    } else if (flying.empty()) {
+                        return;  // closing, and everything has been handed back
+                    }
+                }
+                if (f) {
+                    if (f->version != rp.model_version)
+                        throw std::runtime_error("batch packed for model version " + std::to_string(f->version) + ", stream holds " + std::to_string(rp.model_version));
+                    chn_batch bt;
+                    fill_batch(*f, bt);
+                    const double tk = now();
+                    CHN_CHECK(chn_batch_submit(rp.stream, &bt));
+                    rp.t_submit += now() - tk;
+                    rp.batches += 1; rp.reads += bt.n_reads;
+                    flying.push_back(std::move(f));
+                    continue;
+                }
+                std::unique_ptr<Flight> g = std::move(flying.front());
+                flying.pop_front();
+                finish_wait(*g, rp.stream, rp.t_wait);
+                const uint64_t seq = g->seq;
+                merge.put(seq, std::move(g));
+            }
+        } catch (std::exception &e) {
+            merge.fail("replica " + std::to_string(rp.index) + " (device " + std::to_string(rp.device) + "): " + e.what());
+        }
+        if (!flying.empty()) (void)chn_stream_sync(rp.stream);  // the uploads out of these flights' buffers are over before they are freed
+    };
+    auto stop_replicas = [&]() {
+        for (auto &rp : reps) { std::lock_guard<std::mutex> lk(rp->m); rp->stop = true; rp->cv.notify_all(); }
+        for (auto &rp : reps) if (rp->t.joinable()) rp->t.join();
+    };
+    struct ReplicaJoin { std::function<void()> f; ~ReplicaJoin() { f(); } } replica_join{stop_replicas};
+    // the next flight in input order, back from its replica, on to its rows
+    auto release_next = [&]() {
+        const uint64_t s = merge.next_seq();
+        Replica &owner = *reps[(size_t)(s % n_rep)];
+        { std::lock_guard<std::mutex> lk(owner.m); if (!owner.need_set || owner.need < s) { owner.need = s; owner.need_set = true; } owner.cv.notify_all(); }
+        std::unique_ptr<Flight> f = merge.take();
+        owner.outstanding -= 1;
+        hand_on(f);
+    };
+    auto release_ready = [&]() {  // whatever has come back in order already, without waiting
+        std::unique_ptr<Flight> f;
+        while (merge.try_take(f)) {
+            reps[(size_t)(f->seq % n_rep)]->outstanding -= 1;
+            hand_on(f);
+        }
+    };
+    auto drain_replicas = [&]() {  // every dealt flight back and on to its rows, in order
+        while (merge.next_seq() < next_seq) release_next();
+    };
+    auto start_replicas = [&]() {
+        // the final models on every replica's stream (replica 0's may lag behind the last change in training)
+        result.ensure_device_model();
+        reps[0]->model_version = result.current_model_version();
+        for (size_t r = 1; r < n_rep; ++r) reps[r]->model_version = result.push_model_to_device(reps[r]->stream);
+        for (auto &rp : reps) { Replica *p = rp.get(); p->t = std::thread([&replica_body, p]() { replica_body(*p); }); }
+        dealing = true;
+    };
+    auto deal = [&](std::unique_ptr<Flight> &f) {
+        const uint64_t s = next_seq++;
+        Replica &rp = *reps[(size_t)(s % n_rep)];
+        while (rp.outstanding >= kMaxOutstanding) release_next();
+        f->seq = s;
+        rp.outstanding += 1;
+        std::lock_guard<std::mutex> lk(rp.m);
+        rp.in.push_back(std::move(f));
+        // its earlier flights are wanted back: it waits for them while this one runs (submit i + 1, wait i)
+        if (s >= n_rep && (!rp.need_set || rp.need < s - n_rep)) { rp.need = s - n_rep; rp.need_set = true; }
+        rp.cv.notify_all();
+    };
     try {
-        std::unique_ptr<Flight> pending;
         for (;;) {
             double tp = now();
             std::shared_ptr<HostBatch> hbp = queue.pop();
@@ -754,7 +924,7 @@ int dehost_main(DehostArguments &opt) {
                     const RecView &a = hb.blk1.recs[i], &b = hb.blk2.recs[i];
                     const uint32_t la = a.id_len ? a.id_len - 1 : 0, lb = b.id_len ? b.id_len - 1 : 0;
                     if (la != lb || std::memcmp(a.id, b.id, la) != 0) {
-                        if (pending) retire(pending);
+                        if (dealing) drain_replicas();
                         if (writer.t.joinable()) writer_drain();
                         std::cout.flush();
                         std::cout << std::string(a.id, la) << " " << std::string(b.id, lb);
@@ -775,6 +945,7 @@ int dehost_main(DehostArguments &opt) {
                     if (bases + need > opt.batch_bases) break;
                     bases += need; ++endi;
                 }
+                if (dealing) release_ready();
                 std::unique_ptr<Flight> fl;
                 {
                     std::lock_guard<std::mutex> lk(pool_m);
@@ -792,33 +963,37 @@ int dehost_main(DehostArguments &opt) {
                 t_pack += now() - tk;
                 const size_t n = sub.keep.size();
                 if (n == 0) continue;
-                // a model still in training may change with every read added below: no batch may then be in flight across a change
-                if (pending && !result.models_final()) retire(pending);
+                if (result.models_final()) {
+                    // (nothing is in flight on replica 0 when the models become final: every training batch is retired before the next)
+                    if (!dealing) start_replicas();
+                    fl->version = result.current_model_version();
+                    deal(fl);
+                    release_ready();
+                    continue;
+                }
+                // a model still in training may change with every read added below: every batch is retired before the next is submitted
                 result.ensure_device_model();
                 fl->version = result.current_model_version();
                 chn_batch bt;
-                std::memset(&bt, 0, sizeof bt);
-                bt.struct_size = sizeof bt; bt.on_device = 0; bt.n_reads = n; bt.n_bases = sub.n_bases;
-                bt.bases2 = sub.bases.data(); bt.nmask = sub.any_n ? sub.nmask.data() : nullptr;
-                bt.seg1_offset = sub.off1.data(); bt.seg1_length = sub.len1.data();
-                bt.seg2_offset = opt.is_paired ? sub.off2.data() : nullptr; bt.seg2_length = opt.is_paired ? sub.len2.data() : nullptr;
-                bt.mean_quality = sub.mq.data(); bt.compression = sub.comp.data();
-                bt.gzip_tallies = sub.gz_gpu_len;  // > 0: the call kernel leaves the compression gate to finish()
-                bt.gzip_output = CHN_GZIP_SIZES;   // deflate pass and tree arithmetic on the device: four bytes per read come back
+                fill_batch(*fl, bt);
                 tk = now();
                 CHN_CHECK(chn_batch_submit(stream, &bt));
                 t_submit += now() - tk;
-                if (pending) retire(pending);  // rows of batch i-1 while the GPU works on batch i
-                pending = std::move(fl);
-                if (!result.models_final()) retire(pending);
+                reps[0]->batches += 1; reps[0]->reads += n;
+                retire(fl);
             }
         }
-        if (pending) retire(pending);
+        if (dealing) {
+            drain_replicas();
+            for (auto &rp : reps) { std::lock_guard<std::mutex> lk(rp->m); rp->closing = true; rp->cv.notify_all(); }
+            for (auto &rp : reps) if (rp->t.joinable()) rp->t.join();
+        }
         if (writer.t.joinable()) writer_drain();
         if (!queue.error.empty()) failure = queue.error;
     } catch (std::exception &e) {
         failure = e.what();
         queue.abort();  // the reader thread stops at its next block
+        stop_replicas();
     }
     reader.join();
     if (!failure.empty()) { std::cout.flush(); throw std::runtime_error(failure); }
@@ -841,6 +1016,16 @@ int dehost_main(DehostArguments &opt) {
                       file.t_verify, file.t_stage_alloc, file.t_stage_fill, file.t_device_wait, file.t_popcounts);
         g_log.info(tb);
         std::fprintf(stderr, "charon: %s\n", tb);
+    }
+    for (auto &rp : reps) {
+        g_log.info("replica " + std::to_string(rp->index) + " (device " + std::to_string(rp->device) + "): " + std::to_string(rp->batches) + " batches, " +
+                   std::to_string(rp->reads) + " reads");
+        if (timing && dealing) {
+            char tb[160];
+            std::snprintf(tb, sizeof tb, "timing (replica %zu, device %d, s): submit %.3f  wait-for-gpu %.3f", rp->index, rp->device, rp->t_submit, rp->t_wait);
+            g_log.info(tb);
+            std::fprintf(stderr, "charon: %s\n", tb);
+        }
     }
     if (gz_gpu_max) g_log.info("gzip column: " + std::to_string(gz_on_device) + " reads sized from device deflate tallies (the rest on the host)");
     result.print_summary();

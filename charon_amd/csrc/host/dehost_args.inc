@@ -23,6 +23,9 @@ struct DehostArguments {
     // not in the reference: GPU batching knobs (environment only, so the command line stays identical)
     uint64_t batch_reads = 65536, batch_bases = 1ULL << 30;
     int device = 0;
+    // CHARON_DEVICES: one index replica (own copy of the index, own chn_stream, own driver thread) per entry; empty = the single device above
+    std::vector<int> devices;
+    bool devices_all = false;  // CHARON_DEVICES=all: every visible device (resolved once the HIP runtime is up)
     uint8_t min_hits = 0;  // StatsModel::min_hits_ is uninitialised in the reference; CHARON_MIN_HITS overrides
     std::map<uint8_t, std::vector<std::string>> extract_category_to_file;  // include/dehost_arguments.hpp:20
     // `charon classify` (src/classify_main.cpp:24-119, include/classify_arguments.hpp): the same loop with ReadEntry::classify
@@ -152,4 +155,25 @@ bool parse_dehost(int argc, char **argv, DehostArguments &opt) {
     opt.read_file = pos[0];
     if (pos.size() > 1) opt.read_file2 = pos[1];
     return true;
+}
+
+// CHARON_DEVICES: "all" or a comma list of device ordinals ("0,1,3"; a repeated ordinal is a second replica on that device).  Returns an
+// error message, empty if the value is well formed.
+std::string parse_device_list(const std::string &v, DehostArguments &opt) {
+    opt.devices.clear();
+    opt.devices_all = false;
+    if (v == "all") { opt.devices_all = true; return ""; }
+    size_t at = 0;
+    for (;;) {
+        const size_t comma = v.find(',', at);
+        const std::string item = v.substr(at, comma == std::string::npos ? std::string::npos : comma - at);
+        if (item.empty()) return "empty entry in '" + v + "' (expected 'all' or a comma list of device ordinals such as 0,1,3)";
+        if (item.size() > 9 || item.find_first_not_of("0123456789") != std::string::npos)
+            return "'" + item + "' is not a device ordinal (expected 'all' or a comma list of non-negative integers such as 0,1,3)";
+        if (opt.devices.size() == 64) return "more than 64 entries";
+        opt.devices.push_back(std::atoi(item.c_str()));
+        if (comma == std::string::npos) break;
+        at = comma + 1;
+    }
+    return "";
 }

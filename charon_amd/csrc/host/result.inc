@@ -224,7 +224,11 @@ class Result {
         if (it->second.size() > 1) write_record(it->second[1], e.rec2_id, e.rec2_seq, e.rec2_qual);
     }
 
-    void push_model_to_device() {
+    void push_model_to_device() { push_model_to_device(stream_); }
+
+public:
+    // the current models to the stream of an index replica (`charon dehost` with CHARON_DEVICES), or to the Result's own stream
+    uint32_t push_model_to_device(chn_stream *stream) {
         const uint32_t C = (uint32_t)meta_.categories.size();
         std::vector<const float *> pp(C), np(C);
         std::vector<uint32_t> pn(C), nn(C);
@@ -235,9 +239,12 @@ class Result {
         chn_model m = base_model_;
         m.pos_data = pp.data(); m.pos_n = pn.data(); m.neg_data = np.data(); m.neg_n = nn.data();
         m.dist = training_.dist; m.pos_params = training_.p_pos.data(); m.neg_params = training_.p_neg.data();
-        CHN_CHECK(chn_model_set(stream_, &m));
-        device_model_version_ = training_.version;
+        CHN_CHECK(chn_model_set(stream, &m));
+        if (stream == stream_) device_model_version_ = training_.version;
+        return training_.version;
     }
+
+private:
     // bring prob/call/conf of `es` up to the current models (device K3 on the cached counts)
     void reclassify(std::vector<Entry *> &es) {
         if (es.empty()) return;

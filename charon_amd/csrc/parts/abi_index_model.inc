@@ -203,10 +203,19 @@ extern "C" int chn_index_create(const chn_index_desc *desc, chn_index **out) {
     return CHN_OK;
 }
 
+// Work queued on the index's own stream (Elias-Fano slices, a replica's copy) is waited for on the host before the words are read or
+// written through the null stream: ef_stream is a blocking stream, but the ordering is stated here rather than left to the legacy
+// null-stream semantics.
+static int index_wait_queued(chn_index *idx) {
+    if (idx->ef_stream) HIPCHK(hipStreamSynchronize(idx->ef_stream));
+    return CHN_OK;
+}
+
 extern "C" int chn_index_upload_rows(chn_index *idx, uint64_t row_begin, uint64_t n_rows, const uint64_t *host_words) {
     if (!idx || !host_words) return fail(CHN_E_INVALID, "chn_index_upload_rows: null argument");
     if (row_begin < idx->d.row_begin || row_begin + n_rows > idx->d.row_end) return fail(CHN_E_INVALID, "rows outside this shard");
     HIPCHK(hipSetDevice(idx->d.device));
+    if (const int rc = index_wait_queued(idx)) return rc;
     HIPCHK(hipMemcpy(idx->words + (row_begin - idx->d.row_begin) * idx->d.bin_words, host_words, n_rows * idx->d.bin_words * 8, hipMemcpyHostToDevice));
     return CHN_OK;
 }
@@ -214,6 +223,7 @@ extern "C" int chn_index_download_rows(chn_index *idx, uint64_t row_begin, uint6
     if (!idx || !host_words) return fail(CHN_E_INVALID, "chn_index_download_rows: null argument");
     if (row_begin < idx->d.row_begin || row_begin + n_rows > idx->d.row_end) return fail(CHN_E_INVALID, "rows outside this shard");
     HIPCHK(hipSetDevice(idx->d.device));
+    if (const int rc = index_wait_queued(idx)) return rc;
     HIPCHK(hipMemcpy(host_words, idx->words + (row_begin - idx->d.row_begin) * idx->d.bin_words, n_rows * idx->d.bin_words * 8, hipMemcpyDeviceToHost));
     return CHN_OK;
 }
@@ -226,9 +236,9 @@ extern "C" int chn_index_decode_ef(chn_index *idx, uint64_t m_size, uint32_t wl,
     if (n_high_words > (1ULL << 31)) return fail(CHN_E_INVALID, "chn_index_decode_ef: slice too large (at most 2^31 words)");
     HIPCHK(hipSetDevice(d.device));
     *bad_bits = 0;
-    if (!idx->ef_stream) {
-        if (n_high_words == 0) return CHN_OK;  // nothing was ever decoded
-        HIPCHK(hipStreamCreate(&idx->ef_stream));
+    if (!idx->ef_bad) {
+        if (n_high_words == 0) return index_wait_queued(idx);  // nothing was ever decoded (a replica's copy may be in flight)
+        if (!idx->ef_stream) HIPCHK(hipStreamCreate(&idx->ef_stream));
         HIPCHK(hipEventCreateWithFlags(&idx->ef_copied, hipEventDisableTiming));
         HIPCHK(hipMalloc((void **)&idx->ef_bad, 8));
         HIPCHK(hipMemsetAsync(idx->ef_bad, 0, 8, idx->ef_stream));
@@ -279,7 +289,7 @@ extern "C" int chn_index_bin_popcounts(chn_index *idx, uint64_t *out) {
     if (!idx || !out) return fail(CHN_E_INVALID, "chn_index_bin_popcounts: null argument");
     const chn_index_desc &d = idx->d;
     HIPCHK(hipSetDevice(d.device));
-    if (idx->ef_stream) HIPCHK(hipStreamSynchronize(idx->ef_stream));  // slices still being decoded
+    if (const int rc = index_wait_queued(idx)) return rc;  // slices still being decoded, a replica's copy
     unsigned long long *d_out = nullptr;
     HIPCHK(hipMalloc((void **)&d_out, d.technical_bins * 8));
     HIPCHK(hipMemset(d_out, 0, d.technical_bins * 8));
@@ -302,6 +312,47 @@ extern "C" int chn_index_get_desc(const chn_index *idx, chn_index_desc *out) {
     *out = idx->d;
     return CHN_OK;
 }
+extern "C" int chn_device_count(int *count) {
+    if (!count) return fail(CHN_E_INVALID, "chn_device_count: null argument");
+    *count = 0;
+    HIPCHK(hipGetDeviceCount(count));
+    return CHN_OK;
+}
+// One hipMemcpyPeerAsync of the source's words (the zeroed 64-byte tail included) on the replica's own stream (ef_stream, which every call that
+// reads or writes the words waits for).  Peer access is neither enabled nor required: the runtime stages a copy between devices without it.
+extern "C" int chn_index_replicate(const chn_index *src, int32_t device, chn_index **out) {
+    if (!src || !out) return fail(CHN_E_INVALID, "chn_index_replicate: null argument");
+    *out = nullptr;
+    int n_dev = 0;
+    HIPCHK(hipGetDeviceCount(&n_dev));
+    if (device < 0 || device >= n_dev)
+        return fail(CHN_E_INVALID, "chn_index_replicate: device " + std::to_string(device) + " is not below the device count " + std::to_string(n_dev));
+    chn_index *s = const_cast<chn_index *>(src);  // (only its queued work is waited for)
+    HIPCHK(hipSetDevice(s->d.device));
+    if (const int rc = index_wait_queued(s)) return rc;
+    const size_t bytes = (size_t)(s->rows_local * s->d.bin_words * 8 + 64);
+    HIPCHK(hipSetDevice(device));
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    if (bytes > free_b)
+        return fail(CHN_E_NOMEM, "chn_index_replicate: device " + std::to_string(device) + " needs " + std::to_string(bytes) + " bytes for the index, " +
+                                     std::to_string(free_b) + " bytes free");
+    chn_index *idx = new (std::nothrow) chn_index();
+    if (!idx) return fail(CHN_E_NOMEM, "host allocation failed");
+    idx->d = s->d;
+    idx->d.device = device;
+    idx->rows_local = s->rows_local;
+    idx->single_bin_categories = s->single_bin_categories;
+    hipError_t e = hipMalloc((void **)&idx->words, bytes);
+    if (e == hipSuccess) e = hipStreamCreate(&idx->ef_stream);
+    if (e == hipSuccess) e = hipMemcpyPeerAsync(idx->words, device, s->words, s->d.device, bytes, idx->ef_stream);
+    if (e != hipSuccess) {
+        chn_index_destroy(idx);
+        return fail(e == hipErrorOutOfMemory ? CHN_E_NOMEM : CHN_E_HIP, std::string("chn_index_replicate: ") + hipGetErrorString(e));
+    }
+    *out = idx;
+    return CHN_OK;
+}
 extern "C" int chn_index_destroy(chn_index *idx) {
     if (!idx) return CHN_OK;
     (void)hipSetDevice(idx->d.device);
@@ -315,19 +366,21 @@ extern "C" int chn_index_destroy(chn_index *idx) {
 static std::vector<float> g_def_pos, g_def_neg;
 static const float *g_def_pos_ptr[CHN_MAX_CATEGORIES], *g_def_neg_ptr[CHN_MAX_CATEGORIES];
 static uint32_t g_def_n_pos[CHN_MAX_CATEGORIES], g_def_n_neg[CHN_MAX_CATEGORIES];
+static std::once_flag g_def_once;
 
 extern "C" int chn_model_default(chn_model *m, uint32_t num_categories, uint8_t host_index, int paired) {
     if (!m || num_categories < 1 || num_categories > CHN_MAX_CATEGORIES) return fail(CHN_E_INVALID, "chn_model_default: bad argument");
-    if (g_def_pos.empty()) {
+    // filled once, whatever host thread asks first (the tables are read-only afterwards)
+    std::call_once(g_def_once, []() {
         for (double v : CHN_DEFAULT_POS) g_def_pos.push_back((float)v);
         for (double v : CHN_DEFAULT_NEG) g_def_neg.push_back((float)v);
         std::sort(g_def_pos.begin(), g_def_pos.end());  // KDEParams constructor sorts (include/classify_stats.hpp:214-218)
         std::sort(g_def_neg.begin(), g_def_neg.end());
-    }
-    for (uint32_t c = 0; c < num_categories; ++c) {
-        g_def_pos_ptr[c] = g_def_pos.data(); g_def_neg_ptr[c] = g_def_neg.data();
-        g_def_n_pos[c] = (uint32_t)g_def_pos.size(); g_def_n_neg[c] = (uint32_t)g_def_neg.size();
-    }
+        for (uint32_t c = 0; c < CHN_MAX_CATEGORIES; ++c) {
+            g_def_pos_ptr[c] = g_def_pos.data(); g_def_neg_ptr[c] = g_def_neg.data();
+            g_def_n_pos[c] = (uint32_t)g_def_pos.size(); g_def_n_neg[c] = (uint32_t)g_def_neg.size();
+        }
+    });
     std::memset(m, 0, sizeof(*m));
     m->struct_size = sizeof(chn_model);
     m->num_categories = num_categories;

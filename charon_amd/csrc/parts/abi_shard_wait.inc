@@ -75,6 +75,7 @@ extern "C" int chn_index_emplace(chn_index *idx, const uint64_t *host_values, ui
     if (n_values == 0) return CHN_OK;
     const chn_index_desc &d = idx->d;
     HIPCHK(hipSetDevice(d.device));
+    if (const int rc = index_wait_queued(idx)) return rc;
     uint64_t *dv = nullptr;
     const uint64_t chunk = 1ULL << 26;  // 512 MiB of values at a time
     HIPCHK(hipMalloc((void **)&dv, std::min(chunk, n_values) * 8));

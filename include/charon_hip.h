@@ -10,7 +10,7 @@
  * Conventions: every function returns 0 on success or a negative CHN_E_* code; chn_last_error() returns a
  * thread-local message owned by the library.  No C++ types, exceptions or torch types cross this boundary.
  * All sizes are 64-bit.  The library never writes to stdout/stderr.  A chn_stream is NOT thread-safe;
- * different streams may be driven from different host threads.
+ * different streams may be driven from different host threads (a front end drives one index replica and its stream per thread).
  */
 #ifndef CHARON_HIP_H
 #define CHARON_HIP_H
@@ -88,6 +88,18 @@ int chn_index_device_words(chn_index *idx, uint64_t **device_words, uint64_t *n_
 int chn_index_download_rows(chn_index *idx, uint64_t row_begin, uint64_t n_rows, uint64_t *host_words);
 int chn_index_get_desc(const chn_index *idx, chn_index_desc *out);
 int chn_index_destroy(chn_index *idx);
+/* An independent copy of `src` on HIP device `device` (the same device as src's or another one): same descriptor except `device`, a
+ * row shard included.  The call waits on the host for src's queued Elias-Fano slices, checks that `device` is a valid ordinal
+ * (CHN_E_INVALID otherwise) and that the words fit in its free memory (CHN_E_NOMEM, the message names the device, the bytes needed
+ * and the bytes free), allocates the words and QUEUES one hipMemcpyPeerAsync on the replica's own stream; peer access is not
+ * enabled and no device setting is changed.  Like chn_index_decode_ef it returns as soon as the copy is queued: the replica's
+ * chn_stream_create, chn_index_bin_popcounts, chn_index_download_rows, chn_index_upload_rows, chn_index_emplace and
+ * chn_index_destroy wait for it.  `src` must not be destroyed or written until one of those calls on the replica has returned.
+ * No reference counterpart (the reference is single-process and runs one index): one index replica per device, each fed its own
+ * batches of reads, is the "device list" part of SURVEY 8(b).3. */
+int chn_index_replicate(const chn_index *src, int32_t device, chn_index **out);
+/* Number of HIP devices visible to the process (hipGetDeviceCount). */
+int chn_device_count(int *count);
 
 /* ---- model --------------------------------------------------------------------------------------------
  * Replaces: StatsModel + Model + KDEParams as read by ReadEntry::apply_model / call_host / call_category
