@@ -17,6 +17,10 @@ _L = C.CDLL(LIB_PATH)
 MINIMISER_SEED = 0x8F3F73B5CF1C9ADE
 STREAM_PROFILE = 1
 STREAM_TINY_LOG = 2
+# chn_batch.gzip_output (include/charon_hip.h)
+GZIP_TALLIES, GZIP_SIZES, GZIP_BOTH = 0, 1, 2
+GZIP_SIZES_ALL = 3           # the gzip size of every read of 1 .. gzip_tallies letters, any length, any number of deflate blocks
+GZIP_ANY_LEN = 0xFFFFFFFF    # gzip_tallies under GZIP_SIZES_ALL: no length bound
 
 
 class IndexDesc(C.Structure):
@@ -284,7 +288,8 @@ class Stream:
 
     def submit_host(self, packed, mean_quality=None, compression=None, gzip_tallies=0, gzip_output=0):
         """packed: dict from charon_amd.pack.pack_reads; gzip_tallies: longest read to tally on the device (0 = off);
-        gzip_output: 0 tallies, 1 gzip member sizes (tree arithmetic on the device as well), 2 both"""
+        gzip_output: 0 tallies, 1 gzip member sizes (tree arithmetic on the device as well), 2 both,
+        3 (GZIP_SIZES_ALL) the size of every read up to gzip_tallies letters, whatever its length (GZIP_ANY_LEN: no bound)"""
         b, keep, n = self._host_batch(packed, mean_quality, compression)
         b.gzip_tallies, b.gzip_output = gzip_tallies, gzip_output
         _chk(_L.chn_batch_submit(self.h, C.byref(b)))
@@ -396,7 +401,7 @@ class Stream:
                    flags=np.zeros(n, np.uint8))
         want_gz = len(self._fifo[0]) > 2 and self._fifo[0][2]
         gz_out = self._fifo[0][3] if len(self._fifo[0]) > 3 else 0
-        if want_gz and gz_out != 1:
+        if want_gz and gz_out in (GZIP_TALLIES, GZIP_BOTH):
             out["gzip_tallies"] = np.zeros((n, 320), np.uint16)
         if want_gz and gz_out != 0:
             out["gzip_sizes"] = np.zeros(n, np.uint32)

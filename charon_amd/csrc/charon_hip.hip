@@ -54,6 +54,7 @@
 #include "parts/len_order.inc"
 #include "parts/gzip_tally.inc"
 #include "parts/gzip_size_dev.inc"
+#include "parts/gzip_tally_long.inc"
 #include "parts/ef_decode.inc"
 #include "parts/synth_kernels.inc"
 #include "parts/abi_index_model.inc"

@@ -51,6 +51,28 @@ struct WordBuf {
     const uint32_t *data() const { return p; }
 };
 
+// The default routing of reads beyond CHN_GZIP_MAX_LEN letters (CHN_GZIP_SIZES_ALL): the device sizes every read of the batch of at
+// most the returned length (0: none of them).  One wavefront walks one such read, at about DEV_NS per letter (a lone wavefront's
+// deflate_slow: 0.1-0.2 ms per kb, profiles/r03/sq_gzip_tally.txt), and the device holds WAVES of them at once; the host emulator
+// takes HOST_NS per letter on one thread (about 70 us per 5 kb, DESIGN 6b).  A long read only pays on the device when its walk hides
+// under what the batch costs anyway: the batch's other device work (BATCH_NS per letter of the batch) or the host time of the long
+// reads the device takes off `threads` threads.  So a batch of short reads never waits for one lone 2 Mb read (0.3 s on the device,
+// 28 ms on one host thread), while a batch with many ultra-long reads sends them to the device at -t 1.  Applied only where every read
+// up to CHN_GZIP_MAX_LEN is sized on the device already (fewer than 12 threads): the routing never moves a read below that length.
+static uint32_t gzip_long_device_limit(std::vector<uint32_t> long_lens, uint64_t batch_letters, int threads) {
+    const double DEV_NS = 150.0, HOST_NS = 14.0, BATCH_NS = 0.1, WAVES = 512.0;
+    std::sort(long_lens.begin(), long_lens.end());
+    double rest = 0;  // letters of the reads at most long_lens[i]
+    std::vector<double> upto(long_lens.size());
+    for (size_t i = 0; i < long_lens.size(); ++i) upto[i] = rest += long_lens[i];
+    for (size_t i = long_lens.size(); i-- > 0;) {  // the longest limit that pays
+        const double dev = DEV_NS * std::max<double>(long_lens[i], upto[i] / WAVES);
+        const double hidden = std::max(BATCH_NS * (double)batch_letters, HOST_NS * upto[i] / std::max(1, threads));
+        if (dev <= hidden) return long_lens[i];
+    }
+    return 0;
+}
+
 struct HostBatch {
     RawBlock blk1, blk2;               // records of this batch (views into the blocks' slabs)
     std::vector<Slab> extra;  // further slabs of mate records when one block did not hold enough of them
@@ -159,10 +181,11 @@ struct HostBatch {
         return sum;
     }
     // layout + parallel packing, mean quality and gzip ratio of the records in blk1 (/blk2)
-    // gz_gpu_max > 0: reads of at most that many letters get their gzip size from the device's deflate tallies (finish_compression)
+    // gz_gpu_max > 0: reads of at most that many letters get their gzip size from the device (finish_compression); gz_route_long: and
+    // the reads beyond CHN_GZIP_MAX_LEN that gzip_long_device_limit gives the device in this batch
     std::vector<uint8_t> gz_pending;   // per kept read: its compression ratio is still to come
     uint32_t gz_gpu_len = 0;           // longest such read (what chn_batch.gzip_tallies asks for)
-    void pack(bool paired, int threads, bool skip_compression, uint32_t gz_gpu_max = 0) {
+    void pack(bool paired, int threads, bool skip_compression, uint32_t gz_gpu_max = 0, bool gz_route_long = false) {
         const size_t nrec = blk1.recs.size();
         keep.clear();
         for (size_t i = 0; i < nrec; ++i) {
@@ -184,6 +207,17 @@ struct HostBatch {
         if (cur == 0) { bases.assign_zero(n_bases / 16); nmask.assign_zero(n_bases / 32); }
         else { bases.assign_raw(n_bases / 16); nmask.assign_raw(n_bases / 32); }
         gz_pending.assign(n, 0); gz_gpu_len = 0;
+        // (only where every read up to CHN_GZIP_MAX_LEN goes to the device already: the device then sizes every read up to the limit)
+        if (gz_gpu_max >= CHN_GZIP_MAX_LEN && gz_route_long && !skip_compression) {
+            std::vector<uint32_t> long_lens;
+            uint64_t letters = 0;
+            for (size_t i = 0; i < n; ++i) {
+                const uint64_t L = (uint64_t)len1[i] + (paired ? len2[i] : 0);
+                letters += L;
+                if (L > CHN_GZIP_MAX_LEN) long_lens.push_back((uint32_t)L);
+            }
+            gz_gpu_max = std::max(gz_gpu_max, gzip_long_device_limit(long_lens, letters, threads));
+        }
         if (gz_gpu_max && !skip_compression)
             for (size_t i = 0; i < n; ++i) {
                 const uint64_t L = (uint64_t)len1[i] + (paired ? len2[i] : 0);
@@ -563,7 +597,7 @@ int dehost_main(DehostArguments &opt) {
         std::vector<uint8_t> call, conf, flags;
         std::vector<uint32_t> gz_sizes;
     };
-    uint64_t gz_on_device = 0;
+    uint64_t gz_on_device = 0, gz_long_on_device = 0;
     // CHARON_TIMING=1: wall seconds per phase of the main thread, to the log (where does the CLI's time go?)
     const bool timing = std::getenv("CHARON_TIMING") != nullptr;
     double t_pop = 0, t_pack = 0, t_submit = 0, t_wait = 0, t_gz = 0, t_rows = 0;
@@ -572,8 +606,15 @@ int dehost_main(DehostArguments &opt) {
     // Long reads run few wavefronts per CU there (five for a 60 kb read, its class arrays in global memory): about what sixteen host threads
     // make of them with the size emulator -- so with that many host threads the longest reads (beyond 40 000 letters) stay on the host, in the
     // packing loop beside the GPU; with fewer threads everything up to the device's limit goes to the GPU (sweep: profiles/r02/cli_long_reads.txt).
+    // Reads beyond CHN_GZIP_MAX_LEN are sized by the device's long-read pass (CHN_GZIP_SIZES_ALL) where gzip_long_device_limit says
+    // it pays; CHARON_GZIP_GPU_MAX sets one length limit for everything instead (61440: every longer read on the host).
     uint32_t gz_gpu_max = (std::getenv("CHARON_GZIP_ON_HOST") || std::getenv("CHARON_ZLIB_ONLY") || !g_gzip_emulator) ? 0u : (opt.threads >= 12 ? 40000u : CHN_GZIP_MAX_LEN);
-    if (gz_gpu_max) if (const char *e = std::getenv("CHARON_GZIP_GPU_MAX")) gz_gpu_max = std::min<uint32_t>(CHN_GZIP_MAX_LEN, (uint32_t)std::max(1, std::atoi(e)));
+    bool gz_route_long = gz_gpu_max != 0;
+    if (gz_gpu_max)
+        if (const char *e = std::getenv("CHARON_GZIP_GPU_MAX")) {
+            gz_gpu_max = (uint32_t)std::min<unsigned long long>(CHN_GZIP_ANY_LEN, std::max<unsigned long long>(1, std::strtoull(e, nullptr, 10)));
+            gz_route_long = false;
+        }
     std::vector<Entry> entries;
     // (rows are FORMATTED by the reader's team as well -- -t, but never fewer than four: text out is the mirror of text in; the reference prints inside its
     //  critical section whatever -t is.  With the default -t 1 the main thread formatted rows for 1.0 of a 2.3 s read loop on 4 M reads.)
@@ -623,8 +664,13 @@ int dehost_main(DehostArguments &opt) {
                     if (sub.gz_pending[i]) {
                         if (gz_sizes[i] != 0) {
                             sub.comp[i] = static_cast<float>(static_cast<double>(gz_sizes[i]) / static_cast<double>(L));
+                            if (L <= CHN_GZIP_MAX_LEN) {
 #pragma omp atomic
-                            gz_on_device += 1;
+                                gz_on_device += 1;
+                            } else {
+#pragma omp atomic
+                                gz_long_on_device += 1;
+                            }
                         } else {
                             sub.comp[i] = defl.ratio(sub.blk1.recs[sub.keep[i]], opt.is_paired ? &sub.blk2.recs[sub.keep[i]] : nullptr);
                         }
@@ -794,7 +840,8 @@ int dehost_main(DehostArguments &opt) {
         bt.seg2_offset = opt.is_paired ? sub.off2.data() : nullptr; bt.seg2_length = opt.is_paired ? sub.len2.data() : nullptr;
         bt.mean_quality = sub.mq.data(); bt.compression = sub.comp.data();
         bt.gzip_tallies = sub.gz_gpu_len;  // > 0: the call kernel leaves the compression gate to finish()
-        bt.gzip_output = CHN_GZIP_SIZES;   // deflate pass and tree arithmetic on the device: four bytes per read come back
+        // deflate pass and tree arithmetic on the device: four bytes per read come back (reads beyond CHN_GZIP_MAX_LEN: the long-read pass)
+        bt.gzip_output = sub.gz_gpu_len > CHN_GZIP_MAX_LEN ? CHN_GZIP_SIZES_ALL : CHN_GZIP_SIZES;
     };
 
     // Replica mode, once the models are final (before that every batch runs on replica 0, retired one by one: the models may change with
@@ -959,7 +1006,7 @@ int dehost_main(DehostArguments &opt) {
                 if (opt.is_paired) sub.blk2.recs.assign(hb.blk2.recs.begin() + (long)begin, hb.blk2.recs.begin() + (long)endi);
                 begin = endi;
                 double tk = now();
-                sub.pack(opt.is_paired, opt.threads, skip_compression, gz_gpu_max);  // batch i+1 is packed while the GPU works on batch i
+                sub.pack(opt.is_paired, opt.threads, skip_compression, gz_gpu_max, gz_route_long);  // batch i+1 is packed while the GPU works on batch i
                 t_pack += now() - tk;
                 const size_t n = sub.keep.size();
                 if (n == 0) continue;
@@ -1028,6 +1075,7 @@ int dehost_main(DehostArguments &opt) {
         }
     }
     if (gz_gpu_max) g_log.info("gzip column: " + std::to_string(gz_on_device) + " reads sized from device deflate tallies (the rest on the host)");
+    if (gz_gpu_max) g_log.info("gzip column: " + std::to_string(gz_long_on_device) + " reads beyond " + std::to_string(CHN_GZIP_MAX_LEN) + " letters sized by the device's long-read deflate pass");
     result.print_summary();
     // the process is about to exit: unmapping gigabytes of read file page by page is time nobody needs
     (void)in1p.release(); (void)in2.release();

@@ -111,6 +111,8 @@ struct Slot {
     bool staged = false, gz_staged = false;
     uint32_t gz_output = 0;
     hipEvent_t bases_up = nullptr, gz_done = nullptr;
+    DevBuf d_gzlong;                      // CHN_GZIP_SIZES_ALL: k_gzip_long's sizes [max_reads], then its launches' read counters [64]
+    hipEvent_t gzt_done = nullptr;        // ... the tally launches (stream3) are done: stream5 forms the sizes behind them and its long-read launch
     DevBuf d_order;                       // length-class order of this batch (read by the count kernel on the side stream)
     LogBuf lb;                            // this batch's row log
     DevBuf d_len1, d_len2, d_mq, d_comp;  // staging of the small per-read arrays of host batches (read by k_model_call)
@@ -137,6 +139,7 @@ struct chn_stream {
     hipStream_t stream0 = nullptr;  // host -> device uploads of host batches (truly asynchronous when the caller's memory is pinned)
     hipStream_t stream3 = nullptr;  // deflate tallies (latency-bound LDS work beside the HBM-bound probe kernel)
     hipStream_t stream4 = nullptr;  // the SPLIT launch of k_minimise_probe (long reads), beside the ordinary launch
+    hipStream_t stream5 = nullptr;  // k_gzip_long on the reads beyond CHN_GZIP_MAX_LEN (CHN_GZIP_SIZES_ALL), beside the tally launches (created with the first such batch)
     uint32_t long_bucket = 104;     // reads from this length class on are split over the lanes of a wavefront (256: never)
     DevBuf d_hist, d_model;
     DevBuf d_memo;                    // k_model_call memo table (cleared whenever the model changes)
@@ -152,6 +155,8 @@ struct chn_stream {
     uint64_t overflow_reruns = 0;
     bool gzt_big_lds = false;         // k_gzip_tally's dynamic-LDS limit has been raised
     DevBuf d_gzscratch;               // k_gzip_tally's per-wavefront class arrays (shared by the launches of the stream, which run one after the other)
+    DevBuf d_gzlscratch[2];           // k_gzip_long's per-wavefront epoch arrays: [0] its launches on stream5, [1] the re-runs on stream3
+    bool gzl_big_lds = false;         // k_gzip_long's dynamic-LDS limit has been raised
     uint32_t n_cus = 256;             // compute units of the device
     static const int N_SLOTS = 3;  // batches that may be in flight at once
     Slot slot[N_SLOTS];

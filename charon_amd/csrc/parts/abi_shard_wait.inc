@@ -233,7 +233,7 @@ extern "C" int chn_batch_wait(chn_stream *s, chn_result *r) {
     };
     int frc = CHN_OK;
     if (sl.want_gzt && r->gzip_tallies) {
-        if (sl.gz_output == CHN_GZIP_SIZES) return fail(CHN_E_INVALID, "chn_result.gzip_tallies: the batch asked for sizes only");
+        if (sl.gz_output == CHN_GZIP_SIZES || sl.gz_output == CHN_GZIP_SIZES_ALL) return fail(CHN_E_INVALID, "chn_result.gzip_tallies: the batch asked for sizes only");
         if (sl.gz_staged) std::memcpy(r->gzip_tallies, sl.h_gzt.p, n * GZT_WORDS * 2);
         else HIPCHK(hipMemcpy(r->gzip_tallies, sl.d_gzt.p, n * GZT_WORDS * 2, hipMemcpyDeviceToHost));
     }

@@ -57,6 +57,7 @@ extern "C" int chn_stream_create(chn_index *idx, const chn_stream_cfg *cfg, chn_
         if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.uploaded, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.bases_up, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.gz_done, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.gzt_done, hipEventDisableTiming);
         if (e != hipSuccess) { chn_stream_destroy(s); return fail(CHN_E_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e)); }
         if ((rc = sl.d_num_hashes.ensure(n * 4)) || (rc = sl.d_counts.ensure(n * C * 4)) || (rc = sl.d_unique.ensure(n * C * 4)) ||
             (rc = sl.d_prob.ensure(n * C * 8)) || (rc = sl.d_call.ensure(n)) || (rc = sl.d_conf.ensure(n)) || (rc = sl.d_flags.ensure(n)) ||
@@ -93,6 +94,7 @@ extern "C" int chn_stream_destroy(chn_stream *s) {
     if (s->stream0) { (void)hipStreamSynchronize(s->stream0); (void)hipStreamDestroy(s->stream0); }
     if (s->stream3) { (void)hipStreamSynchronize(s->stream3); (void)hipStreamDestroy(s->stream3); }
     if (s->stream4) { (void)hipStreamSynchronize(s->stream4); (void)hipStreamDestroy(s->stream4); }
+    if (s->stream5) { (void)hipStreamSynchronize(s->stream5); (void)hipStreamDestroy(s->stream5); }
     if (s->stream) (void)hipStreamDestroy(s->stream);
     for (Slot &sl : s->slot) {
         for (int i = 0; i < 8; ++i) if (sl.ev[i]) (void)hipEventDestroy(sl.ev[i]);
@@ -102,14 +104,15 @@ extern "C" int chn_stream_destroy(chn_stream *s) {
         if (sl.uploaded) (void)hipEventDestroy(sl.uploaded);
         if (sl.bases_up) (void)hipEventDestroy(sl.bases_up);
         if (sl.gz_done) (void)hipEventDestroy(sl.gz_done);
+        if (sl.gzt_done) (void)hipEventDestroy(sl.gzt_done);
         sl.h_res.release(); sl.h_gzt.release(); sl.h_gzsize.release(); sl.d_gzsize.release();
         s->h_block.release();
-        DevBuf *bufs[] = {&sl.d_num_hashes, &sl.d_counts, &sl.d_unique, &sl.d_prob, &sl.d_call, &sl.d_conf, &sl.d_flags, &sl.d_ctl, &sl.d_order, &sl.d_gzt, &sl.d_gzidx, &sl.d_gzctr,
+        DevBuf *bufs[] = {&sl.d_num_hashes, &sl.d_counts, &sl.d_unique, &sl.d_prob, &sl.d_call, &sl.d_conf, &sl.d_flags, &sl.d_ctl, &sl.d_order, &sl.d_gzt, &sl.d_gzidx, &sl.d_gzctr, &sl.d_gzlong,
                           &sl.d_len1, &sl.d_len2, &sl.d_mq, &sl.d_comp, &sl.d_bases, &sl.d_nmask, &sl.d_off1, &sl.d_off2};
         for (DevBuf *b : bufs) b->release();
         sl.lb.release();
     }
-    DevBuf *bufs[] = {&s->d_hist, &s->d_model, &s->d_list, &s->d_cbase, &s->d_memo, &s->d_shx_cnt, &s->d_gzscratch,
+    DevBuf *bufs[] = {&s->d_hist, &s->d_model, &s->d_list, &s->d_cbase, &s->d_memo, &s->d_shx_cnt, &s->d_gzscratch, &s->d_gzlscratch[0], &s->d_gzlscratch[1],
                       &s->cc.num_hashes, &s->cc.counts, &s->cc.unique, &s->cc.len1, &s->cc.mq, &s->cc.comp, &s->cc.prob, &s->cc.call,
                       &s->cc.conf, &s->cc.flags};
     for (DevBuf *b : bufs) b->release();
@@ -351,12 +354,58 @@ static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind) {
     // LDS (and with it the number of reads a CU works on at once) goes with the longest read of a launch, so a host batch is cut
     // into occupancy classes (below), one launch per class in use; a device batch is one launch sized by the caller's bound.
     sl.want_gzt = b->gzip_tallies != 0 && !list_mode;
-    if (sl.want_gzt && b->gzip_output > CHN_GZIP_BOTH) return fail(CHN_E_INVALID, "chn_batch.gzip_output: unknown value");
+    if (sl.want_gzt && b->gzip_output > CHN_GZIP_SIZES_ALL) return fail(CHN_E_INVALID, "chn_batch.gzip_output: unknown value");
+    if (sl.want_gzt && b->gzip_output == CHN_GZIP_SIZES_ALL && b->on_device)
+        return fail(CHN_E_INVALID, "chn_batch.gzip_output = CHN_GZIP_SIZES_ALL: host batches only");
     sl.gz_output = b->gzip_output;
     if (sl.want_gzt) {
         int rc = sl.d_gzt.ensure((size_t)s->cfg.max_reads * GZT_WORDS * 2);
         if (rc) return rc;
         const uint32_t bound = std::min<uint32_t>(b->gzip_tallies, GZT_MAX_LEN);
+        // CHN_GZIP_SIZES_ALL: k_gzip_long sizes the reads beyond the tally kernel's reach -- longer than GZT_MAX_LEN (on its own stream,
+        // beside the tally launches) and those the tallies hand back for a second deflate block (behind the tally launches)
+        const bool all_sizes = sl.gz_output == CHN_GZIP_SIZES_ALL;
+        const uint32_t long_bound = b->gzip_tallies;
+        const size_t cap_n = (size_t)s->cfg.max_reads;
+        bool long_launch = false;  // a k_gzip_long launch on stream5: the sizes are formed there, behind it and behind the tallies
+        if (all_sizes) {
+            if (!s->stream5) {
+                int prio_least = 0, prio_greatest = 0;
+                HIPCHK(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+                HIPCHK(hipStreamCreateWithPriority(&s->stream5, hipStreamNonBlocking, prio_least));
+            }
+            if ((rc = sl.d_gzlong.ensure((cap_n + 64) * 4))) return rc;
+            HIPCHK(hipMemsetAsync(sl.d_gzlong.p, 0, n * 4, s->stream0));  // 0: not sized (yet)
+            HIPCHK(hipMemsetAsync(sl.d_gzlong.as<uint32_t>() + cap_n, 0, 64 * 4, s->stream0));
+            if (!s->gzl_big_lds) {
+                HIPCHK(hipFuncSetAttribute((const void *)k_gzip_long<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                HIPCHK(hipFuncSetAttribute((const void *)k_gzip_long<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                s->gzl_big_lds = true;
+            }
+        }
+        // one k_gzip_long launch: as many wavefronts as the device holds at once (LDS), each taking the next read from a counter
+        auto launch_long = [&](hipStream_t st, DevBuf &scratch, uint32_t ctr, uint32_t filter, const uint32_t *index, uint32_t count) -> int {
+            if (count == 0) return CHN_OK;
+            const int bits = nmask ? 4 : 2;
+            const size_t lds = gzl_lds_bytes(bits);
+            const uint32_t wpc = (uint32_t)std::max<size_t>(1, (size_t)160 * 1024 / lds);
+            const uint32_t grid = (uint32_t)std::min<uint64_t>(count, (uint64_t)s->n_cus * wpc);
+            const size_t need = (size_t)grid * GZL_STRIDE32 * 4;
+            if (need > scratch.cap) {
+                int rc2 = scratch.ensure(need);
+                if (rc2) return fail(CHN_E_NOMEM, "gzip sizes of long reads: no room for " + std::to_string(need >> 20) + " MiB of deflate scratch (" + g_err + ")");
+            }
+            GzlArgs gl;
+            std::memset(&gl, 0, sizeof gl);
+            gl.bases = bases; gl.nmask = nmask; gl.off1 = off1; gl.off2 = off2; gl.len1 = sl.len1; gl.len2 = sl.len2; gl.n_bases = b->n_bases;
+            gl.bound = long_bound; gl.short_max = bound; gl.filter = filter; gl.tallies = sl.d_gzt.as<uint16_t>();
+            gl.index = index; gl.count = count; gl.sizes = sl.d_gzlong.as<uint32_t>();
+            gl.scratch = scratch.as<uint32_t>(); gl.counter = sl.d_gzlong.as<uint32_t>() + cap_n + ctr;
+            if (bits == 4) hipLaunchKernelGGL(k_gzip_long<4>, dim3(grid), dim3(WAVE), lds, st, gl);
+            else hipLaunchKernelGGL(k_gzip_long<2>, dim3(grid), dim3(WAVE), lds, st, gl);
+            HIPCHK(hipGetLastError());
+            return CHN_OK;
+        };
         HIPCHK(hipMemsetAsync(sl.d_gzt.p, 1, n * GZT_WORDS * 2, s->stream3));  // status word != 0: "not tallied" unless a launch says otherwise
         GztArgs g;
         std::memset(&g, 0, sizeof g);
@@ -421,37 +470,71 @@ static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind) {
                 std::memcpy(fill, start, sizeof fill);
                 for (uint64_t i = 0; i < n; ++i) { uint32_t L = 0; const uint32_t c = cls_of(i, L); if (c < NCLS) sl.h_gzidx[fill[c]++] = (uint32_t)i; }
             }
+            // CHN_GZIP_SIZES_ALL: behind the class lists, the reads beyond GZT_MAX_LEN (longest first), then the tallied reads long
+            // enough to reach a second deflate block (at least GZT_SYMBOL_LIMIT letters)
+            const size_t long_at = sl.h_gzidx.size();
+            size_t rerun_at = long_at;
+            if (all_sizes) {
+                for (uint64_t i = 0; i < n; ++i) {
+                    const uint64_t L = (uint64_t)b->seg1_length[i] + (paired ? b->seg2_length[i] : 0);
+                    if (L > GZT_MAX_LEN && L <= long_bound && L <= GZL_MAX_READ) sl.h_gzidx.push_back((uint32_t)i);
+                }
+                std::sort(sl.h_gzidx.begin() + long_at, sl.h_gzidx.end(), [&](uint32_t x, uint32_t y) {
+                    const uint64_t lx = (uint64_t)b->seg1_length[x] + (paired ? b->seg2_length[x] : 0), ly = (uint64_t)b->seg1_length[y] + (paired ? b->seg2_length[y] : 0);
+                    return lx != ly ? lx > ly : x < y;
+                });
+                rerun_at = sl.h_gzidx.size();
+                for (size_t j = 0; j < long_at; ++j) {
+                    const uint32_t i = sl.h_gzidx[j];
+                    if ((uint64_t)b->seg1_length[i] + (paired ? b->seg2_length[i] : 0) >= GZT_SYMBOL_LIMIT) sl.h_gzidx.push_back(i);
+                }
+            }
             // (on the copy stream: a pageable upload on the tally stream would wait for the previous batch's tally kernels)
-            if ((rc = upload(sl.d_gzidx, sl.h_gzidx.data(), sl.h_gzidx.size() * 4, s->stream0, (size_t)s->cfg.max_reads * 4))) return rc;
+            if ((rc = upload(sl.d_gzidx, sl.h_gzidx.data(), sl.h_gzidx.size() * 4, s->stream0, (size_t)s->cfg.max_reads * 4 * (all_sizes ? 2 : 1)))) return rc;
             HIPCHK(hipEventRecord(sl.bases_up, s->stream0));
             HIPCHK(hipStreamWaitEvent(s->stream3, sl.bases_up, 0));
+            if (all_sizes && rerun_at > long_at) {
+                HIPCHK(hipStreamWaitEvent(s->stream5, sl.bases_up, 0));
+                if ((rc = launch_long(s->stream5, s->d_gzlscratch[0], 0, GZL_ALL, sl.d_gzidx.as<uint32_t>() + long_at, (uint32_t)(rerun_at - long_at)))) return rc;
+                long_launch = true;
+            }
             for (uint32_t c = 1; c < NCLS; ++c)  // longest first: the slow, low-occupancy launches start early
                 if ((rc = launch(sl.d_gzidx.as<uint32_t>() + start[c], start[c + 1] - start[c], cmax[c]))) return rc;
+            if (all_sizes && (rc = launch_long(s->stream3, s->d_gzlscratch[1], 1, GZL_HANDED_BACK, sl.d_gzidx.as<uint32_t>() + rerun_at, (uint32_t)(sl.h_gzidx.size() - rerun_at)))) return rc;
         } else {
             HIPCHK(hipEventRecord(sl.bases_up, s->stream0));
             HIPCHK(hipStreamWaitEvent(s->stream3, sl.bases_up, 0));
             if ((rc = launch(nullptr, (uint32_t)n, bound))) return rc;
         }
+        // where the sizes are formed and downloaded: behind the tallies on stream3, or -- with a long-read launch -- on stream5 behind both,
+        // so that the next batch's tally launches on stream3 do not queue behind this batch's longest read
+        hipStream_t zs = s->stream3;
+        if (long_launch) {
+            HIPCHK(hipEventRecord(sl.gzt_done, s->stream3));
+            HIPCHK(hipStreamWaitEvent(s->stream5, sl.gzt_done, 0));
+            zs = s->stream5;
+        }
         if (sl.gz_output != CHN_GZIP_TALLIES) {  // the sizes from the tallies, one lane per read
             if ((rc = sl.d_gzsize.ensure((size_t)s->cfg.max_reads * 4))) return rc;
             GzSizeArgs gs;
             gs.tallies = sl.d_gzt.as<uint16_t>(); gs.len1 = sl.len1; gs.len2 = sl.len2; gs.n_reads = (uint32_t)n; gs.sizes = sl.d_gzsize.as<uint32_t>();
-            hipLaunchKernelGGL(k_gzip_size, dim3((uint32_t)((n + WAVE - 1) / WAVE)), dim3(WAVE), 0, s->stream3, gs);
+            gs.long_sizes = all_sizes ? sl.d_gzlong.as<uint32_t>() : nullptr;  // k_gzip_long's sizes fill in where the tallies hand a read back
+            hipLaunchKernelGGL(k_gzip_size, dim3((uint32_t)((n + WAVE - 1) / WAVE)), dim3(WAVE), 0, zs, gs);
             HIPCHK(hipGetLastError());
         }
         sl.gz_staged = false;
         if (!b->on_device) {
-            if (sl.gz_output != CHN_GZIP_SIZES) {
+            if (sl.gz_output == CHN_GZIP_TALLIES || sl.gz_output == CHN_GZIP_BOTH) {
                 if ((rc = sl.h_gzt.ensure(n * GZT_WORDS * 2))) return rc;
                 HIPCHK(hipMemcpyAsync(sl.h_gzt.p, sl.d_gzt.p, n * GZT_WORDS * 2, hipMemcpyDeviceToHost, s->stream3));
             }
             if (sl.gz_output != CHN_GZIP_TALLIES) {
                 if ((rc = sl.h_gzsize.ensure(n * 4))) return rc;
-                HIPCHK(hipMemcpyAsync(sl.h_gzsize.p, sl.d_gzsize.p, n * 4, hipMemcpyDeviceToHost, s->stream3));
+                HIPCHK(hipMemcpyAsync(sl.h_gzsize.p, sl.d_gzsize.p, n * 4, hipMemcpyDeviceToHost, zs));
             }
             sl.gz_staged = true;
         }
-        HIPCHK(hipEventRecord(sl.gz_done, s->stream3));
+        HIPCHK(hipEventRecord(sl.gz_done, zs));
     }
 
     dt[2] = dnow();

@@ -15,6 +15,7 @@ struct GzSizeArgs {
     const uint32_t *len1, *len2;
     uint32_t n_reads;
     uint32_t *sizes;          // [n]: gzip member size in bytes, 0 = not tallied on the device (size it on the host)
+    const uint32_t *long_sizes;  // [n] or null: what k_gzip_long found for the reads the tallies hand back (CHN_GZIP_SIZES_ALL)
 };
 
 namespace gzsize_dev {
@@ -150,24 +151,20 @@ __device__ void scan_tree(Work &w, uint16_t *tlen, int max_code) {
         else { max_count = 7; min_count = 4; }
     }
 }
-}  // namespace gzsize_dev
-
-__global__ __launch_bounds__(WAVE) void k_gzip_size(const GzSizeArgs a) {
-    using namespace gzsize_dev;
-    const uint32_t r = blockIdx.x * WAVE + threadIdx.x;
-    if (r >= a.n_reads) return;
-    const uint16_t *t = a.tallies + (size_t)r * GZT_WORDS;
-    if (t[316] != 0) { a.sizes[r] = 0; return; }
-    const uint64_t stored_len = (uint64_t)a.len1[r] + (a.len2 ? a.len2[r] : 0u);
-    Work w;
+// _tr_flush_block for one block of a deflate stream: the trees of the block's frequencies (lf [L_CODES] without END_BLOCK's count,
+// which is set here; df [D_CODES]), the stored / static / dynamic choice, and the block's bits added to `bits`, the running bit count
+// of the stream: a stored block pads its 3-bit header to a byte from there (buf: zlib still holds the block's bytes, `buf != NULL`);
+// `last` closes the stream with bi_windup.
+template <typename T>
+__device__ void flush_block_bits(Work &w, const T *lf, const T *df, uint64_t stored_len, bool buf, bool last, uint64_t &bits) {
     w.opt_len = w.static_len = 0;
     for (int i = 0; i < BL_CODES; ++i) w.blfreq[i] = 0;
     // literal/length tree
-    for (int i = 0; i < L_CODES; ++i) w.freq[i] = t[i];
+    for (int i = 0; i < L_CODES; ++i) w.freq[i] = lf[i];
     w.freq[END_BLOCK] = 1;
     const int max_l = build_tree(w, 0, L_CODES, MAX_BITS, 257, w.llen);
     // distance tree
-    for (int i = 0; i < D_CODES; ++i) w.freq[i] = t[286 + i];
+    for (int i = 0; i < D_CODES; ++i) w.freq[i] = df[i];
     const int max_d = build_tree(w, 1, D_CODES, MAX_BITS, 0, w.dlen);
     // bit-length tree over the two code-length sequences
     scan_tree(w, w.llen, max_l);
@@ -182,10 +179,22 @@ __global__ __launch_bounds__(WAVE) void k_gzip_size(const GzSizeArgs a) {
     uint64_t opt_lenb = (w.opt_len + 3 + 7) >> 3;
     const uint64_t static_lenb = (w.static_len + 3 + 7) >> 3;
     if (static_lenb <= opt_lenb) opt_lenb = static_lenb;
-    uint64_t bits;
-    if (stored_len + 4 <= opt_lenb) bits = 8 + 32 + 8 * stored_len;   // 3 header bits padded to a byte, LEN + NLEN, the bytes
-    else if (static_lenb == opt_lenb) bits = 3 + w.static_len;
-    else bits = 3 + w.opt_len;
-    bits = (bits + 7) & ~7ULL;  // bi_windup
+    if (stored_len + 4 <= opt_lenb && buf) bits = ((bits + 3 + 7) & ~7ULL) + 32 + 8 * stored_len;  // 3 header bits padded to a byte, LEN + NLEN, the bytes
+    else if (static_lenb == opt_lenb) bits += 3 + w.static_len;
+    else bits += 3 + w.opt_len;
+    if (last) bits = (bits + 7) & ~7ULL;  // bi_windup
+}
+}  // namespace gzsize_dev
+
+__global__ __launch_bounds__(WAVE) void k_gzip_size(const GzSizeArgs a) {
+    using namespace gzsize_dev;
+    const uint32_t r = blockIdx.x * WAVE + threadIdx.x;
+    if (r >= a.n_reads) return;
+    const uint16_t *t = a.tallies + (size_t)r * GZT_WORDS;
+    if (t[316] != 0) { a.sizes[r] = a.long_sizes ? a.long_sizes[r] : 0u; return; }
+    const uint64_t stored_len = (uint64_t)a.len1[r] + (a.len2 ? a.len2[r] : 0u);
+    Work w;
+    uint64_t bits = 0;
+    flush_block_bits(w, t, t + 286, stored_len, true, true, bits);
     a.sizes[r] = (uint32_t)(18 + (bits >> 3));
 }

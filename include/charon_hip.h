@@ -192,7 +192,7 @@ typedef struct chn_batch {
     const float *mean_quality;   /* [n] or NULL */
     const float *compression;    /* [n] or NULL */
     /* Deflate tallies for the `compression` column (get_compression_ratio, src/utils.cpp:114-124) ON THE DEVICE: non-zero = the
-     * longest read (both mates together) to handle there, at most CHN_GZIP_MAX_LEN.  For every read the library then runs zlib's
+     * longest read (both mates together) to handle there, at most CHN_GZIP_MAX_LEN (any length with CHN_GZIP_SIZES_ALL).  For every read the library then runs zlib's
      * level-6 deflate_slow as a kernel and returns the literal/length and distance code frequencies of its deflate block
      * (chn_result.gzip_tallies) -- the caller turns them into the exact gzip size with _tr_flush_block's arithmetic (a few
      * microseconds per read; charon_amd/csrc/host/gzip_size.hpp).  With tallies requested `compression` is not known when the
@@ -201,12 +201,21 @@ typedef struct chn_batch {
     uint32_t gzip_tallies;
     /* What comes back for the reads tallied on the device: CHN_GZIP_TALLIES (0) the tallies; CHN_GZIP_SIZES the gzip member
      * SIZES (chn_result.gzip_sizes) -- _tr_flush_block's tree arithmetic then runs on the device too (k_gzip_size) and only
-     * four bytes per read are downloaded; CHN_GZIP_BOTH both. */
+     * four bytes per read are downloaded; CHN_GZIP_BOTH both.
+     * CHN_GZIP_SIZES_ALL: the SIZE of EVERY read of 1 .. gzip_tallies letters (both mates together), whatever its length and
+     * however many deflate blocks zlib writes for it (host batches; a device-resident batch is refused with CHN_E_INVALID for now); gzip_tallies may exceed CHN_GZIP_MAX_LEN
+     * there (CHN_GZIP_ANY_LEN: no bound).  Reads beyond CHN_GZIP_MAX_LEN, and reads the tallies hand back for a second deflate
+     * block, run through a deflate pass with zlib's window slide and block flushes (k_gzip_long, one wavefront per read, longest
+     * first on a stream of its own); a size of 0 then only means "longer than gzip_tallies" (or an empty read).  Tallies cannot
+     * describe a read of several blocks: this mode returns sizes only.  Its scratch (some 256 KiB per wavefront the device holds
+     * at once) is allocated with the first such batch; CHN_E_NOMEM if it does not fit. */
     uint32_t gzip_output;
 } chn_batch;
 #define CHN_GZIP_TALLIES 0u
 #define CHN_GZIP_SIZES 1u
 #define CHN_GZIP_BOTH 2u
+#define CHN_GZIP_SIZES_ALL 3u
+#define CHN_GZIP_ANY_LEN 0xFFFFFFFFu  /* chn_batch.gzip_tallies under CHN_GZIP_SIZES_ALL: no length bound */
 #define CHN_GZIP_MAX_LEN 61440u  /* one wavefront holds the whole read in LDS; short reads run many wavefronts per CU, a 60 kb read one */
 #define CHN_GZIP_TALLY_WORDS 320u /* per read: [0,286) literal/length code frequencies, [286,316) distance code frequencies,
                                    * [316] status: 0 = tallies valid, non-zero = not handled on the device (longer than asked for,
@@ -236,7 +245,8 @@ typedef struct chn_result {
     uint8_t *flags;            /* [n] */
     uint16_t *gzip_tallies;    /* [n][CHN_GZIP_TALLY_WORDS] when the batch asked for them (may be NULL otherwise) */
     uint32_t *gzip_sizes;      /* [n] bytes of the gzip member (get_compression_ratio's numerator) when the batch asked for sizes;
-                                * 0 = not handled on the device (too long, more than one deflate block): size it on the host */
+                                * 0 = not handled on the device (too long, more than one deflate block): size it on the host
+                                * (CHN_GZIP_SIZES_ALL: 0 only for reads longer than gzip_tallies) */
 } chn_result;
 
 /* Up to THREE batches may be in flight per stream.  Two (submit, submit, wait, submit, wait, ...) let batch i's count and
