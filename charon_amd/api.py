@@ -59,6 +59,20 @@ class Result(C.Structure):
                 ("flags", C.c_void_p), ("gzip_tallies", C.c_void_p), ("gzip_sizes", C.c_void_p)]
 
 
+TEXT_DNA5_RANKS = 1          # chn_text_batch.flags: the text holds seqan3 dna5 ranks (0 A, 1 C, 2 G, 3 N, 4 T), not letters
+
+
+class TextBatch(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_reads", C.c_uint64), ("text", C.c_void_p),
+                ("text_bytes", C.c_uint64), ("seq1_offset", C.c_void_p), ("seq1_length", C.c_void_p), ("qual1_offset", C.c_void_p),
+                ("qual1_length", C.c_void_p), ("seq2_offset", C.c_void_p), ("seq2_length", C.c_void_p), ("qual2_offset", C.c_void_p),
+                ("qual2_length", C.c_void_p), ("compression", C.c_void_p), ("gzip_tallies", C.c_uint32), ("gzip_output", C.c_uint32)]
+
+
+class TextResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("has_n", C.c_uint32), ("n_bases", C.c_uint64), ("mean_quality", C.c_void_p)]
+
+
 class SynthReadsOut(C.Structure):
     _fields_ = [("bases2", C.c_void_p), ("seg1_offset", C.c_void_p), ("seg1_length", C.c_void_p), ("mean_quality", C.c_void_p),
                 ("compression", C.c_void_p), ("n_bases", C.c_uint64)]
@@ -70,7 +84,7 @@ EXPORTS = ["chn_index_create", "chn_index_upload_rows", "chn_index_device_words"
            "chn_model_set", "chn_batch_submit", "chn_batch_wait", "chn_stream_sync", "chn_classify_counts", "chn_classify_counts_raw", "chn_stream_profile",
            "chn_stream_last_batch_bytes", "chn_synth_genomes", "chn_synth_fill_index", "chn_synth_plant", "chn_synth_reads",
            "chn_device_free", "chn_device_download", "chn_device_malloc", "chn_device_upload", "chn_host_alloc", "chn_host_free", "chn_shard_minimise",
-           "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_last_error", "chn_version"]
+           "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_text_submit", "chn_text_wait", "chn_text_pack", "chn_last_error", "chn_version"]
 
 _L.chn_last_error.restype = C.c_char_p
 _L.chn_version.restype = C.c_char_p
@@ -118,6 +132,9 @@ _L.chn_index_bin_popcounts.argtypes = [C.c_void_p, C.c_void_p]
 _L.chn_index_replicate.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
 _L.chn_device_count.argtypes = [C.POINTER(C.c_int)]
 _L.chn_device_download.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64]
+_L.chn_text_submit.argtypes = [C.c_void_p, C.POINTER(TextBatch)]
+_L.chn_text_wait.argtypes = [C.c_void_p, C.POINTER(Result), C.POINTER(TextResult)]
+_L.chn_text_pack.argtypes = [C.c_void_p, C.POINTER(TextBatch)] + [C.c_void_p] * 5 + [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
 
 
 class ChnError(RuntimeError):
@@ -394,7 +411,61 @@ class Stream:
         _chk(_L.chn_batch_submit(self.h, C.byref(b)))
         self._fifo.append((n_reads, None))
 
-    def wait_host(self):
+    # ---- text batches (see include/charon_hip.h) ----
+    def _text_batch(self, tb, compression=None, gzip_tallies=0, gzip_output=0):
+        """tb: dict from charon_amd.pack.text_batch (text may be any uint8 array, e.g. a pinned_array)"""
+        t = TextBatch()
+        n = len(tb["seq1_length"])
+        t.struct_size, t.flags, t.n_reads = C.sizeof(TextBatch), tb.get("flags", 0), n
+        keep = []
+
+        def ptr(a, dt):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dt)
+            keep.append(a)
+            return a.ctypes.data
+
+        text = tb["text"]
+        t.text, t.text_bytes = ptr(text, np.uint8) if len(text) else None, tb.get("text_bytes", len(text))
+        for k, dt in (("seq1_offset", np.uint64), ("seq1_length", np.uint32), ("qual1_offset", np.uint64), ("qual1_length", np.uint32),
+                      ("seq2_offset", np.uint64), ("seq2_length", np.uint32), ("qual2_offset", np.uint64), ("qual2_length", np.uint32)):
+            setattr(t, k, ptr(tb.get(k), dt))
+        t.compression = ptr(compression, np.float32)
+        t.gzip_tallies, t.gzip_output = gzip_tallies, gzip_output
+        return t, keep, n
+
+    def submit_text(self, tb, compression=None, gzip_tallies=0, gzip_output=0):
+        """chn_text_submit: the text and the descriptor arrays may be reused as soon as this returns"""
+        t, keep, n = self._text_batch(tb, compression, gzip_tallies, gzip_output)
+        _chk(_L.chn_text_submit(self.h, C.byref(t)))
+        self._fifo.append((n, None, gzip_tallies, gzip_output))
+
+    def wait_text(self):
+        """chn_text_wait: the dict of wait_host plus mean_quality, has_n, n_bases"""
+        n = self._fifo[0][0]
+        mq = np.zeros(n, np.float32)
+        tr = TextResult(C.sizeof(TextResult), 0, 0, mq.ctypes.data)
+        out = self.wait_host(tr)
+        out["mean_quality"], out["has_n"], out["n_bases"] = mq, int(tr.has_n), int(tr.n_bases)
+        return out
+
+    def text_pack(self, tb):
+        """chn_text_pack: the packed form of a text batch as the dict pack.pack_reads returns (nmask always an array) plus
+        mean_quality and has_n"""
+        t, keep, n = self._text_batch(tb)
+        nb, hn = C.c_uint64(), C.c_uint32()
+        _chk(_L.chn_text_pack(self.h, C.byref(t), None, None, None, None, None, C.byref(nb), C.byref(hn)))  # layout only: sizes the arrays
+        paired = tb.get("seq2_offset") is not None
+        out = dict(bases2=np.zeros(nb.value // 16, np.uint32), nmask=np.zeros(nb.value // 32, np.uint32), seg1_offset=np.zeros(n, np.uint64),
+                   seg1_length=np.array(tb["seq1_length"], np.uint32), seg2_offset=np.zeros(n, np.uint64) if paired else None,
+                   seg2_length=np.array(tb["seq2_length"], np.uint32) if paired else None, mean_quality=np.zeros(n, np.float32))
+        _chk(_L.chn_text_pack(self.h, C.byref(t), out["bases2"].ctypes.data, out["nmask"].ctypes.data, out["seg1_offset"].ctypes.data,
+                              out["seg2_offset"].ctypes.data if paired else None, out["mean_quality"].ctypes.data, C.byref(nb), C.byref(hn)))
+        out["n_bases"], out["has_n"] = int(nb.value), int(hn.value)
+        return out
+
+    def wait_host(self, text_result=None):
         n, Cn = self._fifo[0][0], self.C
         out = dict(num_hashes=np.zeros(n, np.uint32), counts=np.zeros((n, Cn), np.uint32), unique=np.zeros((n, Cn), np.uint32),
                    probs=np.zeros((n, Cn), np.float64), call=np.zeros(n, np.uint8), conf=np.zeros(n, np.uint8),
@@ -409,7 +480,10 @@ class Stream:
                    out["probs"].ctypes.data, out["call"].ctypes.data, out["conf"].ctypes.data, out["flags"].ctypes.data,
                    out["gzip_tallies"].ctypes.data if "gzip_tallies" in out else None,
                    out["gzip_sizes"].ctypes.data if "gzip_sizes" in out else None)
-        _chk(_L.chn_batch_wait(self.h, C.byref(r)))
+        if text_result is not None:
+            _chk(_L.chn_text_wait(self.h, C.byref(r), C.byref(text_result)))
+        else:
+            _chk(_L.chn_batch_wait(self.h, C.byref(r)))
         self._fifo.pop(0)
         return out
 

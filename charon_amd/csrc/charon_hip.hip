@@ -3,6 +3,8 @@
 //
 // Kernel chain per batch (main stream: minimise+probe; side stream: counts, model+call; copy stream: uploads + ordering; a stream for the
 // long reads' launch; up to three batches in flight, no host round trip):
+//   k_text_pack (+ k_text_mq) text batches only (chn_text_submit): one lane per 16 bases turns the uploaded letters into the 2-bit codes and the N mask,
+//                             sums the phred characters per read; on the copy stream behind the text's upload, waited for by the host (is there an N?)
 //   k_len_hist/scatter        order reads by length class, longest first, so that a wavefront holds reads of similar length; publishes how many
 //                             reads are "long" (32 768 bases and more)
 //   k_minimise_probe          ONE LANE PER READ: rolls the canonical base-5 k-mer hash (seqan3 minimiser_hash semantics,
@@ -55,10 +57,12 @@
 #include "parts/gzip_tally.inc"
 #include "parts/gzip_size_dev.inc"
 #include "parts/gzip_tally_long.inc"
+#include "parts/text_pack.inc"
 #include "parts/ef_decode.inc"
 #include "parts/synth_kernels.inc"
 #include "parts/abi_index_model.inc"
 #include "parts/abi_stream_batch.inc"
 #include "parts/abi_shard_wait.inc"
+#include "parts/abi_text_batch.inc"
 #include "parts/abi_shardx.inc"
 #include "parts/abi_synth_memory.inc"

@@ -331,6 +331,12 @@ int main(int argc, char **argv) {
         const std::string err = std::getenv("CHARON_DEVICE") ? std::string("cannot be set together with CHARON_DEVICE") : parse_device_list(e, opt);
         if (!err.empty()) { std::cerr << "charon: CHARON_DEVICES: " << err << std::endl; return 1; }
     }
+    if (const char *e = std::getenv("CHARON_TEXT_BATCHES")) {
+        // checked before the index file is opened and before any HIP call
+        const std::string v(e);
+        if (v != "0" && v != "1") { std::cerr << "charon: CHARON_TEXT_BATCHES: '" << v << "' is neither 0 nor 1" << std::endl; return 1; }
+        opt.text_batches = v == "1";
+    }
     try {
         dehost_main(opt);  // the reference's subcommand callback discards dehost_main's return value (src/dehost_main.cpp:311)
         return 0;

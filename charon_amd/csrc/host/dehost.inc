@@ -83,6 +83,15 @@ struct HostBatch {
     std::vector<float> mq, comp;
     bool any_n = false;
     uint64_t n_bases = 0;
+    // CHARON_TEXT_BATCHES=1: the batch as chn_text_batch describes it -- `text` is the stretch of the block's slab that holds the kept
+    // records (single-end input that was decoded into a slab: nothing is copied) or `tcopy`, a page-locked copy of the letters and
+    // qualities alone (mapped files, whose pages cannot be page-locked, and pairs, whose mates live in two slabs)
+    const uint8_t *text = nullptr;
+    uint64_t text_bytes = 0;
+    std::vector<uint64_t> so1, qo1, so2, qo2;
+    std::vector<uint32_t> ql1, ql2;
+    bool text_quals = false, text_from_slab = false;
+    WordBuf tcopy;
     ~HostBatch() {
         g_dead_ranges.add(blk1.map_token, blk1.map_begin, blk1.map_len); g_dead_ranges.add(blk2.map_token, blk2.map_begin, blk2.map_len);
         g_slab_pool.give(blk1.buf); g_slab_pool.give(blk2.buf);
@@ -180,12 +189,72 @@ struct HostBatch {
         for (uint32_t j = 0; j < n; ++j) sum += (int)q[j] - 33;
         return sum;
     }
+    // the kept records as (offset, length) pairs into one buffer
+    void describe_text(bool paired, const Slab *slab, int copy_threads) {
+        const size_t n = keep.size();
+        so1.assign(n, 0); qo1.assign(n, 0); ql1.assign(n, 0);
+        if (paired) { so2.assign(n, 0); qo2.assign(n, 0); ql2.assign(n, 0); } else { so2.clear(); qo2.clear(); ql2.clear(); }
+        text_quals = false;
+        for (size_t i = 0; i < n && !text_quals; ++i) text_quals = blk1.recs[keep[i]].qual_len != 0 || (paired && blk2.recs[keep[i]].qual_len != 0);
+        text = nullptr; text_bytes = 0; text_from_slab = false;
+        if (n == 0) return;
+        if (!paired && slab && !slab->empty()) {
+            // the slab as it stands: from the first kept stretch to the end of the last (ids and `+` lines ride along)
+            const char *lo = slab->data() + slab->size(), *hi = slab->data();
+            bool inside = true;
+            for (size_t i = 0; i < n; ++i) {
+                const RecView &a = blk1.recs[keep[i]];
+                lo = std::min(lo, a.seq); hi = std::max(hi, a.seq + a.seq_len);
+                if (a.qual_len) { lo = std::min(lo, a.qual); hi = std::max(hi, a.qual + a.qual_len); }
+            }
+            inside = lo >= slab->data() && hi <= slab->data() + slab->size() && lo <= hi;
+            if (inside) {
+                for (size_t i = 0; i < n; ++i) {
+                    const RecView &a = blk1.recs[keep[i]];
+                    so1[i] = (uint64_t)(a.seq - lo);
+                    if (a.qual_len) { qo1[i] = (uint64_t)(a.qual - lo); ql1[i] = a.qual_len; }
+                }
+                text = reinterpret_cast<const uint8_t *>(lo); text_bytes = (uint64_t)(hi - lo); text_from_slab = true;
+                return;
+            }
+        }
+        // a copy of the letters and qualities alone: per read sequence, quality, mate sequence, mate quality
+        uint64_t cur = 0;
+        for (size_t i = 0; i < n; ++i) {
+            const RecView &a = blk1.recs[keep[i]];
+            so1[i] = cur; cur += a.seq_len;
+            qo1[i] = cur; ql1[i] = a.qual_len; cur += a.qual_len;
+            if (paired) {
+                const RecView &b = blk2.recs[keep[i]];
+                so2[i] = cur; cur += b.seq_len;
+                qo2[i] = cur; ql2[i] = b.qual_len; cur += b.qual_len;
+            }
+        }
+        tcopy.want_pinned = true;
+        tcopy.assign_raw((size_t)((cur + 3) / 4) + 1);
+        char *dst = reinterpret_cast<char *>(tcopy.data());
+#pragma omp parallel for num_threads(copy_threads) schedule(dynamic, 64)
+        for (long i = 0; i < (long)n; ++i) {
+            const RecView &a = blk1.recs[keep[i]];
+            std::memcpy(dst + so1[i], a.seq, a.seq_len);
+            if (a.qual_len) std::memcpy(dst + qo1[i], a.qual, a.qual_len);
+            if (paired) {
+                const RecView &b = blk2.recs[keep[i]];
+                std::memcpy(dst + so2[i], b.seq, b.seq_len);
+                if (b.qual_len) std::memcpy(dst + qo2[i], b.qual, b.qual_len);
+            }
+        }
+        text = reinterpret_cast<const uint8_t *>(dst); text_bytes = cur;
+    }
     // layout + parallel packing, mean quality and gzip ratio of the records in blk1 (/blk2)
     // gz_gpu_max > 0: reads of at most that many letters get their gzip size from the device (finish_compression); gz_route_long: and
     // the reads beyond CHN_GZIP_MAX_LEN that gzip_long_device_limit gives the device in this batch
     std::vector<uint8_t> gz_pending;   // per kept read: its compression ratio is still to come
     uint32_t gz_gpu_len = 0;           // longest such read (what chn_batch.gzip_tallies asks for)
-    void pack(bool paired, int threads, bool skip_compression, uint32_t gz_gpu_max = 0, bool gz_route_long = false) {
+    // as_text: lay the batch out and form the host-side gzip ratios as ever, but neither pack the letters nor sum the qualities -- the
+    // device does both (chn_text_submit); `slab`: the slab the records are views into, if they all are
+    void pack(bool paired, int threads, bool skip_compression, uint32_t gz_gpu_max = 0, bool gz_route_long = false, bool as_text = false,
+              const Slab *slab = nullptr) {
         const size_t nrec = blk1.recs.size();
         keep.clear();
         for (size_t i = 0; i < nrec; ++i) {
@@ -204,7 +273,8 @@ struct HostBatch {
             if (paired) { off2[i] = cur; len2[i] = blk2.recs[k].seq_len; cur += pad64(len2[i]); }
         }
         n_bases = std::max<uint64_t>(cur, 64);
-        if (cur == 0) { bases.assign_zero(n_bases / 16); nmask.assign_zero(n_bases / 32); }
+        if (as_text) {}
+        else if (cur == 0) { bases.assign_zero(n_bases / 16); nmask.assign_zero(n_bases / 32); }
         else { bases.assign_raw(n_bases / 16); nmask.assign_raw(n_bases / 32); }
         gz_pending.assign(n, 0); gz_gpu_len = 0;
         // (only where every read up to CHN_GZIP_MAX_LEN goes to the device already: the device then sizes every read up to the limit)
@@ -228,11 +298,12 @@ struct HostBatch {
         // phred values), so it runs on the reader's threads -- `-t`, but never fewer than four -- like the decompression and the record splitting.
         // With the default `-t 1` the main thread used to pack for 3.6 of a 4.8 s read loop (4 M reads of 5 kb).
         const int conv_threads = std::max(threads, g_reader_threads);
-#pragma omp parallel num_threads(conv_threads)
+        if (as_text) describe_text(paired, slab, conv_threads);
+#pragma omp parallel num_threads(conv_threads) if (!as_text)
         {
             bool my_n = false, my_bad = false;
 #pragma omp for schedule(dynamic, 16)
-            for (long i = 0; i < (long)n; ++i) {
+            for (long i = 0; i < (long)(as_text ? 0 : n); ++i) {
                 const RecView &a = blk1.recs[keep[i]];
                 const RecView *b = paired ? &blk2.recs[keep[i]] : nullptr;
                 if (!put(a, off1[i], my_n)) my_bad = true;
@@ -263,6 +334,9 @@ struct HostBatch {
         if (bad) throw std::runtime_error("parse error: illegal character in a sequence (only IUPAC nucleotide letters are accepted)");
     }
 };
+
+// a fault of the input (as opposed to one of the device or the program): reported without naming the replica that met it
+struct InputError : std::runtime_error { using std::runtime_error::runtime_error; };
 
 // bounded hand-over of parsed blocks from the reader thread
 struct BlockQueue {
@@ -365,6 +439,11 @@ int dehost_main(DehostArguments &opt) {
         g_log.warn(std::string("gzip size emulator disagrees with the linked zlib ") + zlibVersion() + "; using zlib for the compression column");
     }
 
+    // CHARON_TEXT_BATCHES=1: slabs are page-locked from the first one on (the reader thread below allocates them); those left in the pool
+    // are released when this function is left, after everything that hands slabs back, while the HIP runtime is certainly still up
+    g_pin_slabs = opt.text_batches;
+    struct SlabPoolDrain { ~SlabPoolDrain() { std::lock_guard<std::mutex> lk(g_slab_pool.m); g_slab_pool.v.clear(); } } slab_pool_drain;
+    if (opt.text_batches) g_log.info("CHARON_TEXT_BATCHES=1: reads go to the device as text (letters -> codes and mean quality on the GPU)");
     // reader thread: parses whole-record blocks while the previous batch is packed / compressed / classified / printed.  It starts
     // before the device is touched, so the first block is parsed while the HIP runtime initialises and the index is decoded.
     BlockQueue queue;
@@ -598,6 +677,7 @@ int dehost_main(DehostArguments &opt) {
         std::vector<uint32_t> gz_sizes;
     };
     uint64_t gz_on_device = 0, gz_long_on_device = 0;
+    std::atomic<uint64_t> text_slab_batches{0}, text_copy_batches{0};  // CHARON_TEXT_BATCHES=1: batches sent as their slab / as a page-locked copy
     // CHARON_TIMING=1: wall seconds per phase of the main thread, to the log (where does the CLI's time go?)
     const bool timing = std::getenv("CHARON_TIMING") != nullptr;
     double t_pop = 0, t_pack = 0, t_submit = 0, t_wait = 0, t_gz = 0, t_rows = 0;
@@ -639,7 +719,15 @@ int dehost_main(DehostArguments &opt) {
         const bool tallied = sub.gz_gpu_len != 0;
         if (tallied) { gz_sizes.resize(n); rs.gzip_sizes = gz_sizes.data(); }
         double tt = now();
-        CHN_CHECK(chn_batch_wait(st, &rs));
+        if (opt.text_batches) {  // the mean-quality column comes back with the results
+            chn_text_result tr;
+            std::memset(&tr, 0, sizeof tr);
+            tr.struct_size = sizeof tr; tr.mean_quality = sub.mq.data();
+            CHN_CHECK(chn_text_wait(st, &rs, &tr));
+            sub.any_n = tr.has_n != 0;
+        } else {
+            CHN_CHECK(chn_batch_wait(st, &rs));
+        }
         acc_wait += now() - tt;
     };
     auto finish_rows = [&](Flight &fl) {
@@ -844,6 +932,35 @@ int dehost_main(DehostArguments &opt) {
         bt.gzip_output = sub.gz_gpu_len > CHN_GZIP_MAX_LEN ? CHN_GZIP_SIZES_ALL : CHN_GZIP_SIZES;
     };
 
+    // a packed batch through chn_batch_submit, or (CHARON_TEXT_BATCHES=1) the text itself through chn_text_submit
+    auto submit_flight = [&](chn_stream *st, Flight &fl) {
+        if (!opt.text_batches) {
+            chn_batch bt;
+            fill_batch(fl, bt);
+            CHN_CHECK(chn_batch_submit(st, &bt));
+            return;
+        }
+        HostBatch &sub = fl.sub;
+        chn_text_batch tb;
+        std::memset(&tb, 0, sizeof tb);
+        tb.struct_size = sizeof tb; tb.n_reads = sub.keep.size(); tb.text = sub.text; tb.text_bytes = sub.text_bytes;
+        tb.seq1_offset = sub.so1.data(); tb.seq1_length = sub.len1.data();
+        if (sub.text_quals) { tb.qual1_offset = sub.qo1.data(); tb.qual1_length = sub.ql1.data(); }
+        if (opt.is_paired) {
+            tb.seq2_offset = sub.so2.data(); tb.seq2_length = sub.len2.data();
+            if (sub.text_quals) { tb.qual2_offset = sub.qo2.data(); tb.qual2_length = sub.ql2.data(); }
+        }
+        tb.compression = sub.comp.data();
+        tb.gzip_tallies = sub.gz_gpu_len;
+        tb.gzip_output = sub.gz_gpu_len > CHN_GZIP_MAX_LEN ? CHN_GZIP_SIZES_ALL : CHN_GZIP_SIZES;
+        (sub.text_from_slab ? text_slab_batches : text_copy_batches) += 1;
+        const int rc = chn_text_submit(st, &tb);
+        // (the device met a byte that is no IUPAC nucleotide letter: what HostBatch::pack reports for a packed batch)
+        if (rc == CHN_E_INVALID && std::strstr(chn_last_error(), "illegal byte"))
+            throw InputError("parse error: illegal character in a sequence (only IUPAC nucleotide letters are accepted)");
+        if (rc != CHN_OK) throw std::runtime_error(std::string("chn_text_submit failed: ") + chn_last_error());
+    };
+
     // Replica mode, once the models are final (before that every batch runs on replica 0, retired one by one: the models may change with
     // every read).  The main thread reads, splits and packs as before and deals the packed batches round-robin, numbered in input order;
     // each replica's thread submits them on its own stream and waits for them, and the ordered merge hands them back to the row writer
@@ -894,12 +1011,10 @@ int dehost_main(DehostArguments &opt) {
                 if (f) {
                     if (f->version != rp.model_version)
                         throw std::runtime_error("batch packed for model version " + std::to_string(f->version) + ", stream holds " + std::to_string(rp.model_version));
-                    chn_batch bt;
-                    fill_batch(*f, bt);
                     const double tk = now();
-                    CHN_CHECK(chn_batch_submit(rp.stream, &bt));
+                    submit_flight(rp.stream, *f);
                     rp.t_submit += now() - tk;
-                    rp.batches += 1; rp.reads += bt.n_reads;
+                    rp.batches += 1; rp.reads += f->sub.keep.size();
                     flying.push_back(std::move(f));
                     continue;
                 }
@@ -909,6 +1024,8 @@ int dehost_main(DehostArguments &opt) {
                 const uint64_t seq = g->seq;
                 merge.put(seq, std::move(g));
             }
+        } catch (InputError &e) {
+            merge.fail(e.what());  // the input's fault, not the replica's: the message a run without replicas gives
         } catch (std::exception &e) {
             merge.fail("replica " + std::to_string(rp.index) + " (device " + std::to_string(rp.device) + "): " + e.what());
         }
@@ -1006,7 +1123,8 @@ int dehost_main(DehostArguments &opt) {
                 if (opt.is_paired) sub.blk2.recs.assign(hb.blk2.recs.begin() + (long)begin, hb.blk2.recs.begin() + (long)endi);
                 begin = endi;
                 double tk = now();
-                sub.pack(opt.is_paired, opt.threads, skip_compression, gz_gpu_max, gz_route_long);  // batch i+1 is packed while the GPU works on batch i
+                sub.pack(opt.is_paired, opt.threads, skip_compression, gz_gpu_max, gz_route_long, opt.text_batches,
+                         (!opt.is_paired && !hb.blk1.map_begin) ? &hb.blk1.buf : nullptr);  // batch i+1 is packed while the GPU works on batch i
                 t_pack += now() - tk;
                 const size_t n = sub.keep.size();
                 if (n == 0) continue;
@@ -1021,10 +1139,8 @@ int dehost_main(DehostArguments &opt) {
                 // a model still in training may change with every read added below: every batch is retired before the next is submitted
                 result.ensure_device_model();
                 fl->version = result.current_model_version();
-                chn_batch bt;
-                fill_batch(*fl, bt);
                 tk = now();
-                CHN_CHECK(chn_batch_submit(stream, &bt));
+                submit_flight(stream, *fl);
                 t_submit += now() - tk;
                 reps[0]->batches += 1; reps[0]->reads += n;
                 retire(fl);
@@ -1074,6 +1190,9 @@ int dehost_main(DehostArguments &opt) {
             std::fprintf(stderr, "charon: %s\n", tb);
         }
     }
+    if (opt.text_batches)
+        g_log.info("text batches: " + std::to_string(text_slab_batches.load()) + " sent as the block's slab, " + std::to_string(text_copy_batches.load()) +
+                   " as a page-locked copy of letters and qualities");
     if (gz_gpu_max) g_log.info("gzip column: " + std::to_string(gz_on_device) + " reads sized from device deflate tallies (the rest on the host)");
     if (gz_gpu_max) g_log.info("gzip column: " + std::to_string(gz_long_on_device) + " reads beyond " + std::to_string(CHN_GZIP_MAX_LEN) + " letters sized by the device's long-read deflate pass");
     result.print_summary();

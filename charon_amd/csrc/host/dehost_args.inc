@@ -26,6 +26,8 @@ struct DehostArguments {
     // CHARON_DEVICES: one index replica (own copy of the index, own chn_stream, own driver thread) per entry; empty = the single device above
     std::vector<int> devices;
     bool devices_all = false;  // CHARON_DEVICES=all: every visible device (resolved once the HIP runtime is up)
+    // CHARON_TEXT_BATCHES=1: reads go to the device as text (chn_text_submit): letters -> codes and the mean quality are formed there
+    bool text_batches = false;
     uint8_t min_hits = 0;  // StatsModel::min_hits_ is uninitialised in the reference; CHARON_MIN_HITS overrides
     std::map<uint8_t, std::vector<std::string>> extract_category_to_file;  // include/dehost_arguments.hpp:20
     // `charon classify` (src/classify_main.cpp:24-119, include/classify_arguments.hpp): the same loop with ReadEntry::classify

@@ -613,8 +613,8 @@ struct Deflater {
         const size_t n = (size_t)a.seq_len + (b ? b->seq_len : 0);
         up.clear();
         up.reserve(n + gzsize::GzipSizer::PAD);
-        for (uint32_t i = 0; i < a.seq_len; ++i) up.push_back("ACGTN"[g_codes.t[(unsigned char)a.seq[i]] & 7]);
-        if (b) for (uint32_t i = 0; i < b->seq_len; ++i) up.push_back("ACGTN"[g_codes.t[(unsigned char)b->seq[i]] & 7]);
+        for (uint32_t i = 0; i < a.seq_len; ++i) up.push_back("ACGTNNNN"[g_codes.t[(unsigned char)a.seq[i]] & 7]);
+        if (b) for (uint32_t i = 0; i < b->seq_len; ++i) up.push_back("ACGTNNNN"[g_codes.t[(unsigned char)b->seq[i]] & 7]);
         up.append(gzsize::GzipSizer::PAD, '\0');
     }
     float ratio(const RecView &a, const RecView *b) {

@@ -24,10 +24,39 @@
 
 // Slabs of inflated text: byte vectors whose resize() does not zero-fill (every byte is written by an inflate right afterwards;
 // zero-filling 256 MB per block on the reader thread is time the other threads wait for).
+// CHARON_TEXT_BATCHES=1: slabs of a megabyte and more are page-locked (chn_host_alloc), so that the upload of a batch's text straight out
+// of its slab is an asynchronous DMA; g_pinned_slabs remembers which allocations are, for deallocate.  Off: plain operator new as before.
+bool g_pin_slabs = false;
+struct PinnedSlabs {
+    std::mutex m;
+    std::unordered_set<void *> v;
+    void *take(size_t bytes) {
+        void *p = nullptr;
+        if (chn_host_alloc(bytes, &p) != CHN_OK || !p) return nullptr;
+        std::lock_guard<std::mutex> lk(m);
+        v.insert(p);
+        return p;
+    }
+    bool give(void *p) {
+        { std::lock_guard<std::mutex> lk(m); if (!v.erase(p)) return false; }
+        (void)chn_host_free(p);
+        return true;
+    }
+};
+PinnedSlabs g_pinned_slabs;
 template <class T> struct NoInitAlloc : std::allocator<T> {
     template <class U> struct rebind { typedef NoInitAlloc<U> other; };
     NoInitAlloc() = default;
     template <class U> NoInitAlloc(const NoInitAlloc<U> &) {}
+    T *allocate(size_t n) {
+        if (g_pin_slabs && n * sizeof(T) >= ((size_t)1 << 20))
+            if (void *p = g_pinned_slabs.take(n * sizeof(T))) return static_cast<T *>(p);
+        return std::allocator<T>::allocate(n);
+    }
+    void deallocate(T *p, size_t n) {
+        if (n * sizeof(T) >= ((size_t)1 << 20) && g_pinned_slabs.give(p)) return;
+        std::allocator<T>::deallocate(p, n);
+    }
     template <class U> void construct(U *p) noexcept { ::new (static_cast<void *>(p)) U; }  // default-initialise: nothing for char
     template <class U, class... A> void construct(U *p, A &&...a) { ::new (static_cast<void *>(p)) U(std::forward<A>(a)...); }
 };

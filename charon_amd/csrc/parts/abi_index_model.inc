@@ -117,6 +117,16 @@ struct Slot {
     LogBuf lb;                            // this batch's row log
     DevBuf d_len1, d_len2, d_mq, d_comp;  // staging of the small per-read arrays of host batches (read by k_model_call)
     DevBuf d_bases, d_nmask, d_off1, d_off2;  // staging of the large arrays: per slot, so batch i+1 uploads while batch i computes
+    // text batches (abi_text_batch.inc; allocated with the first one): the uploaded text with 64 bytes of padding at both ends, the
+    // byte offsets and quality lengths of its reads, k_text_pack's three words; page-locked staging of those words and of the
+    // mean-quality column
+    DevBuf d_text, d_tdesc, d_tctl;
+    PinBuf h_text;
+    std::vector<uint64_t> h_toff1, h_toff2;  // the segment layout chn_text_submit computed
+    bool is_text = false;
+    hipEvent_t tev[4] = {nullptr, nullptr, nullptr, nullptr};  // profiling streams: text upload 0-1, k_text_pack + k_text_mq 2-3
+    uint32_t text_has_n = 0;
+    uint64_t text_n_bases = 0;
     hipEvent_t uploaded = nullptr;
     const uint32_t *len1 = nullptr, *len2 = nullptr;
     const float *mq = nullptr, *comp = nullptr;
@@ -172,6 +182,8 @@ struct chn_stream {
     double prof_ms[4] = {0, 0, 0, 0};
     uint64_t prof_n[4] = {0, 0, 0, 0};
     uint64_t last_bytes = 0, last_min = 0, last_fetches = 0;
+    double text_ms[2] = {0, 0};  // text batches of a profiling stream: upload of the text, pack kernels
+    uint64_t text_n = 0;
 };
 
 static uint64_t pow5(unsigned e) { uint64_t p = 1; while (e--) p *= 5; return p; }

@@ -106,6 +106,8 @@ extern "C" int chn_stream_destroy(chn_stream *s) {
         if (sl.gz_done) (void)hipEventDestroy(sl.gz_done);
         if (sl.gzt_done) (void)hipEventDestroy(sl.gzt_done);
         sl.h_res.release(); sl.h_gzt.release(); sl.h_gzsize.release(); sl.d_gzsize.release();
+        sl.h_text.release(); sl.d_text.release(); sl.d_tdesc.release(); sl.d_tctl.release();
+        for (int i = 0; i < 4; ++i) if (sl.tev[i]) (void)hipEventDestroy(sl.tev[i]);
         s->h_block.release();
         DevBuf *bufs[] = {&sl.d_num_hashes, &sl.d_counts, &sl.d_unique, &sl.d_prob, &sl.d_call, &sl.d_conf, &sl.d_flags, &sl.d_ctl, &sl.d_order, &sl.d_gzt, &sl.d_gzidx, &sl.d_gzctr, &sl.d_gzlong,
                           &sl.d_len1, &sl.d_len2, &sl.d_mq, &sl.d_comp, &sl.d_bases, &sl.d_nmask, &sl.d_off1, &sl.d_off2};
@@ -283,7 +285,9 @@ static hipError_t launch_k1_mode(int mode, uint32_t W, const K1Args &a, size_t l
 // worst-case layout on s->big) or LIST_SPARSE (sparse row-sharded mode: density-sized regions claimed from the cursor on s->shx);
 // 0: the whole chain
 enum { LIST_NONE = 0, LIST_DENSE = 1, LIST_SPARSE = 2 };
-static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind) {
+// born_on_device: a text batch (abi_text_batch.inc) -- a host batch whose bases, N mask, layout and mean quality k_text_pack has
+// already written into the slot's buffers (b->bases2 / nmask only say which of them exist, b->mean_quality is the host copy)
+static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind, bool born_on_device = false) {
     const bool list_mode = list_kind != LIST_NONE;
     if (!s || !b || b->struct_size != sizeof(chn_batch)) return fail(CHN_E_INVALID, "chn_batch_submit: bad argument");
     if (!list_mode && (s->idx->d.row_begin != 0 || s->idx->d.row_end != s->idx->d.bin_size))
@@ -306,6 +310,7 @@ static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind) {
     auto dnow = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double dt[6] = {dnow(), 0, 0, 0, 0, 0};
     sl.host_batch = !b->on_device;
+    sl.is_text = born_on_device;
     sl.fused = fused; sl.list_mode = list_mode;
     const uint32_t *bases, *nmask;
     const uint64_t *off1, *off2;
@@ -324,11 +329,13 @@ static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind) {
         // waited for before this submit could happen (at most N_SLOTS batches in flight), so its staging is free.
         hipStream_t cs = s->stream0;
         const size_t cap_b = (size_t)s->cfg.max_bases, cap_n = (size_t)s->cfg.max_reads;
-        if ((rc = upload(sl.d_bases, b->bases2, b->n_bases / 4, cs, cap_b / 4))) return rc;
-        if (b->nmask && (rc = upload(sl.d_nmask, b->nmask, b->n_bases / 8, cs, cap_b / 8))) return rc;
-        if ((rc = upload(sl.d_off1, b->seg1_offset, n * 8, cs, cap_n * 8)) || (rc = upload(sl.d_len1, b->seg1_length, n * 4, cs, cap_n * 4))) return rc;
-        if (paired && ((rc = upload(sl.d_off2, b->seg2_offset, n * 8, cs, cap_n * 8)) || (rc = upload(sl.d_len2, b->seg2_length, n * 4, cs, cap_n * 4)))) return rc;
-        if (b->mean_quality && (rc = upload(sl.d_mq, b->mean_quality, n * 4, cs, cap_n * 4))) return rc;
+        if (!born_on_device) {
+            if ((rc = upload(sl.d_bases, b->bases2, b->n_bases / 4, cs, cap_b / 4))) return rc;
+            if (b->nmask && (rc = upload(sl.d_nmask, b->nmask, b->n_bases / 8, cs, cap_b / 8))) return rc;
+            if ((rc = upload(sl.d_off1, b->seg1_offset, n * 8, cs, cap_n * 8)) || (rc = upload(sl.d_len1, b->seg1_length, n * 4, cs, cap_n * 4))) return rc;
+            if (paired && ((rc = upload(sl.d_off2, b->seg2_offset, n * 8, cs, cap_n * 8)) || (rc = upload(sl.d_len2, b->seg2_length, n * 4, cs, cap_n * 4)))) return rc;
+            if (b->mean_quality && (rc = upload(sl.d_mq, b->mean_quality, n * 4, cs, cap_n * 4))) return rc;
+        }
         if (b->compression && (rc = upload(sl.d_comp, b->compression, n * 4, cs, cap_n * 4))) return rc;
         bases = sl.d_bases.as<uint32_t>();
         nmask = b->nmask ? sl.d_nmask.as<uint32_t>() : nullptr;

@@ -68,3 +68,44 @@ def unpack_reads(bases2, offsets, lengths, nmask=None):
             isn[j::32] = ((m >> np.uint32(j)) & 1).astype(bool)
         letters = np.where(isn[:letters.size], ord("N"), letters).astype(np.uint8)
     return [letters[int(o):int(o) + int(l)].tobytes() for o, l in zip(offsets, lengths)]
+
+
+_RANK = np.full(256, 255, dtype=np.uint8)  # seqan3 dna5 ranks: 0 A, 1 C, 2 G, 3 N, 4 T
+for _ch, _v in (("A", 0), ("C", 1), ("G", 2), ("T", 4), ("U", 4)):
+    _RANK[ord(_ch)] = _RANK[ord(_ch.lower())] = _v
+for _ch in "NRYSWKMBDHV":
+    _RANK[ord(_ch)] = _RANK[ord(_ch.lower())] = 3
+
+
+def text_batch(seqs, quals=None, mates=None, mate_quals=None, gap=b"", ranks=False):
+    """Lay reads out as a TEXT batch (include/charon_hip.h, chn_text_batch): one buffer that holds every string as it stands,
+    `gap` bytes in front of each of them (so a caller controls every start alignment), and one (offset, length) pair per
+    string.  Order in the buffer per read: sequence, quality, mate sequence, mate quality.
+    ranks=True: the sequences are stored as seqan3 dna5 ranks (a letter outside the IUPAC set becomes rank 255).
+    Returns dict(text, flags, seq1_offset, seq1_length[, qual1_*, seq2_*, qual2_*]) for api.Stream.submit_text / text_pack."""
+    enc = lambda s: s.encode() if isinstance(s, str) else bytes(s)
+    gap = enc(gap)
+    n = len(seqs)
+    cols = [("seq1", seqs, True), ("qual1", quals, False), ("seq2", mates, True), ("qual2", mate_quals, False)]
+    out = dict(flags=1 if ranks else 0)
+    for name, col, _ in cols:
+        if col is not None:
+            assert len(col) == n
+            out[name + "_offset"] = np.zeros(n, np.uint64)
+            out[name + "_length"] = np.zeros(n, np.uint32)
+    parts, cur = [], 0
+    for i in range(n):
+        for name, col, is_seq in cols:
+            if col is None:
+                continue
+            s = enc(col[i])
+            if is_seq and ranks:
+                s = _RANK[np.frombuffer(s, np.uint8)].tobytes()
+            parts.append(gap)
+            cur += len(gap)
+            out[name + "_offset"][i] = cur
+            out[name + "_length"][i] = len(s)
+            parts.append(s)
+            cur += len(s)
+    out["text"] = np.frombuffer(b"".join(parts), np.uint8).copy()
+    return out

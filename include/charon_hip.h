@@ -264,6 +264,70 @@ int chn_batch_submit(chn_stream *s, const chn_batch *b);   /* asynchronous */
 int chn_batch_wait(chn_stream *s, chn_result *r);          /* blocks; fills / points `r` */
 int chn_stream_sync(chn_stream *s);
 
+/* ---- text batches: reads as they stand in the caller's input buffer ---------------------------------------
+ * Replaces, together with chn_batch_submit, the whole per-read body of src/dehost_main.cpp:344-373 / :430-468 including the
+ * mean-quality loop (:355-360): the caller hands over `record.sequence()` as one byte per base and the phred characters, as
+ * (offset, length) pairs into ONE host buffer (e.g. the decoded FASTQ block itself -- ids and `+` lines may lie between the
+ * stretches), and k_text_pack forms the packed batch in device memory: 2-bit codes, N mask, 64-base-aligned segments (read
+ * i's mate 1 at `cur`, cur += pad64(len1), then mate 2; n_bases = max(cur, 64)) and the mean quality -- bit for bit what a host
+ * packer that follows the chn_batch rules writes.
+ * Letters: A a -> 0, C c -> 1, G g -> 2, T t U u -> 3; N R Y S W K M B D H V in either case -> N (mask bit set, code bits 0);
+ * any other byte is ILLEGAL.  With CHN_TEXT_DNA5_RANKS the bytes are seqan3 dna5 ranks instead (what std::vector<seqan3::dna5>
+ * holds): 0 A, 1 C, 2 G, 3 N, 4 T; a byte above 4 is illegal.
+ * Mean quality of a read: int sum of (signed char)q - 33 over the quality bytes of both mates / their number, one float
+ * division, 0.0f where there are none (and for a read without any letter).  A quality string may be longer than its sequence
+ * (the reference's reader allows it); every byte of it counts.
+ * Every descriptor is checked on the host: offset + length <= text_bytes, else CHN_E_INVALID and nothing is launched. */
+#define CHN_TEXT_DNA5_RANKS 1u
+typedef struct chn_text_batch {
+    uint32_t struct_size;
+    uint32_t flags;               /* CHN_TEXT_DNA5_RANKS */
+    uint64_t n_reads;
+    const uint8_t *text;          /* HOST memory; page-locked memory (chn_host_alloc) is uploaded asynchronously */
+    uint64_t text_bytes;
+    const uint64_t *seq1_offset;  /* [n] bytes into `text` */
+    const uint32_t *seq1_length;  /* [n] */
+    const uint64_t *qual1_offset; /* [n], or NULL together with qual1_length (FASTA: mean quality 0) */
+    const uint32_t *qual1_length; /* [n]; may exceed seq1_length */
+    const uint64_t *seq2_offset;  /* [n] or NULL together with seq2_length (single-end) */
+    const uint32_t *seq2_length;
+    const uint64_t *qual2_offset; /* [n] or NULL together with qual2_length; needs seq2_* */
+    const uint32_t *qual2_length;
+    const float *compression;     /* [n] or NULL, as chn_batch.compression */
+    uint32_t gzip_tallies;        /* as chn_batch.gzip_tallies */
+    uint32_t gzip_output;         /* as chn_batch.gzip_output */
+} chn_text_batch;
+typedef struct chn_text_result {
+    uint32_t struct_size;
+    uint32_t has_n;               /* out: 1 if any base of the batch is N */
+    uint64_t n_bases;             /* out: extent of the packed batch (multiple of 64) */
+    float *mean_quality;          /* [n] HOST buffer to fill, or NULL */
+} chn_text_result;
+/* chn_text_submit takes a slot exactly like chn_batch_submit (three batches in flight, text and packed batches freely mixed;
+ * chn_batch_wait and chn_text_wait both return the OLDEST batch).  It lays the segments out, checks the capacity of the stream
+ * (CHN_E_CAPACITY), uploads text and descriptors on the stream's copy stream, runs k_text_pack behind them and WAITS for that
+ * kernel's verdict -- does the batch hold an N, does it hold an illegal byte -- before it queues the chain: the chain's kernels
+ * are picked on the host by whether the batch has an N mask.  A batch without N then runs exactly the launches of
+ * chn_batch_submit with nmask = NULL, so every result column equals that of the host-packed batch.  The wait covers one upload
+ * and one streaming kernel while the device keeps working on the batches in flight.  Consequences:
+ *   - `text` and the descriptor arrays may be reused as soon as chn_text_submit returns;
+ *   - an illegal byte makes chn_text_submit ITSELF return CHN_E_INVALID (the message names the smallest read index that holds
+ *     one and the number of such bytes); nothing is queued, no slot is taken and the stream stays usable.
+ * The device text staging (per slot, text_bytes + padding, grow-only) is allocated with the first text batch (CHN_E_NOMEM if it
+ * does not fit); a process that never submits text allocates nothing for it.  The mean quality is downloaded into page-locked
+ * staging for the host re-evaluation of borderline reads that chn_batch_wait does.
+ * chn_text_wait = chn_batch_wait + the text columns; CHN_E_STATE (nothing consumed) if the oldest batch is not a text batch.
+ * chn_batch_wait on a text batch works and simply drops the text columns. */
+int chn_text_submit(chn_stream *s, const chn_text_batch *t);
+int chn_text_wait(chn_stream *s, chn_result *r, chn_text_result *t);
+/* chn_text_pack: the packing alone, synchronous (what a caller uses who wants the packed form back, as chn_minimisers exists
+ * for `charon index`): the packed form of `t` downloaded into host arrays (any of them NULL = skip): bases2
+ * [n_bases / 16], nmask [n_bases / 32] (all zero exactly when *has_n == 0), seg1_offset / seg2_offset [n], mean_quality [n].
+ * Size the arrays from the layout rule above (or call once with NULL arrays for *n_bases).  Fewer than three batches may be in
+ * flight.  Errors as chn_text_submit. */
+int chn_text_pack(chn_stream *s, const chn_text_batch *t, uint32_t *bases2, uint32_t *nmask, uint64_t *seg1_offset,
+                  uint64_t *seg2_offset, float *mean_quality, uint64_t *n_bases, uint32_t *has_n);
+
 /* Model + call only (k_model_call) on per-read counts the caller already holds -- used for reads that the
  * Result state machine cached while the KDE models were still training (include/result.hpp:139-151,181-198)
  * and that must be classified with the models as they are later.  All pointers are HOST arrays; outputs as in
@@ -335,7 +399,9 @@ int chn_index_emplace(chn_index *idx, const uint64_t *host_values, uint64_t n_va
  * which: 0 = minimise+probe kernel, 1 = count kernel, 2 = model+call kernel, 3 = whole batch chain;
  * 4 (any stream): *launches = number of batches chn_batch_wait re-ran on worst-case buffers after a row-log overflow;
  * 5 (any stream): *launches = row fetches the last waited batch's minimise+probe kernel issued (h per minimiser; fewer for an index of
- *   at most four bins, whose rows are fetched one at a time and only while the AND so far still has a bin set). */
+ *   at most four bins, whose rows are fetched one at a time and only while the AND so far still has a bin set);
+ * 6, 7 (text batches of a CHN_STREAM_PROFILE stream): the host -> device copy of the text / k_text_pack and the mean-quality division,
+ *   timed with events on the copy stream; *launches = text batches packed (chn_text_submit and chn_text_pack; reset with which = 7). */
 int chn_stream_profile(chn_stream *s, int which, double *total_ms, uint64_t *launches, int reset);
 /* Algorithmic bytes of the last batch by SURVEY 8(d): sum over reads of ceil(L/4) + M*h*W*8 + (8 + 8C). */
 int chn_stream_last_batch_bytes(chn_stream *s, uint64_t *bytes, uint64_t *total_minimisers);
