@@ -73,6 +73,18 @@ class TextResult(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("has_n", C.c_uint32), ("n_bases", C.c_uint64), ("mean_quality", C.c_void_p)]
 
 
+INFLATE_MAX_OUT = 65536      # CHN_INFLATE_MAX_OUT
+# chn_inflate_job.status values
+INFLATE_STATUS = {0: "ok", 1: "input exhausted", 2: "bad block header", 3: "bad code lengths", 4: "bad symbol or distance",
+                  5: "more output than out_length", 6: "stream ended short of out_length"}
+
+
+class InflateJob(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_members", C.c_uint64), ("in_", C.c_void_p), ("in_bytes", C.c_uint64),
+                ("in_offset", C.c_void_p), ("in_length", C.c_void_p), ("out", C.c_void_p), ("out_bytes", C.c_uint64),
+                ("out_offset", C.c_void_p), ("out_length", C.c_void_p), ("status", C.c_void_p)]
+
+
 class SynthReadsOut(C.Structure):
     _fields_ = [("bases2", C.c_void_p), ("seg1_offset", C.c_void_p), ("seg1_length", C.c_void_p), ("mean_quality", C.c_void_p),
                 ("compression", C.c_void_p), ("n_bases", C.c_uint64)]
@@ -84,7 +96,8 @@ EXPORTS = ["chn_index_create", "chn_index_upload_rows", "chn_index_device_words"
            "chn_model_set", "chn_batch_submit", "chn_batch_wait", "chn_stream_sync", "chn_classify_counts", "chn_classify_counts_raw", "chn_stream_profile",
            "chn_stream_last_batch_bytes", "chn_synth_genomes", "chn_synth_fill_index", "chn_synth_plant", "chn_synth_reads",
            "chn_device_free", "chn_device_download", "chn_device_malloc", "chn_device_upload", "chn_host_alloc", "chn_host_free", "chn_shard_minimise",
-           "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_text_submit", "chn_text_wait", "chn_text_pack", "chn_last_error", "chn_version"]
+           "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_text_submit", "chn_text_wait", "chn_text_pack", "chn_inflate_create", "chn_inflate_run",
+           "chn_inflate_run_host", "chn_inflate_destroy", "chn_inflate_kernel_ms", "chn_last_error", "chn_version"]
 
 _L.chn_last_error.restype = C.c_char_p
 _L.chn_version.restype = C.c_char_p
@@ -135,6 +148,11 @@ _L.chn_device_download.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64]
 _L.chn_text_submit.argtypes = [C.c_void_p, C.POINTER(TextBatch)]
 _L.chn_text_wait.argtypes = [C.c_void_p, C.POINTER(Result), C.POINTER(TextResult)]
 _L.chn_text_pack.argtypes = [C.c_void_p, C.POINTER(TextBatch)] + [C.c_void_p] * 5 + [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+_L.chn_inflate_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
+_L.chn_inflate_run.argtypes = [C.c_void_p, C.POINTER(InflateJob)]
+_L.chn_inflate_run_host.argtypes = [C.POINTER(InflateJob)]
+_L.chn_inflate_destroy.argtypes = [C.c_void_p]
+_L.chn_inflate_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
 
 
 class ChnError(RuntimeError):
@@ -531,6 +549,84 @@ class Stream:
     def destroy(self):
         if self.h:
             _L.chn_stream_destroy(self.h)
+            self.h = None
+
+
+# ---- raw deflate members (see include/charon_hip.h) ----
+def inflate_job(members, sizes, guard=0, out=None):
+    """the chn_inflate_job of `members` (raw deflate streams as bytes) with expected `sizes`: the members back to back in one input
+    array, the outputs in order with `guard` untouched bytes (0xA5) behind each.  `out`: a uint8 array to decode into (e.g. a
+    pinned_array) instead of a fresh one.  Returns (job, arrays) -- `arrays` keeps the memory alive and names it."""
+    n = len(members)
+    in_length = np.array([len(m) for m in members], np.uint32)
+    in_offset = np.zeros(n, np.uint64)
+    if n:
+        in_offset[1:] = np.cumsum(in_length[:-1], dtype=np.uint64)
+    data = np.frombuffer(b"".join(members), np.uint8) if n and int(in_length.sum()) else np.zeros(0, np.uint8)
+    out_length = np.array([int(x) for x in sizes], np.uint32)
+    out_offset = np.zeros(n, np.uint64)
+    if n:
+        out_offset[1:] = np.cumsum(out_length[:-1].astype(np.uint64) + np.uint64(guard), dtype=np.uint64)
+    out_bytes = int(out_length.astype(np.uint64).sum()) + guard * n
+    if out is None:
+        out = np.empty(max(out_bytes, 1), np.uint8)
+    assert out.dtype == np.uint8 and out.size >= out_bytes
+    out[:] = 0xA5
+    status = np.full(max(n, 1), 0xFFFFFFFF, np.uint32)
+    j = InflateJob()
+    j.struct_size, j.flags, j.n_members = C.sizeof(InflateJob), 0, n
+    j.in_, j.in_bytes = (data.ctypes.data if data.size else None), data.size
+    j.in_offset, j.in_length = in_offset.ctypes.data, in_length.ctypes.data
+    j.out, j.out_bytes = out.ctypes.data, out_bytes
+    j.out_offset, j.out_length, j.status = out_offset.ctypes.data, out_length.ctypes.data, status.ctypes.data
+    return j, dict(data=data, in_offset=in_offset, in_length=in_length, out=out, out_offset=out_offset, out_length=out_length,
+                   status=status, guard=guard, n=n)
+
+
+def _inflate_results(a):
+    """(list of bytes or None, status array) of a finished job; the guard bytes must be untouched"""
+    res, st = [], a["status"][:a["n"]].copy()
+    for i in range(a["n"]):
+        o, l = int(a["out_offset"][i]), int(a["out_length"][i])
+        res.append(a["out"][o:o + l].tobytes() if st[i] == 0 else None)
+        if a["guard"] and not (a["out"][o + l:o + l + a["guard"]] == 0xA5).all():
+            raise ChnError("inflate: member %d wrote behind its out_length" % i)
+    return res, st
+
+
+def inflate_host(members, sizes, guard=0):
+    """chn_inflate_run_host: the decoder the GPU runs, on the CPU.  Returns (list of bytes, or None where status != 0; status array)."""
+    j, a = inflate_job(members, sizes, guard)
+    _chk(_L.chn_inflate_run_host(C.byref(j)))
+    return _inflate_results(a)
+
+
+class Inflater:
+    """chn_inflate: raw deflate members decoded on the device, one wavefront a member.  One thread at a time per object."""
+
+    def __init__(self, device=0):
+        self.h = C.c_void_p()
+        _chk(_L.chn_inflate_create(device, C.byref(self.h)))
+
+    def run(self, members, sizes, guard=0, out=None):
+        """members: list of raw deflate streams (bytes); sizes: their expected inflated sizes (<= INFLATE_MAX_OUT).
+        Returns (list of bytes, or None where status != 0; status array)."""
+        j, a = inflate_job(members, sizes, guard, out)
+        _chk(_L.chn_inflate_run(self.h, C.byref(j)))
+        return _inflate_results(a)
+
+    def run_job(self, job):
+        """chn_inflate_run on a prepared InflateJob (inflate_job): no copies on the Python side, for measurements"""
+        _chk(_L.chn_inflate_run(self.h, C.byref(job)))
+
+    def kernel_ms(self):
+        ms = C.c_double()
+        _chk(_L.chn_inflate_kernel_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def destroy(self):
+        if self.h:
+            _L.chn_inflate_destroy(self.h)
             self.h = None
 
 

@@ -86,6 +86,18 @@ bool g_gzip_emulator = true;
 }  // namespace
 
 std::string g_inflate_stats;
+// CHARON_GPU_INFLATE: 1 = BGZF members are inflated on the device, 0 or unset = on the reader's threads; anything else is an error.
+// The device is CHARON_DEVICE, or the first entry of CHARON_DEVICES.
+static bool parse_gpu_inflate_env(const DehostArguments *opt) {
+    const char *e = std::getenv("CHARON_GPU_INFLATE");
+    if (!e) return true;
+    const std::string v(e);
+    if (v != "0" && v != "1") { std::cerr << "charon: CHARON_GPU_INFLATE: '" << v << "' is neither 0 nor 1" << std::endl; return false; }
+    g_gpu_inflate = v == "1";
+    if (opt) g_gpu_inflate_device = opt->devices.empty() ? opt->device : opt->devices[0];
+    else if (const char *d = std::getenv("CHARON_DEVICE")) g_gpu_inflate_device = std::atoi(d);
+    return true;
+}
 int main(int argc, char **argv) {
     if (argc < 2) { std::cerr << "A subcommand is required\nRun with --help for more information.\n"; return 106; }
     const std::string sub = argv[1];
@@ -277,9 +289,10 @@ int main(int argc, char **argv) {
         if (threads < 1 || threads > 256) return 2;
         return ordered_merge_selftest(threads, std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10));
     }
-    if (sub == "_records") {  // hidden diagnostic: dump what the block reader sees (no GPU involved)
+    if (sub == "_records") {  // hidden diagnostic: dump what the block reader sees (no GPU involved unless CHARON_GPU_INFLATE=1)
         try {
             if (argc < 3) return 2;
+            if (!parse_gpu_inflate_env(nullptr)) return 1;
             if (const char *t = std::getenv("CHARON_READER_THREADS")) g_reader_threads = std::max(1, std::atoi(t));
             BlockReader in(argv[2]);
             RawBlock blk;
@@ -337,6 +350,7 @@ int main(int argc, char **argv) {
         if (v != "0" && v != "1") { std::cerr << "charon: CHARON_TEXT_BATCHES: '" << v << "' is neither 0 nor 1" << std::endl; return 1; }
         opt.text_batches = v == "1";
     }
+    if (!parse_gpu_inflate_env(&opt)) return 1;  // checked before the index file is opened and before any HIP call
     try {
         dehost_main(opt);  // the reference's subcommand callback discards dehost_main's return value (src/dehost_main.cpp:311)
         return 0;

@@ -441,8 +441,9 @@ int dehost_main(DehostArguments &opt) {
 
     // CHARON_TEXT_BATCHES=1: slabs are page-locked from the first one on (the reader thread below allocates them); those left in the pool
     // are released when this function is left, after everything that hands slabs back, while the HIP runtime is certainly still up
-    g_pin_slabs = opt.text_batches;
+    g_pin_slabs = opt.text_batches || g_gpu_inflate;  // (CHARON_GPU_INFLATE=1 downloads straight into the slab)
     struct SlabPoolDrain { ~SlabPoolDrain() { std::lock_guard<std::mutex> lk(g_slab_pool.m); g_slab_pool.v.clear(); } } slab_pool_drain;
+    if (g_gpu_inflate) g_log.info("CHARON_GPU_INFLATE=1: BGZF members are inflated on device " + std::to_string(g_gpu_inflate_device) + " (size and CRC-32 still checked on the reader's threads)");
     if (opt.text_batches) g_log.info("CHARON_TEXT_BATCHES=1: reads go to the device as text (letters -> codes and mean quality on the GPU)");
     // reader thread: parses whole-record blocks while the previous batch is packed / compressed / classified / printed.  It starts
     // before the device is touched, so the first block is parsed while the HIP runtime initialises and the index is decoded.
@@ -1171,6 +1172,11 @@ int dehost_main(DehostArguments &opt) {
         std::snprintf(tb, sizeof tb, "timing (reader thread, s): inflate %.3f  record splitting %.3f", g_reader_fill_s, g_reader_parse_s);
         g_log.info(tb);
         std::fprintf(stderr, "charon: %s\n", tb);
+        if (g_gpu_inflate) {
+            std::snprintf(tb, sizeof tb, "timing (reader thread, s): inside chn_inflate_run %.3f (part of inflate)", g_gpu_inflate_s);
+            g_log.info(tb);
+            std::fprintf(stderr, "charon: %s\n", tb);
+        }
         std::snprintf(tb, sizeof tb, "timing (start-up, s): index file read %.3f  device + index create %.3f  index decode, stream, models %.3f (of which reference self-check %.3f)  read loop %.3f",
                       t_meta - t_entry, t_hip - t_meta, t_ready - t_hip, t_ready - t_sc0, now() - t_ready);
         g_log.info(tb);

@@ -77,7 +77,13 @@ SlabPool g_slab_pool;
 // compressed size in a 'BC' extra subfield (SAM specification, section 4.1).  Members are therefore found without inflating anything
 // and inflated in parallel -- what seqan3's bgzf input stream does for the reference's reader (src/dehost_main.cpp:324,335-339).
 // An ordinary .gz is ONE deflate stream and stays on zlib's single inflate (about 0.4 GB/s).
+// CHARON_GPU_INFLATE=1: the members of a block are inflated on the device (chn_inflate_run) instead of in the OpenMP loop below; size and
+// CRC-32 of every member are still checked here, on the reader's threads.
+bool g_gpu_inflate = false;
+int g_gpu_inflate_device = 0;
+double g_gpu_inflate_s = 0;  // reader-thread seconds inside chn_inflate_run (CHARON_TIMING)
 class BgzfSource {
+    chn_inflate *gpu_ = nullptr;  // one handle per source, created on first use
     const unsigned char *z_ = nullptr;
     size_t size_ = 0, pos_ = 0;
     std::string path_;
@@ -100,7 +106,10 @@ class BgzfSource {
         return 0;
     }
 public:
-    ~BgzfSource() { if (z_) ::munmap(const_cast<unsigned char *>(z_), size_); }
+    ~BgzfSource() {
+        if (gpu_) (void)chn_inflate_destroy(gpu_);
+        if (z_) ::munmap(const_cast<unsigned char *>(z_), size_);
+    }
     // true if `path` starts with a BGZF member (the file is then mapped)
     bool open(const std::string &path) {
         path_ = path;
@@ -145,6 +154,33 @@ public:
         char *dst = buf.data() + old;
         bool bad = false;
         const int nt = std::max(1, std::min<int>(g_reader_threads, (int)ms.size()));
+        if (g_gpu_inflate) {
+            if (!gpu_ && chn_inflate_create(g_gpu_inflate_device, &gpu_) != CHN_OK)
+                throw std::runtime_error(std::string("CHARON_GPU_INFLATE: ") + chn_last_error());
+            const size_t n = ms.size();
+            std::vector<uint64_t> in_off(n), out_off(n);
+            std::vector<uint32_t> in_len(n), out_len(n), status(n, 0);
+            for (size_t i = 0; i < n; ++i) {
+                in_off[i] = (uint64_t)(ms[i].cdata - z_); in_len[i] = ms[i].clen;
+                out_off[i] = ms[i].out; out_len[i] = ms[i].isize;
+            }
+            chn_inflate_job job;
+            std::memset(&job, 0, sizeof job);
+            job.struct_size = sizeof job; job.n_members = n;
+            job.in = z_; job.in_bytes = size_; job.in_offset = in_off.data(); job.in_length = in_len.data();
+            job.out = reinterpret_cast<uint8_t *>(dst); job.out_bytes = total; job.out_offset = out_off.data(); job.out_length = out_len.data();
+            job.status = status.data();
+            const double t0 = omp_get_wtime();
+            if (chn_inflate_run(gpu_, &job) != CHN_OK) throw std::runtime_error(std::string("CHARON_GPU_INFLATE: ") + chn_last_error());
+            g_gpu_inflate_s += omp_get_wtime() - t0;
+#pragma omp parallel for num_threads(nt) schedule(dynamic, 16) reduction(|| : bad)
+            for (long i = 0; i < (long)n; ++i) {
+                const Member &mb = ms[(size_t)i];
+                if (status[(size_t)i] != 0 ||
+                    fast_crc32((uint32_t)crc32(0L, Z_NULL, 0), reinterpret_cast<const unsigned char *>(dst + mb.out), mb.isize) != mb.crc)
+                    bad = true;
+            }
+        } else {
 #pragma omp parallel num_threads(nt)
         {
             z_stream zs;
@@ -168,6 +204,7 @@ public:
 #pragma omp critical(bgzf_bad)
                 bad = true;
             }
+        }
         }
         if (bad) throw std::runtime_error("gzip read error in " + path_ + ": a BGZF member is corrupt (inflate, size or CRC32 mismatch)");
     }

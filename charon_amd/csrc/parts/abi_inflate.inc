@@ -1,0 +1,238 @@
+// abi_inflate.inc -- chn_inflate_create / chn_inflate_run / chn_inflate_run_host / chn_inflate_destroy: raw deflate members on the device
+// Part of the single translation unit charon_hip.hip (included in order); not a stand-alone source.
+//
+// chn_inflate_run works through a job in groups of members (about 32 MiB of output each) on three streams of the handle's own:
+// while group g is decoded, the compressed bytes of group g + 1 are packed into page-locked staging (member by member, each on a
+// 16-byte boundary, so nothing of `in` between or around the members is uploaded) and uploaded, and the output of group g - 1 is
+// downloaded -- straight into `out` where that is page-locked and the group's members lie back to back there, through staging otherwise.
+// Two sets of grow-only buffers take turns.
+
+static const uint64_t INF_GROUP_OUT = 32ull << 20, INF_GROUP_IN = 64ull << 20;
+static const uint32_t INF_GROUP_MEMBERS = 1u << 16;
+
+struct InflateSet {
+    DevBuf d_in, d_out, d_desc, d_status, d_cursor;
+    PinBuf h_in, h_out, h_desc, h_status;
+    hipEvent_t up = nullptr, done = nullptr, down = nullptr, k0 = nullptr, k1 = nullptr;
+    uint64_t first = 0, n = 0, out_bytes = 0;  // the group in this set
+    bool direct = false, busy = false;
+};
+struct chn_inflate {
+    int device = 0;
+    hipStream_t s_up = nullptr, s_run = nullptr, s_down = nullptr;
+    InflateSet set[2];
+    double kernel_ms = 0;  // device time of the last run's kernels
+    int cus = 0;
+};
+
+static int inflate_check_job(const chn_inflate_job *j, const char *who) {
+    const std::string W(who);
+    if (!j) return fail(CHN_E_INVALID, W + ": null job");
+    if (j->struct_size != sizeof(chn_inflate_job)) return fail(CHN_E_INVALID, W + ": bad struct_size");
+    if (j->flags) return fail(CHN_E_INVALID, W + ": unknown flag");
+    const uint64_t n = j->n_members;
+    if (n == 0) return CHN_OK;
+    if (!j->in_offset || !j->in_length || !j->out_offset || !j->out_length || !j->status) return fail(CHN_E_INVALID, W + ": a descriptor array is NULL");
+    if ((!j->in && j->in_bytes) || (!j->out && j->out_bytes)) return fail(CHN_E_INVALID, W + ": in / out is NULL");
+    uint64_t out_end = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const std::string M = W + ": member " + std::to_string(i);
+        if (j->in_offset[i] > j->in_bytes || j->in_length[i] > j->in_bytes - j->in_offset[i]) return fail(CHN_E_INVALID, M + " reaches beyond in_bytes");
+        if (j->out_length[i] > CHN_INFLATE_MAX_OUT) return fail(CHN_E_INVALID, M + " has out_length above CHN_INFLATE_MAX_OUT");
+        if (j->out_offset[i] > j->out_bytes || j->out_length[i] > j->out_bytes - j->out_offset[i]) return fail(CHN_E_INVALID, M + " reaches beyond out_bytes");
+        if (j->out_offset[i] < out_end) return fail(CHN_E_INVALID, M + " overlaps the output of the member in front of it");
+        out_end = j->out_offset[i] + j->out_length[i];
+    }
+    return CHN_OK;
+}
+
+extern "C" int chn_inflate_run_host(const chn_inflate_job *j) {
+    int rc = inflate_check_job(j, "chn_inflate_run_host");
+    if (rc || j->n_members == 0) return rc;
+    InfShared *sh = new (std::nothrow) InfShared;
+    if (!sh) return fail(CHN_E_NOMEM, "chn_inflate_run_host: no memory for the decoder's tables");
+    for (uint64_t i = 0; i < j->n_members; ++i)
+        j->status[i] = (uint32_t)inf_member_host(*sh, j->in + j->in_offset[i], j->in_length[i], j->out + j->out_offset[i], j->out_length[i]);
+    delete sh;
+    return CHN_OK;
+}
+
+extern "C" int chn_inflate_create(int32_t device, chn_inflate **out) {
+    if (!out) return fail(CHN_E_INVALID, "chn_inflate_create: null argument");
+    *out = nullptr;
+    int count = 0;
+    HIPCHK(hipGetDeviceCount(&count));
+    if (device < 0 || device >= count) return fail(CHN_E_INVALID, "chn_inflate_create: device " + std::to_string(device) + " is not below the device count " + std::to_string(count));
+    HIPCHK(hipSetDevice(device));
+    chn_inflate *h = new (std::nothrow) chn_inflate;
+    if (!h) return fail(CHN_E_NOMEM, "chn_inflate_create: no memory");
+    h->device = device;
+    hipDeviceProp_t prop;
+    hipError_t e = hipGetDeviceProperties(&prop, device);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->s_up, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->s_run, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->s_down, hipStreamNonBlocking);
+    for (int s = 0; s < 2 && e == hipSuccess; ++s) {
+        InflateSet &st = h->set[s];
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&st.up, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&st.done, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&st.down, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreate(&st.k0);
+        if (e == hipSuccess) e = hipEventCreate(&st.k1);
+    }
+    if (e != hipSuccess) {
+        const std::string msg = std::string("chn_inflate_create: ") + hipGetErrorString(e);
+        chn_inflate_destroy(h);
+        return fail(CHN_E_HIP, msg);
+    }
+    h->cus = prop.multiProcessorCount;
+    *out = h;
+    return CHN_OK;
+}
+
+extern "C" int chn_inflate_destroy(chn_inflate *h) {
+    if (!h) return CHN_OK;
+    (void)hipSetDevice(h->device);
+    if (h->s_up) (void)hipStreamSynchronize(h->s_up);
+    if (h->s_run) (void)hipStreamSynchronize(h->s_run);
+    if (h->s_down) (void)hipStreamSynchronize(h->s_down);
+    for (InflateSet &st : h->set) {
+        st.d_in.release(); st.d_out.release(); st.d_desc.release(); st.d_status.release(); st.d_cursor.release();
+        st.h_in.release(); st.h_out.release(); st.h_desc.release(); st.h_status.release();
+        for (hipEvent_t ev : {st.up, st.done, st.down, st.k0, st.k1}) if (ev) (void)hipEventDestroy(ev);
+    }
+    if (h->s_up) (void)hipStreamDestroy(h->s_up);
+    if (h->s_run) (void)hipStreamDestroy(h->s_run);
+    if (h->s_down) (void)hipStreamDestroy(h->s_down);
+    delete h;
+    return CHN_OK;
+}
+
+// is [p, p + bytes) page-locked memory the runtime knows?
+static bool inflate_is_pinned(const void *p, uint64_t bytes) {
+    if (!p || !bytes) return false;
+    hipPointerAttribute_t a;
+    std::memset(&a, 0, sizeof a);
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (a.type != hipMemoryTypeHost) return false;
+    hipPointerAttribute_t b;
+    std::memset(&b, 0, sizeof b);
+    if (hipPointerGetAttributes(&b, static_cast<const char *>(p) + bytes - 1) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return b.type == hipMemoryTypeHost;
+}
+
+// pack, upload, decode and start the download of members [first, first + n) in set `st`
+static int inflate_issue(chn_inflate *h, InflateSet &st, const chn_inflate_job *j, uint64_t first, uint64_t n, bool out_pinned) {
+    uint64_t in_bytes = 0, out_bytes = 0;
+    bool contiguous = true;
+    for (uint64_t i = first; i < first + n; ++i) {
+        in_bytes += ((uint64_t)j->in_length[i] + 15) & ~15ull;
+        if (i > first && j->out_offset[i] != j->out_offset[i - 1] + j->out_length[i - 1]) contiguous = false;
+        out_bytes += j->out_length[i];
+    }
+    st.first = first; st.n = n; st.out_bytes = out_bytes; st.direct = out_pinned && contiguous;
+    int rc;
+    // descriptors in one block: in_off[n] out_off[n] (64-bit), in_len[n] out_len[n] (32-bit)
+    const size_t desc_bytes = (size_t)n * 24;
+    if ((rc = st.h_desc.ensure(desc_bytes + desc_bytes / 4)) || (rc = st.d_desc.ensure(st.h_desc.cap)) ||
+        (rc = st.h_in.ensure((size_t)in_bytes + 2 * INF_PAD + (st.h_in.cap < in_bytes + 2 * INF_PAD ? in_bytes / 4 : 0))) || (rc = st.d_in.ensure(st.h_in.cap)) ||
+        (rc = st.d_out.ensure((size_t)out_bytes + 64 + (st.d_out.cap < out_bytes + 64 ? out_bytes / 4 : 0))) ||
+        (rc = st.h_status.ensure((size_t)n * 4 + (st.h_status.cap < n * 4 ? n : 0))) || (rc = st.d_status.ensure(st.h_status.cap)) || (rc = st.d_cursor.ensure(16)))
+        return rc;
+    if (!st.direct && (rc = st.h_out.ensure(st.d_out.cap))) return rc;
+    uint64_t *in_off = st.h_desc.as<uint64_t>(), *out_off = in_off + n;
+    uint32_t *in_len = reinterpret_cast<uint32_t *>(out_off + n), *out_len = in_len + n;
+    uint8_t *stage = st.h_in.as<uint8_t>();
+    std::memset(stage, 0, INF_PAD);
+    uint64_t ip = INF_PAD, op = 0;
+    for (uint64_t k = 0; k < n; ++k) {
+        const uint64_t i = first + k;
+        in_off[k] = ip; in_len[k] = j->in_length[i];
+        out_off[k] = op; out_len[k] = j->out_length[i];
+        if (j->in_length[i]) std::memcpy(stage + ip, j->in + j->in_offset[i], j->in_length[i]);
+        ip += ((uint64_t)j->in_length[i] + 15) & ~15ull;
+        op += j->out_length[i];
+    }
+    std::memset(stage + ip, 0, INF_PAD);
+    HIPCHK(hipMemcpyAsync(st.d_in.p, stage, ip + INF_PAD, hipMemcpyHostToDevice, h->s_up));
+    HIPCHK(hipMemcpyAsync(st.d_desc.p, st.h_desc.p, desc_bytes, hipMemcpyHostToDevice, h->s_up));
+    HIPCHK(hipMemsetAsync(st.d_cursor.p, 0, 4, h->s_up));
+    HIPCHK(hipEventRecord(st.up, h->s_up));
+    HIPCHK(hipStreamWaitEvent(h->s_run, st.up, 0));
+    InflateArgs a;
+    a.in = st.d_in.as<uint8_t>();
+    a.in_off = st.d_desc.as<uint64_t>(); a.out_off = a.in_off + n;
+    a.in_len = reinterpret_cast<const uint32_t *>(a.out_off + n); a.out_len = a.in_len + n;
+    a.out = st.d_out.as<uint8_t>(); a.status = st.d_status.as<uint32_t>(); a.cursor = st.d_cursor.as<uint32_t>();
+    a.n = (uint32_t)n;
+    // a looping grid: two workgroups of one wavefront fit a CU's LDS; the cursor hands out members
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(n, (uint64_t)std::max(1, h->cus) * 2);
+    HIPCHK(hipEventRecord(st.k0, h->s_run));
+    hipLaunchKernelGGL(k_inflate_members, dim3(blocks), dim3(WAVE), 0, h->s_run, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(st.k1, h->s_run));
+    HIPCHK(hipEventRecord(st.done, h->s_run));
+    HIPCHK(hipStreamWaitEvent(h->s_down, st.done, 0));
+    if (out_bytes) {
+        void *dst = st.direct ? static_cast<void *>(j->out + j->out_offset[first]) : st.h_out.p;
+        HIPCHK(hipMemcpyAsync(dst, st.d_out.p, out_bytes, hipMemcpyDeviceToHost, h->s_down));
+    }
+    HIPCHK(hipMemcpyAsync(st.h_status.p, st.d_status.p, n * 4, hipMemcpyDeviceToHost, h->s_down));
+    HIPCHK(hipEventRecord(st.down, h->s_down));
+    st.busy = true;
+    return CHN_OK;
+}
+
+// wait for the group in set `st` and hand its output and statuses to the caller
+static int inflate_collect(chn_inflate *h, InflateSet &st, const chn_inflate_job *j) {
+    if (!st.busy) return CHN_OK;
+    st.busy = false;
+    HIPCHK(hipEventSynchronize(st.down));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, st.k0, st.k1));
+    h->kernel_ms += ms;
+    std::memcpy(j->status + st.first, st.h_status.p, st.n * 4);
+    if (!st.direct) {
+        const uint8_t *src = st.h_out.as<uint8_t>();
+        for (uint64_t i = st.first; i < st.first + st.n; ++i) {
+            if (j->out_length[i]) std::memcpy(j->out + j->out_offset[i], src, j->out_length[i]);
+            src += j->out_length[i];
+        }
+    }
+    return CHN_OK;
+}
+
+extern "C" int chn_inflate_run(chn_inflate *h, const chn_inflate_job *j) {
+    if (!h) return fail(CHN_E_INVALID, "chn_inflate_run: null handle");
+    int rc = inflate_check_job(j, "chn_inflate_run");
+    if (rc || j->n_members == 0) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    h->kernel_ms = 0;
+    const bool out_pinned = inflate_is_pinned(j->out, j->out_bytes);
+    uint64_t first = 0, g = 0;
+    while (first < j->n_members) {
+        uint64_t n = 0, ob = 0, ib = 0;
+        while (first + n < j->n_members && n < INF_GROUP_MEMBERS && (n == 0 || (ob + j->out_length[first + n] <= INF_GROUP_OUT && ib + j->in_length[first + n] <= INF_GROUP_IN))) {
+            ob += j->out_length[first + n]; ib += j->in_length[first + n]; ++n;
+        }
+        InflateSet &st = h->set[g & 1];
+        // the set's staging and device buffers are free: its last group was collected when the one after it was issued
+        rc = inflate_issue(h, st, j, first, n, out_pinned);
+        if (rc == CHN_OK && g > 0) rc = inflate_collect(h, h->set[(g - 1) & 1], j);
+        if (rc) {  // nothing of this call may still be on its way into the caller's memory
+            (void)hipStreamSynchronize(h->s_up); (void)hipStreamSynchronize(h->s_run); (void)hipStreamSynchronize(h->s_down);
+            h->set[0].busy = h->set[1].busy = false;
+            return rc;
+        }
+        first += n; ++g;
+    }
+    rc = inflate_collect(h, h->set[(g - 1) & 1], j);
+    if (rc) { (void)hipStreamSynchronize(h->s_down); h->set[0].busy = h->set[1].busy = false; }
+    return rc;
+}
+
+extern "C" int chn_inflate_kernel_ms(chn_inflate *h, double *ms) {
+    if (!h || !ms) return fail(CHN_E_INVALID, "chn_inflate_kernel_ms: null argument");
+    *ms = h->kernel_ms;
+    return CHN_OK;
+}

@@ -1,0 +1,469 @@
+// inflate_members.inc -- raw deflate (RFC 1951) decoder for small independent members (BGZF), one wavefront per member
+// Part of the single translation unit charon_hip.hip (included in order); not a stand-alone source.
+//
+// ONE decoder source for the device and the host.  Everything that decides what is accepted -- the bit reader, the block headers, the
+// code-length parsing, the table construction, the symbol loop and every bounds check -- is __host__ __device__ code templated on a
+// small policy.  On the device the policy is a wavefront: the decoder state (bit buffer, positions, table entries) is wave-uniform, the
+// 64 lanes share the table construction and the match copy, and nothing diverges.  On the host the policy has one lane and the same
+// loops run serially.  chn_inflate_run_host and the CPU tests therefore exercise the logic the kernel runs.
+//
+// Layout of a member's work in LDS (InfShared, 78 KiB -- two workgroups of one wavefront per CU):
+//   win    the member's whole output (at most 64 KiB): a back-reference is an LDS read; it is written out once at the end, 16 bytes a lane
+//   stage  two 1 KiB chunks of input: chunk c + 1 waits in registers (one 16-byte vector load per lane) while chunk c is consumed
+//   ll/dd  literal/length table (10-bit first level + sub-tables) and distance table (8-bit first level + sub-tables), one word an entry
+//
+// What is accepted is what zlib's inflate accepts: over-subscribed code sets and incomplete ones are rejected (except a literal/length or
+// distance set that is a single 1-bit code, and an empty distance set), as are a missing end-of-block code, HLIT > 286, HDIST > 30, block
+// type 3, a stored LEN/NLEN mismatch, a distance reaching before the member's first byte; bytes behind the final block are ignored.
+// Every loop consumes input bits, and consuming more than the member holds ends the decode, so it terminates on any input.
+
+#ifndef __HIPCC__  // a CPU build of the decoder alone (tools/fuzz/inflate_fuzz.cpp)
+#define __host__
+#define __device__
+#endif
+
+enum { INF_OK = 0, INF_E_INPUT = 1, INF_E_HEADER = 2, INF_E_LENGTHS = 3, INF_E_SYMBOL = 4, INF_E_OVER = 5, INF_E_SHORT = 6 };
+
+static const uint32_t INF_MAX_OUT = 65536;
+static const uint32_t INF_LL_ROOT = 10, INF_LL_CAP = 2048;  // zlib's `enough 286 10 15` is 1334 entries
+static const uint32_t INF_DD_ROOT = 8, INF_DD_CAP = 512;    // `enough 30 8 15` is 402
+static const uint32_t INF_PRE_ROOT = 7, INF_PRE_CAP = 128;  // code-length codes are at most 7 bits: no sub-tables
+static const uint32_t INF_CHUNK_WORDS = 256;                // 64 lanes x 16 bytes
+static const uint32_t INF_PAD = 64;                         // bytes the library keeps in front of and behind the device input
+
+struct alignas(16) InfShared {
+    uint8_t win[INF_MAX_OUT + 16];  // output byte k lives at win[wmis + k], wmis = the destination's misalignment to 16 bytes
+    uint32_t ll[INF_LL_CAP];
+    uint32_t dd[INF_DD_CAP];
+    uint32_t pre[INF_PRE_CAP];
+    uint32_t stage[2 * INF_CHUNK_WORDS];
+    uint32_t alloc;                 // sub-table allocation cursor of the table under construction
+    uint8_t lens[320];              // code lengths: literal/length symbols, then distance symbols
+    uint8_t plens[32];              // code lengths of the code-length code
+};
+
+// table entry: bits 0-3 code bits to drop, 4-7 kind, 8-12 extra bits (or sub-table index bits), 16-31 base value (or sub-table offset)
+enum { INF_K_INVALID = 0, INF_K_LIT = 1, INF_K_LEN = 2, INF_K_EOB = 3, INF_K_SUB = 4 };
+enum { INF_T_PRE = 0, INF_T_LL = 1, INF_T_DD = 2 };
+__host__ __device__ static inline uint32_t inf_entry(uint32_t kind, uint32_t bits, uint32_t extra, uint32_t base) {
+    return bits | (kind << 4) | (extra << 8) | (base << 16);
+}
+__host__ __device__ static inline uint32_t inf_symbol_entry(int table, uint32_t sym, uint32_t bits) {
+    if (table == INF_T_PRE) return inf_entry(INF_K_LIT, bits, 0, sym);
+    if (table == INF_T_LL) {
+        if (sym < 256) return inf_entry(INF_K_LIT, bits, 0, sym);
+        if (sym == 256) return inf_entry(INF_K_EOB, bits, 0, 0);
+        if (sym > 285) return inf_entry(INF_K_INVALID, bits, 0, 0);
+        const uint32_t i = sym - 257;
+        if (i < 8) return inf_entry(INF_K_LEN, bits, 0, 3 + i);
+        if (i == 28) return inf_entry(INF_K_LEN, bits, 0, 258);
+        const uint32_t x = (i >> 2) - 1;
+        return inf_entry(INF_K_LEN, bits, x, 3 + ((4 + (i & 3)) << x));
+    }
+    if (sym > 29) return inf_entry(INF_K_INVALID, bits, 0, 0);
+    if (sym < 4) return inf_entry(INF_K_LEN, bits, 0, sym + 1);
+    const uint32_t x = (sym >> 1) - 1;
+    return inf_entry(INF_K_LEN, bits, x, 1 + ((2 + (sym & 1)) << x));
+}
+__host__ __device__ static inline uint32_t inf_reverse(uint32_t code, uint32_t bits) {
+    uint32_t r = 0;
+    for (uint32_t i = 0; i < bits; ++i) r |= ((code >> i) & 1u) << (bits - 1 - i);
+    return r;
+}
+__host__ __device__ static inline uint32_t inf_popc64(uint64_t m) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return (uint32_t)__popcll(m);
+#else
+    return (uint32_t)__builtin_popcountll(m);
+#endif
+}
+
+// ---- policies --------------------------------------------------------------------------------------------------------------------
+// host: one lane, the member's bytes read in place (bytes behind the member read as zero)
+struct InfHostPolicy {
+    static const uint32_t LANES = 1;
+    const uint8_t *in;
+    uint64_t len;
+    uint32_t lane() const { return 0; }
+    uint32_t uni(uint32_t v) const { return v; }
+    uint64_t ballot(bool p) const { return p ? 1u : 0u; }
+    uint32_t below(uint64_t) const { return 0; }  // lanes below this one that are set in a ballot
+    void sync() const {}
+    uint32_t first_word() const { return 0; }
+    uint64_t bit_begin() const { return 0; }
+    uint64_t bit_end() const { return len * 8; }
+    uint32_t word(uint32_t w) const {
+        const uint64_t b = (uint64_t)w * 4;
+        uint32_t v = 0;
+        for (uint32_t i = 0; i < 4; ++i) if (b + i < len) v |= (uint32_t)in[b + i] << (8 * i);
+        return v;
+    }
+    uint32_t fetch_add(uint32_t *p, uint32_t n) const { const uint32_t o = *p; *p = o + n; return o; }
+    void fetch_max(uint32_t *p, uint32_t v) const { if (v > *p) *p = v; }
+};
+
+#ifdef __HIPCC__
+// device: one wavefront.  The input is read from `abase` (the member's first byte rounded down to 16 bytes) in chunks of 1 KiB, each
+// lane one aligned 16-byte load; bytes in front of the member are skipped, bytes behind it are masked to zero, and no load starts at or
+// behind the member's end -- so at most 15 bytes on either side are touched, inside the padding the library allocates.
+struct InfWavePolicy {
+    static const uint32_t LANES = WAVE;
+    const uint8_t *abase;
+    uint64_t begin, end;  // the member's bytes are [begin, end) from abase; begin < 16
+    uint32_t *stage;
+    uint32_t staged;      // chunks written to `stage` so far; chunk `staged` waits in `reg`
+    u32x4_t reg;
+    __device__ uint32_t lane() const { return lane_id(); }
+    __device__ uint32_t uni(uint32_t v) const { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+    __device__ uint64_t ballot(bool p) const { return __ballot(p ? 1 : 0); }
+    __device__ uint32_t below(uint64_t m) const { return (uint32_t)__popcll(m & ((1ull << lane_id()) - 1)); }
+    // one wavefront per workgroup: its LDS operations execute in order, the fence keeps the compiler from moving them across
+    __device__ void sync() const { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); }
+    __device__ uint32_t first_word() const { return (uint32_t)(begin >> 2); }
+    __device__ uint64_t bit_begin() const { return begin * 8; }
+    __device__ uint64_t bit_end() const { return end * 8; }
+    __device__ u32x4_t load_chunk(uint32_t c) const {
+        const uint64_t off = (uint64_t)c * (INF_CHUNK_WORDS * 4) + (uint64_t)lane_id() * 16;
+        u32x4_t v = {0u, 0u, 0u, 0u};
+        if (off < end) {
+            v = *reinterpret_cast<const u32x4_t *>(abase + off);
+            if (end - off < 16) {
+                const uint32_t keep = (uint32_t)(end - off);  // 1 .. 15 bytes of this lane's 16 belong to the member
+                uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (uint32_t q = 0; q < 4; ++q) {
+                    const uint32_t k = keep > 4 * q ? keep - 4 * q : 0;
+                    if (k < 4) w[q] = k ? (w[q] & ((1u << (8 * k)) - 1)) : 0u;
+                }
+                v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+            }
+        }
+        return v;
+    }
+    __device__ void start() { staged = 0; reg = load_chunk(0); }
+    __device__ void advance() {
+        uint32_t *slot = stage + (staged & 1u) * INF_CHUNK_WORDS + lane_id() * 4;
+        *reinterpret_cast<u32x4_t *>(slot) = reg;
+        ++staged;
+        reg = load_chunk(staged);  // consumed a kilobyte from now
+        sync();
+    }
+    __device__ uint32_t word(uint32_t w) {
+        while ((w / INF_CHUNK_WORDS) >= staged) advance();  // w is wave-uniform and grows by one: at most one round
+        return uni(stage[w & (2 * INF_CHUNK_WORDS - 1)]);
+    }
+    __device__ uint32_t fetch_add(uint32_t *p, uint32_t n) const { return atomicAdd(p, n); }
+    __device__ void fetch_max(uint32_t *p, uint32_t v) const { atomicMax(p, v); }
+};
+#endif
+
+// ---- the decoder -----------------------------------------------------------------------------------------------------------------
+template <class P> struct InfDecoder {
+    P &p;
+    InfShared &sh;
+    uint64_t bb = 0;      // bit buffer
+    uint32_t bc = 0;      // bits in it
+    uint32_t wpos = 0;    // next input word
+    uint64_t bit_end;     // the member's last bit, counted like wpos * 32 - bc
+    uint32_t opos = 0, out_len, wmis;
+
+    __host__ __device__ InfDecoder(P &p_, InfShared &sh_, uint32_t out_len_, uint32_t wmis_) : p(p_), sh(sh_), bit_end(p_.bit_end()), out_len(out_len_), wmis(wmis_) {
+        wpos = p.first_word();
+        refill(); refill();
+        const uint32_t skip = (uint32_t)(p.bit_begin() - (uint64_t)p.first_word() * 32);  // 0, 8, 16 or 24 bits in front of the member
+        drop(skip);
+    }
+    __host__ __device__ void refill() {  // at least 33 bits afterwards
+        if (bc <= 32) { bb |= (uint64_t)p.word(wpos) << bc; ++wpos; bc += 32; }
+    }
+    __host__ __device__ uint32_t peek(uint32_t n) const { return (uint32_t)(bb & ((1ull << n) - 1)); }
+    __host__ __device__ void drop(uint32_t n) { bb >>= n; bc -= n; }
+    __host__ __device__ uint32_t bits(uint32_t n) { const uint32_t v = peek(n); drop(n); return v; }
+    // more bits consumed than the member holds (bits behind its end read as zero, so nothing is decided by them unnoticed)
+    __host__ __device__ bool over() const { return (uint64_t)wpos * 32 - bc > bit_end; }
+
+    // Build the decode table of `n` code lengths.  Lanes take symbols: a symbol's canonical code is the first code of its length plus the
+    // number of symbols of that length in front of it.
+    __host__ __device__ int build(const uint8_t *lens, uint32_t n, uint32_t *tab, uint32_t root, uint32_t cap, int table) {
+        const uint32_t lane = p.lane();
+        uint32_t cnt[16];
+#pragma unroll
+        for (uint32_t l = 0; l < 16; ++l) cnt[l] = 0;
+        for (uint32_t base = 0; base < n; base += P::LANES) {
+            const uint32_t s = base + lane, L = s < n ? lens[s] : 0;
+#pragma unroll
+            for (uint32_t l = 1; l < 16; ++l) cnt[l] += inf_popc64(p.ballot(L == l));
+        }
+        for (uint32_t i = lane; i < cap; i += P::LANES) tab[i] = 0;  // every entry invalid
+        if (lane == 0) sh.alloc = 1u << root;
+        int left = 1;
+        uint32_t max = 0;
+#pragma unroll
+        for (uint32_t l = 1; l < 16; ++l) {
+            left = (left << 1) - (int)cnt[l];
+            if (left < 0) return INF_E_LENGTHS;  // over-subscribed
+            if (cnt[l]) max = l;
+        }
+        p.sync();
+        if (max == 0) return table == INF_T_DD ? INF_OK : INF_E_LENGTHS;     // no code at all: only a distance set may be empty
+        if (left > 0 && (table == INF_T_PRE || max != 1)) return INF_E_LENGTHS;  // incomplete (zlib lets a single 1-bit code pass)
+        uint32_t next[16];
+        next[0] = 0; next[1] = 0;
+#pragma unroll
+        for (uint32_t l = 2; l < 16; ++l) next[l] = (next[l - 1] + cnt[l - 1]) << 1;
+        // pass 1: codes; symbols longer than the first level leave the longest length of their first-level slot there
+        const uint32_t rmask = (1u << root) - 1;
+        for (uint32_t base = 0; base < n; base += P::LANES) {
+            const uint32_t s = base + lane, L = s < n ? lens[s] : 0;
+            uint32_t code = 0;
+#pragma unroll
+            for (uint32_t l = 1; l < 16; ++l) {
+                const uint64_t m = p.ballot(L == l);
+                if (L == l) code = next[l] + p.below(m);
+                next[l] += inf_popc64(m);
+            }
+            if (L > root) p.fetch_max(&tab[inf_reverse(code, L) & rmask], L);
+        }
+        p.sync();
+        // pass 2: a sub-table of 2^(longest - root) entries for every such slot
+        bool bad = false;
+        if (max > root)
+            for (uint32_t i = lane; i <= rmask; i += P::LANES) {
+                const uint32_t m = tab[i];
+                if (m == 0) continue;
+                const uint32_t sub = m - root, off = p.fetch_add(&sh.alloc, 1u << sub);
+                if (off + (1u << sub) > cap) { bad = true; tab[i] = 0; }
+                else tab[i] = inf_entry(INF_K_SUB, root, sub, off);
+            }
+        if (p.ballot(bad) != 0) return INF_E_LENGTHS;  // (cannot happen: the capacities are above zlib's `enough` bounds)
+        p.sync();
+        // pass 3: fill.  The codes are computed again (cheaper than keeping them)
+        next[1] = 0;
+#pragma unroll
+        for (uint32_t l = 2; l < 16; ++l) next[l] = (next[l - 1] + cnt[l - 1]) << 1;
+        for (uint32_t base = 0; base < n; base += P::LANES) {
+            const uint32_t s = base + lane, L = s < n ? lens[s] : 0;
+            uint32_t code = 0;
+#pragma unroll
+            for (uint32_t l = 1; l < 16; ++l) {
+                const uint64_t m = p.ballot(L == l);
+                if (L == l) code = next[l] + p.below(m);
+                next[l] += inf_popc64(m);
+            }
+            if (L == 0) continue;
+            const uint32_t r = inf_reverse(code, L);
+            if (L <= root) {
+                const uint32_t e = inf_symbol_entry(table, s, L);
+                for (uint32_t i = r; i <= rmask; i += 1u << L) tab[i] = e;
+            } else {
+                const uint32_t link = tab[r & rmask], sub = (link >> 8) & 31, off = link >> 16;
+                const uint32_t e = inf_symbol_entry(table, s, L - root);
+                for (uint32_t i = r >> root; i < (1u << sub); i += 1u << (L - root)) tab[off + i] = e;
+            }
+        }
+        p.sync();
+        return INF_OK;
+    }
+
+    // one symbol of table `tab`: the entry (its code bits dropped).  The caller has refilled.
+    __host__ __device__ uint32_t symbol(const uint32_t *tab, uint32_t root) {
+        uint32_t e = p.uni(tab[peek(root)]);
+        if (((e >> 4) & 15) == INF_K_SUB) {
+            drop(root);
+            e = p.uni(tab[(e >> 16) + peek((e >> 8) & 31)]);
+        }
+        drop(e & 15);
+        return e;
+    }
+
+    __host__ __device__ int stored() {
+        drop(bc & 7);  // to the byte boundary (wpos * 32 is one)
+        refill();
+        const uint32_t len = bits(16), nlen = bits(16);
+        if (over()) return INF_E_INPUT;
+        if ((len ^ nlen) != 0xFFFFu) return INF_E_HEADER;
+        if (opos + len > out_len) return INF_E_OVER;
+        if ((bit_end - ((uint64_t)wpos * 32 - bc)) / 8 < len) return INF_E_INPUT;
+        uint32_t left = len;
+        const uint32_t lane = p.lane();
+        while (left >= 4) {
+            refill();
+            const uint32_t v = bits(32);
+            for (uint32_t i = lane; i < 4; i += P::LANES) sh.win[wmis + opos + i] = (uint8_t)(v >> (8 * i));
+            opos += 4; left -= 4;
+        }
+        while (left) {
+            refill();
+            const uint32_t v = bits(8);
+            if (lane == 0) sh.win[wmis + opos] = (uint8_t)v;
+            ++opos; --left;
+        }
+        p.sync();
+        return INF_OK;
+    }
+
+    __host__ __device__ int fixed_tables() {
+        const uint32_t lane = p.lane();
+        for (uint32_t s = lane; s < 288; s += P::LANES) sh.lens[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8;
+        for (uint32_t s = lane; s < 32; s += P::LANES) sh.lens[288 + s] = 5;
+        p.sync();
+        int rc = build(sh.lens, 288, sh.ll, INF_LL_ROOT, INF_LL_CAP, INF_T_LL);
+        if (rc) return rc;
+        return build(sh.lens + 288, 32, sh.dd, INF_DD_ROOT, INF_DD_CAP, INF_T_DD);
+    }
+
+    __host__ __device__ int dynamic_tables() {
+        const uint32_t lane = p.lane();
+        refill();
+        const uint32_t hlit = bits(5) + 257, hdist = bits(5) + 1, hclen = bits(4) + 4;
+        if (over()) return INF_E_INPUT;
+        if (hlit > 286 || hdist > 30) return INF_E_LENGTHS;
+        const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+        for (uint32_t i = lane; i < 19; i += P::LANES) sh.plens[i] = 0;
+        p.sync();
+        for (uint32_t i = 0; i < hclen; ++i) {
+            refill();
+            const uint32_t v = bits(3);
+            if (lane == 0) sh.plens[order[i]] = (uint8_t)v;
+        }
+        if (over()) return INF_E_INPUT;
+        p.sync();
+        int rc = build(sh.plens, 19, sh.pre, INF_PRE_ROOT, INF_PRE_CAP, INF_T_PRE);
+        if (rc) return rc;
+        const uint32_t total = hlit + hdist;
+        uint32_t i = 0, prev = 0;
+        while (i < total) {
+            refill();
+            const uint32_t e = symbol(sh.pre, INF_PRE_ROOT);
+            if (((e >> 4) & 15) != INF_K_LIT) return over() ? INF_E_INPUT : INF_E_LENGTHS;
+            const uint32_t s = e >> 16;
+            uint32_t rep = 1, val = s;
+            if (s == 16) { if (i == 0) return over() ? INF_E_INPUT : INF_E_LENGTHS; val = prev; rep = 3 + bits(2); }
+            else if (s == 17) { val = 0; rep = 3 + bits(3); }
+            else if (s == 18) { val = 0; rep = 11 + bits(7); }
+            if (over()) return INF_E_INPUT;
+            if (i + rep > total) return INF_E_LENGTHS;
+            if (lane == 0) for (uint32_t k = 0; k < rep; ++k) sh.lens[i + k] = (uint8_t)val;
+            i += rep; prev = val;
+        }
+        p.sync();
+        if (p.uni(sh.lens[256]) == 0) return INF_E_LENGTHS;  // no end-of-block code
+        rc = build(sh.lens, hlit, sh.ll, INF_LL_ROOT, INF_LL_CAP, INF_T_LL);
+        if (rc) return rc;
+        return build(sh.lens + hlit, hdist, sh.dd, INF_DD_ROOT, INF_DD_CAP, INF_T_DD);
+    }
+
+    __host__ __device__ int symbols() {
+        const uint32_t lane = p.lane();
+        for (;;) {
+            refill();
+            const uint32_t e = symbol(sh.ll, INF_LL_ROOT);
+            const uint32_t kind = (e >> 4) & 15;
+            if (over()) return INF_E_INPUT;
+            if (kind == INF_K_LIT) {
+                if (opos >= out_len) return INF_E_OVER;
+                if (lane == 0) sh.win[wmis + opos] = (uint8_t)(e >> 16);
+                ++opos;
+                continue;
+            }
+            if (kind == INF_K_EOB) return INF_OK;
+            if (kind != INF_K_LEN) return INF_E_SYMBOL;
+            const uint32_t len = (e >> 16) + bits((e >> 8) & 31);
+            refill();
+            const uint32_t d = symbol(sh.dd, INF_DD_ROOT);
+            if (((d >> 4) & 15) != INF_K_LEN) return over() ? INF_E_INPUT : INF_E_SYMBOL;
+            const uint32_t dist = (d >> 16) + bits((d >> 8) & 31);
+            if (over()) return INF_E_INPUT;
+            if (dist > opos) return INF_E_SYMBOL;  // reaches before the member's first byte
+            if (opos + len > out_len) return INF_E_OVER;
+            p.sync();  // the literals written so far are visible to every lane
+            // lane j copies byte j; an overlapping copy (dist < len) repeats the dist bytes in front of it
+            uint8_t *to = sh.win + wmis + opos;
+            const uint8_t *from = to - dist;
+            if (dist >= len) for (uint32_t k = lane; k < len; k += P::LANES) to[k] = from[k];
+            else if (dist == 1) { const uint8_t b = from[0]; for (uint32_t k = lane; k < len; k += P::LANES) to[k] = b; }
+            else for (uint32_t k = lane; k < len; k += P::LANES) to[k] = from[k % dist];
+            opos += len;
+            p.sync();
+        }
+    }
+
+    __host__ __device__ int run() {
+        for (;;) {
+            refill();
+            const uint32_t hdr = bits(3);
+            if (over()) return INF_E_INPUT;
+            const uint32_t type = hdr >> 1;
+            int rc;
+            if (type == 0) rc = stored();
+            else if (type == 3) return INF_E_HEADER;
+            else {
+                rc = type == 1 ? fixed_tables() : dynamic_tables();
+                if (rc == INF_OK) rc = symbols();
+            }
+            if (rc) return rc;
+            if (hdr & 1) break;
+        }
+        return opos == out_len ? INF_OK : INF_E_SHORT;
+    }
+};
+
+// host entry: one member, `sh` is the caller's scratch; writes min(produced, out_len) bytes
+static int inf_member_host(InfShared &sh, const uint8_t *in, uint64_t in_len, uint8_t *out, uint32_t out_len) {
+    InfHostPolicy pol{in, in_len};
+    InfDecoder<InfHostPolicy> d(pol, sh, out_len, 0);
+    const int st = d.run();
+    if (d.opos) std::memcpy(out, sh.win, std::min(d.opos, out_len));
+    return st;
+}
+
+#ifdef __HIPCC__
+// ---- kernel ----------------------------------------------------------------------------------------------------------------------
+struct InflateArgs {
+    const uint8_t *in;          // packed members, INF_PAD bytes of padding in front and behind
+    const uint64_t *in_off;     // [n] from `in`
+    const uint32_t *in_len;
+    uint8_t *out;               // packed outputs
+    const uint64_t *out_off;
+    const uint32_t *out_len;    // <= INF_MAX_OUT (checked on the host)
+    uint32_t *status;
+    uint32_t *cursor;
+    uint32_t n;
+};
+
+__global__ void __launch_bounds__(WAVE) k_inflate_members(InflateArgs a) {
+    __shared__ InfShared sh;
+    const uint32_t lane = lane_id();
+    for (;;) {
+        uint32_t m = 0;
+        if (lane == 0) m = atomicAdd(a.cursor, 1u);
+        m = (uint32_t)__builtin_amdgcn_readfirstlane((int)m);
+        if (m >= a.n) break;
+        const uint8_t *src = a.in + a.in_off[m];
+        uint8_t *dst = a.out + a.out_off[m];
+        const uint32_t out_len = min(a.out_len[m], INF_MAX_OUT);
+        const uint32_t wmis = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15);
+        InfWavePolicy pol;
+        const uint64_t mis = reinterpret_cast<uintptr_t>(src) & 15;
+        pol.abase = src - mis; pol.begin = mis; pol.end = mis + a.in_len[m]; pol.stage = sh.stage;
+        pol.start();
+        int st;
+        uint32_t produced;
+        {
+            InfDecoder<InfWavePolicy> d(pol, sh, out_len, wmis);
+            st = d.run();
+            produced = min(d.opos, out_len);
+        }
+        pol.sync();
+        // write the window out: whole 16-byte pieces as one vector store per lane, the ragged ends byte by byte
+        uint8_t *abase = dst - wmis;
+        const uint32_t lo = wmis, hi = wmis + produced;  // window bytes [lo, hi)
+        for (uint32_t b = lane * 16; b < hi; b += WAVE * 16) {
+            if (b >= lo && b + 16 <= hi) *reinterpret_cast<u32x4_t *>(abase + b) = *reinterpret_cast<const u32x4_t *>(sh.win + b);
+            else for (uint32_t i = b > lo ? b : lo; i < b + 16 && i < hi; ++i) abase[i] = sh.win[i];
+        }
+        if (lane == 0) a.status[m] = (uint32_t)st;
+        pol.sync();  // the window and the tables are the next member's from here
+    }
+}
+#endif

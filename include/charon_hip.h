@@ -406,6 +406,39 @@ int chn_stream_profile(chn_stream *s, int which, double *total_ms, uint64_t *lau
 /* Algorithmic bytes of the last batch by SURVEY 8(d): sum over reads of ceil(L/4) + M*h*W*8 + (8 + 8C). */
 int chn_stream_last_batch_bytes(chn_stream *s, uint64_t *bytes, uint64_t *total_minimisers);
 
+/* ---- raw deflate members on the device (BGZF input of the front end; no reference counterpart: the reference reads through
+ * seqan3's bgzf stream on CPU threads) ------------------------------------------------------------------------------------------
+ * A job names n_members independent raw deflate streams (RFC 1951, no zlib or gzip wrapper) inside `in` and where in `out` each one's
+ * bytes go.  The expected size of every member is known beforehand (a BGZF member carries it in its trailer) and is at most
+ * CHN_INFLATE_MAX_OUT.  k_inflate_members decodes one member per wavefront; what it accepts is what zlib's inflate accepts, bytes of a
+ * member behind its final block are ignored.  The descriptors are checked before anything runs: in_offset[i] + in_length[i] <= in_bytes,
+ * out_length[i] <= CHN_INFLATE_MAX_OUT, out_offset[i] + out_length[i] <= out_bytes, out_offset[i + 1] >= out_offset[i] + out_length[i];
+ * a violation is CHN_E_INVALID, chn_last_error() names the member, and nothing has run.  A corrupt member is NOT an error of the call:
+ * the call returns 0, status[i] != 0, and every other member is decoded; the bytes of a failed member's stretch of `out` are
+ * unspecified, bytes outside the members' stretches are never written.  n_members == 0 is a no-op and out_length[i] == 0 is legal
+ * (BGZF's end-of-file marker).  The CRC-32 of a member is the caller's to check.
+ * A chn_inflate owns its streams and staging buffers (grow-only); it is used by ONE thread at a time, different handles may be driven
+ * from different threads.  chn_inflate_run is synchronous. */
+#define CHN_INFLATE_MAX_OUT 65536u
+/* status[i]: 0 ok | 1 input exhausted | 2 bad block header (type 3, stored LEN/NLEN) | 3 bad code lengths
+ * | 4 bad symbol or distance | 5 more output than out_length | 6 stream ended short of out_length */
+typedef struct chn_inflate chn_inflate;
+typedef struct chn_inflate_job {
+    uint32_t struct_size, flags;              /* flags: 0 */
+    uint64_t n_members;
+    const uint8_t *in;  uint64_t in_bytes;    /* HOST; pageable (e.g. a mapped file) or page-locked */
+    const uint64_t *in_offset; const uint32_t *in_length;    /* [n] raw deflate data of member i */
+    uint8_t *out;  uint64_t out_bytes;        /* HOST */
+    const uint64_t *out_offset; const uint32_t *out_length;  /* [n] expected size, <= CHN_INFLATE_MAX_OUT */
+    uint32_t *status;                         /* [n] out */
+} chn_inflate_job;
+int chn_inflate_create(int32_t device, chn_inflate **out);
+int chn_inflate_run(chn_inflate *h, const chn_inflate_job *job);       /* synchronous */
+int chn_inflate_run_host(const chn_inflate_job *job);                  /* same decoder source on the CPU, one thread; no GPU needed */
+int chn_inflate_destroy(chn_inflate *h);
+/* measurement aid: device time of the kernels of the handle's last chn_inflate_run, from events around them */
+int chn_inflate_kernel_ms(chn_inflate *h, double *ms);
+
 /* ---- synthetic workload fabrication on the device (bench / tests; no reference counterpart) ---------- */
 /* Measurement aid: the rate this device sustains for NOTHING BUT the index's probe pattern -- independent uniformly random row
  * fetches of 8 * bin_words bytes from THIS index's words (one load per thread in flight, 32 wavefronts per CU, `nt` cache policy if
