@@ -427,7 +427,7 @@ class Stream:
         b.seg2_offset, b.seg2_length, b.mean_quality, b.compression = seg2_offset, seg2_length, mean_quality, compression
         b.gzip_tallies, b.gzip_output = gzip_tallies, gzip_output
         _chk(_L.chn_batch_submit(self.h, C.byref(b)))
-        self._fifo.append((n_reads, None))
+        self._fifo.append((n_reads, None, gzip_tallies, gzip_output))
 
     # ---- text batches (see include/charon_hip.h) ----
     def _text_batch(self, tb, compression=None, gzip_tallies=0, gzip_output=0):

@@ -106,7 +106,11 @@ __global__ __launch_bounds__(WAVE) void k_gzip_tally(const GztArgs a) {
             outside = (o1 & 63u) || o1 > a.n_bases || l1 > a.n_bases - o1 || (a.off2 && ((o2 & 63u) || o2 > a.n_bases || l2 > a.n_bases - o2));
         }
         if (n == 0 || n > a.max_len || n > GZT_MAX_LEN || outside) {
-            if (lane == 0) out[316] = 1;
+            // EVERY lane stores the word: the wavefront must come round the loop whole.  With `if (lane == 0)` in front of the store the
+            // compiler sent lanes 1 .. 63 round on their own; their `item` is 0 and lane 0 is not there to fetch one, so they tallied read 0
+            // once more, without lane 0's candidate and counters, over the proper tallies of read 0 (and for ever, if read 0 is skipped itself).
+            // Only a device batch comes here: a host batch's launches list the reads to tally.
+            out[316] = 1;
             continue;
         }
         for (uint32_t i = lane; i < 256; i += WAVE) tall[i] = 0;

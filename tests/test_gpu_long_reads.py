@@ -22,13 +22,6 @@ def api():
     return api
 
 
-def _to_device(api, arr):
-    arr = np.ascontiguousarray(arr)
-    p = api.device_malloc(0, max(arr.nbytes, 16))
-    api.device_upload(0, p, arr)
-    return p
-
-
 def _run(api, gidx, reads, split_bucket=0, tiny_log=False, twice=False):
     from charon_amd import pack
     p = pack.pack_reads(reads)
@@ -123,8 +116,8 @@ def test_device_batch_with_long_reads(api, oracle_lib):
     reads = util.sample_reads(r, gs, 300, (500, 9000)) + [util.mutate(r, gs[0][:250000], 0.05), b"C" * 40000, util.random_seq(r, 33000)]
     p = pack.pack_reads(reads)
     n = len(reads)
-    dev = [_to_device(api, np.ascontiguousarray(p[key], dt)) for key, dt in (("bases2", np.uint32), ("seg1_offset", np.uint64), ("seg1_length", np.uint32))]
-    mq = _to_device(api, np.full(n, 40.0, np.float32))
+    dev = [util.to_device(api, np.ascontiguousarray(p[key], dt)) for key, dt in (("bases2", np.uint32), ("seg1_offset", np.uint64), ("seg1_length", np.uint32))]
+    mq = util.to_device(api, np.full(n, 40.0, np.float32))
     for oidx in (fused, rows):
         orc = run_oracle(oidx, reads)
         g = util.gpu_index_from_oracle(api, oidx)
@@ -162,8 +155,8 @@ def test_one_megabase_read_does_not_hold_up_a_batch(api, oracle_lib):
     offs2 = np.concatenate([offs, np.array([rd.n_bases], np.uint64)])
     lens2 = np.concatenate([lens, np.array([1000000], np.uint32)])
     nb2 = rd.n_bases + pl["n_bases"]
-    d_b, d_o, d_l = _to_device(api, bases2), _to_device(api, offs2), _to_device(api, lens2)
-    mq = _to_device(api, np.full(n + 1, 40.0, np.float32))
+    d_b, d_o, d_l = util.to_device(api, bases2), util.to_device(api, offs2), util.to_device(api, lens2)
+    mq = util.to_device(api, np.full(n + 1, 40.0, np.float32))
 
     def timed(nr, nb, split_bucket):
         st = api.Stream(g, n + 1, nb2, split_bucket=split_bucket)

@@ -103,14 +103,65 @@ def assert_parity(gpu, orc, prob_tol=1e-6):
     assert np.max(np.abs(a[ok] - b[ok]), initial=0.0) <= prob_tol
 
 
-def download_results(api, res, n, ncat, device=0):
-    """device-resident chn_result -> the dict layout of Stream.wait_host()"""
-    return dict(num_hashes=api.device_download(device, res.num_hashes, n * 4, np.uint32),
-                counts=api.device_download(device, res.counts, n * ncat * 4, np.uint32).reshape(n, ncat),
-                unique=api.device_download(device, res.unique_counts, n * ncat * 4, np.uint32).reshape(n, ncat),
-                probs=api.device_download(device, res.probabilities, n * ncat * 8, np.float64).reshape(n, ncat),
-                call=api.device_download(device, res.call, n, np.uint8), conf=api.device_download(device, res.confidence, n, np.uint8),
-                flags=api.device_download(device, res.flags, n, np.uint8))
+def download_results(api, res, n, ncat, device=0, gzip_output=None):
+    """device-resident chn_result -> the dict layout of Stream.wait_host().  gzip_output: what the batch asked for (its
+    chn_batch.gzip_output; None: no gzip column) -- the columns the result carries for it come back as gzip_sizes and gzip_tallies
+    ([n][320] uint16; with device results the tallies' status word is there in every mode)"""
+    out = dict(num_hashes=api.device_download(device, res.num_hashes, n * 4, np.uint32),
+               counts=api.device_download(device, res.counts, n * ncat * 4, np.uint32).reshape(n, ncat),
+               unique=api.device_download(device, res.unique_counts, n * ncat * 4, np.uint32).reshape(n, ncat),
+               probs=api.device_download(device, res.probabilities, n * ncat * 8, np.float64).reshape(n, ncat),
+               call=api.device_download(device, res.call, n, np.uint8), conf=api.device_download(device, res.confidence, n, np.uint8),
+               flags=api.device_download(device, res.flags, n, np.uint8))
+    if gzip_output is not None:
+        if res.gzip_sizes:
+            out["gzip_sizes"] = api.device_download(device, res.gzip_sizes, n * 4, np.uint32)
+        if res.gzip_tallies:
+            out["gzip_tallies"] = api.device_download(device, res.gzip_tallies, n * 320 * 2, np.uint16).reshape(n, 320)
+    return out
+
+
+def to_device(api, arr, device=0):
+    """a device buffer holding `arr` (at least 16 bytes); the caller frees it with api.device_free"""
+    arr = np.ascontiguousarray(arr)
+    p = api.device_malloc(device, max(arr.nbytes, 16))
+    if arr.nbytes:
+        api.device_upload(device, p, arr)
+    return p
+
+
+class DeviceBatch:
+    """what pack.pack_reads returns, in device buffers of its own: the pointers of a chn_batch with on_device = 1"""
+    POINTERS = ("bases2", "nmask", "seg1_offset", "seg1_length", "seg2_offset", "seg2_length", "mean_quality", "compression")
+
+    def __init__(self, api, packed, mq=None, comp=None, device=0):
+        self.api, self.device = api, device
+        self.n_reads, self.n_bases = len(packed["seg1_length"]), int(packed["n_bases"])
+        col = lambda v: None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32), (self.n_reads,)))
+        host = dict(bases2=(packed["bases2"], np.uint32), nmask=(packed.get("nmask"), np.uint32),
+                    seg1_offset=(packed["seg1_offset"], np.uint64), seg1_length=(packed["seg1_length"], np.uint32),
+                    seg2_offset=(packed.get("seg2_offset"), np.uint64), seg2_length=(packed.get("seg2_length"), np.uint32),
+                    mean_quality=(col(mq), np.float32), compression=(col(comp), np.float32))
+        for key, (a, dt) in host.items():
+            setattr(self, key, None if a is None else to_device(api, np.ascontiguousarray(a, dtype=dt), device))
+
+    def submit(self, st, gzip_tallies=0, gzip_output=0, **other):
+        """chn_batch_submit of this batch on stream `st`; other: pointers to use instead of the batch's own (nmask=None, ...)"""
+        p = {key: other.get(key, getattr(self, key)) for key in self.POINTERS}
+        st.submit_device(self.n_reads, self.n_bases, p["bases2"], p["seg1_offset"], p["seg1_length"], p["mean_quality"], p["compression"],
+                         nmask=p["nmask"], seg2_offset=p["seg2_offset"], seg2_length=p["seg2_length"], gzip_tallies=gzip_tallies,
+                         gzip_output=gzip_output)
+
+    def free(self):
+        for key in self.POINTERS:
+            self.api.device_free(self.device, getattr(self, key))
+            setattr(self, key, None)
+
+
+def to_device_batch(api, packed, mq=None, comp=None, device=0):
+    """upload a packed batch (bases2, nmask if present, seg1_*, seg2_* if present, the two float columns -- scalars or arrays, None:
+    no column) -> DeviceBatch"""
+    return DeviceBatch(api, packed, mq, comp, device)
 
 
 def free_synth_reads(api, rd, device=0):
