@@ -281,6 +281,205 @@ static hipError_t launch_k1_mode(int mode, uint32_t W, const K1Args &a, size_t l
                                                                    : launch_k1_w<MODE_ROWS>(W, a, lds, st);
 }
 
+// ---- the gzip column: deflate tallies / gzip member sizes of a batch's reads (k_gzip_tally, k_gzip_long, k_gzip_size) ----
+// What a launch of either deflate kernel needs beside its arguments.  A launch is as many wavefronts as the device holds at once (a CU's
+// LDS over the launch's LDS per wavefront, max_wpc at most), each taking the next read from a counter, each with stride32 words of
+// scratch for its class arrays.  The launches of a stream run one after the other, so they share the scratch; it only grows (hipFree
+// waits for the kernels in flight), with a quarter to spare if `spare`.  lds beyond the default limit: the kernels' limit is raised,
+// once, to the whole CU.  no_room: how a failed growth is reported (null: as the allocation reports it).
+static int gz_launch_room(const chn_stream *s, size_t lds, uint32_t max_wpc, uint32_t count, size_t stride32, DevBuf &scratch, bool spare, const char *no_room,
+                          const void *k4, const void *k2, bool &whole_cu, uint32_t &grid) {
+    const uint32_t wpc = (uint32_t)std::min<size_t>(max_wpc, std::max<size_t>(1, (size_t)160 * 1024 / lds));
+    grid = (uint32_t)std::min<uint64_t>(count, (uint64_t)s->n_cus * wpc);
+    const size_t need = (size_t)grid * stride32 * 4;
+    if (need > scratch.cap) {
+        const int rc = scratch.ensure(need + (spare ? need / 4 : 0));
+        if (rc) return no_room ? fail(CHN_E_NOMEM, std::string(no_room) + ": no room for " + std::to_string(need >> 20) + " MiB of deflate scratch (" + g_err + ")") : rc;
+    }
+    if (lds > 48 * 1024 && !whole_cu) {
+        HIPCHK(hipFuncSetAttribute(k4, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIPCHK(hipFuncSetAttribute(k2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        whole_cu = true;
+    }
+    return CHN_OK;
+}
+// f(integral_constant<int, BITS>): the kernels' form for a batch with N (4-bit codes) or without (2-bit codes: half the LDS, twice the
+// wavefronts for long reads)
+template <class F>
+static void gz_by_bits(int bits, F f) {
+    if (bits == 4) f(std::integral_constant<int, 4>());
+    else f(std::integral_constant<int, 2>());
+}
+
+// The kernel's LDS (and with it the number of reads a CU works on at once) goes with the longest read of a launch, so a host batch is
+// cut into occupancy classes (below), one launch per class in use; a device batch is one launch sized by the caller's bound.
+static int submit_gzip_column(chn_stream *s, Slot &sl, const chn_batch *b, const uint32_t *bases, const uint32_t *nmask, const uint64_t *off1, const uint64_t *off2,
+                              uint64_t n, bool paired) {
+    sl.want_gzt = b->gzip_tallies != 0 && !sl.list_mode;
+    if (sl.want_gzt && b->gzip_output > CHN_GZIP_SIZES_ALL) return fail(CHN_E_INVALID, "chn_batch.gzip_output: unknown value");
+    if (sl.want_gzt && b->gzip_output == CHN_GZIP_SIZES_ALL && b->on_device)
+        return fail(CHN_E_INVALID, "chn_batch.gzip_output = CHN_GZIP_SIZES_ALL: host batches only");
+    sl.gz_output = b->gzip_output;
+    if (!sl.want_gzt) return CHN_OK;
+    int rc = sl.d_gzt.ensure((size_t)s->cfg.max_reads * GZT_WORDS * 2);
+    if (rc) return rc;
+    const int bits = nmask ? 4 : 2;
+    const uint32_t bound = std::min<uint32_t>(b->gzip_tallies, GZT_MAX_LEN);
+    // CHN_GZIP_SIZES_ALL: k_gzip_long sizes the reads beyond the tally kernel's reach -- longer than GZT_MAX_LEN (on its own stream,
+    // beside the tally launches) and those the tallies hand back for a second deflate block (behind the tally launches)
+    const bool all_sizes = sl.gz_output == CHN_GZIP_SIZES_ALL;
+    const uint32_t long_bound = b->gzip_tallies;
+    const size_t cap_n = (size_t)s->cfg.max_reads;
+    bool long_launch = false;  // a k_gzip_long launch on stream5: the sizes are formed there, behind it and behind the tallies
+    if (all_sizes) {
+        if (!s->stream5) {
+            int prio_least = 0, prio_greatest = 0;
+            HIPCHK(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+            HIPCHK(hipStreamCreateWithPriority(&s->stream5, hipStreamNonBlocking, prio_least));
+        }
+        if ((rc = sl.d_gzlong.ensure((cap_n + 64) * 4))) return rc;
+        HIPCHK(hipMemsetAsync(sl.d_gzlong.p, 0, n * 4, s->stream0));  // 0: not sized (yet)
+        HIPCHK(hipMemsetAsync(sl.d_gzlong.as<uint32_t>() + cap_n, 0, 64 * 4, s->stream0));
+    }
+    // one k_gzip_long launch
+    auto launch_long = [&](hipStream_t st, DevBuf &scratch, uint32_t ctr, uint32_t filter, const uint32_t *index, uint32_t count) -> int {
+        if (count == 0) return CHN_OK;
+        const size_t lds = gzl_lds_bytes(bits);
+        uint32_t grid = 0;
+        if (int rc2 = gz_launch_room(s, lds, ~0u, count, GZL_STRIDE32, scratch, false, "gzip sizes of long reads", (const void *)k_gzip_long<4>, (const void *)k_gzip_long<2>,
+                                     s->gzl_big_lds, grid))
+            return rc2;
+        GzlArgs gl;
+        std::memset(&gl, 0, sizeof gl);
+        gl.bases = bases; gl.nmask = nmask; gl.off1 = off1; gl.off2 = off2; gl.len1 = sl.len1; gl.len2 = sl.len2; gl.n_bases = b->n_bases;
+        gl.bound = long_bound; gl.short_max = bound; gl.filter = filter; gl.tallies = sl.d_gzt.as<uint16_t>();
+        gl.index = index; gl.count = count; gl.sizes = sl.d_gzlong.as<uint32_t>();
+        gl.scratch = scratch.as<uint32_t>(); gl.counter = sl.d_gzlong.as<uint32_t>() + cap_n + ctr;
+        gz_by_bits(bits, [&](auto B) { hipLaunchKernelGGL(k_gzip_long<decltype(B)::value>, dim3(grid), dim3(WAVE), lds, st, gl); });
+        HIPCHK(hipGetLastError());
+        return CHN_OK;
+    };
+    HIPCHK(hipMemsetAsync(sl.d_gzt.p, 1, n * GZT_WORDS * 2, s->stream3));  // status word != 0: "not tallied" unless a launch says otherwise
+    GztArgs g;
+    std::memset(&g, 0, sizeof g);
+    g.bases = bases; g.nmask = nmask; g.off1 = off1; g.off2 = off2; g.len1 = sl.len1; g.len2 = sl.len2;
+    g.n_reads = (uint32_t)n; g.out = sl.d_gzt.as<uint16_t>(); g.n_bases = b->n_bases;
+    // every launch of the batch takes its reads from a counter of its own
+    if ((rc = sl.d_gzctr.ensure(32 * 4))) return rc;
+    HIPCHK(hipMemsetAsync(sl.d_gzctr.p, 0, 32 * 4, s->stream3));
+    uint32_t n_launch = 0;
+    // one k_gzip_tally launch (LDS: half a byte per letter; scratch: 6 bytes per letter)
+    auto launch = [&](const uint32_t *index, uint32_t count, uint32_t max_len) -> int {
+        if (count == 0) return CHN_OK;
+        size_t glds = gzt_lds_bytes(max_len, bits);
+        if (const char *pad = diag_env("CHN_GZT_LDS_PAD")) glds += (size_t)std::atoi(pad);  // occupancy-sensitivity diagnostic
+        if (glds > 160 * 1024) return fail(CHN_E_INVALID, "deflate tallies: read too long for a CU's LDS");
+        uint32_t max_wpc = GZT_WAVES_PER_CU;
+        if (const char *w = diag_env("CHN_GZT_WAVES_PER_CU")) max_wpc = (uint32_t)std::max(1, std::min((int)max_wpc, std::atoi(w)));
+        g.index = index; g.count = count; g.max_len = max_len;
+        g.stride32 = gzt_stride32(max_len);
+        uint32_t grid = 0;
+        if (int rc2 = gz_launch_room(s, glds, max_wpc, count, g.stride32, s->d_gzscratch, true, nullptr, (const void *)k_gzip_tally<4>, (const void *)k_gzip_tally<2>,
+                                     s->gzt_big_lds, grid))
+            return rc2;
+        g.scratch = s->d_gzscratch.as<uint32_t>();
+        g.counter = sl.d_gzctr.as<uint32_t>() + (n_launch++ & 31u);
+        gz_by_bits(bits, [&](auto B) { hipLaunchKernelGGL(k_gzip_tally<decltype(B)::value>, dim3(grid), dim3(WAVE), glds, s->stream3, g); });
+        HIPCHK(hipGetLastError());
+        return CHN_OK;
+    };
+    if (!b->on_device) {
+        // Counting sort of the read numbers by OCCUPANCY class: class w holds the reads of which w wavefronts fit a CU's LDS
+        // (2.5 bytes per letter); reads short enough for 16 and more share class 16.  One launch per class in use, its LDS sized
+        // for the longest read of the class in this batch -- few launches with many reads each (512-letter classes left a
+        // long-read batch with some 90 launches of 30 reads on a 256-CU device).
+        const uint32_t NCLS = 17;  // classes 1 .. 16 (0 unused)
+        const size_t lds_cu = (size_t)160 * 1024;
+        uint32_t start[NCLS + 1], cmax[NCLS];
+        std::memset(start, 0, sizeof start);
+        std::memset(cmax, 0, sizeof cmax);
+        auto cls_of = [&](uint64_t i, uint32_t &L32) -> uint32_t {
+            const uint64_t L = (uint64_t)b->seg1_length[i] + (paired ? b->seg2_length[i] : 0);
+            if (L == 0 || L > bound) return NCLS;
+            L32 = (uint32_t)L;
+            return (uint32_t)std::min<size_t>(16, std::max<size_t>(1, lds_cu / gzt_lds_bytes(L32, bits)));
+        };
+        for (uint64_t i = 0; i < n; ++i) { uint32_t L = 0; const uint32_t c = cls_of(i, L); if (c < NCLS) { ++start[c + 1]; cmax[c] = std::max(cmax[c], L); } }
+        for (uint32_t c = 0; c < NCLS; ++c) start[c + 1] += start[c];
+        sl.h_gzidx.resize(start[NCLS]);
+        {
+            uint32_t fill[NCLS];
+            std::memcpy(fill, start, sizeof fill);
+            for (uint64_t i = 0; i < n; ++i) { uint32_t L = 0; const uint32_t c = cls_of(i, L); if (c < NCLS) sl.h_gzidx[fill[c]++] = (uint32_t)i; }
+        }
+        // CHN_GZIP_SIZES_ALL: behind the class lists, the reads beyond GZT_MAX_LEN (longest first), then the tallied reads long
+        // enough to reach a second deflate block (at least GZT_SYMBOL_LIMIT letters)
+        const size_t long_at = sl.h_gzidx.size();
+        size_t rerun_at = long_at;
+        if (all_sizes) {
+            for (uint64_t i = 0; i < n; ++i) {
+                const uint64_t L = (uint64_t)b->seg1_length[i] + (paired ? b->seg2_length[i] : 0);
+                if (L > GZT_MAX_LEN && L <= long_bound && L <= GZL_MAX_READ) sl.h_gzidx.push_back((uint32_t)i);
+            }
+            std::sort(sl.h_gzidx.begin() + long_at, sl.h_gzidx.end(), [&](uint32_t x, uint32_t y) {
+                const uint64_t lx = (uint64_t)b->seg1_length[x] + (paired ? b->seg2_length[x] : 0), ly = (uint64_t)b->seg1_length[y] + (paired ? b->seg2_length[y] : 0);
+                return lx != ly ? lx > ly : x < y;
+            });
+            rerun_at = sl.h_gzidx.size();
+            for (size_t j = 0; j < long_at; ++j) {
+                const uint32_t i = sl.h_gzidx[j];
+                if ((uint64_t)b->seg1_length[i] + (paired ? b->seg2_length[i] : 0) >= GZT_SYMBOL_LIMIT) sl.h_gzidx.push_back(i);
+            }
+        }
+        // (on the copy stream: a pageable upload on the tally stream would wait for the previous batch's tally kernels)
+        if ((rc = upload(sl.d_gzidx, sl.h_gzidx.data(), sl.h_gzidx.size() * 4, s->stream0, (size_t)s->cfg.max_reads * 4 * (all_sizes ? 2 : 1)))) return rc;
+        HIPCHK(hipEventRecord(sl.bases_up, s->stream0));
+        HIPCHK(hipStreamWaitEvent(s->stream3, sl.bases_up, 0));
+        if (all_sizes && rerun_at > long_at) {
+            HIPCHK(hipStreamWaitEvent(s->stream5, sl.bases_up, 0));
+            if ((rc = launch_long(s->stream5, s->d_gzlscratch[0], 0, GZL_ALL, sl.d_gzidx.as<uint32_t>() + long_at, (uint32_t)(rerun_at - long_at)))) return rc;
+            long_launch = true;
+        }
+        for (uint32_t c = 1; c < NCLS; ++c)  // longest first: the slow, low-occupancy launches start early
+            if ((rc = launch(sl.d_gzidx.as<uint32_t>() + start[c], start[c + 1] - start[c], cmax[c]))) return rc;
+        if (all_sizes && (rc = launch_long(s->stream3, s->d_gzlscratch[1], 1, GZL_HANDED_BACK, sl.d_gzidx.as<uint32_t>() + rerun_at, (uint32_t)(sl.h_gzidx.size() - rerun_at)))) return rc;
+    } else {
+        HIPCHK(hipEventRecord(sl.bases_up, s->stream0));
+        HIPCHK(hipStreamWaitEvent(s->stream3, sl.bases_up, 0));
+        if ((rc = launch(nullptr, (uint32_t)n, bound))) return rc;
+    }
+    // where the sizes are formed and downloaded: behind the tallies on stream3, or -- with a long-read launch -- on stream5 behind both,
+    // so that the next batch's tally launches on stream3 do not queue behind this batch's longest read
+    hipStream_t zs = s->stream3;
+    if (long_launch) {
+        HIPCHK(hipEventRecord(sl.gzt_done, s->stream3));
+        HIPCHK(hipStreamWaitEvent(s->stream5, sl.gzt_done, 0));
+        zs = s->stream5;
+    }
+    if (sl.gz_output != CHN_GZIP_TALLIES) {  // the sizes from the tallies, one lane per read
+        if ((rc = sl.d_gzsize.ensure((size_t)s->cfg.max_reads * 4))) return rc;
+        GzSizeArgs gs;
+        gs.tallies = sl.d_gzt.as<uint16_t>(); gs.len1 = sl.len1; gs.len2 = sl.len2; gs.n_reads = (uint32_t)n; gs.sizes = sl.d_gzsize.as<uint32_t>();
+        gs.long_sizes = all_sizes ? sl.d_gzlong.as<uint32_t>() : nullptr;  // k_gzip_long's sizes fill in where the tallies hand a read back
+        hipLaunchKernelGGL(k_gzip_size, dim3((uint32_t)((n + WAVE - 1) / WAVE)), dim3(WAVE), 0, zs, gs);
+        HIPCHK(hipGetLastError());
+    }
+    sl.gz_staged = false;
+    if (!b->on_device) {
+        if (sl.gz_output == CHN_GZIP_TALLIES || sl.gz_output == CHN_GZIP_BOTH) {
+            if ((rc = sl.h_gzt.ensure(n * GZT_WORDS * 2))) return rc;
+            HIPCHK(hipMemcpyAsync(sl.h_gzt.p, sl.d_gzt.p, n * GZT_WORDS * 2, hipMemcpyDeviceToHost, s->stream3));
+        }
+        if (sl.gz_output != CHN_GZIP_TALLIES) {
+            if ((rc = sl.h_gzsize.ensure(n * 4))) return rc;
+            HIPCHK(hipMemcpyAsync(sl.h_gzsize.p, sl.d_gzsize.p, n * 4, hipMemcpyDeviceToHost, zs));
+        }
+        sl.gz_staged = true;
+    }
+    HIPCHK(hipEventRecord(sl.gz_done, zs));
+    return CHN_OK;
+}
+
 // list_kind != 0: stop after logging the minimiser VALUES -- LIST_DENSE (dense row-sharded mode, chn_minimisers: deterministic
 // worst-case layout on s->big) or LIST_SPARSE (sparse row-sharded mode: density-sized regions claimed from the cursor on s->shx);
 // 0: the whole chain
@@ -357,192 +556,8 @@ static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind, bool bo
     for (int i = 0; i < 4; ++i) sl.ev_used[i] = false;
     if (prof) HIPCHK(hipEventRecord(sl.ev[6], s->stream));
 
-    // 0. deflate tallies for the gzip column, if asked for: their own stream, as soon as the bases are on the device.  The kernel's
-    // LDS (and with it the number of reads a CU works on at once) goes with the longest read of a launch, so a host batch is cut
-    // into occupancy classes (below), one launch per class in use; a device batch is one launch sized by the caller's bound.
-    sl.want_gzt = b->gzip_tallies != 0 && !list_mode;
-    if (sl.want_gzt && b->gzip_output > CHN_GZIP_SIZES_ALL) return fail(CHN_E_INVALID, "chn_batch.gzip_output: unknown value");
-    if (sl.want_gzt && b->gzip_output == CHN_GZIP_SIZES_ALL && b->on_device)
-        return fail(CHN_E_INVALID, "chn_batch.gzip_output = CHN_GZIP_SIZES_ALL: host batches only");
-    sl.gz_output = b->gzip_output;
-    if (sl.want_gzt) {
-        int rc = sl.d_gzt.ensure((size_t)s->cfg.max_reads * GZT_WORDS * 2);
-        if (rc) return rc;
-        const uint32_t bound = std::min<uint32_t>(b->gzip_tallies, GZT_MAX_LEN);
-        // CHN_GZIP_SIZES_ALL: k_gzip_long sizes the reads beyond the tally kernel's reach -- longer than GZT_MAX_LEN (on its own stream,
-        // beside the tally launches) and those the tallies hand back for a second deflate block (behind the tally launches)
-        const bool all_sizes = sl.gz_output == CHN_GZIP_SIZES_ALL;
-        const uint32_t long_bound = b->gzip_tallies;
-        const size_t cap_n = (size_t)s->cfg.max_reads;
-        bool long_launch = false;  // a k_gzip_long launch on stream5: the sizes are formed there, behind it and behind the tallies
-        if (all_sizes) {
-            if (!s->stream5) {
-                int prio_least = 0, prio_greatest = 0;
-                HIPCHK(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-                HIPCHK(hipStreamCreateWithPriority(&s->stream5, hipStreamNonBlocking, prio_least));
-            }
-            if ((rc = sl.d_gzlong.ensure((cap_n + 64) * 4))) return rc;
-            HIPCHK(hipMemsetAsync(sl.d_gzlong.p, 0, n * 4, s->stream0));  // 0: not sized (yet)
-            HIPCHK(hipMemsetAsync(sl.d_gzlong.as<uint32_t>() + cap_n, 0, 64 * 4, s->stream0));
-            if (!s->gzl_big_lds) {
-                HIPCHK(hipFuncSetAttribute((const void *)k_gzip_long<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                HIPCHK(hipFuncSetAttribute((const void *)k_gzip_long<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                s->gzl_big_lds = true;
-            }
-        }
-        // one k_gzip_long launch: as many wavefronts as the device holds at once (LDS), each taking the next read from a counter
-        auto launch_long = [&](hipStream_t st, DevBuf &scratch, uint32_t ctr, uint32_t filter, const uint32_t *index, uint32_t count) -> int {
-            if (count == 0) return CHN_OK;
-            const int bits = nmask ? 4 : 2;
-            const size_t lds = gzl_lds_bytes(bits);
-            const uint32_t wpc = (uint32_t)std::max<size_t>(1, (size_t)160 * 1024 / lds);
-            const uint32_t grid = (uint32_t)std::min<uint64_t>(count, (uint64_t)s->n_cus * wpc);
-            const size_t need = (size_t)grid * GZL_STRIDE32 * 4;
-            if (need > scratch.cap) {
-                int rc2 = scratch.ensure(need);
-                if (rc2) return fail(CHN_E_NOMEM, "gzip sizes of long reads: no room for " + std::to_string(need >> 20) + " MiB of deflate scratch (" + g_err + ")");
-            }
-            GzlArgs gl;
-            std::memset(&gl, 0, sizeof gl);
-            gl.bases = bases; gl.nmask = nmask; gl.off1 = off1; gl.off2 = off2; gl.len1 = sl.len1; gl.len2 = sl.len2; gl.n_bases = b->n_bases;
-            gl.bound = long_bound; gl.short_max = bound; gl.filter = filter; gl.tallies = sl.d_gzt.as<uint16_t>();
-            gl.index = index; gl.count = count; gl.sizes = sl.d_gzlong.as<uint32_t>();
-            gl.scratch = scratch.as<uint32_t>(); gl.counter = sl.d_gzlong.as<uint32_t>() + cap_n + ctr;
-            if (bits == 4) hipLaunchKernelGGL(k_gzip_long<4>, dim3(grid), dim3(WAVE), lds, st, gl);
-            else hipLaunchKernelGGL(k_gzip_long<2>, dim3(grid), dim3(WAVE), lds, st, gl);
-            HIPCHK(hipGetLastError());
-            return CHN_OK;
-        };
-        HIPCHK(hipMemsetAsync(sl.d_gzt.p, 1, n * GZT_WORDS * 2, s->stream3));  // status word != 0: "not tallied" unless a launch says otherwise
-        GztArgs g;
-        std::memset(&g, 0, sizeof g);
-        g.bases = bases; g.nmask = nmask; g.off1 = off1; g.off2 = off2; g.len1 = sl.len1; g.len2 = sl.len2;
-        g.n_reads = (uint32_t)n; g.out = sl.d_gzt.as<uint16_t>(); g.n_bases = b->n_bases;
-        // every launch of the batch takes its reads from a counter of its own
-        if ((rc = sl.d_gzctr.ensure(32 * 4))) return rc;
-        HIPCHK(hipMemsetAsync(sl.d_gzctr.p, 0, 32 * 4, s->stream3));
-        uint32_t n_launch = 0;
-        auto launch = [&](const uint32_t *index, uint32_t count, uint32_t max_len) -> int {
-            if (count == 0) return CHN_OK;
-            // As many wavefronts as the device holds at once (LDS: half a byte per letter), each with its own scratch for the positions-by-class
-            // and position-info arrays (6 bytes per letter).  The launches of a stream run one after the other (one HIP stream), so they share
-            // the scratch; it only grows (hipFree waits for the kernels in flight).
-            const int bits = nmask ? 4 : 2;  // a batch without N: the codes two bits each (half the LDS: twice the wavefronts for long reads)
-            size_t glds = gzt_lds_bytes(max_len, bits);
-            if (const char *pad = diag_env("CHN_GZT_LDS_PAD")) glds += (size_t)std::atoi(pad);  // occupancy-sensitivity diagnostic
-            if (glds > 160 * 1024) return fail(CHN_E_INVALID, "deflate tallies: read too long for a CU's LDS");
-            uint32_t wpc = (uint32_t)std::min<size_t>(GZT_WAVES_PER_CU, std::max<size_t>(1, (size_t)160 * 1024 / glds));
-            if (const char *w = diag_env("CHN_GZT_WAVES_PER_CU")) wpc = std::max(1, std::min((int)wpc, std::atoi(w)));
-            const uint32_t grid = (uint32_t)std::min<uint64_t>(count, (uint64_t)s->n_cus * wpc);
-            g.index = index; g.count = count; g.max_len = max_len;
-            g.stride32 = gzt_stride32(max_len);
-            const size_t need = (size_t)grid * g.stride32 * 4;
-            if (need > s->d_gzscratch.cap) {
-                int rc2 = s->d_gzscratch.ensure(need + need / 4);
-                if (rc2) return rc2;
-            }
-            g.scratch = s->d_gzscratch.as<uint32_t>();
-            g.counter = sl.d_gzctr.as<uint32_t>() + (n_launch++ & 31u);
-            if (glds > 48 * 1024 && !s->gzt_big_lds) {  // once: up to the whole CU
-                HIPCHK(hipFuncSetAttribute((const void *)k_gzip_tally<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                HIPCHK(hipFuncSetAttribute((const void *)k_gzip_tally<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                s->gzt_big_lds = true;
-            }
-            if (bits == 4) hipLaunchKernelGGL(k_gzip_tally<4>, dim3(grid), dim3(WAVE), glds, s->stream3, g);
-            else hipLaunchKernelGGL(k_gzip_tally<2>, dim3(grid), dim3(WAVE), glds, s->stream3, g);
-            HIPCHK(hipGetLastError());
-            return CHN_OK;
-        };
-        if (!b->on_device) {
-            // Counting sort of the read numbers by OCCUPANCY class: class w holds the reads of which w wavefronts fit a CU's LDS
-            // (2.5 bytes per letter); reads short enough for 16 and more share class 16.  One launch per class in use, its LDS sized
-            // for the longest read of the class in this batch -- few launches with many reads each (512-letter classes left a
-            // long-read batch with some 90 launches of 30 reads on a 256-CU device).
-            const uint32_t NCLS = 17;  // classes 1 .. 16 (0 unused)
-            const size_t lds_cu = (size_t)160 * 1024;
-            uint32_t start[NCLS + 1], cmax[NCLS];
-            std::memset(start, 0, sizeof start);
-            std::memset(cmax, 0, sizeof cmax);
-            auto cls_of = [&](uint64_t i, uint32_t &L32) -> uint32_t {
-                const uint64_t L = (uint64_t)b->seg1_length[i] + (paired ? b->seg2_length[i] : 0);
-                if (L == 0 || L > bound) return NCLS;
-                L32 = (uint32_t)L;
-                return (uint32_t)std::min<size_t>(16, std::max<size_t>(1, lds_cu / gzt_lds_bytes(L32, nmask ? 4 : 2)));
-            };
-            for (uint64_t i = 0; i < n; ++i) { uint32_t L = 0; const uint32_t c = cls_of(i, L); if (c < NCLS) { ++start[c + 1]; cmax[c] = std::max(cmax[c], L); } }
-            for (uint32_t c = 0; c < NCLS; ++c) start[c + 1] += start[c];
-            sl.h_gzidx.resize(start[NCLS]);
-            {
-                uint32_t fill[NCLS];
-                std::memcpy(fill, start, sizeof fill);
-                for (uint64_t i = 0; i < n; ++i) { uint32_t L = 0; const uint32_t c = cls_of(i, L); if (c < NCLS) sl.h_gzidx[fill[c]++] = (uint32_t)i; }
-            }
-            // CHN_GZIP_SIZES_ALL: behind the class lists, the reads beyond GZT_MAX_LEN (longest first), then the tallied reads long
-            // enough to reach a second deflate block (at least GZT_SYMBOL_LIMIT letters)
-            const size_t long_at = sl.h_gzidx.size();
-            size_t rerun_at = long_at;
-            if (all_sizes) {
-                for (uint64_t i = 0; i < n; ++i) {
-                    const uint64_t L = (uint64_t)b->seg1_length[i] + (paired ? b->seg2_length[i] : 0);
-                    if (L > GZT_MAX_LEN && L <= long_bound && L <= GZL_MAX_READ) sl.h_gzidx.push_back((uint32_t)i);
-                }
-                std::sort(sl.h_gzidx.begin() + long_at, sl.h_gzidx.end(), [&](uint32_t x, uint32_t y) {
-                    const uint64_t lx = (uint64_t)b->seg1_length[x] + (paired ? b->seg2_length[x] : 0), ly = (uint64_t)b->seg1_length[y] + (paired ? b->seg2_length[y] : 0);
-                    return lx != ly ? lx > ly : x < y;
-                });
-                rerun_at = sl.h_gzidx.size();
-                for (size_t j = 0; j < long_at; ++j) {
-                    const uint32_t i = sl.h_gzidx[j];
-                    if ((uint64_t)b->seg1_length[i] + (paired ? b->seg2_length[i] : 0) >= GZT_SYMBOL_LIMIT) sl.h_gzidx.push_back(i);
-                }
-            }
-            // (on the copy stream: a pageable upload on the tally stream would wait for the previous batch's tally kernels)
-            if ((rc = upload(sl.d_gzidx, sl.h_gzidx.data(), sl.h_gzidx.size() * 4, s->stream0, (size_t)s->cfg.max_reads * 4 * (all_sizes ? 2 : 1)))) return rc;
-            HIPCHK(hipEventRecord(sl.bases_up, s->stream0));
-            HIPCHK(hipStreamWaitEvent(s->stream3, sl.bases_up, 0));
-            if (all_sizes && rerun_at > long_at) {
-                HIPCHK(hipStreamWaitEvent(s->stream5, sl.bases_up, 0));
-                if ((rc = launch_long(s->stream5, s->d_gzlscratch[0], 0, GZL_ALL, sl.d_gzidx.as<uint32_t>() + long_at, (uint32_t)(rerun_at - long_at)))) return rc;
-                long_launch = true;
-            }
-            for (uint32_t c = 1; c < NCLS; ++c)  // longest first: the slow, low-occupancy launches start early
-                if ((rc = launch(sl.d_gzidx.as<uint32_t>() + start[c], start[c + 1] - start[c], cmax[c]))) return rc;
-            if (all_sizes && (rc = launch_long(s->stream3, s->d_gzlscratch[1], 1, GZL_HANDED_BACK, sl.d_gzidx.as<uint32_t>() + rerun_at, (uint32_t)(sl.h_gzidx.size() - rerun_at)))) return rc;
-        } else {
-            HIPCHK(hipEventRecord(sl.bases_up, s->stream0));
-            HIPCHK(hipStreamWaitEvent(s->stream3, sl.bases_up, 0));
-            if ((rc = launch(nullptr, (uint32_t)n, bound))) return rc;
-        }
-        // where the sizes are formed and downloaded: behind the tallies on stream3, or -- with a long-read launch -- on stream5 behind both,
-        // so that the next batch's tally launches on stream3 do not queue behind this batch's longest read
-        hipStream_t zs = s->stream3;
-        if (long_launch) {
-            HIPCHK(hipEventRecord(sl.gzt_done, s->stream3));
-            HIPCHK(hipStreamWaitEvent(s->stream5, sl.gzt_done, 0));
-            zs = s->stream5;
-        }
-        if (sl.gz_output != CHN_GZIP_TALLIES) {  // the sizes from the tallies, one lane per read
-            if ((rc = sl.d_gzsize.ensure((size_t)s->cfg.max_reads * 4))) return rc;
-            GzSizeArgs gs;
-            gs.tallies = sl.d_gzt.as<uint16_t>(); gs.len1 = sl.len1; gs.len2 = sl.len2; gs.n_reads = (uint32_t)n; gs.sizes = sl.d_gzsize.as<uint32_t>();
-            gs.long_sizes = all_sizes ? sl.d_gzlong.as<uint32_t>() : nullptr;  // k_gzip_long's sizes fill in where the tallies hand a read back
-            hipLaunchKernelGGL(k_gzip_size, dim3((uint32_t)((n + WAVE - 1) / WAVE)), dim3(WAVE), 0, zs, gs);
-            HIPCHK(hipGetLastError());
-        }
-        sl.gz_staged = false;
-        if (!b->on_device) {
-            if (sl.gz_output == CHN_GZIP_TALLIES || sl.gz_output == CHN_GZIP_BOTH) {
-                if ((rc = sl.h_gzt.ensure(n * GZT_WORDS * 2))) return rc;
-                HIPCHK(hipMemcpyAsync(sl.h_gzt.p, sl.d_gzt.p, n * GZT_WORDS * 2, hipMemcpyDeviceToHost, s->stream3));
-            }
-            if (sl.gz_output != CHN_GZIP_TALLIES) {
-                if ((rc = sl.h_gzsize.ensure(n * 4))) return rc;
-                HIPCHK(hipMemcpyAsync(sl.h_gzsize.p, sl.d_gzsize.p, n * 4, hipMemcpyDeviceToHost, zs));
-            }
-            sl.gz_staged = true;
-        }
-        HIPCHK(hipEventRecord(sl.gz_done, zs));
-    }
+    // 0. deflate tallies for the gzip column, if asked for: their own stream, as soon as the bases are on the device
+    if (int rc = submit_gzip_column(s, sl, b, bases, nmask, off1, off2, n, paired)) return rc;
 
     dt[2] = dnow();
     // 1. length-class ordering: two launches (the first also clears the slot's control words).  They run on the copy stream, behind
