@@ -76,13 +76,18 @@ class TextResult(C.Structure):
 INFLATE_MAX_OUT = 65536      # CHN_INFLATE_MAX_OUT
 # chn_inflate_job.status values
 INFLATE_STATUS = {0: "ok", 1: "input exhausted", 2: "bad block header", 3: "bad code lengths", 4: "bad symbol or distance",
-                  5: "more output than out_length", 6: "stream ended short of out_length"}
+                  5: "more output than out_length", 6: "stream ended short of out_length", 7: "CRC-32 differs from the expected one"}
+INFLATE_E_CRC = 7            # CHN_INFLATE_E_CRC
 
 
 class InflateJob(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_members", C.c_uint64), ("in_", C.c_void_p), ("in_bytes", C.c_uint64),
                 ("in_offset", C.c_void_p), ("in_length", C.c_void_p), ("out", C.c_void_p), ("out_bytes", C.c_uint64),
                 ("out_offset", C.c_void_p), ("out_length", C.c_void_p), ("status", C.c_void_p)]
+
+
+class InflateCrc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("expected", C.c_void_p), ("crc32", C.c_void_p)]
 
 
 class SynthReadsOut(C.Structure):
@@ -97,7 +102,7 @@ EXPORTS = ["chn_index_create", "chn_index_upload_rows", "chn_index_device_words"
            "chn_stream_last_batch_bytes", "chn_synth_genomes", "chn_synth_fill_index", "chn_synth_plant", "chn_synth_reads",
            "chn_device_free", "chn_device_download", "chn_device_malloc", "chn_device_upload", "chn_host_alloc", "chn_host_free", "chn_shard_minimise",
            "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_text_submit", "chn_text_wait", "chn_text_pack", "chn_inflate_create", "chn_inflate_run",
-           "chn_inflate_run_host", "chn_inflate_destroy", "chn_inflate_kernel_ms", "chn_last_error", "chn_version"]
+           "chn_inflate_run_host", "chn_inflate_destroy", "chn_inflate_kernel_ms", "chn_inflate_run_crc", "chn_inflate_run_host_crc", "chn_last_error", "chn_version"]
 
 _L.chn_last_error.restype = C.c_char_p
 _L.chn_version.restype = C.c_char_p
@@ -153,6 +158,8 @@ _L.chn_inflate_run.argtypes = [C.c_void_p, C.POINTER(InflateJob)]
 _L.chn_inflate_run_host.argtypes = [C.POINTER(InflateJob)]
 _L.chn_inflate_destroy.argtypes = [C.c_void_p]
 _L.chn_inflate_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+_L.chn_inflate_run_crc.argtypes = [C.c_void_p, C.POINTER(InflateJob), C.POINTER(InflateCrc)]
+_L.chn_inflate_run_host_crc.argtypes = [C.POINTER(InflateJob), C.POINTER(InflateCrc)]
 
 
 class ChnError(RuntimeError):
@@ -584,21 +591,50 @@ def inflate_job(members, sizes, guard=0, out=None):
 
 
 def _inflate_results(a):
-    """(list of bytes or None, status array) of a finished job; the guard bytes must be untouched"""
+    """(list of bytes -- None where the decode failed --, status array) of a finished job; the guard bytes must be untouched"""
     res, st = [], a["status"][:a["n"]].copy()
     for i in range(a["n"]):
         o, l = int(a["out_offset"][i]), int(a["out_length"][i])
-        res.append(a["out"][o:o + l].tobytes() if st[i] == 0 else None)
+        res.append(a["out"][o:o + l].tobytes() if st[i] in (0, INFLATE_E_CRC) else None)  # (a CRC mismatch still has its bytes)
         if a["guard"] and not (a["out"][o + l:o + l + a["guard"]] == 0xA5).all():
             raise ChnError("inflate: member %d wrote behind its out_length" % i)
     return res, st
 
 
-def inflate_host(members, sizes, guard=0):
-    """chn_inflate_run_host: the decoder the GPU runs, on the CPU.  Returns (list of bytes, or None where status != 0; status array)."""
+def inflate_crc(n, expected=None, want_crc=False):
+    """the chn_inflate_crc of a job of n members: `expected` (n CRC-32 values) is compared, want_crc asks for the CRCs.  Returns
+    (struct, arrays) -- `arrays` keeps the memory alive; arrays["crc32"] is None unless want_crc."""
+    c = InflateCrc()
+    c.struct_size, c.reserved = C.sizeof(InflateCrc), 0
+    exp = None
+    if expected is not None:
+        exp = np.array([int(x) & 0xFFFFFFFF for x in expected], np.uint32)
+        assert exp.size == n
+        exp = np.concatenate([exp, np.zeros(1, np.uint32)])  # (never empty)
+        c.expected = exp.ctypes.data
+    crc = np.full(max(n, 1), 0xFFFFFFFF, np.uint32) if want_crc else None
+    if want_crc:
+        c.crc32 = crc.ctypes.data
+    return c, dict(expected=exp, crc32=crc)
+
+
+def _inflate_crc_results(a, ca, want_crc):
+    """_inflate_results, and the CRC array behind it if it was asked for"""
+    res, st = _inflate_results(a)
+    return (res, st, ca["crc32"][:a["n"]].copy()) if want_crc else (res, st)
+
+
+def inflate_host(members, sizes, guard=0, expected=None, want_crc=False):
+    """chn_inflate_run_host: the decoder the GPU runs, on the CPU.  Returns (list of bytes, or None where status != 0; status array).
+    expected: the members' CRC-32 values to compare with (a difference is status INFLATE_E_CRC); want_crc: the CRC-32 array is
+    returned as a third value (chn_inflate_run_host_crc: the 64 slices and the join the kernel runs, serially)."""
     j, a = inflate_job(members, sizes, guard)
-    _chk(_L.chn_inflate_run_host(C.byref(j)))
-    return _inflate_results(a)
+    if expected is None and not want_crc:
+        _chk(_L.chn_inflate_run_host(C.byref(j)))
+        return _inflate_results(a)
+    c, ca = inflate_crc(a["n"], expected, want_crc)
+    _chk(_L.chn_inflate_run_host_crc(C.byref(j), C.byref(c)))
+    return _inflate_crc_results(a, ca, want_crc)
 
 
 class Inflater:
@@ -608,16 +644,25 @@ class Inflater:
         self.h = C.c_void_p()
         _chk(_L.chn_inflate_create(device, C.byref(self.h)))
 
-    def run(self, members, sizes, guard=0, out=None):
+    def run(self, members, sizes, guard=0, out=None, expected=None, want_crc=False):
         """members: list of raw deflate streams (bytes); sizes: their expected inflated sizes (<= INFLATE_MAX_OUT).
-        Returns (list of bytes, or None where status != 0; status array)."""
+        Returns (list of bytes, or None where status != 0; status array).  expected / want_crc as in inflate_host
+        (chn_inflate_run_crc: the CRC-32 is taken on the device)."""
         j, a = inflate_job(members, sizes, guard, out)
-        _chk(_L.chn_inflate_run(self.h, C.byref(j)))
-        return _inflate_results(a)
+        if expected is None and not want_crc:
+            _chk(_L.chn_inflate_run(self.h, C.byref(j)))
+            return _inflate_results(a)
+        c, ca = inflate_crc(a["n"], expected, want_crc)
+        _chk(_L.chn_inflate_run_crc(self.h, C.byref(j), C.byref(c)))
+        return _inflate_crc_results(a, ca, want_crc)
 
-    def run_job(self, job):
-        """chn_inflate_run on a prepared InflateJob (inflate_job): no copies on the Python side, for measurements"""
-        _chk(_L.chn_inflate_run(self.h, C.byref(job)))
+    def run_job(self, job, crc=None):
+        """chn_inflate_run (or chn_inflate_run_crc with an InflateCrc) on a prepared InflateJob (inflate_job): no copies on the
+        Python side, for measurements"""
+        if crc is None:
+            _chk(_L.chn_inflate_run(self.h, C.byref(job)))
+        else:
+            _chk(_L.chn_inflate_run_crc(self.h, C.byref(job), C.byref(crc)))
 
     def kernel_ms(self):
         ms = C.c_double()

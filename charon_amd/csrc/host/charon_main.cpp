@@ -198,6 +198,56 @@ int main(int argc, char **argv) {
             return total == ztotal || std::getenv("CHARON_SKIP_ZLIB") ? 0 : 3;
         } catch (std::exception &e) { std::cerr << "charon: " << e.what() << std::endl; return 1; }
     }
+    if (sub == "_bgzf_crc") {  // hidden diagnostic: the CRC-32 pass of the reader's threads over the first members of a BGZF file (no GPU involved)
+        try {                  // _bgzf_crc <file> <members> <-t value> [repetitions]: what CHARON_GPU_INFLATE=1 no longer does on the host
+            if (argc < 5) return 2;
+            g_reader_threads = reader_threads_for(std::max(1, std::atoi(argv[4])));
+            const size_t want = (size_t)std::atol(argv[3]);
+            const int reps = argc > 5 ? std::max(1, std::atoi(argv[5])) : 7;
+            std::ifstream f(argv[2], std::ios::binary);
+            std::vector<unsigned char> text;
+            std::vector<std::pair<size_t, uint32_t>> ms;  // offset in text, size
+            std::vector<uint32_t> crcs;
+            std::vector<unsigned char> body;
+            unsigned char head[18];
+            while (ms.size() < want && f.read(reinterpret_cast<char *>(head), 18)) {
+                if (head[0] != 0x1f || head[1] != 0x8b || head[3] != 4 || head[12] != 'B' || head[13] != 'C') { std::cerr << "charon: not a BGZF member\n"; return 1; }
+                const size_t total = ((size_t)head[16] | ((size_t)head[17] << 8)) + 1;
+                body.resize(total - 18);
+                if (!f.read(reinterpret_cast<char *>(body.data()), (std::streamsize)body.size())) return 1;
+                const unsigned char *tail = body.data() + body.size() - 8;
+                const uint32_t crc = (uint32_t)tail[0] | ((uint32_t)tail[1] << 8) | ((uint32_t)tail[2] << 16) | ((uint32_t)tail[3] << 24);
+                const uint32_t isize = (uint32_t)tail[4] | ((uint32_t)tail[5] << 8) | ((uint32_t)tail[6] << 16) | ((uint32_t)tail[7] << 24);
+                if (isize == 0) continue;
+                const size_t at = text.size();
+                text.resize(at + isize);
+                z_stream zs;
+                std::memset(&zs, 0, sizeof zs);
+                if (inflateInit2(&zs, -15) != Z_OK) return 1;
+                zs.next_in = body.data(); zs.avail_in = (uInt)(body.size() - 8);
+                zs.next_out = text.data() + at; zs.avail_out = isize;
+                const int rc = inflate(&zs, Z_FINISH);
+                inflateEnd(&zs);
+                if (rc != Z_STREAM_END || zs.total_out != isize) { std::cerr << "charon: a member does not inflate\n"; return 1; }
+                ms.emplace_back(at, isize); crcs.push_back(crc);
+            }
+            const int nt = std::max(1, std::min<int>(g_reader_threads, (int)ms.size()));
+            std::vector<double> secs;
+            bool bad = false;
+            for (int r = 0; r <= reps; ++r) {  // the loop BgzfSource::fill ran behind chn_inflate_run; the first round warms up
+                const double t0 = omp_get_wtime();
+#pragma omp parallel for num_threads(nt) schedule(dynamic, 16) reduction(|| : bad)
+                for (long i = 0; i < (long)ms.size(); ++i)
+                    if (fast_crc32((uint32_t)crc32(0L, Z_NULL, 0), text.data() + ms[(size_t)i].first, ms[(size_t)i].second) != crcs[(size_t)i]) bad = true;
+                if (r) secs.push_back(omp_get_wtime() - t0);
+            }
+            std::sort(secs.begin(), secs.end());
+            std::cout << "bgzf_crc: " << ms.size() << " members, " << text.size() << " bytes, " << nt << " threads (" << (g_crc_clmul ? "pclmulqdq folding" : "zlib")
+                      << "): min " << secs.front() * 1e3 << " ms  median " << secs[secs.size() / 2] * 1e3 << " ms  max " << secs.back() * 1e3 << " ms -> "
+                      << text.size() / secs[secs.size() / 2] / 1e9 << " GB/s (median)" << (bad ? "  CRC MISMATCH" : "") << "\n";
+            return bad ? 3 : 0;
+        } catch (std::exception &e) { std::cerr << "charon: " << e.what() << std::endl; return 1; }
+    }
     if (sub == "_gfmt") {  // hidden self-test: format_g6 against printf's %g on random values of every kind a row holds
         const unsigned long long n = argc > 2 ? std::strtoull(argv[2], nullptr, 10) : 1000000ULL;
         unsigned long long x = argc > 3 ? std::strtoull(argv[3], nullptr, 10) : 1, bad = 0, fast = 0;

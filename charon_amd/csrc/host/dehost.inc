@@ -443,7 +443,7 @@ int dehost_main(DehostArguments &opt) {
     // are released when this function is left, after everything that hands slabs back, while the HIP runtime is certainly still up
     g_pin_slabs = opt.text_batches || g_gpu_inflate;  // (CHARON_GPU_INFLATE=1 downloads straight into the slab)
     struct SlabPoolDrain { ~SlabPoolDrain() { std::lock_guard<std::mutex> lk(g_slab_pool.m); g_slab_pool.v.clear(); } } slab_pool_drain;
-    if (g_gpu_inflate) g_log.info("CHARON_GPU_INFLATE=1: BGZF members are inflated on device " + std::to_string(g_gpu_inflate_device) + " (size and CRC-32 still checked on the reader's threads)");
+    if (g_gpu_inflate) g_log.info("CHARON_GPU_INFLATE=1: BGZF members are inflated on device " + std::to_string(g_gpu_inflate_device) + " (size and CRC-32 are checked on the device)");
     if (opt.text_batches) g_log.info("CHARON_TEXT_BATCHES=1: reads go to the device as text (letters -> codes and mean quality on the GPU)");
     // reader thread: parses whole-record blocks while the previous batch is packed / compressed / classified / printed.  It starts
     // before the device is touched, so the first block is parsed while the HIP runtime initialises and the index is decoded.

@@ -77,11 +77,11 @@ SlabPool g_slab_pool;
 // compressed size in a 'BC' extra subfield (SAM specification, section 4.1).  Members are therefore found without inflating anything
 // and inflated in parallel -- what seqan3's bgzf input stream does for the reference's reader (src/dehost_main.cpp:324,335-339).
 // An ordinary .gz is ONE deflate stream and stays on zlib's single inflate (about 0.4 GB/s).
-// CHARON_GPU_INFLATE=1: the members of a block are inflated on the device (chn_inflate_run) instead of in the OpenMP loop below; size and
-// CRC-32 of every member are still checked here, on the reader's threads.
+// CHARON_GPU_INFLATE=1: the members of a block are inflated on the device (chn_inflate_run_crc) instead of in the OpenMP loop below; the
+// size and the CRC-32 of every member are checked there too, against the trailers' values, and come back as the member's status.
 bool g_gpu_inflate = false;
 int g_gpu_inflate_device = 0;
-double g_gpu_inflate_s = 0;  // reader-thread seconds inside chn_inflate_run (CHARON_TIMING)
+double g_gpu_inflate_s = 0;  // reader-thread seconds inside chn_inflate_run_crc (CHARON_TIMING)
 class BgzfSource {
     chn_inflate *gpu_ = nullptr;  // one handle per source, created on first use
     const unsigned char *z_ = nullptr;
@@ -159,10 +159,11 @@ public:
                 throw std::runtime_error(std::string("CHARON_GPU_INFLATE: ") + chn_last_error());
             const size_t n = ms.size();
             std::vector<uint64_t> in_off(n), out_off(n);
-            std::vector<uint32_t> in_len(n), out_len(n), status(n, 0);
+            std::vector<uint32_t> in_len(n), out_len(n), status(n, 0), expected(n);
             for (size_t i = 0; i < n; ++i) {
                 in_off[i] = (uint64_t)(ms[i].cdata - z_); in_len[i] = ms[i].clen;
                 out_off[i] = ms[i].out; out_len[i] = ms[i].isize;
+                expected[i] = ms[i].crc;
             }
             chn_inflate_job job;
             std::memset(&job, 0, sizeof job);
@@ -170,16 +171,13 @@ public:
             job.in = z_; job.in_bytes = size_; job.in_offset = in_off.data(); job.in_length = in_len.data();
             job.out = reinterpret_cast<uint8_t *>(dst); job.out_bytes = total; job.out_offset = out_off.data(); job.out_length = out_len.data();
             job.status = status.data();
+            chn_inflate_crc crc;
+            std::memset(&crc, 0, sizeof crc);
+            crc.struct_size = sizeof crc; crc.expected = expected.data();
             const double t0 = omp_get_wtime();
-            if (chn_inflate_run(gpu_, &job) != CHN_OK) throw std::runtime_error(std::string("CHARON_GPU_INFLATE: ") + chn_last_error());
+            if (chn_inflate_run_crc(gpu_, &job, &crc) != CHN_OK) throw std::runtime_error(std::string("CHARON_GPU_INFLATE: ") + chn_last_error());
             g_gpu_inflate_s += omp_get_wtime() - t0;
-#pragma omp parallel for num_threads(nt) schedule(dynamic, 16) reduction(|| : bad)
-            for (long i = 0; i < (long)n; ++i) {
-                const Member &mb = ms[(size_t)i];
-                if (status[(size_t)i] != 0 ||
-                    fast_crc32((uint32_t)crc32(0L, Z_NULL, 0), reinterpret_cast<const unsigned char *>(dst + mb.out), mb.isize) != mb.crc)
-                    bad = true;
-            }
+            for (size_t i = 0; i < n; ++i) bad = bad || status[i] != 0;  // a decode failure, a wrong size, or CHN_INFLATE_E_CRC
         } else {
 #pragma omp parallel num_threads(nt)
         {

@@ -1,4 +1,4 @@
-// abi_inflate.inc -- chn_inflate_create / chn_inflate_run / chn_inflate_run_host / chn_inflate_destroy: raw deflate members on the device
+// abi_inflate.inc -- chn_inflate_create / chn_inflate_run[_crc] / chn_inflate_run_host[_crc] / chn_inflate_destroy: raw deflate members on the device
 // Part of the single translation unit charon_hip.hip (included in order); not a stand-alone source.
 //
 // chn_inflate_run works through a job in groups of members (about 32 MiB of output each) on three streams of the handle's own:
@@ -6,6 +6,8 @@
 // 16-byte boundary, so nothing of `in` between or around the members is uploaded) and uploaded, and the output of group g - 1 is
 // downloaded -- straight into `out` where that is page-locked and the group's members lie back to back there, through staging otherwise.
 // Two sets of grow-only buffers take turns.
+// With a chn_inflate_crc that names an array, the CRC form of the kernel runs: `expected` travels behind the descriptors in their
+// upload, the CRCs behind the statuses in their download -- no further copy, launch or wait.
 
 static const uint64_t INF_GROUP_OUT = 32ull << 20, INF_GROUP_IN = 64ull << 20;
 static const uint32_t INF_GROUP_MEMBERS = 1u << 16;
@@ -15,7 +17,7 @@ struct InflateSet {
     PinBuf h_in, h_out, h_desc, h_status;
     hipEvent_t up = nullptr, done = nullptr, down = nullptr, k0 = nullptr, k1 = nullptr;
     uint64_t first = 0, n = 0, out_bytes = 0;  // the group in this set
-    bool direct = false, busy = false;
+    bool direct = false, busy = false, crc = false;
 };
 struct chn_inflate {
     int device = 0;
@@ -46,16 +48,34 @@ static int inflate_check_job(const chn_inflate_job *j, const char *who) {
     return CHN_OK;
 }
 
-extern "C" int chn_inflate_run_host(const chn_inflate_job *j) {
-    int rc = inflate_check_job(j, "chn_inflate_run_host");
+static int inflate_check_crc(const chn_inflate_crc *c, const char *who) {
+    if (!c) return CHN_OK;
+    if (c->struct_size != sizeof(chn_inflate_crc)) return fail(CHN_E_INVALID, std::string(who) + ": bad struct_size of the chn_inflate_crc");
+    if (c->reserved) return fail(CHN_E_INVALID, std::string(who) + ": chn_inflate_crc.reserved is not 0");
+    return CHN_OK;
+}
+
+static int inflate_run_host(const chn_inflate_job *j, const chn_inflate_crc *c, const char *who) {
+    int rc = inflate_check_crc(c, who);
+    if (rc == CHN_OK) rc = inflate_check_job(j, who);
     if (rc || j->n_members == 0) return rc;
+    const bool want = c && (c->expected || c->crc32);
     InfShared *sh = new (std::nothrow) InfShared;
-    if (!sh) return fail(CHN_E_NOMEM, "chn_inflate_run_host: no memory for the decoder's tables");
-    for (uint64_t i = 0; i < j->n_members; ++i)
-        j->status[i] = (uint32_t)inf_member_host(*sh, j->in + j->in_offset[i], j->in_length[i], j->out + j->out_offset[i], j->out_length[i]);
+    if (!sh) return fail(CHN_E_NOMEM, std::string(who) + ": no memory for the decoder's tables");
+    for (uint64_t i = 0; i < j->n_members; ++i) {
+        uint32_t crc = 0;
+        uint32_t st = (uint32_t)inf_member_host(*sh, j->in + j->in_offset[i], j->in_length[i], j->out + j->out_offset[i], j->out_length[i], want ? &crc : nullptr);
+        if (want && st == 0) {
+            if (c->expected && crc != c->expected[i]) st = CHN_INFLATE_E_CRC;
+            if (c->crc32) c->crc32[i] = crc;
+        }
+        j->status[i] = st;
+    }
     delete sh;
     return CHN_OK;
 }
+extern "C" int chn_inflate_run_host(const chn_inflate_job *j) { return inflate_run_host(j, nullptr, "chn_inflate_run_host"); }
+extern "C" int chn_inflate_run_host_crc(const chn_inflate_job *j, const chn_inflate_crc *c) { return inflate_run_host(j, c, "chn_inflate_run_host_crc"); }
 
 extern "C" int chn_inflate_create(int32_t device, chn_inflate **out) {
     if (!out) return fail(CHN_E_INVALID, "chn_inflate_create: null argument");
@@ -122,7 +142,7 @@ static bool inflate_is_pinned(const void *p, uint64_t bytes) {
 }
 
 // pack, upload, decode and start the download of members [first, first + n) in set `st`
-static int inflate_issue(chn_inflate *h, InflateSet &st, const chn_inflate_job *j, uint64_t first, uint64_t n, bool out_pinned) {
+static int inflate_issue(chn_inflate *h, InflateSet &st, const chn_inflate_job *j, const chn_inflate_crc *c, uint64_t first, uint64_t n, bool out_pinned) {
     uint64_t in_bytes = 0, out_bytes = 0;
     bool contiguous = true;
     for (uint64_t i = first; i < first + n; ++i) {
@@ -131,13 +151,16 @@ static int inflate_issue(chn_inflate *h, InflateSet &st, const chn_inflate_job *
         out_bytes += j->out_length[i];
     }
     st.first = first; st.n = n; st.out_bytes = out_bytes; st.direct = out_pinned && contiguous;
+    st.crc = c != nullptr;
+    const bool expect = c && c->expected;
     int rc;
-    // descriptors in one block: in_off[n] out_off[n] (64-bit), in_len[n] out_len[n] (32-bit)
-    const size_t desc_bytes = (size_t)n * 24;
+    // descriptors in one block: in_off[n] out_off[n] (64-bit), in_len[n] out_len[n] (32-bit), and expected[n] where CRCs are compared;
+    // statuses in one block: status[n], and crc[n] behind them where CRCs are taken
+    const size_t desc_bytes = (size_t)n * (expect ? 28 : 24), status_bytes = (size_t)n * (st.crc ? 8 : 4);
     if ((rc = st.h_desc.ensure(desc_bytes + desc_bytes / 4)) || (rc = st.d_desc.ensure(st.h_desc.cap)) ||
         (rc = st.h_in.ensure((size_t)in_bytes + 2 * INF_PAD + (st.h_in.cap < in_bytes + 2 * INF_PAD ? in_bytes / 4 : 0))) || (rc = st.d_in.ensure(st.h_in.cap)) ||
         (rc = st.d_out.ensure((size_t)out_bytes + 64 + (st.d_out.cap < out_bytes + 64 ? out_bytes / 4 : 0))) ||
-        (rc = st.h_status.ensure((size_t)n * 4 + (st.h_status.cap < n * 4 ? n : 0))) || (rc = st.d_status.ensure(st.h_status.cap)) || (rc = st.d_cursor.ensure(16)))
+        (rc = st.h_status.ensure(status_bytes + (st.h_status.cap < status_bytes ? status_bytes / 4 : 0))) || (rc = st.d_status.ensure(st.h_status.cap)) || (rc = st.d_cursor.ensure(16)))
         return rc;
     if (!st.direct && (rc = st.h_out.ensure(st.d_out.cap))) return rc;
     uint64_t *in_off = st.h_desc.as<uint64_t>(), *out_off = in_off + n;
@@ -154,6 +177,7 @@ static int inflate_issue(chn_inflate *h, InflateSet &st, const chn_inflate_job *
         op += j->out_length[i];
     }
     std::memset(stage + ip, 0, INF_PAD);
+    if (expect) std::memcpy(out_len + n, c->expected + first, (size_t)n * 4);
     HIPCHK(hipMemcpyAsync(st.d_in.p, stage, ip + INF_PAD, hipMemcpyHostToDevice, h->s_up));
     HIPCHK(hipMemcpyAsync(st.d_desc.p, st.h_desc.p, desc_bytes, hipMemcpyHostToDevice, h->s_up));
     HIPCHK(hipMemsetAsync(st.d_cursor.p, 0, 4, h->s_up));
@@ -165,10 +189,13 @@ static int inflate_issue(chn_inflate *h, InflateSet &st, const chn_inflate_job *
     a.in_len = reinterpret_cast<const uint32_t *>(a.out_off + n); a.out_len = a.in_len + n;
     a.out = st.d_out.as<uint8_t>(); a.status = st.d_status.as<uint32_t>(); a.cursor = st.d_cursor.as<uint32_t>();
     a.n = (uint32_t)n;
+    a.expected = expect ? a.out_len + n : nullptr;
+    a.crc = st.crc ? a.status + n : nullptr;
     // a looping grid: two workgroups of one wavefront fit a CU's LDS; the cursor hands out members
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(n, (uint64_t)std::max(1, h->cus) * 2);
     HIPCHK(hipEventRecord(st.k0, h->s_run));
-    hipLaunchKernelGGL(k_inflate_members, dim3(blocks), dim3(WAVE), 0, h->s_run, a);
+    if (st.crc) hipLaunchKernelGGL(k_inflate_members<true>, dim3(blocks), dim3(WAVE), 0, h->s_run, a);
+    else hipLaunchKernelGGL(k_inflate_members<false>, dim3(blocks), dim3(WAVE), 0, h->s_run, a);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(st.k1, h->s_run));
     HIPCHK(hipEventRecord(st.done, h->s_run));
@@ -177,14 +204,14 @@ static int inflate_issue(chn_inflate *h, InflateSet &st, const chn_inflate_job *
         void *dst = st.direct ? static_cast<void *>(j->out + j->out_offset[first]) : st.h_out.p;
         HIPCHK(hipMemcpyAsync(dst, st.d_out.p, out_bytes, hipMemcpyDeviceToHost, h->s_down));
     }
-    HIPCHK(hipMemcpyAsync(st.h_status.p, st.d_status.p, n * 4, hipMemcpyDeviceToHost, h->s_down));
+    HIPCHK(hipMemcpyAsync(st.h_status.p, st.d_status.p, status_bytes, hipMemcpyDeviceToHost, h->s_down));
     HIPCHK(hipEventRecord(st.down, h->s_down));
     st.busy = true;
     return CHN_OK;
 }
 
 // wait for the group in set `st` and hand its output and statuses to the caller
-static int inflate_collect(chn_inflate *h, InflateSet &st, const chn_inflate_job *j) {
+static int inflate_collect(chn_inflate *h, InflateSet &st, const chn_inflate_job *j, const chn_inflate_crc *c) {
     if (!st.busy) return CHN_OK;
     st.busy = false;
     HIPCHK(hipEventSynchronize(st.down));
@@ -192,6 +219,8 @@ static int inflate_collect(chn_inflate *h, InflateSet &st, const chn_inflate_job
     HIPCHK(hipEventElapsedTime(&ms, st.k0, st.k1));
     h->kernel_ms += ms;
     std::memcpy(j->status + st.first, st.h_status.p, st.n * 4);
+    if (st.crc && c->crc32)  // defined where the status is 0 or CHN_INFLATE_E_CRC; the kernel leaves the others unwritten
+        std::memcpy(c->crc32 + st.first, st.h_status.as<uint32_t>() + st.n, st.n * 4);
     if (!st.direct) {
         const uint8_t *src = st.h_out.as<uint8_t>();
         for (uint64_t i = st.first; i < st.first + st.n; ++i) {
@@ -202,10 +231,12 @@ static int inflate_collect(chn_inflate *h, InflateSet &st, const chn_inflate_job
     return CHN_OK;
 }
 
-extern "C" int chn_inflate_run(chn_inflate *h, const chn_inflate_job *j) {
-    if (!h) return fail(CHN_E_INVALID, "chn_inflate_run: null handle");
-    int rc = inflate_check_job(j, "chn_inflate_run");
+static int inflate_run(chn_inflate *h, const chn_inflate_job *j, const chn_inflate_crc *c, const char *who) {
+    if (!h) return fail(CHN_E_INVALID, std::string(who) + ": null handle");
+    int rc = inflate_check_crc(c, who);
+    if (rc == CHN_OK) rc = inflate_check_job(j, who);
     if (rc || j->n_members == 0) return rc;
+    if (c && !c->expected && !c->crc32) c = nullptr;  // decode only: the plain kernel
     HIPCHK(hipSetDevice(h->device));
     h->kernel_ms = 0;
     const bool out_pinned = inflate_is_pinned(j->out, j->out_bytes);
@@ -217,8 +248,8 @@ extern "C" int chn_inflate_run(chn_inflate *h, const chn_inflate_job *j) {
         }
         InflateSet &st = h->set[g & 1];
         // the set's staging and device buffers are free: its last group was collected when the one after it was issued
-        rc = inflate_issue(h, st, j, first, n, out_pinned);
-        if (rc == CHN_OK && g > 0) rc = inflate_collect(h, h->set[(g - 1) & 1], j);
+        rc = inflate_issue(h, st, j, c, first, n, out_pinned);
+        if (rc == CHN_OK && g > 0) rc = inflate_collect(h, h->set[(g - 1) & 1], j, c);
         if (rc) {  // nothing of this call may still be on its way into the caller's memory
             (void)hipStreamSynchronize(h->s_up); (void)hipStreamSynchronize(h->s_run); (void)hipStreamSynchronize(h->s_down);
             h->set[0].busy = h->set[1].busy = false;
@@ -226,10 +257,12 @@ extern "C" int chn_inflate_run(chn_inflate *h, const chn_inflate_job *j) {
         }
         first += n; ++g;
     }
-    rc = inflate_collect(h, h->set[(g - 1) & 1], j);
+    rc = inflate_collect(h, h->set[(g - 1) & 1], j, c);
     if (rc) { (void)hipStreamSynchronize(h->s_down); h->set[0].busy = h->set[1].busy = false; }
     return rc;
 }
+extern "C" int chn_inflate_run(chn_inflate *h, const chn_inflate_job *j) { return inflate_run(h, j, nullptr, "chn_inflate_run"); }
+extern "C" int chn_inflate_run_crc(chn_inflate *h, const chn_inflate_job *j, const chn_inflate_crc *c) { return inflate_run(h, j, c, "chn_inflate_run_crc"); }
 
 extern "C" int chn_inflate_kernel_ms(chn_inflate *h, double *ms) {
     if (!h || !ms) return fail(CHN_E_INVALID, "chn_inflate_kernel_ms: null argument");

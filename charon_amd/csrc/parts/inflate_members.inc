@@ -16,6 +16,13 @@
 // distance set that is a single 1-bit code, and an empty distance set), as are a missing end-of-block code, HLIT > 286, HDIST > 30, block
 // type 3, a stored LEN/NLEN mismatch, a distance reaching before the member's first byte; bytes behind the final block are ignored.
 // Every loop consumes input bits, and consuming more than the member holds ends the decode, so it terminates on any input.
+//
+// CRC-32 (inf_crc32, behind chn_inflate_run_crc / chn_inflate_run_host_crc): taken over the finished window, before it is written out.
+// The member is cut into 64 slices of equal length S = ceil(n / 64) by OUTPUT byte position, zero bytes imagined in front of the first
+// byte where 64 S > n (zero bytes in front of everything leave a CRC register of 0 at 0); every slice goes through a slice-by-4 loop
+// whose four tables the lanes build in `ll` (dead once decoding has ended), and the 64 registers are joined exactly in a six-round tree:
+// left * x^(8 S 2^r) + right modulo the reflected polynomial, the multiplier wave-uniform.  The host policy walks the same 64 slices and
+// the same tree serially.
 
 #ifndef __HIPCC__  // a CPU build of the decoder alone (tools/fuzz/inflate_fuzz.cpp)
 #define __host__
@@ -30,6 +37,8 @@ static const uint32_t INF_DD_ROOT = 8, INF_DD_CAP = 512;    // `enough 30 8 15` 
 static const uint32_t INF_PRE_ROOT = 7, INF_PRE_CAP = 128;  // code-length codes are at most 7 bits: no sub-tables
 static const uint32_t INF_CHUNK_WORDS = 256;                // 64 lanes x 16 bytes
 static const uint32_t INF_PAD = 64;                         // bytes the library keeps in front of and behind the device input
+static const uint32_t INF_CRC_SLICES = 64;                  // slices a member's CRC-32 is taken in (the wavefront's lanes)
+static const uint32_t INF_CRC_POLY = 0xEDB88320u;           // the gzip polynomial, reflected: bit 31 is x^0
 
 struct alignas(16) InfShared {
     uint8_t win[INF_MAX_OUT + 16];  // output byte k lives at win[wmis + k], wmis = the destination's misalignment to 16 bytes
@@ -100,6 +109,8 @@ struct InfHostPolicy {
     }
     uint32_t fetch_add(uint32_t *p, uint32_t n) const { const uint32_t o = *p; *p = o + n; return o; }
     void fetch_max(uint32_t *p, uint32_t v) const { if (v > *p) *p = v; }
+    // CRC join: the register of slice k + d (0 behind the last slice); this lane holds every slice, in order
+    uint32_t slice_down(const uint32_t *part, uint32_t k, uint32_t d) const { return k + d < INF_CRC_SLICES ? part[k + d] : 0u; }
 };
 
 #ifdef __HIPCC__
@@ -154,6 +165,11 @@ struct InfWavePolicy {
     }
     __device__ uint32_t fetch_add(uint32_t *p, uint32_t n) const { return atomicAdd(p, n); }
     __device__ void fetch_max(uint32_t *p, uint32_t v) const { atomicMax(p, v); }
+    // CRC join: lane l holds slice l alone; the register of slice l + d comes from lane l + d
+    __device__ uint32_t slice_down(const uint32_t *part, uint32_t, uint32_t d) const {
+        const uint32_t v = (uint32_t)__shfl_down((int)part[0], d);
+        return lane_id() + d < INF_CRC_SLICES ? v : 0u;
+    }
 };
 #endif
 
@@ -408,12 +424,77 @@ template <class P> struct InfDecoder {
     }
 };
 
-// host entry: one member, `sh` is the caller's scratch; writes min(produced, out_len) bytes
-static int inf_member_host(InfShared &sh, const uint8_t *in, uint64_t in_len, uint8_t *out, uint32_t out_len) {
+// ---- CRC-32 of a decoded member ----------------------------------------------------------------------------------------------------
+// a * b modulo the polynomial, both reflected (bit 31 is x^0, so 0x80000000 is 1): what zlib's crc32_combine multiplies with
+__host__ __device__ static inline uint32_t inf_crc_mul(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+    for (uint32_t i = 0; i < 32; ++i) {
+        p ^= b & (0u - ((a >> (31 - i)) & 1u));
+        b = (b >> 1) ^ (INF_CRC_POLY & (0u - (b & 1u)));
+    }
+    return p;
+}
+// x^(8 n) modulo the polynomial: what n zero bytes do to a register
+__host__ __device__ static inline uint32_t inf_crc_shift(uint32_t n) {
+    uint32_t r = 0x80000000u, sq = 0x00800000u;  // 1, x^8
+    for (; n; n >>= 1) {
+        if (n & 1u) r = inf_crc_mul(r, sq);
+        sq = inf_crc_mul(sq, sq);
+    }
+    return r;
+}
+// the register after window bytes [a, e), slice-by-4: bytes up to a 4-byte boundary of the window, whole words (both targets are
+// little-endian), the rest.  tab[j * 256 + v] is what byte v does to the register j + 1 bytes later.
+__host__ __device__ static inline uint32_t inf_crc_slice(const uint32_t *tab, const uint8_t *win, uint32_t a, uint32_t e, uint32_t reg) {
+    for (; a < e && (a & 3u); ++a) reg = tab[(reg ^ win[a]) & 255u] ^ (reg >> 8);
+    for (; a + 4 <= e; a += 4) {
+        uint32_t w;
+        __builtin_memcpy(&w, __builtin_assume_aligned(win + a, 4), 4);
+        reg ^= w;
+        reg = tab[768 + (reg & 255u)] ^ tab[512 + ((reg >> 8) & 255u)] ^ tab[256 + ((reg >> 16) & 255u)] ^ tab[reg >> 24];
+    }
+    for (; a < e; ++a) reg = tab[(reg ^ win[a]) & 255u] ^ (reg >> 8);
+    return reg;
+}
+// zlib's crc32(0, data, n) of output bytes [0, n), which live at win[wmis ..).  Overwrites `ll`: the decode has ended.  Wave-uniform result.
+template <class P> __host__ __device__ static uint32_t inf_crc32(P &p, InfShared &sh, uint32_t wmis, uint32_t n) {
+    if (n == 0) return 0;
+    const uint32_t lane = p.lane();
+    uint32_t *tab = sh.ll;  // 4 x 256 words of its 2 048
+    for (uint32_t v = lane; v < 256; v += P::LANES) {
+        uint32_t c = v;
+        for (uint32_t k = 0; k < 8; ++k) c = (c >> 1) ^ (INF_CRC_POLY & (0u - (c & 1u)));
+        tab[v] = c;
+    }
+    p.sync();
+    for (uint32_t v = lane; v < 256; v += P::LANES) {
+        uint32_t c = tab[v];
+        for (uint32_t j = 1; j < 4; ++j) { c = tab[c & 255u] ^ (c >> 8); tab[j * 256 + v] = c; }
+    }
+    p.sync();
+    // slice s covers output positions [s S - pad, (s + 1) S - pad), cut at 0; the one that holds position 0 starts from gzip's register of ones
+    const uint32_t S = (n + INF_CRC_SLICES - 1) / INF_CRC_SLICES, pad = INF_CRC_SLICES * S - n;
+    uint32_t part[INF_CRC_SLICES / P::LANES];
+    for (uint32_t k = 0; k < INF_CRC_SLICES / P::LANES; ++k) {
+        const uint32_t s = k * P::LANES + lane, end = (s + 1) * S;
+        const uint32_t a = s * S > pad ? s * S - pad : 0, e = end > pad ? end - pad : 0;
+        part[k] = e ? inf_crc_slice(tab, sh.win, wmis + a, wmis + e, s * S <= pad ? 0xFFFFFFFFu : 0u) : 0u;
+    }
+    uint32_t mult = inf_crc_shift(S);  // x^(8 S 2^r) in round r
+    for (uint32_t r = 0; r < 6; ++r) {
+        for (uint32_t k = 0; k < INF_CRC_SLICES / P::LANES; ++k) part[k] = inf_crc_mul(part[k], mult) ^ p.slice_down(part, k, 1u << r);
+        mult = inf_crc_mul(mult, mult);
+    }
+    return ~p.uni(part[0]);
+}
+
+// host entry: one member, `sh` is the caller's scratch; writes min(produced, out_len) bytes; *crc (if asked for) is set where the status is 0
+static int inf_member_host(InfShared &sh, const uint8_t *in, uint64_t in_len, uint8_t *out, uint32_t out_len, uint32_t *crc = nullptr) {
     InfHostPolicy pol{in, in_len};
     InfDecoder<InfHostPolicy> d(pol, sh, out_len, 0);
     const int st = d.run();
     if (d.opos) std::memcpy(out, sh.win, std::min(d.opos, out_len));
+    if (crc && st == INF_OK) *crc = inf_crc32(pol, sh, 0, out_len);
     return st;
 }
 
@@ -429,9 +510,12 @@ struct InflateArgs {
     uint32_t *status;
     uint32_t *cursor;
     uint32_t n;
+    const uint32_t *expected;   // CRC kernel only: [n] or NULL
+    uint32_t *crc;              // CRC kernel only: [n]
 };
 
-__global__ void __launch_bounds__(WAVE) k_inflate_members(InflateArgs a) {
+// CRC = false is the plain decode; CRC = true also takes the member's CRC-32 from the window and compares it with `expected`
+template <bool CRC> __global__ void __launch_bounds__(WAVE) k_inflate_members(InflateArgs a) {
     __shared__ InfShared sh;
     const uint32_t lane = lane_id();
     for (;;) {
@@ -455,6 +539,11 @@ __global__ void __launch_bounds__(WAVE) k_inflate_members(InflateArgs a) {
             produced = min(d.opos, out_len);
         }
         pol.sync();
+        if (CRC && st == INF_OK) {  // (wave-uniform) only a member that decoded completely has a CRC
+            const uint32_t crc = inf_crc32(pol, sh, wmis, produced);
+            if (a.expected && crc != a.expected[m]) st = CHN_INFLATE_E_CRC;
+            if (lane == 0) a.crc[m] = crc;
+        }
         // write the window out: whole 16-byte pieces as one vector store per lane, the ragged ends byte by byte
         uint8_t *abase = dst - wmis;
         const uint32_t lo = wmis, hi = wmis + produced;  // window bytes [lo, hi)

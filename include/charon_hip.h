@@ -416,7 +416,8 @@ int chn_stream_last_batch_bytes(chn_stream *s, uint64_t *bytes, uint64_t *total_
  * a violation is CHN_E_INVALID, chn_last_error() names the member, and nothing has run.  A corrupt member is NOT an error of the call:
  * the call returns 0, status[i] != 0, and every other member is decoded; the bytes of a failed member's stretch of `out` are
  * unspecified, bytes outside the members' stretches are never written.  n_members == 0 is a no-op and out_length[i] == 0 is legal
- * (BGZF's end-of-file marker).  The CRC-32 of a member is the caller's to check.
+ * (BGZF's end-of-file marker).  chn_inflate_run / chn_inflate_run_host leave the CRC-32 of a member to the caller; the _crc forms take
+ * it on the way (below).
  * A chn_inflate owns its streams and staging buffers (grow-only); it is used by ONE thread at a time, different handles may be driven
  * from different threads.  chn_inflate_run is synchronous. */
 #define CHN_INFLATE_MAX_OUT 65536u
@@ -436,8 +437,23 @@ int chn_inflate_create(int32_t device, chn_inflate **out);
 int chn_inflate_run(chn_inflate *h, const chn_inflate_job *job);       /* synchronous */
 int chn_inflate_run_host(const chn_inflate_job *job);                  /* same decoder source on the CPU, one thread; no GPU needed */
 int chn_inflate_destroy(chn_inflate *h);
-/* measurement aid: device time of the kernels of the handle's last chn_inflate_run, from events around them */
+/* measurement aid: device time of the kernels of the handle's last chn_inflate_run / chn_inflate_run_crc, from events around them */
 int chn_inflate_kernel_ms(chn_inflate *h, double *ms);
+/* The same calls with the members' CRC-32 -- the gzip trailer's, zlib's crc32(0, data, out_length); 0 for a member of length 0 -- taken
+ * by the decoder itself: on the device by the member's wavefront, from the decoded bytes while they are still in LDS.  With `expected`,
+ * a member that decodes completely (status 0) but whose CRC-32 differs from expected[i] gets status CHN_INFLATE_E_CRC; a decode failure
+ * keeps its status 1..6.  crc32[i] is defined where status[i] is 0 or CHN_INFLATE_E_CRC and unspecified elsewhere; the bytes of a member
+ * with CHN_INFLATE_E_CRC are what its stream decodes to.  crc == NULL is chn_inflate_run / chn_inflate_run_host exactly, and so is a
+ * chn_inflate_crc with both arrays NULL (nothing is taken).  A wrong struct_size or a non-zero `reserved` is CHN_E_INVALID before anything
+ * runs; the job is checked as above. */
+#define CHN_INFLATE_E_CRC 7u   /* status: decoded completely, but the CRC-32 differs from expected[i] */
+typedef struct chn_inflate_crc {
+    uint32_t struct_size, reserved;   /* reserved: 0 */
+    const uint32_t *expected;         /* [n] HOST, or NULL: nothing is compared */
+    uint32_t *crc32;                  /* [n] HOST out, or NULL */
+} chn_inflate_crc;
+int chn_inflate_run_crc(chn_inflate *h, const chn_inflate_job *job, const chn_inflate_crc *crc);   /* synchronous */
+int chn_inflate_run_host_crc(const chn_inflate_job *job, const chn_inflate_crc *crc);
 
 /* ---- synthetic workload fabrication on the device (bench / tests; no reference counterpart) ---------- */
 /* Measurement aid: the rate this device sustains for NOTHING BUT the index's probe pattern -- independent uniformly random row
