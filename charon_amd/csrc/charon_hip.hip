@@ -54,6 +54,7 @@
 #include "parts/shardx_kernels.inc"
 #include "parts/k3_model_call.inc"
 #include "parts/len_order.inc"
+#include "parts/gzip_trees.inc"
 #include "parts/gzip_walk.inc"
 #include "parts/gzip_tally.inc"
 #include "parts/gzip_size_dev.inc"

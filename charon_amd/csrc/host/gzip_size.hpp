@@ -9,6 +9,8 @@
 // identically (same candidates in the same order, same chain and lazy-match limits, same Huffman code lengths), so the size
 // is bit-exact; tests/test_cli_cpu.py and tools/gzip_size_check.cpp compare it with the linked zlib on millions of inputs, and
 // the front end re-checks a few known strings at start-up and falls back to zlib itself if they ever disagree.
+// This file holds the walk (deflate_slow, longest_match); the trees.c arithmetic of a block flush is ../parts/gzip_trees.inc, the one
+// source the GPU kernels run too.
 //
 // Fast path (inputs made of A, C, G, T, N only -- what sequence_to_string produces): longest_match is a pure function of the
 // candidate set E = the first `chain_length` same-hash positions inside the window, in recency order: it returns the most recent
@@ -25,8 +27,10 @@
 #include <cstdint>
 #include <cstring>
 #include <vector>
+#include "../parts/gzip_trees.inc"
 
 namespace gzsize {
+using namespace gztrees;  // zlib's constants, the code maps, Work and flush_block_bits
 
 class GzipSizer {
 public:
@@ -59,24 +63,13 @@ public:
     // include/charon_hip.h chn_batch.gzip_tallies): lfreq[286] literal/length code frequencies WITHOUT the end-of-block symbol's
     // count being trusted (it is set here), dfreq[30] distance code frequencies, n input bytes.
     uint32_t size_from_tallies(const uint16_t *lfreq, const uint16_t *dfreq, size_t n) {
-        ensure_tables();
-        total_bits_ = 0;
-        init_block();
-        for (int i = 0; i < L_CODES; ++i) lfreq_[i] = lfreq[i];
-        lfreq_[END_BLOCK] = 1;
-        for (int i = 0; i < D_CODES; ++i) dfreq_[i] = dfreq[i];
-        flush_block(n, true, true);
-        return (uint32_t)(18 + ((total_bits_ + 7) >> 3));
+        uint64_t bits = 0;
+        flush_block_bits(work_, lfreq, dfreq, n, true, true, bits);
+        return (uint32_t)(18 + (bits >> 3));
     }
 
 private:
-    enum {
-        MIN_MATCH = 3, MAX_MATCH = 258, W_SIZE = 32768, MIN_LOOKAHEAD = MAX_MATCH + MIN_MATCH + 1, MAX_DIST = W_SIZE - MIN_LOOKAHEAD,
-        TOO_FAR = 4096, GOOD_MATCH = 8, MAX_LAZY = 16, NICE_MATCH = 128, MAX_CHAIN = 128,  // configuration_table[6], deflate_slow
-        LIT_BUFSIZE = 1 << (8 + 6),  // memLevel 8
-        L_CODES = 286, D_CODES = 30, BL_CODES = 19, LITERALS = 256, END_BLOCK = 256, MAX_BITS = 15, MAX_BL_BITS = 7,
-        HEAP_SIZE = 2 * L_CODES + 1, REP_3_6 = 16, REPZ_3_10 = 17, REPZ_11_138 = 18, HASH_SIZE = 32768
-    };
+    enum { HASH_SIZE = 32768 };
 
     // ---- input + occurrence arrays -----------------------------------------------------------------------------------
     std::vector<uint8_t> buf_;        // input + zero padding (zlib zeroes WIN_INIT bytes behind the data, so compares past the end see 0)
@@ -294,44 +287,24 @@ private:
         return best_len <= lookahead ? best_len : lookahead;
     }
 
-    // ---- trees.c: tallies and block sizes --------------------------------------------------------------------------------
-    uint32_t lfreq_[HEAP_SIZE], dfreq_[2 * D_CODES + 1], blfreq_[2 * BL_CODES + 1];
+    // ---- tallies; the block sizes are trees.c's arithmetic, shared with the GPU kernels (parts/gzip_trees.inc) --------------------
+    uint32_t lfreq_[L_CODES], dfreq_[D_CODES];
     uint32_t last_lit_ = 0;
-    uint64_t total_bits_ = 0, opt_len_ = 0, static_len_ = 0;
-    uint8_t length_code_[256], dist_code_[512];
+    uint64_t total_bits_ = 0;
+    Work work_;
+    uint8_t length_code_[256], dist_code_[512];  // _length_code / _dist_code, as tables for tally_dist
     bool tables_ = false;
 
-    static const int *extra_lbits() {
-        static const int t[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
-        return t;
-    }
-    static const int *extra_dbits() {
-        static const int t[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
-        return t;
-    }
-    static const int *extra_blbits() {
-        static const int t[19] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 2, 3, 7};
-        return t;
-    }
-    void init_tables() {  // tr_static_init
-        int length = 0, code;
-        for (code = 0; code < 28; ++code)
-            for (int n = 0; n < (1 << extra_lbits()[code]); ++n) length_code_[length++] = (uint8_t)code;
-        length_code_[length - 1] = (uint8_t)code;
-        int dist = 0;
-        for (code = 0; code < 16; ++code)
-            for (int n = 0; n < (1 << extra_dbits()[code]); ++n) dist_code_[dist++] = (uint8_t)code;
-        dist >>= 7;
-        for (; code < D_CODES; ++code)
-            for (int n = 0; n < (1 << (extra_dbits()[code] - 7)); ++n) dist_code_[256 + dist++] = (uint8_t)code;
+    void ensure_tables() {
+        if (tables_) return;
+        for (uint32_t lc = 0; lc < 256; ++lc) length_code_[lc] = (uint8_t)length_code(lc);
+        for (uint32_t d = 0; d < 256; ++d) dist_code_[d] = (uint8_t)dist_code(d);
+        for (uint32_t d = 0; d < 256; ++d) dist_code_[256 + d] = (uint8_t)dist_code(d << 7);  // distances from 257 on, by dist >> 7
         tables_ = true;
     }
     void init_block() {
         std::memset(lfreq_, 0, sizeof lfreq_);
         std::memset(dfreq_, 0, sizeof dfreq_);
-        std::memset(blfreq_, 0, sizeof blfreq_);
-        lfreq_[END_BLOCK] = 1;
-        opt_len_ = static_len_ = 0;
         last_lit_ = 0;
     }
     bool tally_lit(uint8_t c) {
@@ -344,173 +317,13 @@ private:
         dfreq_[dist < 256 ? dist_code_[dist] : dist_code_[256 + (dist >> 7)]]++;
         return ++last_lit_ == LIT_BUFSIZE - 1;
     }
-
-    struct TreeDesc {
-        uint32_t *freq;       // [2*elems+1]
-        const uint8_t *slen;  // static code lengths or null
-        const int *extra;
-        int extra_base, elems, max_length, max_code;
-    };
-    uint16_t len_[HEAP_SIZE], dad_[HEAP_SIZE];
-    uint16_t llen_[HEAP_SIZE], dlen_[2 * D_CODES + 1], bllen_[2 * BL_CODES + 1];
-    int heap_[HEAP_SIZE], heap_len_ = 0, heap_max_ = 0;
-    uint8_t depth_[HEAP_SIZE];
-    uint16_t bl_count_[MAX_BITS + 1];
-
-    bool smaller(const uint32_t *f, int n, int m) const { return f[n] < f[m] || (f[n] == f[m] && depth_[n] <= depth_[m]); }
-    void pqdownheap(const uint32_t *f, int k) {
-        const int v = heap_[k];
-        int j = k << 1;
-        while (j <= heap_len_) {
-            if (j < heap_len_ && smaller(f, heap_[j + 1], heap_[j])) j++;
-            if (smaller(f, v, heap_[j])) break;
-            heap_[k] = heap_[j];
-            k = j;
-            j <<= 1;
-        }
-        heap_[k] = v;
-    }
-    void build_tree(TreeDesc &d, uint16_t *outlen) {
-        uint32_t *f = d.freq;
-        const int elems = d.elems;
-        int max_code = -1, node;
-        heap_len_ = 0;
-        heap_max_ = HEAP_SIZE;
-        for (int n = 0; n < elems; ++n) {
-            if (f[n] != 0) { heap_[++heap_len_] = max_code = n; depth_[n] = 0; }
-            else len_[n] = 0;
-        }
-        while (heap_len_ < 2) {
-            node = heap_[++heap_len_] = (max_code < 2 ? ++max_code : 0);
-            f[node] = 1;
-            depth_[node] = 0;
-            opt_len_--;
-            if (d.slen) static_len_ -= d.slen[node];
-        }
-        d.max_code = max_code;
-        for (int n = heap_len_ / 2; n >= 1; --n) pqdownheap(f, n);
-        node = elems;
-        do {
-            const int n = heap_[1];
-            heap_[1] = heap_[heap_len_--];
-            pqdownheap(f, 1);
-            const int m = heap_[1];
-            heap_[--heap_max_] = n;
-            heap_[--heap_max_] = m;
-            f[node] = f[n] + f[m];
-            depth_[node] = (uint8_t)((depth_[n] >= depth_[m] ? depth_[n] : depth_[m]) + 1);
-            dad_[n] = dad_[m] = (uint16_t)node;
-            heap_[1] = node++;
-            pqdownheap(f, 1);
-        } while (heap_len_ >= 2);
-        heap_[--heap_max_] = heap_[1];
-        // gen_bitlen
-        int h, overflow = 0;
-        for (int bits = 0; bits <= MAX_BITS; ++bits) bl_count_[bits] = 0;
-        len_[heap_[heap_max_]] = 0;
-        for (h = heap_max_ + 1; h < HEAP_SIZE; ++h) {
-            const int n = heap_[h];
-            int bits = len_[dad_[n]] + 1;
-            if (bits > d.max_length) { bits = d.max_length; overflow++; }
-            len_[n] = (uint16_t)bits;
-            if (n > max_code) continue;
-            bl_count_[bits]++;
-            int xbits = 0;
-            if (n >= d.extra_base) xbits = d.extra[n - d.extra_base];
-            opt_len_ += (uint64_t)f[n] * (unsigned)(bits + xbits);
-            if (d.slen) static_len_ += (uint64_t)f[n] * (unsigned)(d.slen[n] + xbits);
-        }
-        if (overflow != 0) {
-            do {
-                int bits = d.max_length - 1;
-                while (bl_count_[bits] == 0) bits--;
-                bl_count_[bits]--;
-                bl_count_[bits + 1] += 2;
-                bl_count_[d.max_length]--;
-                overflow -= 2;
-            } while (overflow > 0);
-            for (int bits = d.max_length; bits != 0; --bits) {
-                int n = bl_count_[bits];
-                while (n != 0) {
-                    const int m = heap_[--h];
-                    if (m > max_code) continue;
-                    if ((unsigned)len_[m] != (unsigned)bits) {
-                        opt_len_ += ((uint64_t)bits - len_[m]) * f[m];
-                        len_[m] = (uint16_t)bits;
-                    }
-                    n--;
-                }
-            }
-        }
-        for (int n = 0; n <= max_code; ++n) outlen[n] = len_[n];
-        for (int n = max_code + 1; n < elems; ++n) outlen[n] = 0;
-    }
-    void scan_tree(uint16_t *tlen, int max_code) {
-        int prevlen = -1, curlen, nextlen = tlen[0], count = 0, max_count = 7, min_count = 4;
-        if (nextlen == 0) { max_count = 138; min_count = 3; }
-        tlen[max_code + 1] = (uint16_t)0xffff;  // guard
-        for (int n = 0; n <= max_code; ++n) {
-            curlen = nextlen;
-            nextlen = tlen[n + 1];
-            if (++count < max_count && curlen == nextlen) continue;
-            else if (count < min_count) blfreq_[curlen] += (uint32_t)count;
-            else if (curlen != 0) {
-                if (curlen != prevlen) blfreq_[curlen]++;
-                blfreq_[REP_3_6]++;
-            } else if (count <= 10) blfreq_[REPZ_3_10]++;
-            else blfreq_[REPZ_11_138]++;
-            count = 0;
-            prevlen = curlen;
-            if (nextlen == 0) { max_count = 138; min_count = 3; }
-            else if (curlen == nextlen) { max_count = 6; min_count = 3; }
-            else { max_count = 7; min_count = 4; }
-        }
-    }
-    uint8_t static_llen_[L_CODES + 2], static_dlen_[D_CODES];
-
     // _tr_flush_block: adds the bits of this block to total_bits_
-    void flush_block(uint64_t stored_len, bool last, bool buf_available = true) {
-        TreeDesc ld = {lfreq_, static_llen_, extra_lbits(), LITERALS + 1, L_CODES, MAX_BITS, -1};
-        TreeDesc dd = {dfreq_, static_dlen_, extra_dbits(), 0, D_CODES, MAX_BITS, -1};
-        TreeDesc bd = {blfreq_, nullptr, extra_blbits(), 0, BL_CODES, MAX_BL_BITS, -1};
-        build_tree(ld, llen_);
-        build_tree(dd, dlen_);
-        scan_tree(llen_, ld.max_code);
-        scan_tree(dlen_, dd.max_code);
-        build_tree(bd, bllen_);
-        static const uint8_t bl_order[BL_CODES] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-        int max_blindex;
-        for (max_blindex = BL_CODES - 1; max_blindex >= 3; --max_blindex)
-            if (bllen_[bl_order[max_blindex]] != 0) break;
-        opt_len_ += 3 * ((uint64_t)max_blindex + 1) + 5 + 5 + 4;
-        uint64_t opt_lenb = (opt_len_ + 3 + 7) >> 3;
-        const uint64_t static_lenb = (static_len_ + 3 + 7) >> 3;
-        if (static_lenb <= opt_lenb) opt_lenb = static_lenb;
-        if (stored_len + 4 <= opt_lenb && buf_available) {
-            // _tr_stored_block: 3 header bits, pad to a byte, LEN + NLEN, the bytes
-            total_bits_ += 3;
-            total_bits_ = (total_bits_ + 7) & ~7ULL;
-            total_bits_ += 32 + 8 * stored_len;
-        } else if (static_lenb == opt_lenb) {
-            total_bits_ += 3 + static_len_;
-        } else {
-            total_bits_ += 3 + opt_len_;
-        }
+    void flush_block(uint64_t stored_len, bool last, bool buf_available) {
+        flush_block_bits(work_, lfreq_, dfreq_, stored_len, buf_available, last, total_bits_);
         init_block();
-        if (last) total_bits_ = (total_bits_ + 7) & ~7ULL;  // bi_windup
     }
 
     // ---- deflate_slow ----------------------------------------------------------------------------------------------------
-    void ensure_tables() {
-        if (!tables_) {
-            init_tables();
-            for (int n = 0; n <= 143; ++n) static_llen_[n] = 8;
-            for (int n = 144; n <= 255; ++n) static_llen_[n] = 9;
-            for (int n = 256; n <= 279; ++n) static_llen_[n] = 7;
-            for (int n = 280; n < L_CODES + 2; ++n) static_llen_[n] = 8;
-            for (int n = 0; n < D_CODES; ++n) static_dlen_[n] = 5;
-        }
-    }
     void run(size_t n_in) {
         ensure_tables();
         const uint32_t n = (uint32_t)n_in;

@@ -22,11 +22,11 @@
 //      symbol tallies are kept in registers: lane c counts the literals of code c, lane j the matches of length j + 3, lane d the
 //      matches of distance code d;
 //   3. the tallies (286 literal/length + 30 distance frequencies) leave as 16-bit words; the host turns them into the block size
-//      with the same _tr_flush_block restatement it uses for its own emulator (charon_amd/csrc/host/gzip_size.hpp) -- a few
-//      microseconds per read instead of ~70 -- or k_gzip_size does on the device.
+//      with the one _tr_flush_block restatement (gzip_trees.inc, through GzipSizer::size_from_tallies of host/gzip_size.hpp) -- a
+//      few microseconds per read instead of ~70 -- or k_gzip_size does on the device.
 // Scope: A/C/G/T/N letters, 1 <= n <= GZT_MAX_LEN, one deflate block (fewer than 16 383 symbols), no window slide
-// (n < 65 274 is implied).  Anything else is flagged and sized on the host.  Exactness is established against the host
-// emulator (itself checked against zlib on millions of inputs): tests/test_gpu_parity.py::test_gzip_tallies_equal_the_host_emulator.
+// (n < 65 274 is implied).  Anything else is flagged and sized on the host.  Exactness is established against zlib:
+// tests/test_gpu_parity.py::test_gzip_sizes_on_the_device_equal_zlib, tests/test_gpu_gzip_any_length.py.
 // ------------------------------------------------------------------------------------------------
 #define GZT_MAX_LEN 61440u  // half a byte of LDS per letter: five wavefronts per CU at this length (and below 65 274, where zlib's window starts to slide)
 #define GZT_WORDS 320u      // per read: [0, 286) literal/length freqs, [286, 316) distance freqs, [316] status (0 ok, 1 = size on the host), pad
@@ -57,7 +57,7 @@ struct GztArgs {
 // mismatch at n, whatever the candidate holds there).
 template <int BITS>
 __global__ __launch_bounds__(WAVE) void k_gzip_tally(const GztArgs a) {
-    constexpr uint32_t FIRST = GzCodes<BITS>::FIRST, MIN_MATCH = GZ_MIN_MATCH, MAX_DIST = GZ_MAX_DIST;
+    constexpr uint32_t FIRST = GzCodes<BITS>::FIRST, MIN_MATCH = gztrees::MIN_MATCH, MAX_DIST = gztrees::MAX_DIST;
     extern __shared__ __align__(16) unsigned char gsm[];
     const uint32_t lane = lane_id();
     // LDS (sized for max_len on the host): 1 280 bytes + half a byte per letter
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(WAVE) void k_gzip_tally(const GztArgs a) {
                 uint32_t best = PL;
                 if ((mx >> 16) + 3u > best) { best = (mx >> 16) + 3u; MS = mx & 0xFFFFu; }
                 ML = best <= look ? best : look;
-                if (ML == MIN_MATCH) { if (S - MS > GZ_TOO_FAR) ML = MIN_MATCH - 1; }
+                if (ML == MIN_MATCH) { if (S - MS > gztrees::TOO_FAR) ML = MIN_MATCH - 1; }
             }
             if (gz_emit<BITS>(t, tall, lane, PL, PM, here, S, Sv, ML) == GZ_LONG_MATCH) ++n_long;  // (not in len_cnt)
         }

@@ -1,6 +1,6 @@
 // gzip_tally_long.inc -- k_gzip_long: zlib level-6 deflate_slow of reads of ANY length (window slide, any number of deflate blocks),
 // each block sized in place: the gzip member size of every read (chn_batch.gzip_output = CHN_GZIP_SIZES_ALL)
-// Part of the single translation unit charon_hip.hip (included in order, after gzip_walk.inc, gzip_tally.inc and gzip_size_dev.inc); not a stand-alone source.
+// Part of the single translation unit charon_hip.hip (included in order, after gzip_trees.inc, gzip_walk.inc, gzip_tally.inc and gzip_size_dev.inc); not a stand-alone source.
 
 // ------------------------------------------------------------------------------------------------
 // The walk of gzip_walk.inc, which k_gzip_tally instantiates too (one wavefront per read, the trigram classes as arrays, the
@@ -20,7 +20,7 @@
 //    (candidate + 65 536 - strstart): inside the window that is 16 bits, and larger means more recent.
 //  * Block flushes: a scalar symbol counter; when the 16 383rd symbol of a block is tallied (match branch or lazy-literal branch)
 //    the block record (the 286 + 30 frequencies in LDS, stored_len = strstart - block_start, buf = block_start >= base) is sized
-//    at once by lane 0 with _tr_flush_block's arithmetic (gzsize_dev::flush_block_bits, shared with k_gzip_size; its heap in LDS),
+//    at once by lane 0 with _tr_flush_block's arithmetic (gztrees::flush_block_bits, the one k_gzip_size and the host emulator run; its heap in LDS),
 //    the running bit count carries the stored blocks' byte padding, and the tallies restart.  The final block (the pending literal
 //    first, then the flush with last = 1; it may be empty) closes the member: size = 18 + bits / 8.
 // Per wavefront: LDS 3 328 B of tallies and class ranges + 7 088 B of tree work + the ring (64 KiB with 4-bit codes, 32 KiB with
@@ -31,7 +31,6 @@
 #define GZL_RING_EPOCHS 4u      // epochs of codes in the LDS ring
 #define GZL_GUARD 4u            // ring words mirrored behind its end
 #define GZL_HEAD_WORDS 832u     // LDS: tallies [320], class cursors / starts of this epoch, class starts / ends of the previous one [4][128]
-#define GZL_BLOCK_SYMBOLS 16383u  // lit_bufsize - 1 (memLevel 8): zlib flushes a block when it holds this many symbols
 #define GZL_MAX_READ 0xFFF00000u  // the walk's absolute positions stay below 2^32 (two epochs of codes are loaded ahead)
 enum { GZL_ALL = 0, GZL_HANDED_BACK = 1 };
 struct GzlArgs {
@@ -51,21 +50,23 @@ struct GzlArgs {
 };
 #define GZL_STRIDE32 (GZL_EPOCH + GZL_EPOCH + GZT_WIN)  // occ[2][GZL_EPOCH] 16-bit, pinfo[GZL_EPOCH + GZT_WIN]: a multiple of 32 words
 
-__host__ __device__ constexpr size_t gzl_work_bytes() { return (sizeof(gzsize_dev::Work) + 15) & ~(size_t)15; }
-static size_t gzl_lds_bytes(int bits) {
+__host__ __device__ constexpr size_t gzl_work_bytes() { return (sizeof(gztrees::Work) + 15) & ~(size_t)15; }
+constexpr size_t gzl_lds_bytes(int bits) {
     return (size_t)GZL_HEAD_WORDS * 4 + gzl_work_bytes() + ((size_t)GZL_EPOCH * GZL_RING_EPOCHS * bits / 32 + GZL_GUARD) * 4;
 }
+// the figures of the head comment: they decide two / three wavefronts per CU
+static_assert(gzl_work_bytes() == 7088 && gzl_lds_bytes(4) == 75968 && gzl_lds_bytes(2) == 43200, "k_gzip_long's LDS must not move");
 
 template <int BITS>
 __global__ __launch_bounds__(WAVE) void k_gzip_long(const GzlArgs a) {
-    constexpr uint32_t MIN_MATCH = GZ_MIN_MATCH, MAX_DIST = GZ_MAX_DIST, W_SIZE = GZL_EPOCH, MIN_LOOKAHEAD = 262;
+    constexpr uint32_t MIN_MATCH = gztrees::MIN_MATCH, MAX_DIST = gztrees::MAX_DIST, W_SIZE = GZL_EPOCH, MIN_LOOKAHEAD = gztrees::MIN_LOOKAHEAD;
     constexpr uint32_t FIRST = GzCodes<BITS>::FIRST;
     constexpr uint32_t EPW = GZL_EPOCH / GzCodes<BITS>::CPW, RWORDS = EPW * GZL_RING_EPOCHS, RMASK = RWORDS - 1u;
     extern __shared__ __align__(16) unsigned char gsm[];
     const uint32_t lane = lane_id();
     uint32_t *tall = reinterpret_cast<uint32_t *>(gsm);  // [320] the block's tallies (long match lengths during the walk, everything at a flush)
     uint32_t *ccur = tall + GZT_WORDS, *cst = ccur + 128, *pst = cst + 128, *pen = pst + 128;
-    gzsize_dev::Work *work = reinterpret_cast<gzsize_dev::Work *>(gsm + GZL_HEAD_WORDS * 4);
+    gztrees::Work *work = reinterpret_cast<gztrees::Work *>(gsm + GZL_HEAD_WORDS * 4);
     uint32_t *ring = reinterpret_cast<uint32_t *>(gsm + GZL_HEAD_WORDS * 4 + gzl_work_bytes());
     GzCodeReader<BITS, GzRingStore<BITS, RMASK>> codes{ring, 0u};
     uint16_t *occ = reinterpret_cast<uint16_t *>(a.scratch + (size_t)blockIdx.x * GZL_STRIDE32);  // [2][GZL_EPOCH]
@@ -123,7 +124,7 @@ __global__ __launch_bounds__(WAVE) void k_gzip_long(const GzlArgs a) {
         auto flush = [&](uint32_t stored_len, bool buf, bool last) {
             gz_store_tallies(t, tall, lane);
             __syncthreads();
-            if (lane == 0) gzsize_dev::flush_block_bits(*work, tall, tall + 286, stored_len, buf, last, bits);
+            if (lane == 0) gztrees::flush_block_bits(*work, tall, tall + 286, stored_len, buf, last, bits);
             __syncthreads();
             for (uint32_t i = lane; i < GZT_WORDS; i += WAVE) tall[i] = 0;
             __syncthreads();
@@ -183,10 +184,10 @@ __global__ __launch_bounds__(WAVE) void k_gzip_long(const GzlArgs a) {
                 uint32_t best = PL;
                 if ((mx >> 16) + 3u > best) { best = (mx >> 16) + 3u; MS = S + (mx & 0xFFFFu) - 65536u; }
                 ML = best <= look ? best : look;
-                if (ML == MIN_MATCH) { if (S - MS > GZ_TOO_FAR) ML = MIN_MATCH - 1; }
+                if (ML == MIN_MATCH) { if (S - MS > gztrees::TOO_FAR) ML = MIN_MATCH - 1; }
             }
             const uint32_t kind = gz_emit<BITS>(t, tall, lane, PL, PM, here, S, Sv, ML);
-            if (kind != GZ_NOTHING && ++nsym == GZL_BLOCK_SYMBOLS) {
+            if (kind != GZ_NOTHING && ++nsym == gztrees::LIT_BUFSIZE - 1) {
                 // zlib flushes right behind the tally: a match has moved strstart on by then, a literal has not yet
                 const uint32_t at = kind == GZ_LITERAL ? S - 1u : S;
                 flush(at - block_start, block_start >= base, false);

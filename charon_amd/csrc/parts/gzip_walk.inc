@@ -1,5 +1,5 @@
 // gzip_walk.inc -- the deflate_slow walk that k_gzip_tally (gzip_tally.inc) and k_gzip_long (gzip_tally_long.inc) both instantiate
-// Part of the single translation unit charon_hip.hip (included in order, before gzip_tally.inc); not a stand-alone source.
+// Part of the single translation unit charon_hip.hip (included in order, behind gzip_trees.inc and before gzip_tally.inc); not a stand-alone source.
 
 // ------------------------------------------------------------------------------------------------
 // One wavefront restates zlib's level-6 deflate_slow for one read (the scheme is described at the head of gzip_tally.inc).  What the
@@ -9,7 +9,6 @@
 // What differs for good reason stays in the kernels: where the candidates come from, NIL and the window's limit, what a step's best
 // candidate decodes to, blocks and output.
 // ------------------------------------------------------------------------------------------------
-constexpr uint32_t GZ_MIN_MATCH = 3, GZ_MAX_MATCH = 258, GZ_MAX_DIST = 32768 - 262, GZ_TOO_FAR = 4096;
 template <int BITS>
 struct GzCodes {
     static constexpr uint32_t CPW = 32 / BITS, LOGC = BITS == 4 ? 3 : 4, CMASK = (1u << BITS) - 1u;  // codes per word
@@ -17,19 +16,6 @@ struct GzCodes {
     static constexpr uint32_t CSH = BITS == 4 ? 2 : 1;    // bit index -> code index
     static constexpr uint32_t PAD = BITS == 4 ? 0xFu : 0u;  // the code behind the data
 };
-__device__ __constant__ uint8_t c_gz_extra_lbits[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
-
-__device__ __forceinline__ uint32_t gz_length_code(uint32_t lc) {  // _length_code[lc], lc = match length - 3 (trees.c tr_static_init)
-    if (lc == 255) return 28;
-    if (lc < 8) return lc;
-    const uint32_t hb = 31u - (uint32_t)__clz((int)lc);  // lc in [2^hb, 2^(hb+1)); 4 codes per power of two from 8 on
-    return (hb - 1) * 4 + ((lc >> (hb - 2)) & 3u);
-}
-__device__ __forceinline__ uint32_t gz_dist_code(uint32_t d) {  // d_code(dist), dist = match distance - 1
-    if (d < 4) return d;
-    const uint32_t hb = 31u - (uint32_t)__clz((int)d);
-    return hb * 2 + ((d >> (hb - 1)) & 1u);
-}
 
 // wave-wide unsigned max by DPP (row shifts inside the rows of 16, then the two row broadcasts of GFX9): no LDS traffic, result uniform
 __device__ __forceinline__ uint32_t gz_wave_umax(uint32_t v) {
@@ -175,7 +161,7 @@ __device__ __forceinline__ void gz_build_classes(const CODES &codes, uint32_t la
 template <int BITS, class CODES>
 __device__ __forceinline__ uint32_t gz_longest_match(const CODES &codes, uint32_t lane, uint32_t S, uint32_t next8, uint32_t curA, uint32_t curB, uint32_t packA,
                                                      uint32_t packB, bool okA, bool okB, uint32_t kk, uint32_t PL, uint32_t look, bool force_general) {
-    constexpr uint32_t FIRST = GzCodes<BITS>::FIRST, CSH = GzCodes<BITS>::CSH, MAX_MATCH = GZ_MAX_MATCH;
+    constexpr uint32_t FIRST = GzCodes<BITS>::FIRST, CSH = GzCodes<BITS>::CSH, MAX_MATCH = gztrees::MAX_MATCH;
     // common prefix: same class = same trigram, then a word of codes at once (the 0xF behind the data ends every match at n).
     // (lanes without a candidate read position 3 onwards: in range, ignored)
     const uint32_t xa = next8 ^ codes.codes8(curA + 3u);
@@ -241,15 +227,15 @@ enum { GZ_NOTHING = 0, GZ_LITERAL = 1, GZ_MATCH = 2, GZ_LONG_MATCH = 3 };  // wh
 // waiting literal is, if there is one, and the walk moves one on.  (INSERT_STRING: nothing to do -- the class arrays hold every position.)
 template <int BITS>
 __device__ __forceinline__ uint32_t gz_emit(GzTallies &t, uint32_t *tall, uint32_t lane, uint32_t PL, uint32_t PM, uint32_t here, uint32_t &S, uint32_t &Sv, uint32_t &ML) {
-    if (PL >= GZ_MIN_MATCH && ML <= PL) {
+    if (PL >= gztrees::MIN_MATCH && ML <= PL) {
         // length PL, distance S - 1 - PM (tally_dist counts dist - 1)
-        const uint32_t lc = PL - GZ_MIN_MATCH;
+        const uint32_t lc = PL - gztrees::MIN_MATCH;
         uint32_t kind = GZ_MATCH;
         t.len_cnt += lane == lc ? 1u : 0u;
         if (lc >= 64u) {
             asm volatile("" ::: "memory");
             kind = GZ_LONG_MATCH;
-            if (lane == 0) atomicAdd(&tall[257 + gz_length_code(lc)], 1u);
+            if (lane == 0) atomicAdd(&tall[257 + gztrees::length_code(lc)], 1u);
         }
         // d_code(d): the exponent and the first mantissa bit of d as a float (exact below 2^24), d itself below 2
         const uint32_t d = Sv - (PM + 2u);
@@ -257,7 +243,7 @@ __device__ __forceinline__ uint32_t gz_emit(GzTallies &t, uint32_t *tall, uint32
         t.dist_cnt += lane == dc ? 1u : 0u;
         S += PL - 1; Sv += PL - 1;
         t.code_prev = 255;
-        ML = GZ_MIN_MATCH - 1;
+        ML = gztrees::MIN_MATCH - 1;
         return kind;
     }
     const uint32_t kind = t.code_prev != 255u ? GZ_LITERAL : GZ_NOTHING;
@@ -269,6 +255,6 @@ __device__ __forceinline__ uint32_t gz_emit(GzTallies &t, uint32_t *tall, uint32
 // the register tallies into a block's record in LDS: tall[0, 286) literal/length frequencies, tall[286, 316) distance frequencies
 __device__ __forceinline__ void gz_store_tallies(const GzTallies &t, uint32_t *tall, uint32_t lane) {
     if (lane < 5) tall[gz_letter_of(lane)] = t.lit_cnt;
-    if (t.len_cnt) atomicAdd(&tall[257 + gz_length_code(lane)], t.len_cnt);
+    if (t.len_cnt) atomicAdd(&tall[257 + gztrees::length_code(lane)], t.len_cnt);
     if (lane < 30) tall[286 + lane] = t.dist_cnt;
 }

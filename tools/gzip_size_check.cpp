@@ -1,4 +1,5 @@
-// Compares gzsize::GzipSizer (charon_amd/csrc/host/gzip_size.hpp) with the linked zlib on synthetic DNA of many shapes, and times both.
+// Compares gzsize::GzipSizer (charon_amd/csrc/host/gzip_size.hpp: its own deflate_slow walk, and the trees.c arithmetic the GPU kernels
+// run too, charon_amd/csrc/parts/gzip_trees.inc) with the linked zlib on synthetic DNA of many shapes, and times both.
 //   g++ -O2 -std=c++14 -Icharon_amd/csrc/host -o /tmp/gzip_size_check tools/gzip_size_check.cpp -lz && /tmp/gzip_size_check [n_cases] [seed]
 #include <chrono>
 #include <cstdio>
