@@ -137,14 +137,16 @@ struct Slot {
     std::vector<float> h_mq, h_comp;
     hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // K1 0-1, K2 2-3, K3 4-5, chain 6-7
     hipEvent_t k1_done = nullptr, done = nullptr, split_done = nullptr;
-    uint32_t split_bound = 0;             // most reads this batch's SPLIT launch (long reads over the lanes of a wavefront) can meet; 0: no such launch
+    bool new_anchor = false;              // profiling streams: the stream's next time anchor was recorded behind this batch's probe kernel
+    uint32_t split_bound = 0;            // most reads this batch's SPLIT launch (long reads over the lanes of a wavefront) can meet; 0: no such launch
     bool ev_used[4] = {false, false, false, false};
 };
 
 struct chn_stream {
     chn_index *idx = nullptr;
     chn_stream_cfg cfg;
-    hipStream_t stream = nullptr;   // ordering + minimise+probe
+    hipStream_t stream = nullptr;   // minimise+probe of the even batches; the list-mode chains, chn_classify_counts, re-runs after a log overflow
+    hipStream_t stream1 = nullptr;  // minimise+probe of the odd batches: the next batch's wavefronts take the slots a draining grid frees
     hipStream_t stream2 = nullptr;  // count + model+call (overlap the next batch's minimise+probe)
     hipStream_t stream0 = nullptr;  // host -> device uploads of host batches (truly asynchronous when the caller's memory is pinned)
     hipStream_t stream3 = nullptr;  // deflate tallies (latency-bound LDS work beside the HBM-bound probe kernel)
@@ -173,6 +175,8 @@ struct chn_stream {
     PinBuf h_block;    // the slots' result staging in one allocation (small streams)
     int head = 0;      // slot of the next submit
     int inflight = 0;  // batches submitted and not yet waited for (FIFO)
+    uint64_t batch_seq = 0;  // whole-chain batches submitted so far: batch i's probe kernel runs on probe stream i & 1
+    bool last_had_long = false;  // the batch waited for last had reads for the SPLIT launch: while that is so, every batch takes the first probe stream
     HostModel model;
     K3Args k3;
     // chn_classify_counts(_raw): inputs and outputs of k_model_call on the caller's counts.  A set of its own (allocated on first use,
@@ -181,6 +185,16 @@ struct chn_stream {
     // profiling
     double prof_ms[4] = {0, 0, 0, 0};
     uint64_t prof_n[4] = {0, 0, 0, 0};
+    // prof_ms[0] is the time ATTRIBUTABLE to a batch's probe kernel: the part of its interval behind the end of the probe kernels
+    // waited for before it (two probe grids overlap; bracket times would count the shared time twice).  A slot's events are
+    // re-recorded by the third-next submit, so that end is kept as milliseconds behind an anchor event, and the anchor moves on
+    // (prof_anchor[prof_cur ^ 1], recorded behind a batch's probe kernel, takes over when that batch is waited for) before a float
+    // of milliseconds loses the 0.01 ms
+    hipEvent_t prof_anchor[2] = {nullptr, nullptr};
+    int prof_cur = 0;
+    bool prof_anchor_pending = false, prof_have_end = false;
+    double prof_prev_end = 0;  // ms behind prof_anchor[prof_cur]
+    std::chrono::steady_clock::time_point prof_anchor_at;
     uint64_t last_bytes = 0, last_min = 0, last_fetches = 0;
     double text_ms[2] = {0, 0};  // text batches of a profiling stream: upload of the text, pack kernels
     uint64_t text_n = 0;

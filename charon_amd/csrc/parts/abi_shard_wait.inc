@@ -145,6 +145,7 @@ extern "C" int chn_stream_sync(chn_stream *s) {
     HIPCHK(hipSetDevice(s->idx->d.device));
     HIPCHK(hipStreamSynchronize(s->stream0));
     HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream1));
     HIPCHK(hipStreamSynchronize(s->stream4));
     HIPCHK(hipStreamSynchronize(s->stream2));
     return CHN_OK;
@@ -153,6 +154,9 @@ extern "C" int chn_stream_sync(chn_stream *s) {
 // A wavefront's log region (sized for twice the minimiser density of random sequence) overflowed: run the batch again on the
 // stream's worst-case buffers (one entry per base, every row escaped), synchronously.  Inputs are still in place: host batches
 // sit in the slot's staging, device batches are owned by the caller until chn_batch_wait returns.
+// Later batches may be running meanwhile, on either probe stream and on the side stream: they work on their own slots (control words,
+// order, row log, results) and on the caller's or their slot's inputs; s->big belongs to this call (the list modes, its other users,
+// refuse to run with batches in flight), and s->d_hist is only touched by the ordering kernels on the copy stream, which do not run here.
 static int rerun_worst_case(chn_stream *s, Slot &sl) {
     const chn_index_desc &d = s->idx->d;
     unsigned long long *ctl = sl.d_ctl.as<unsigned long long>();
@@ -170,7 +174,7 @@ static int rerun_worst_case(chn_stream *s, Slot &sl) {
     fill_k1_log(a, sl, s->big, true);
     const size_t lds = k1_lds_bytes(a.wn, d.num_categories, MODE_ROWS, a.h, (uint32_t)d.bin_words, (uint32_t)d.bins);
     hipError_t e = launch_k1_mode(MODE_ROWS, (uint32_t)d.bin_words, a, lds, s->stream);
-    if (e == hipSuccess && sl.split_bound) e = launch_k1_split_mode(MODE_ROWS, (uint32_t)d.bin_words, a, lds, s->stream, std::min<uint32_t>(sl.split_bound, 8192u));
+    if (e == hipSuccess && sl.split_bound) e = launch_k1_split_mode(MODE_ROWS, (uint32_t)d.bin_words, a, lds, s->stream, split_grid(sl.split_bound));
     if (e != hipSuccess) return fail(CHN_E_HIP, std::string("k_minimise_probe re-run: ") + hipGetErrorString(e));
     if ((rc = launch_tail(s, sl, s->big, s->stream))) return rc;
     HIPCHK(hipStreamSynchronize(s->stream));
@@ -197,6 +201,22 @@ extern "C" int chn_batch_wait(chn_stream *s, chn_result *r) {
         if (sl.ev_used[i]) {
             float ms = 0;
             HIPCHK(hipEventElapsedTime(&ms, sl.ev[evpair[i][0]], sl.ev[evpair[i][1]]));
+            if (i == 0) {
+                // the probe kernel: only what lies behind the end of the probe kernels before it (they overlap, on two streams) -- the
+                // sum over batches is the time some probe kernel was running, and one batch at a time gives the bracket time
+                float t0 = 0, t1 = 0;
+                HIPCHK(hipEventElapsedTime(&t0, s->prof_anchor[s->prof_cur], sl.ev[0]));
+                HIPCHK(hipEventElapsedTime(&t1, s->prof_anchor[s->prof_cur], sl.ev[1]));
+                if (s->prof_have_end && s->prof_prev_end > (double)t0) ms = (float)std::max(0.0, (double)t1 - s->prof_prev_end);
+                if (!s->prof_have_end || (double)t1 > s->prof_prev_end) s->prof_prev_end = t1;
+                s->prof_have_end = true;
+                if (sl.new_anchor) {
+                    float off = 0;
+                    HIPCHK(hipEventElapsedTime(&off, s->prof_anchor[s->prof_cur], s->prof_anchor[s->prof_cur ^ 1]));
+                    s->prof_prev_end -= off; s->prof_cur ^= 1;
+                    sl.new_anchor = s->prof_anchor_pending = false;
+                }
+            }
             s->prof_ms[i] += ms; s->prof_n[i] += 1;
         }
     unsigned long long ctl[CTL_WORDS];
@@ -218,6 +238,7 @@ extern "C" int chn_batch_wait(chn_stream *s, chn_result *r) {
         if (ctl[CTL_STATUS] & 1) return fail(CHN_E_CAPACITY, "row log overflow at worst-case capacity (a wavefront of 64 reads with more than 2^24 escaped rows)");
     }
     s->last_bytes = ctl[CTL_BYTES]; s->last_min = ctl[CTL_MINIMISERS]; s->last_fetches = ctl[CTL_FETCHES];
+    if (!sl.list_mode) s->last_had_long = ctl[CTL_NLONG] != 0;  // (decides the next batches' probe stream: chn_batch_submit)
     if (r->on_device) {  // valid until the third-next chn_batch_submit
         r->num_hashes = sl.d_num_hashes.as<uint32_t>(); r->counts = sl.d_counts.as<uint32_t>(); r->unique_counts = sl.d_unique.as<uint32_t>();
         r->probabilities = sl.d_prob.as<double>(); r->call = sl.d_call.as<uint8_t>(); r->confidence = sl.d_conf.as<uint8_t>();
@@ -353,6 +374,13 @@ extern "C" int chn_stream_profile(chn_stream *s, int which, double *total_ms, ui
     if (total_ms) *total_ms = s->prof_ms[which];
     if (launches) *launches = s->prof_n[which];
     if (reset) { s->prof_ms[which] = 0; s->prof_n[which] = 0; }
+    if (reset && which == 0 && s->prof_anchor[0]) {  // no earlier probe kernel to count behind; idle streams: a fresh anchor as well
+        s->prof_have_end = false;
+        if (s->inflight == 0) {
+            HIPCHK(hipSetDevice(s->idx->d.device));
+            HIPCHK(prof_anchor_now(s));
+        }
+    }
     return CHN_OK;
 }
 extern "C" int chn_stream_last_batch_bytes(chn_stream *s, uint64_t *bytes, uint64_t *total_minimisers) {

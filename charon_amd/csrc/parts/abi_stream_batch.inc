@@ -11,6 +11,18 @@ struct ResLayout {
     }
 };
 
+// Profiling streams: the age from which the time anchor is replaced at the next submit (at 10 s a float of milliseconds still resolves 0.001 ms)
+static const int PROF_ANCHOR_SECONDS = 8;
+// Profiling streams, with no batch in flight (the streams are idle): a fresh anchor, and no probe kernel behind which the next one counts
+static hipError_t prof_anchor_now(chn_stream *s) {
+    for (Slot &sl : s->slot) sl.new_anchor = false;
+    s->prof_cur = 0; s->prof_anchor_pending = false; s->prof_have_end = false; s->prof_prev_end = 0;
+    hipError_t e = hipEventRecord(s->prof_anchor[0], s->stream);
+    if (e == hipSuccess) e = hipEventSynchronize(s->prof_anchor[0]);
+    s->prof_anchor_at = std::chrono::steady_clock::now();
+    return e;
+}
+
 extern "C" int chn_stream_create(chn_index *idx, const chn_stream_cfg *cfg, chn_stream **out) {
     if (!idx || !cfg || !out || cfg->struct_size != sizeof(chn_stream_cfg)) return fail(CHN_E_INVALID, "chn_stream_create: bad argument");
     if (cfg->max_reads == 0 || cfg->max_reads > 0xFFFFFF00ULL) return fail(CHN_E_INVALID, "max_reads out of range");
@@ -19,7 +31,11 @@ extern "C" int chn_stream_create(chn_index *idx, const chn_stream_cfg *cfg, chn_
     chn_stream *s = new (std::nothrow) chn_stream();
     if (!s) return fail(CHN_E_NOMEM, "host allocation failed");
     s->idx = idx; s->cfg = *cfg;
-    // Priorities: the probe kernel's stream is the ordinary one.  The side stream (count, model + call, result download of batch i)
+    // Two probe streams, used alternately: batch i + 1's probe kernel does not wait for the last wavefront of batch i's, its workgroups
+    // take the slots that batch i's retiring wavefronts free once batch i has none left to dispatch (equal-length reads leave a last
+    // generation of one wavefront per CU; a front end's 65 536-read batches never fill the device at all).  Batch i + 2 queues behind
+    // batch i, so at most two probe grids are on the device.
+    // Priorities: the probe kernels' streams are the ordinary ones.  The side stream (count, model + call, result download of batch i)
     // and the copy stream (uploads and the two tiny ordering kernels of batch i+1) run ABOVE it: their short kernels must get
     // workgroup slots as the probe kernel of the neighbouring batch retires waves, or batch i only completes when batch i+1's probe
     // kernel does and a caller with host buffers cannot start the next upload in time.  The tally stream runs BELOW it: the
@@ -28,6 +44,7 @@ extern "C" int chn_stream_create(chn_index *idx, const chn_stream_cfg *cfg, chn_
     int prio_least = 0, prio_greatest = 0;
     hipError_t e = hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->stream1, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipStreamCreateWithPriority(&s->stream2, hipStreamNonBlocking, prio_greatest);
     if (e == hipSuccess) e = hipStreamCreateWithPriority(&s->stream0, hipStreamNonBlocking, prio_greatest);
     if (e == hipSuccess) e = hipStreamCreateWithPriority(&s->stream3, hipStreamNonBlocking, prio_least);
@@ -68,6 +85,11 @@ extern "C" int chn_stream_create(chn_index *idx, const chn_stream_cfg *cfg, chn_
         if (!fused && !sharded && (rc = sl.lb.ensure(cfg->max_bases, nw, (uint32_t)idx->d.bin_words, s->cap_num, s->esc_shift, (n + WAVE - 1) / WAVE + n))) { chn_stream_destroy(s); return rc; }
     }
     if ((rc = s->d_hist.ensure(LEN_BLOCKS * 256 * 4))) { chn_stream_destroy(s); return rc; }
+    if (cfg->flags & CHN_STREAM_PROFILE) {  // the anchor the probe kernels' times are taken against (chn_stream_profile, which = 0)
+        for (hipEvent_t &a : s->prof_anchor) if (e == hipSuccess) e = hipEventCreate(&a);
+        if (e == hipSuccess) e = prof_anchor_now(s);
+        if (e != hipSuccess) { chn_stream_destroy(s); return fail(CHN_E_HIP, std::string("profiling anchor: ") + hipGetErrorString(e)); }
+    }
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, idx->d.device) == hipSuccess && cus > 0) s->n_cus = (uint32_t)cus;
@@ -90,12 +112,14 @@ extern "C" int chn_stream_destroy(chn_stream *s) {
     if (!s) return CHN_OK;
     (void)hipSetDevice(s->idx->d.device);
     if (s->stream) { (void)hipStreamSynchronize(s->stream); }
+    if (s->stream1) { (void)hipStreamSynchronize(s->stream1); (void)hipStreamDestroy(s->stream1); }
     if (s->stream2) { (void)hipStreamSynchronize(s->stream2); (void)hipStreamDestroy(s->stream2); }
     if (s->stream0) { (void)hipStreamSynchronize(s->stream0); (void)hipStreamDestroy(s->stream0); }
     if (s->stream3) { (void)hipStreamSynchronize(s->stream3); (void)hipStreamDestroy(s->stream3); }
     if (s->stream4) { (void)hipStreamSynchronize(s->stream4); (void)hipStreamDestroy(s->stream4); }
     if (s->stream5) { (void)hipStreamSynchronize(s->stream5); (void)hipStreamDestroy(s->stream5); }
     if (s->stream) (void)hipStreamDestroy(s->stream);
+    for (hipEvent_t a : s->prof_anchor) if (a) (void)hipEventDestroy(a);
     for (Slot &sl : s->slot) {
         for (int i = 0; i < 8; ++i) if (sl.ev[i]) (void)hipEventDestroy(sl.ev[i]);
         if (sl.k1_done) (void)hipEventDestroy(sl.k1_done);
@@ -173,6 +197,7 @@ extern "C" int chn_model_set(chn_stream *s, const chn_model *m) {
         flat.insert(flat.end(), M.neg[c].begin(), M.neg[c].end());
     }
     HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream1));
     HIPCHK(hipStreamSynchronize(s->stream2));
     // From here on the device tables are being replaced: a failure leaves the stream WITHOUT a model (never with a torn one).
     s->model.set = false;
@@ -238,6 +263,11 @@ static uint32_t split_bound(const chn_stream *s, const Slot &sl, uint64_t n, uin
     for (uint32_t L : sl.h_len1) c += L >= floor_len;
     return (uint32_t)c;
 }
+// Workgroups of a SPLIT launch: they loop over the long reads in strides of the grid.  More than the device holds at once (1 792 at seven
+// per CU) on purpose: the reads a workgroup meets differ in length, and with four times as many workgroups as slots the dispatcher evens
+// that out as slots fall free.  A grid of exactly what is resident was measured on 500 b - 50 kb reads: the step 3 ms (4 %) longer
+// (profiles/r06/probe_overlap_ab.txt).  A device batch's bound is all its reads; its workgroups beyond the long reads return at once.
+static uint32_t split_grid(uint32_t bound) { return std::min<uint32_t>(bound, 8192u); }
 template <int MODE>
 static hipError_t launch_k1_w(uint32_t W, const K1Args &a, size_t lds, hipStream_t st) {
     switch (W) {
@@ -554,7 +584,22 @@ static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind, bool bo
     dt[1] = dnow();
     const bool prof = (s->cfg.flags & CHN_STREAM_PROFILE) != 0;
     for (int i = 0; i < 4; ++i) sl.ev_used[i] = false;
-    if (prof) HIPCHK(hipEventRecord(sl.ev[6], s->stream));
+    // This batch's probe stream: the ordinary launch and everything that brackets it.  The list modes run with nothing in flight and keep
+    // to the first.  So do the batches of a caller whose reads are long enough for the SPLIT launch (judged by the batch waited for last:
+    // a front end's length distribution does not change from batch to batch): there the SPLIT launches carry most of the bases, the
+    // length order already fills the ordinary grid's tail with its shortest reads, and a second ordinary grid beside them measured
+    // 1 - 2 % SLOWER (DESIGN section 5).  Diagnostics builds: CHN_PROBE_STREAMS=1 puts every batch on the first stream (the schedule
+    // before there were two), CHN_PROBE_STREAMS=2 alternates whatever the reads.
+    static const int probe_streams = [] { const char *v = diag_env("CHN_PROBE_STREAMS"); return v ? std::atoi(v) : 0; }();
+    const bool alternate = probe_streams == 2 || (probe_streams != 1 && !s->last_had_long);
+    const hipStream_t ps = list_mode || !alternate || !(s->batch_seq & 1) ? s->stream : s->stream1;
+    if (sl.new_anchor) { sl.new_anchor = false; s->prof_anchor_pending = false; }  // (left by a submit that failed half-way)
+    if (prof) {
+        // nothing in flight and the time anchor is old (the caller paused): a fresh one, or this batch's times would be floats of the
+        // milliseconds since before the pause (the anchor otherwise only moves on behind a running batch, below)
+        if (s->inflight == 0 && std::chrono::steady_clock::now() - s->prof_anchor_at > std::chrono::seconds(PROF_ANCHOR_SECONDS)) HIPCHK(prof_anchor_now(s));
+        HIPCHK(hipEventRecord(sl.ev[6], ps));
+    }
 
     // 0. deflate tallies for the gzip column, if asked for: their own stream, as soon as the bases are on the device
     if (int rc = submit_gzip_column(s, sl, b, bases, nmask, off1, off2, n, paired)) return rc;
@@ -571,7 +616,7 @@ static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind, bool bo
                        ctl, sl.split_bound ? s->long_bucket : 256u, sl.split_bound);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(sl.uploaded, s->stream0));
-    HIPCHK(hipStreamWaitEvent(s->stream, sl.uploaded, 0));
+    HIPCHK(hipStreamWaitEvent(ps, sl.uploaded, 0));
 
     // 2. minimise + probe
     K1Args &a = sl.k1;
@@ -598,9 +643,9 @@ static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind, bool bo
         // minimisers at the same positions)
         fill_k1_log(a, sl, s->big, false);
         a.rows = s->d_list.as<uint64_t>();
-        hipLaunchKernelGGL(k_wave_caps, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s->stream, sl.d_order.as<uint32_t>(), sl.len1, sl.len2,
+        hipLaunchKernelGGL(k_wave_caps, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ps, sl.d_order.as<uint32_t>(), sl.len1, sl.len2,
                            (uint32_t)n, s->big.cap_num, s->big.esc_shift, s->big.meta.as<WaveMeta>());
-        hipLaunchKernelGGL(k_scan_meta, dim3(1), dim3(1024), 0, s->stream, s->big.meta.as<WaveMeta>(), n_waves);
+        hipLaunchKernelGGL(k_scan_meta, dim3(1), dim3(1024), 0, ps, s->big.meta.as<WaveMeta>(), n_waves);
         HIPCHK(hipGetLastError());
     } else if (!fused) {
         fill_k1_log(a, sl, sl.lb, true);
@@ -612,23 +657,29 @@ static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind, bool bo
     if (sl.split_bound) {
         // the long reads first, on a stream of their own: a few wavefronts that run beside the ordinary launch instead of holding it up
         HIPCHK(hipStreamWaitEvent(s->stream4, sl.uploaded, 0));
-        hipError_t e4 = launch_k1_split_mode(mode, W, a, lds, s->stream4, std::min<uint32_t>(sl.split_bound, 8192u));
+        hipError_t e4 = launch_k1_split_mode(mode, W, a, lds, s->stream4, split_grid(sl.split_bound));
         if (e4 != hipSuccess) return fail(CHN_E_HIP, std::string("k_minimise_probe (split) launch: ") + hipGetErrorString(e4));
         HIPCHK(hipEventRecord(sl.split_done, s->stream4));
     }
-    if (prof) { HIPCHK(hipEventRecord(sl.ev[0], s->stream)); }
-    hipError_t e = launch_k1_mode(mode, W, a, lds, s->stream);
+    if (prof) { HIPCHK(hipEventRecord(sl.ev[0], ps)); }
+    hipError_t e = launch_k1_mode(mode, W, a, lds, ps);
     if (e != hipSuccess) return fail(CHN_E_HIP, std::string("k_minimise_probe launch: ") + hipGetErrorString(e));
     if (prof) {
         // (profiling streams: the probe kernel's time is the time until BOTH its launches are done -- with long reads in the batch the SPLIT launch may
         //  carry most of the bases)
-        if (sl.split_bound) HIPCHK(hipStreamWaitEvent(s->stream, sl.split_done, 0));
-        HIPCHK(hipEventRecord(sl.ev[1], s->stream)); sl.ev_used[0] = true;
+        if (sl.split_bound) HIPCHK(hipStreamWaitEvent(ps, sl.split_done, 0));
+        HIPCHK(hipEventRecord(sl.ev[1], ps)); sl.ev_used[0] = true;
+        // the stream's time anchor moves on every few seconds: the next one behind this kernel, in use from this batch's wait on
+        if (!s->prof_anchor_pending && std::chrono::steady_clock::now() - s->prof_anchor_at > std::chrono::seconds(PROF_ANCHOR_SECONDS)) {
+            HIPCHK(hipEventRecord(s->prof_anchor[s->prof_cur ^ 1], ps));
+            s->prof_anchor_at = std::chrono::steady_clock::now();
+            sl.new_anchor = s->prof_anchor_pending = true;
+        }
     }
 
     if (list_mode) return CHN_OK;  // the caller continues with chn_shard_probe / chn_shard_finish
     dt[3] = dnow();
-    HIPCHK(hipEventRecord(sl.k1_done, s->stream));
+    HIPCHK(hipEventRecord(sl.k1_done, ps));
     HIPCHK(hipStreamWaitEvent(s->stream2, sl.k1_done, 0));
     if (sl.split_bound) HIPCHK(hipStreamWaitEvent(s->stream2, sl.split_done, 0));
     int rc = launch_tail(s, sl, sl.lb, s->stream2);
@@ -637,6 +688,7 @@ static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind, bool bo
                                (dt[1] - dt[0]) * 1e3, (dt[2] - dt[1]) * 1e3, (dt[3] - dt[2]) * 1e3, (dnow() - dt[3]) * 1e3);
     s->head = (s->head + 1) % chn_stream::N_SLOTS;
     s->inflight += 1;
+    s->batch_seq += 1;
     return CHN_OK;
 }
 

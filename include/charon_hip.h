@@ -395,8 +395,16 @@ int chn_shardx_finish(chn_stream *s, const uint64_t *dev_rows_back);
 int chn_minimisers(chn_stream *s, const chn_batch *b, uint64_t *host_values, uint64_t capacity, uint64_t *n_values);
 int chn_index_emplace(chn_index *idx, const uint64_t *host_values, uint64_t n_values, uint32_t bin);
 
-/* Per-kernel device time accumulated since the last reset (CHN_STREAM_PROFILE streams only).
+/* Per-kernel device time accumulated since the last reset (CHN_STREAM_PROFILE streams only), added up as the batches are waited for.
  * which: 0 = minimise+probe kernel, 1 = count kernel, 2 = model+call kernel, 3 = whole batch chain;
+ *   0 is the device time ATTRIBUTABLE to each batch's minimise+probe kernel (both its launches): the probe kernels of consecutive
+ *   batches run on two streams and overlap (unless the batch waited for last held reads long enough to be split over a wavefront:
+ *   then every batch takes the first of the two), so a batch counts from max(its kernel's start, the latest end of the probe kernels of the
+ *   batches waited for before it) to its kernel's end.  With one batch in flight that is the kernel's own time from start to end; with
+ *   several, the total is the time during which some probe kernel was running (the union of their intervals, never more than the wall
+ *   time around them) and total / launches is what a batch adds to it.  *launches counts batches.  reset forgets the previous end.
+ *   1, 2 and 3 are event-bracketed times of each batch on its own; 3 runs from the batch's turn on its probe stream to the end of its
+ *   model+call kernel and so contains the time its probe kernel shares the device with its neighbour's;
  * 4 (any stream): *launches = number of batches chn_batch_wait re-ran on worst-case buffers after a row-log overflow;
  * 5 (any stream): *launches = row fetches the last waited batch's minimise+probe kernel issued (h per minimiser; fewer for an index of
  *   at most four bins, whose rows are fetched one at a time and only while the AND so far still has a bin set);

@@ -4,6 +4,9 @@
 # (CHN_DIAG_NO_STORE / CHN_DIAG_NO_ESC_STORE builds are NOT offered here any more: they leave the row log unwritten, and the
 #  count kernel then chases garbage escaped-row indices -- a GPU memory fault; they were only ever meaningful with the
 #  count kernel's output ignored.)
+#   tools/diag/libcharon_hip_CHN_DIAG.so    -DCHN_DIAG: the library reads the CHN_* environment switches (a product build reads none), e.g.
+#       CHN_PROBE_STREAMS=1   every batch's probe kernel on one stream, as before the two probe streams (A/B of the overlap)
+#       CHN_PROBE_STREAMS=2   the two probe streams alternately for every batch, also while batches hold reads for the SPLIT launch
 # Use with CHARON_HIP_LIB=<path> python bench.py ...
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
