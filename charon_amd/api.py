@@ -90,6 +90,16 @@ class InflateCrc(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("expected", C.c_void_p), ("crc32", C.c_void_p)]
 
 
+DEFLATE_MAX_IN = 65280       # CHN_DEFLATE_MAX_IN
+DEFLATE_BGZF = 1             # CHN_DEFLATE_BGZF
+
+
+class DeflateJob(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_members", C.c_uint64), ("in_", C.c_void_p), ("in_bytes", C.c_uint64),
+                ("in_offset", C.c_void_p), ("in_length", C.c_void_p), ("out", C.c_void_p), ("out_bytes", C.c_uint64),
+                ("out_offset", C.c_void_p), ("out_length", C.c_void_p), ("out_used", C.c_void_p), ("crc32", C.c_void_p)]
+
+
 class SynthReadsOut(C.Structure):
     _fields_ = [("bases2", C.c_void_p), ("seg1_offset", C.c_void_p), ("seg1_length", C.c_void_p), ("mean_quality", C.c_void_p),
                 ("compression", C.c_void_p), ("n_bases", C.c_uint64)]
@@ -102,7 +112,8 @@ EXPORTS = ["chn_index_create", "chn_index_upload_rows", "chn_index_device_words"
            "chn_stream_last_batch_bytes", "chn_synth_genomes", "chn_synth_fill_index", "chn_synth_plant", "chn_synth_reads",
            "chn_device_free", "chn_device_download", "chn_device_malloc", "chn_device_upload", "chn_host_alloc", "chn_host_free", "chn_shard_minimise",
            "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_text_submit", "chn_text_wait", "chn_text_pack", "chn_inflate_create", "chn_inflate_run",
-           "chn_inflate_run_host", "chn_inflate_destroy", "chn_inflate_kernel_ms", "chn_inflate_run_crc", "chn_inflate_run_host_crc", "chn_last_error", "chn_version"]
+           "chn_inflate_run_host", "chn_inflate_destroy", "chn_inflate_kernel_ms", "chn_inflate_run_crc", "chn_inflate_run_host_crc", "chn_deflate_create", "chn_deflate_run", "chn_deflate_run_host",
+           "chn_deflate_destroy", "chn_deflate_bound", "chn_deflate_kernel_ms", "chn_deflate_group_members", "chn_last_error", "chn_version"]
 
 _L.chn_last_error.restype = C.c_char_p
 _L.chn_version.restype = C.c_char_p
@@ -160,6 +171,13 @@ _L.chn_inflate_destroy.argtypes = [C.c_void_p]
 _L.chn_inflate_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
 _L.chn_inflate_run_crc.argtypes = [C.c_void_p, C.POINTER(InflateJob), C.POINTER(InflateCrc)]
 _L.chn_inflate_run_host_crc.argtypes = [C.POINTER(InflateJob), C.POINTER(InflateCrc)]
+_L.chn_deflate_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
+_L.chn_deflate_run.argtypes = [C.c_void_p, C.POINTER(DeflateJob)]
+_L.chn_deflate_run_host.argtypes = [C.POINTER(DeflateJob)]
+_L.chn_deflate_destroy.argtypes = [C.c_void_p]
+_L.chn_deflate_bound.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
+_L.chn_deflate_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+_L.chn_deflate_group_members.argtypes = [C.c_void_p, C.c_uint32]
 
 
 class ChnError(RuntimeError):
@@ -672,6 +690,94 @@ class Inflater:
     def destroy(self):
         if self.h:
             _L.chn_inflate_destroy(self.h)
+            self.h = None
+
+
+# ---- deflate on the device (see include/charon_hip.h) ----
+def deflate_bound(n_members, in_bytes_total, flags=0):
+    b = C.c_uint64()
+    _chk(_L.chn_deflate_bound(n_members, in_bytes_total, flags, C.byref(b)))
+    return b.value
+
+
+def deflate_job(pieces, flags=0, data=None, out=None, slack=0):
+    """the chn_deflate_job of `pieces`.  pieces: a list of bytes (laid back to back into one input array), or -- with `data`, a uint8
+    array (e.g. a pinned_array) that holds them -- a list of (offset, length).  `out`: a uint8 array to compress into instead of a fresh
+    one of chn_deflate_bound + slack bytes.  Returns (job, arrays) -- `arrays` keeps the memory alive and names it."""
+    n = len(pieces)
+    if data is None:
+        in_length = np.array([len(m) for m in pieces], np.uint32)
+        in_offset = np.zeros(n, np.uint64)
+        if n:
+            in_offset[1:] = np.cumsum(in_length[:-1], dtype=np.uint64)
+        data = np.frombuffer(b"".join(pieces), np.uint8) if n and int(in_length.sum()) else np.zeros(0, np.uint8)
+    else:
+        in_offset = np.array([int(o) for o, _ in pieces], np.uint64)
+        in_length = np.array([int(l) for _, l in pieces], np.uint32)
+    in_offset = np.concatenate([in_offset, np.zeros(1, np.uint64)])  # (never empty)
+    in_length = np.concatenate([in_length, np.zeros(1, np.uint32)])
+    bound = deflate_bound(n, int(in_length.astype(np.uint64).sum()), flags & DEFLATE_BGZF)
+    if out is None:
+        out = np.empty(max(bound + slack, 1), np.uint8)
+    assert out.dtype == np.uint8
+    out[:] = 0xA5
+    out_offset = np.full(n + 1, 0xFFFFFFFFFFFFFFFF, np.uint64)
+    out_length = np.full(n + 1, 0xFFFFFFFF, np.uint32)
+    crc = np.full(n + 1, 0xFFFFFFFF, np.uint32)
+    used = np.full(1, 0xFFFFFFFFFFFFFFFF, np.uint64)
+    j = DeflateJob()
+    j.struct_size, j.flags, j.n_members = C.sizeof(DeflateJob), flags, n
+    j.in_, j.in_bytes = (data.ctypes.data if data.size else None), data.size
+    j.in_offset, j.in_length = in_offset.ctypes.data, in_length.ctypes.data
+    j.out, j.out_bytes = out.ctypes.data, out.size
+    j.out_offset, j.out_length, j.out_used, j.crc32 = out_offset.ctypes.data, out_length.ctypes.data, used.ctypes.data, crc.ctypes.data
+    return j, dict(data=data, in_offset=in_offset, in_length=in_length, out=out, out_offset=out_offset, out_length=out_length,
+                   used=used, crc32=crc, bound=bound, n=n)
+
+
+def _deflate_results(a):
+    """a finished job as a dict: out (bytes, out[0 .. out_used)), offset, length, crc32 (arrays of n), used, bound"""
+    n, used = a["n"], int(a["used"][0])
+    return dict(out=a["out"][:used].tobytes(), offset=a["out_offset"][:n].copy(), length=a["out_length"][:n].copy(),
+                crc32=a["crc32"][:n].copy(), used=used, bound=a["bound"])
+
+
+def deflate_host(pieces, flags=0, data=None):
+    """chn_deflate_run_host: the compressor the GPU runs, on the CPU -- the same bytes.  See _deflate_results for what is returned."""
+    j, a = deflate_job(pieces, flags, data)
+    _chk(_L.chn_deflate_run_host(C.byref(j)))
+    return _deflate_results(a)
+
+
+class Deflater:
+    """chn_deflate: pieces of at most DEFLATE_MAX_IN bytes deflated on the device, one wavefront a piece, optionally framed as BGZF
+    blocks.  One thread at a time per object."""
+
+    def __init__(self, device=0):
+        self.h = C.c_void_p()
+        _chk(_L.chn_deflate_create(device, C.byref(self.h)))
+
+    def run(self, pieces, flags=0, data=None, out=None):
+        j, a = deflate_job(pieces, flags, data, out)
+        _chk(_L.chn_deflate_run(self.h, C.byref(j)))
+        return _deflate_results(a)
+
+    def run_job(self, job):
+        """chn_deflate_run on a prepared DeflateJob (deflate_job): no copies on the Python side, for measurements"""
+        _chk(_L.chn_deflate_run(self.h, C.byref(job)))
+
+    def group_members(self, members):
+        """testing / measurement: at most `members` members in a group of the pipeline (1 .. 1024)"""
+        _chk(_L.chn_deflate_group_members(self.h, members))
+
+    def kernel_ms(self):
+        ms = C.c_double()
+        _chk(_L.chn_deflate_kernel_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def destroy(self):
+        if self.h:
+            _L.chn_deflate_destroy(self.h)
             self.h = None
 
 

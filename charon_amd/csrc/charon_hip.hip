@@ -61,6 +61,7 @@
 #include "parts/gzip_tally_long.inc"
 #include "parts/text_pack.inc"
 #include "parts/inflate_members.inc"
+#include "parts/deflate_members.inc"
 #include "parts/ef_decode.inc"
 #include "parts/synth_kernels.inc"
 #include "parts/abi_index_model.inc"
@@ -68,5 +69,6 @@
 #include "parts/abi_shard_wait.inc"
 #include "parts/abi_text_batch.inc"
 #include "parts/abi_inflate.inc"
+#include "parts/abi_deflate.inc"
 #include "parts/abi_shardx.inc"
 #include "parts/abi_synth_memory.inc"

@@ -98,6 +98,17 @@ static bool parse_gpu_inflate_env(const DehostArguments *opt) {
     else if (const char *d = std::getenv("CHARON_DEVICE")) g_gpu_inflate_device = std::atoi(d);
     return true;
 }
+// CHARON_GPU_DEFLATE: 1 = the extract files are compressed on the device as BGZF, 0 or unset = by zlib on the -t threads; anything else
+// is an error.  The device is CHARON_DEVICE, or the first entry of CHARON_DEVICES.
+static bool parse_gpu_deflate_env(const DehostArguments &opt) {
+    const char *e = std::getenv("CHARON_GPU_DEFLATE");
+    if (!e) return true;
+    const std::string v(e);
+    if (v != "0" && v != "1") { std::cerr << "charon: CHARON_GPU_DEFLATE: '" << v << "' is neither 0 nor 1" << std::endl; return false; }
+    g_gpu_deflate = v == "1";
+    g_gpu_deflate_device = opt.devices.empty() ? opt.device : opt.devices[0];
+    return true;
+}
 int main(int argc, char **argv) {
     if (argc < 2) { std::cerr << "A subcommand is required\nRun with --help for more information.\n"; return 106; }
     const std::string sub = argv[1];
@@ -401,6 +412,7 @@ int main(int argc, char **argv) {
         opt.text_batches = v == "1";
     }
     if (!parse_gpu_inflate_env(&opt)) return 1;  // checked before the index file is opened and before any HIP call
+    if (!parse_gpu_deflate_env(opt)) return 1;   // likewise
     try {
         dehost_main(opt);  // the reference's subcommand callback discards dehost_main's return value (src/dehost_main.cpp:311)
         return 0;

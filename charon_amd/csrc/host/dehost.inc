@@ -444,6 +444,7 @@ int dehost_main(DehostArguments &opt) {
     g_pin_slabs = opt.text_batches || g_gpu_inflate;  // (CHARON_GPU_INFLATE=1 downloads straight into the slab)
     struct SlabPoolDrain { ~SlabPoolDrain() { std::lock_guard<std::mutex> lk(g_slab_pool.m); g_slab_pool.v.clear(); } } slab_pool_drain;
     if (g_gpu_inflate) g_log.info("CHARON_GPU_INFLATE=1: BGZF members are inflated on device " + std::to_string(g_gpu_inflate_device) + " (size and CRC-32 are checked on the device)");
+    if (g_gpu_deflate) g_log.info("CHARON_GPU_DEFLATE=1: extract files are compressed on device " + std::to_string(g_gpu_deflate_device) + " (BGZF members of 65280 bytes)");
     if (opt.text_batches) g_log.info("CHARON_TEXT_BATCHES=1: reads go to the device as text (letters -> codes and mean quality on the GPU)");
     // reader thread: parses whole-record blocks while the previous batch is packed / compressed / classified / printed.  It starts
     // before the device is touched, so the first block is parsed while the HIP runtime initialises and the index is decoded.
@@ -1174,6 +1175,11 @@ int dehost_main(DehostArguments &opt) {
         std::fprintf(stderr, "charon: %s\n", tb);
         if (g_gpu_inflate) {
             std::snprintf(tb, sizeof tb, "timing (reader thread, s): inside chn_inflate_run %.3f (part of inflate)", g_gpu_inflate_s);
+            g_log.info(tb);
+            std::fprintf(stderr, "charon: %s\n", tb);
+        }
+        if (g_gpu_deflate) {
+            std::snprintf(tb, sizeof tb, "timing (main thread, s): inside chn_deflate_run %.3f (extract files)", g_gpu_deflate_s);
             g_log.info(tb);
             std::fprintf(stderr, "charon: %s\n", tb);
         }

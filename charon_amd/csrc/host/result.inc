@@ -121,6 +121,12 @@ void format_row(const IndexMeta &meta, const Entry &e, std::string &out);
         if (_rc != CHN_OK) throw std::runtime_error(std::string(#call) + " failed: " + chn_last_error()); \
     } while (0)
 
+// CHARON_GPU_DEFLATE=1: the extract files are compressed on the device (chn_deflate_run, BGZF members of 65 280 bytes) instead of by zlib
+// on the -t threads; set in main() before anything else runs
+bool g_gpu_deflate = false;
+int g_gpu_deflate_device = 0;
+double g_gpu_deflate_s = 0;  // main-thread seconds inside chn_deflate_run (CHARON_TIMING)
+
 // Result (include/result.hpp): cache while training, classify, print, count
 class Result {
     const IndexMeta &meta_;
@@ -147,6 +153,8 @@ class Result {
         std::vector<size_t> cuts;  // record boundaries in `pending`, about 1 MB apart
     };
     std::map<uint8_t, std::vector<ExtractFile>> extract_;
+    chn_deflate *deflater_ = nullptr;  // CHARON_GPU_DEFLATE=1: created with the first piece
+    std::vector<uint8_t> deflated_;
 
     static std::string gzip_member(const char *p, size_t n) {
         z_stream zs;
@@ -163,7 +171,39 @@ class Result {
         out.resize(produced);
         return out;
     }
+    // CHARON_GPU_DEFLATE=1: the pending bytes in pieces of CHN_DEFLATE_MAX_IN bytes, one BGZF member each (record boundaries do not matter
+    // to BGZF), in one chn_deflate_run.  A tail shorter than a piece stays pending unless the file is being closed.
+    void flush_extract_gpu(ExtractFile &x, bool closing) {
+        const size_t piece = CHN_DEFLATE_MAX_IN, whole = x.pending.size() / piece, take = closing ? x.pending.size() : whole * piece;
+        const size_t n = (take + piece - 1) / piece;
+        x.cuts.clear();
+        if (n == 0) return;
+        std::vector<uint64_t> in_off(n), out_off(n);
+        std::vector<uint32_t> in_len(n), out_len(n);
+        for (size_t i = 0; i < n; ++i) { in_off[i] = i * piece; in_len[i] = (uint32_t)std::min(piece, take - i * piece); }
+        uint64_t bound = 0, used = 0;
+        bool ok = chn_deflate_bound(n, take, CHN_DEFLATE_BGZF, &bound) == CHN_OK;
+        if (ok && !deflater_) ok = chn_deflate_create(g_gpu_deflate_device, &deflater_) == CHN_OK;
+        if (ok) {
+            if (deflated_.size() < bound) deflated_.resize(bound);
+            chn_deflate_job job;
+            std::memset(&job, 0, sizeof job);
+            job.struct_size = sizeof job; job.flags = CHN_DEFLATE_BGZF; job.n_members = n;
+            job.in = reinterpret_cast<const uint8_t *>(x.pending.data()); job.in_bytes = take;
+            job.in_offset = in_off.data(); job.in_length = in_len.data();
+            job.out = deflated_.data(); job.out_bytes = deflated_.size();
+            job.out_offset = out_off.data(); job.out_length = out_len.data(); job.out_used = &used;
+            const double t0 = omp_get_wtime();
+            ok = chn_deflate_run(deflater_, &job) == CHN_OK;
+            g_gpu_deflate_s += omp_get_wtime() - t0;
+        }
+        if (!ok) throw std::runtime_error("compressing the extract file " + x.path + " failed: " + chn_last_error());
+        if (std::fwrite(deflated_.data(), 1, used, x.f) != used) throw std::runtime_error("write to extract file " + x.path + " failed");
+        x.wrote = true;
+        x.pending.erase(0, take);
+    }
     void flush_extract(ExtractFile &x) {
+        if (g_gpu_deflate) { flush_extract_gpu(x, false); return; }
         if (x.pending.empty()) return;
         std::vector<size_t> b(1, 0);
         for (size_t c : x.cuts) if (c > b.back() && c < x.pending.size()) b.push_back(c);
@@ -187,6 +227,14 @@ class Result {
     }
     void close_extract(ExtractFile &x) {
         if (!x.f) return;
+        if (g_gpu_deflate) {  // every file ends with BGZF's end-of-file marker; one that got no record is the marker alone
+            flush_extract_gpu(x, true);
+            static const unsigned char eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+            const bool ok = std::fwrite(eof, 1, sizeof eof, x.f) == sizeof eof;
+            if (std::fclose(x.f) != 0 || !ok) { x.f = nullptr; throw std::runtime_error("write to extract file " + x.path + " failed"); }
+            x.f = nullptr;
+            return;
+        }
         flush_extract(x);
         if (!x.wrote) { const std::string m = gzip_member("", 0); (void)std::fwrite(m.data(), 1, m.size(), x.f); }  // an empty member, as gzclose writes
         std::fclose(x.f);
@@ -316,6 +364,7 @@ public:
             for (ExtractFile &x : kv.second) {
                 try { close_extract(x); } catch (...) { if (x.f) std::fclose(x.f); x.f = nullptr; }
             }
+        if (deflater_) (void)chn_deflate_destroy(deflater_);
     }
     Result(const Result &) = delete;
     Result &operator=(const Result &) = delete;

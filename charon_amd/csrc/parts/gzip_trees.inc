@@ -7,6 +7,8 @@
 // build_bl_tree and the stored / static / dynamic choice of _tr_flush_block.  k_gzip_size runs it with one lane per read, lane 0 of
 // k_gzip_long at every block flush, GzipSizer at every block flush of the host walk -- so every CPU comparison of GzipSizer with zlib
 // (tests/test_cli_cpu.py, tools/gzip_size_check.cpp) checks the statements the kernels run.  zlib is the yardstick on both sides.
+// deflate_members.inc, which writes blocks instead of sizing them, takes its trees and its choice from here too (plan_block) and its
+// block header through send_tree.
 
 #ifndef __HIPCC__  // a CPU build (the host front end, tools/gzip_size_check.cpp)
 #define __host__
@@ -163,6 +165,61 @@ __host__ __device__ static inline void scan_tree(Work &w, uint16_t *tlen, int ma
         else if (curlen == nextlen) { max_count = 6; min_count = 3; }
         else { max_count = 7; min_count = 4; }
     }
+}
+// send_tree: the code-length sequence tlen[0 .. max_code] as scan_tree counted it, sent through `s`: s.bl(sym) sends the bit-length
+// code of sym, s.bits(value, n) n plain bits (deflate_members.inc writes them; the sizers only count and never call this)
+template <class S> __host__ __device__ static inline void send_tree(S &s, uint16_t *tlen, int max_code) {
+    int prevlen = -1, curlen, nextlen = tlen[0], count = 0, max_count = 7, min_count = 4;
+    if (nextlen == 0) { max_count = 138; min_count = 3; }
+    tlen[max_code + 1] = (uint16_t)0xffff;  // guard, as scan_tree left it
+    for (int n = 0; n <= max_code; ++n) {
+        curlen = nextlen;
+        nextlen = tlen[n + 1];
+        if (++count < max_count && curlen == nextlen) continue;
+        else if (count < min_count) { do { s.bl(curlen); } while (--count != 0); }
+        else if (curlen != 0) {
+            if (curlen != prevlen) { s.bl(curlen); count--; }
+            s.bl(REP_3_6); s.bits((uint32_t)(count - 3), 2);
+        } else if (count <= 10) { s.bl(REPZ_3_10); s.bits((uint32_t)(count - 3), 3); }
+        else { s.bl(REPZ_11_138); s.bits((uint32_t)(count - 11), 7); }
+        count = 0;
+        prevlen = curlen;
+        if (nextlen == 0) { max_count = 138; min_count = 3; }
+        else if (curlen == nextlen) { max_count = 6; min_count = 3; }
+        else { max_count = 7; min_count = 4; }
+    }
+}
+// The steps of flush_block_bits (below) up to its choice, for a caller that goes on to WRITE the block (deflate_members.inc): the
+// block's frequencies are lf [L_CODES] without END_BLOCK's count, which is set here, and df [D_CODES].  Leaves the code lengths in
+// w.llen / w.dlen / w.bllen and the bit counts in w.opt_len / w.static_len (both without the 3 header bits); opt_lenb is the smaller of
+// the two byte counts, as in zlib.  (flush_block_bits keeps its own statement of these calls: the sizers' kernels are tuned around
+// the code it compiles to.)
+struct BlockPlan { int max_l, max_d, max_blindex; uint64_t opt_lenb, static_lenb; };
+template <typename T>
+__host__ __device__ static inline BlockPlan plan_block(Work &w, const T *lf, const T *df) {
+    BlockPlan b;
+    w.opt_len = w.static_len = 0;
+    for (int i = 0; i < BL_CODES; ++i) w.blfreq[i] = 0;
+    // literal/length tree
+    for (int i = 0; i < L_CODES; ++i) w.freq[i] = lf[i];
+    w.freq[END_BLOCK] = 1;
+    b.max_l = build_tree(w, 0, L_CODES, MAX_BITS, LITERALS + 1, w.llen);
+    // distance tree
+    for (int i = 0; i < D_CODES; ++i) w.freq[i] = df[i];
+    b.max_d = build_tree(w, 1, D_CODES, MAX_BITS, 0, w.dlen);
+    // bit-length tree over the two code-length sequences
+    scan_tree(w, w.llen, b.max_l);
+    scan_tree(w, w.dlen, b.max_d);
+    for (int i = 0; i < BL_CODES; ++i) w.freq[i] = w.blfreq[i];
+    (void)build_tree(w, 2, BL_CODES, MAX_BL_BITS, 0, w.bllen);
+    const uint8_t order[BL_CODES] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+    for (b.max_blindex = BL_CODES - 1; b.max_blindex >= 3; --b.max_blindex)
+        if (w.bllen[order[b.max_blindex]] != 0) break;
+    w.opt_len += 3 * ((uint64_t)b.max_blindex + 1) + 5 + 5 + 4;
+    b.opt_lenb = (w.opt_len + 3 + 7) >> 3;
+    b.static_lenb = (w.static_len + 3 + 7) >> 3;
+    if (b.static_lenb <= b.opt_lenb) b.opt_lenb = b.static_lenb;
+    return b;
 }
 // _tr_flush_block for one block of a deflate stream: the trees of the block's frequencies (lf [L_CODES] without END_BLOCK's count,
 // which is set here; df [D_CODES]), the stored / static / dynamic choice, and the block's bits added to `bits`, the running bit count

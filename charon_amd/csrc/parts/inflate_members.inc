@@ -457,10 +457,10 @@ __host__ __device__ static inline uint32_t inf_crc_slice(const uint32_t *tab, co
     return reg;
 }
 // zlib's crc32(0, data, n) of output bytes [0, n), which live at win[wmis ..).  Overwrites `ll`: the decode has ended.  Wave-uniform result.
-template <class P> __host__ __device__ static uint32_t inf_crc32(P &p, InfShared &sh, uint32_t wmis, uint32_t n) {
+// inf_crc32_at is the same over any byte array `win` with 1 024 words of scratch `tab` (deflate_members.inc: the input piece in LDS).
+template <class P> __host__ __device__ static uint32_t inf_crc32_at(P &p, uint32_t *tab, const uint8_t *win, uint32_t wmis, uint32_t n) {
     if (n == 0) return 0;
     const uint32_t lane = p.lane();
-    uint32_t *tab = sh.ll;  // 4 x 256 words of its 2 048
     for (uint32_t v = lane; v < 256; v += P::LANES) {
         uint32_t c = v;
         for (uint32_t k = 0; k < 8; ++k) c = (c >> 1) ^ (INF_CRC_POLY & (0u - (c & 1u)));
@@ -478,7 +478,7 @@ template <class P> __host__ __device__ static uint32_t inf_crc32(P &p, InfShared
     for (uint32_t k = 0; k < INF_CRC_SLICES / P::LANES; ++k) {
         const uint32_t s = k * P::LANES + lane, end = (s + 1) * S;
         const uint32_t a = s * S > pad ? s * S - pad : 0, e = end > pad ? end - pad : 0;
-        part[k] = e ? inf_crc_slice(tab, sh.win, wmis + a, wmis + e, s * S <= pad ? 0xFFFFFFFFu : 0u) : 0u;
+        part[k] = e ? inf_crc_slice(tab, win, wmis + a, wmis + e, s * S <= pad ? 0xFFFFFFFFu : 0u) : 0u;
     }
     uint32_t mult = inf_crc_shift(S);  // x^(8 S 2^r) in round r
     for (uint32_t r = 0; r < 6; ++r) {
@@ -486,6 +486,9 @@ template <class P> __host__ __device__ static uint32_t inf_crc32(P &p, InfShared
         mult = inf_crc_mul(mult, mult);
     }
     return ~p.uni(part[0]);
+}
+template <class P> __host__ __device__ static uint32_t inf_crc32(P &p, InfShared &sh, uint32_t wmis, uint32_t n) {
+    return inf_crc32_at(p, sh.ll, sh.win, wmis, n);  // 4 x 256 words of its 2 048
 }
 
 // host entry: one member, `sh` is the caller's scratch; writes min(produced, out_len) bytes; *crc (if asked for) is set where the status is 0

@@ -463,6 +463,45 @@ typedef struct chn_inflate_crc {
 int chn_inflate_run_crc(chn_inflate *h, const chn_inflate_job *job, const chn_inflate_crc *crc);   /* synchronous */
 int chn_inflate_run_host_crc(const chn_inflate_job *job, const chn_inflate_crc *crc);
 
+/* ---- deflate on the device (the extract files of the front end; no reference counterpart: the reference writes through zlib's
+ * gzFile on one CPU thread) -------------------------------------------------------------------------------------------------------
+ * A job names n_members independent pieces of at most CHN_DEFLATE_MAX_IN bytes (bgzip's block size) inside `in`.  Every piece becomes
+ * one raw deflate stream (RFC 1951) of a single block with BFINAL = 1 -- stored, static or dynamic, whichever zlib's own rule finds
+ * smallest, so never more than in_length + 5 bytes -- and with CHN_DEFLATE_BGZF a complete BGZF block: the 18-byte gzip header with the
+ * BC subfield and BSIZE, the deflate data, CRC-32 and ISIZE.  The members come out back to back in member order: member i at
+ * out_offset[i] with out_length[i] bytes, out_offset[0] = 0, out_offset[i + 1] = out_offset[i] + out_length[i], *out_used = the end of
+ * the last, so out[0 .. *out_used) can be written to a file as it stands.  in_length[i] == 0 is legal and yields the empty member:
+ * under CHN_DEFLATE_BGZF the 28-byte end-of-file marker.  crc32 (optional) receives zlib's crc32(0, piece, in_length[i]).
+ * The descriptors are checked before anything runs: struct_size, no unknown flag, in_offset[i] + in_length[i] <= in_bytes,
+ * in_length[i] <= CHN_DEFLATE_MAX_IN, out_bytes >= chn_deflate_bound(n_members, sum of in_length, flags); a violation is CHN_E_INVALID,
+ * chn_last_error() names the member, and nothing has run or been written.  n_members == 0 is a no-op (*out_used = 0).
+ * k_deflate_members compresses one piece per wavefront; chn_deflate_run_host runs the same compressor source on the CPU and gives the
+ * same bytes.  A chn_deflate owns its streams, staging and scratch (grow-only); ONE thread at a time per handle.  chn_deflate_run is
+ * synchronous. */
+#define CHN_DEFLATE_MAX_IN 65280u
+#define CHN_DEFLATE_BGZF 1u
+typedef struct chn_deflate chn_deflate;
+typedef struct chn_deflate_job {
+    uint32_t struct_size, flags;              /* flags: 0 or CHN_DEFLATE_BGZF */
+    uint64_t n_members;
+    const uint8_t *in;  uint64_t in_bytes;    /* HOST; pageable or page-locked */
+    const uint64_t *in_offset; const uint32_t *in_length;    /* [n] piece i; the pieces may lie anywhere in `in` */
+    uint8_t *out;  uint64_t out_bytes;        /* HOST; pageable or page-locked */
+    uint64_t *out_offset; uint32_t *out_length;              /* [n] out */
+    uint64_t *out_used;                       /* out */
+    uint32_t *crc32;                          /* [n] out, or NULL */
+} chn_deflate_job;
+int chn_deflate_create(int32_t device, chn_deflate **out);
+int chn_deflate_run(chn_deflate *h, const chn_deflate_job *job);       /* synchronous */
+int chn_deflate_run_host(const chn_deflate_job *job);                  /* same compressor source on the CPU, one thread; no GPU needed */
+int chn_deflate_destroy(chn_deflate *h);
+/* bytes that `out` must have for n_members pieces of in_bytes_total bytes altogether */
+int chn_deflate_bound(uint64_t n_members, uint64_t in_bytes_total, uint32_t flags, uint64_t *bytes);
+/* measurement aid: device time of the kernels of the handle's last chn_deflate_run, from events around them */
+int chn_deflate_kernel_ms(chn_deflate *h, double *ms);
+/* testing and measurement aid: at most `members` (1 .. 1024, the default) members in one group of chn_deflate_run's pipeline */
+int chn_deflate_group_members(chn_deflate *h, uint32_t members);
+
 /* ---- synthetic workload fabrication on the device (bench / tests; no reference counterpart) ---------- */
 /* Measurement aid: the rate this device sustains for NOTHING BUT the index's probe pattern -- independent uniformly random row
  * fetches of 8 * bin_words bytes from THIS index's words (one load per thread in flight, 32 wavefronts per CU, `nt` cache policy if
