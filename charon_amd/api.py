@@ -60,6 +60,8 @@ class Result(C.Structure):
 
 
 TEXT_DNA5_RANKS = 1          # chn_text_batch.flags: the text holds seqan3 dna5 ranks (0 A, 1 C, 2 G, 3 N, 4 T), not letters
+TEXT_ON_DEVICE = 2           # chn_text_batch.flags: `text` is device memory (16-byte aligned, readable up to text_bytes rounded up to 16)
+TEXT_SPLIT_MAX_BYTES = 1 << 31   # CHN_TEXT_SPLIT_MAX_BYTES
 
 
 class TextBatch(C.Structure):
@@ -67,6 +69,13 @@ class TextBatch(C.Structure):
                 ("text_bytes", C.c_uint64), ("seq1_offset", C.c_void_p), ("seq1_length", C.c_void_p), ("qual1_offset", C.c_void_p),
                 ("qual1_length", C.c_void_p), ("seq2_offset", C.c_void_p), ("seq2_length", C.c_void_p), ("qual2_offset", C.c_void_p),
                 ("qual2_length", C.c_void_p), ("compression", C.c_void_p), ("gzip_tallies", C.c_uint32), ("gzip_output", C.c_uint32)]
+
+
+class TextSplitJob(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("text", C.c_void_p), ("text_bytes", C.c_uint64), ("start", C.c_uint64),
+                ("max_records", C.c_uint64), ("id_offset", C.c_void_p), ("id_length", C.c_void_p), ("seq_offset", C.c_void_p),
+                ("seq_length", C.c_void_p), ("qual_offset", C.c_void_p), ("ids", C.c_void_p), ("ids_capacity", C.c_uint64),
+                ("n_records", C.c_uint64), ("consumed", C.c_uint64), ("ids_bytes", C.c_uint64)]
 
 
 class TextResult(C.Structure):
@@ -78,6 +87,7 @@ INFLATE_MAX_OUT = 65536      # CHN_INFLATE_MAX_OUT
 INFLATE_STATUS = {0: "ok", 1: "input exhausted", 2: "bad block header", 3: "bad code lengths", 4: "bad symbol or distance",
                   5: "more output than out_length", 6: "stream ended short of out_length", 7: "CRC-32 differs from the expected one"}
 INFLATE_E_CRC = 7            # CHN_INFLATE_E_CRC
+INFLATE_OUT_DEVICE = 1       # CHN_INFLATE_OUT_DEVICE: chn_inflate_job.out is device memory
 
 
 class InflateJob(C.Structure):
@@ -111,7 +121,7 @@ EXPORTS = ["chn_index_create", "chn_index_upload_rows", "chn_index_device_words"
            "chn_model_set", "chn_batch_submit", "chn_batch_wait", "chn_stream_sync", "chn_classify_counts", "chn_classify_counts_raw", "chn_stream_profile",
            "chn_stream_last_batch_bytes", "chn_synth_genomes", "chn_synth_fill_index", "chn_synth_plant", "chn_synth_reads",
            "chn_device_free", "chn_device_download", "chn_device_malloc", "chn_device_upload", "chn_host_alloc", "chn_host_free", "chn_shard_minimise",
-           "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_text_submit", "chn_text_wait", "chn_text_pack", "chn_inflate_create", "chn_inflate_run",
+           "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_text_submit", "chn_text_wait", "chn_text_pack", "chn_text_split", "chn_text_split_host", "chn_inflate_create", "chn_inflate_run",
            "chn_inflate_run_host", "chn_inflate_destroy", "chn_inflate_kernel_ms", "chn_inflate_run_crc", "chn_inflate_run_host_crc", "chn_deflate_create", "chn_deflate_run", "chn_deflate_run_host",
            "chn_deflate_destroy", "chn_deflate_bound", "chn_deflate_kernel_ms", "chn_deflate_group_members", "chn_last_error", "chn_version"]
 
@@ -164,6 +174,8 @@ _L.chn_device_download.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64]
 _L.chn_text_submit.argtypes = [C.c_void_p, C.POINTER(TextBatch)]
 _L.chn_text_wait.argtypes = [C.c_void_p, C.POINTER(Result), C.POINTER(TextResult)]
 _L.chn_text_pack.argtypes = [C.c_void_p, C.POINTER(TextBatch)] + [C.c_void_p] * 5 + [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+_L.chn_text_split.argtypes = [C.c_void_p, C.POINTER(TextSplitJob)]
+_L.chn_text_split_host.argtypes = [C.POINTER(TextSplitJob)]
 _L.chn_inflate_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
 _L.chn_inflate_run.argtypes = [C.c_void_p, C.POINTER(InflateJob)]
 _L.chn_inflate_run_host.argtypes = [C.POINTER(InflateJob)]
@@ -455,11 +467,12 @@ class Stream:
         self._fifo.append((n_reads, None, gzip_tallies, gzip_output))
 
     # ---- text batches (see include/charon_hip.h) ----
-    def _text_batch(self, tb, compression=None, gzip_tallies=0, gzip_output=0):
-        """tb: dict from charon_amd.pack.text_batch (text may be any uint8 array, e.g. a pinned_array)"""
+    def _text_batch(self, tb, compression=None, gzip_tallies=0, gzip_output=0, text_device=None):
+        """tb: dict from charon_amd.pack.text_batch (text may be any uint8 array, e.g. a pinned_array).  text_device: (device pointer,
+        text_bytes) of the same text in device memory -- CHN_TEXT_ON_DEVICE; tb["text"] is then not looked at"""
         t = TextBatch()
         n = len(tb["seq1_length"])
-        t.struct_size, t.flags, t.n_reads = C.sizeof(TextBatch), tb.get("flags", 0), n
+        t.struct_size, t.flags, t.n_reads = C.sizeof(TextBatch), tb.get("flags", 0) | (TEXT_ON_DEVICE if text_device is not None else 0), n
         keep = []
 
         def ptr(a, dt):
@@ -469,8 +482,11 @@ class Stream:
             keep.append(a)
             return a.ctypes.data
 
-        text = tb["text"]
-        t.text, t.text_bytes = ptr(text, np.uint8) if len(text) else None, tb.get("text_bytes", len(text))
+        if text_device is not None:
+            t.text, t.text_bytes = text_device
+        else:
+            text = tb["text"]
+            t.text, t.text_bytes = ptr(text, np.uint8) if len(text) else None, tb.get("text_bytes", len(text))
         for k, dt in (("seq1_offset", np.uint64), ("seq1_length", np.uint32), ("qual1_offset", np.uint64), ("qual1_length", np.uint32),
                       ("seq2_offset", np.uint64), ("seq2_length", np.uint32), ("qual2_offset", np.uint64), ("qual2_length", np.uint32)):
             setattr(t, k, ptr(tb.get(k), dt))
@@ -478,9 +494,9 @@ class Stream:
         t.gzip_tallies, t.gzip_output = gzip_tallies, gzip_output
         return t, keep, n
 
-    def submit_text(self, tb, compression=None, gzip_tallies=0, gzip_output=0):
-        """chn_text_submit: the text and the descriptor arrays may be reused as soon as this returns"""
-        t, keep, n = self._text_batch(tb, compression, gzip_tallies, gzip_output)
+    def submit_text(self, tb, compression=None, gzip_tallies=0, gzip_output=0, text_device=None):
+        """chn_text_submit: the text and the descriptor arrays may be reused as soon as this returns.  text_device: see _text_batch"""
+        t, keep, n = self._text_batch(tb, compression, gzip_tallies, gzip_output, text_device)
         _chk(_L.chn_text_submit(self.h, C.byref(t)))
         self._fifo.append((n, None, gzip_tallies, gzip_output))
 
@@ -493,10 +509,10 @@ class Stream:
         out["mean_quality"], out["has_n"], out["n_bases"] = mq, int(tr.has_n), int(tr.n_bases)
         return out
 
-    def text_pack(self, tb):
+    def text_pack(self, tb, text_device=None):
         """chn_text_pack: the packed form of a text batch as the dict pack.pack_reads returns (nmask always an array) plus
-        mean_quality and has_n"""
-        t, keep, n = self._text_batch(tb)
+        mean_quality and has_n.  text_device: see _text_batch"""
+        t, keep, n = self._text_batch(tb, text_device=text_device)
         nb, hn = C.c_uint64(), C.c_uint32()
         _chk(_L.chn_text_pack(self.h, C.byref(t), None, None, None, None, None, C.byref(nb), C.byref(hn)))  # layout only: sizes the arrays
         paired = tb.get("seq2_offset") is not None
@@ -507,6 +523,12 @@ class Stream:
                               out["seg2_offset"].ctypes.data if paired else None, out["mean_quality"].ctypes.data, C.byref(nb), C.byref(hn)))
         out["n_bases"], out["has_n"] = int(nb.value), int(hn.value)
         return out
+
+    def text_split(self, dev_ptr, nbytes, start=0, max_records=None, want_ids=True, ids_capacity=None):
+        """chn_text_split: the FASTQ records of device text [start, nbytes) -- see text_split_host for what comes back"""
+        j, a = text_split_job(dev_ptr, nbytes, start, max_records, want_ids, ids_capacity)
+        _chk(_L.chn_text_split(self.h, C.byref(j)))
+        return _text_split_results(j, a)
 
     def wait_host(self, text_result=None):
         n, Cn = self._fifo[0][0], self.C
@@ -577,11 +599,53 @@ class Stream:
             self.h = None
 
 
+# ---- FASTQ records of a text (see include/charon_hip.h) ----
+def text_split_job(text_ptr, nbytes, start=0, max_records=None, want_ids=True, ids_capacity=None):
+    """the chn_text_split_job of the text at `text_ptr`.  max_records defaults to the most records the text can hold (one per 8
+    bytes: callers with large texts pass what they expect), ids_capacity to the bytes behind `start`.  Returns (job, arrays)."""
+    nbytes, start = int(nbytes), int(start)
+    if max_records is None:
+        max_records = max(nbytes - start, 0) // 8
+    m = max(int(max_records), 1)
+    a = dict(id_offset=np.zeros(m, np.uint64), id_length=np.zeros(m, np.uint32), seq_offset=np.zeros(m, np.uint64),
+             seq_length=np.zeros(m, np.uint32), qual_offset=np.zeros(m, np.uint64), ids=None)
+    j = TextSplitJob()
+    j.struct_size, j.flags, j.text, j.text_bytes, j.start, j.max_records = C.sizeof(TextSplitJob), 0, text_ptr, nbytes, start, int(max_records)
+    for k in ("id_offset", "id_length", "seq_offset", "seq_length", "qual_offset"):
+        setattr(j, k, a[k].ctypes.data)
+    if want_ids:
+        cap = max(nbytes - start, 0) if ids_capacity is None else int(ids_capacity)
+        a["ids"] = np.zeros(max(cap, 1), np.uint8)
+        j.ids, j.ids_capacity = a["ids"].ctypes.data, cap
+    return j, a
+
+
+def _text_split_results(j, a):
+    n = int(j.n_records)
+    out = {k: a[k][:n].copy() for k in ("id_offset", "id_length", "seq_offset", "seq_length", "qual_offset")}
+    out.update(n_records=n, consumed=int(j.consumed), ids_bytes=int(j.ids_bytes),
+               ids=a["ids"][:int(j.ids_bytes)].tobytes() if a["ids"] is not None else None)
+    return out
+
+
+def text_split_host(data, start=0, max_records=None, want_ids=True, ids_capacity=None, nbytes=None):
+    """chn_text_split_host: the rule the GPU runs, on the CPU, over `data` (bytes or a uint8 array).  Returns a dict: n_records,
+    consumed, ids_bytes, the descriptor arrays id_offset / id_length / seq_offset / seq_length / qual_offset cut to n_records, and
+    ids (the id bytes back to back, None without want_ids)."""
+    buf = np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, np.uint8)
+    nbytes = buf.size if nbytes is None else nbytes
+    j, a = text_split_job(buf.ctypes.data if buf.size else None, nbytes, start, max_records, want_ids, ids_capacity)
+    _chk(_L.chn_text_split_host(C.byref(j)))
+    return _text_split_results(j, a)
+
+
 # ---- raw deflate members (see include/charon_hip.h) ----
-def inflate_job(members, sizes, guard=0, out=None):
+def inflate_job(members, sizes, guard=0, out=None, out_device=None, out_offset=None):
     """the chn_inflate_job of `members` (raw deflate streams as bytes) with expected `sizes`: the members back to back in one input
     array, the outputs in order with `guard` untouched bytes (0xA5) behind each.  `out`: a uint8 array to decode into (e.g. a
-    pinned_array) instead of a fresh one.  Returns (job, arrays) -- `arrays` keeps the memory alive and names it."""
+    pinned_array) instead of a fresh one.  out_device: (device pointer, bytes) to decode into instead -- CHN_INFLATE_OUT_DEVICE; the
+    caller fills and reads that memory, arrays["out"] is None.  out_offset: the members' places in `out`, where they are not to lie
+    in order `guard` bytes apart.  Returns (job, arrays) -- `arrays` keeps the memory alive and names it."""
     n = len(members)
     in_length = np.array([len(m) for m in members], np.uint32)
     in_offset = np.zeros(n, np.uint64)
@@ -589,20 +653,28 @@ def inflate_job(members, sizes, guard=0, out=None):
         in_offset[1:] = np.cumsum(in_length[:-1], dtype=np.uint64)
     data = np.frombuffer(b"".join(members), np.uint8) if n and int(in_length.sum()) else np.zeros(0, np.uint8)
     out_length = np.array([int(x) for x in sizes], np.uint32)
-    out_offset = np.zeros(n, np.uint64)
-    if n:
-        out_offset[1:] = np.cumsum(out_length[:-1].astype(np.uint64) + np.uint64(guard), dtype=np.uint64)
-    out_bytes = int(out_length.astype(np.uint64).sum()) + guard * n
-    if out is None:
-        out = np.empty(max(out_bytes, 1), np.uint8)
-    assert out.dtype == np.uint8 and out.size >= out_bytes
-    out[:] = 0xA5
+    if out_offset is not None:
+        out_offset = np.array([int(x) for x in out_offset], np.uint64)
+        out_bytes = int(out_offset[-1]) + int(out_length[-1]) + guard if n else 0
+    else:
+        out_offset = np.zeros(n, np.uint64)
+        if n:
+            out_offset[1:] = np.cumsum(out_length[:-1].astype(np.uint64) + np.uint64(guard), dtype=np.uint64)
+        out_bytes = int(out_length.astype(np.uint64).sum()) + guard * n
+    if out_device is not None:
+        out = None
+        assert out_device[1] >= out_bytes
+    else:
+        if out is None:
+            out = np.empty(max(out_bytes, 1), np.uint8)
+        assert out.dtype == np.uint8 and out.size >= out_bytes
+        out[:] = 0xA5
     status = np.full(max(n, 1), 0xFFFFFFFF, np.uint32)
     j = InflateJob()
-    j.struct_size, j.flags, j.n_members = C.sizeof(InflateJob), 0, n
+    j.struct_size, j.flags, j.n_members = C.sizeof(InflateJob), INFLATE_OUT_DEVICE if out_device is not None else 0, n
     j.in_, j.in_bytes = (data.ctypes.data if data.size else None), data.size
     j.in_offset, j.in_length = in_offset.ctypes.data, in_length.ctypes.data
-    j.out, j.out_bytes = out.ctypes.data, out_bytes
+    j.out, j.out_bytes = (out_device[0] if out_device is not None else out.ctypes.data), out_bytes
     j.out_offset, j.out_length, j.status = out_offset.ctypes.data, out_length.ctypes.data, status.ctypes.data
     return j, dict(data=data, in_offset=in_offset, in_length=in_length, out=out, out_offset=out_offset, out_length=out_length,
                    status=status, guard=guard, n=n)
@@ -662,16 +734,21 @@ class Inflater:
         self.h = C.c_void_p()
         _chk(_L.chn_inflate_create(device, C.byref(self.h)))
 
-    def run(self, members, sizes, guard=0, out=None, expected=None, want_crc=False):
+    def run(self, members, sizes, guard=0, out=None, expected=None, want_crc=False, out_device=None, out_offset=None):
         """members: list of raw deflate streams (bytes); sizes: their expected inflated sizes (<= INFLATE_MAX_OUT).
         Returns (list of bytes, or None where status != 0; status array).  expected / want_crc as in inflate_host
-        (chn_inflate_run_crc: the CRC-32 is taken on the device)."""
-        j, a = inflate_job(members, sizes, guard, out)
+        (chn_inflate_run_crc: the CRC-32 is taken on the device).  out_device=(device pointer, bytes): the members are written into
+        that device memory (CHN_INFLATE_OUT_DEVICE) at out_offset (default: in order, `guard` bytes apart) and the first value
+        returned is None -- the bytes are the caller's to download."""
+        j, a = inflate_job(members, sizes, guard, out, out_device, out_offset)
         if expected is None and not want_crc:
             _chk(_L.chn_inflate_run(self.h, C.byref(j)))
-            return _inflate_results(a)
+            return _inflate_results(a) if out_device is None else (None, a["status"][:a["n"]].copy())
         c, ca = inflate_crc(a["n"], expected, want_crc)
         _chk(_L.chn_inflate_run_crc(self.h, C.byref(j), C.byref(c)))
+        if out_device is not None:
+            st = a["status"][:a["n"]].copy()
+            return (None, st, ca["crc32"][:a["n"]].copy()) if want_crc else (None, st)
         return _inflate_crc_results(a, ca, want_crc)
 
     def run_job(self, job, crc=None):

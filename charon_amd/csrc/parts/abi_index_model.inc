@@ -142,6 +142,20 @@ struct Slot {
     bool ev_used[4] = {false, false, false, false};
 };
 
+// chn_text_split's scratch (abi_text_split.inc; allocated with the first call): tile counts and offsets, line starts, the descriptor
+// columns, id positions, the ids back to back, the control words and their page-locked copy
+struct TextSplitScratch {
+    DevBuf d_tile, d_line, d_desc, d_idpos, d_ids, d_ctl;
+    PinBuf h_ctl;
+    hipEvent_t ev[2] = {nullptr, nullptr};  // profiling streams: around the kernels in front of the first wait
+    double ms = 0;
+    uint64_t calls = 0;
+    void release() {
+        d_tile.release(); d_line.release(); d_desc.release(); d_idpos.release(); d_ids.release(); d_ctl.release(); h_ctl.release();
+        for (hipEvent_t &e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    }
+};
+
 struct chn_stream {
     chn_index *idx = nullptr;
     chn_stream_cfg cfg;
@@ -198,6 +212,7 @@ struct chn_stream {
     uint64_t last_bytes = 0, last_min = 0, last_fetches = 0;
     double text_ms[2] = {0, 0};  // text batches of a profiling stream: upload of the text, pack kernels
     uint64_t text_n = 0;
+    TextSplitScratch tsp;
 };
 
 static uint64_t pow5(unsigned e) { uint64_t p = 1; while (e--) p *= 5; return p; }

@@ -8,6 +8,9 @@
 // Two sets of grow-only buffers take turns.
 // With a chn_inflate_crc that names an array, the CRC form of the kernel runs: `expected` travels behind the descriptors in their
 // upload, the CRCs behind the statuses in their download -- no further copy, launch or wait.
+// With CHN_INFLATE_OUT_DEVICE `out` is the caller's device memory: the kernel writes every member to out + out_offset[i] itself (its
+// write-out handles any misalignment and never leaves the member's stretch), nothing of the output is staged or downloaded, and the
+// wait for the statuses is the wait for the bytes.
 
 static const uint64_t INF_GROUP_OUT = 32ull << 20, INF_GROUP_IN = 64ull << 20;
 static const uint32_t INF_GROUP_MEMBERS = 1u << 16;
@@ -17,7 +20,7 @@ struct InflateSet {
     PinBuf h_in, h_out, h_desc, h_status;
     hipEvent_t up = nullptr, done = nullptr, down = nullptr, k0 = nullptr, k1 = nullptr;
     uint64_t first = 0, n = 0, out_bytes = 0;  // the group in this set
-    bool direct = false, busy = false, crc = false;
+    bool direct = false, busy = false, crc = false, dev_out = false;
 };
 struct chn_inflate {
     int device = 0;
@@ -27,11 +30,12 @@ struct chn_inflate {
     int cus = 0;
 };
 
-static int inflate_check_job(const chn_inflate_job *j, const char *who) {
+static int inflate_check_job(const chn_inflate_job *j, const char *who, bool host_call) {
     const std::string W(who);
     if (!j) return fail(CHN_E_INVALID, W + ": null job");
     if (j->struct_size != sizeof(chn_inflate_job)) return fail(CHN_E_INVALID, W + ": bad struct_size");
-    if (j->flags) return fail(CHN_E_INVALID, W + ": unknown flag");
+    if (j->flags & ~CHN_INFLATE_OUT_DEVICE) return fail(CHN_E_INVALID, W + ": unknown flag");
+    if (host_call && j->flags) return fail(CHN_E_INVALID, W + ": CHN_INFLATE_OUT_DEVICE is for chn_inflate_run / chn_inflate_run_crc (the CPU decoder writes host memory)");
     const uint64_t n = j->n_members;
     if (n == 0) return CHN_OK;
     if (!j->in_offset || !j->in_length || !j->out_offset || !j->out_length || !j->status) return fail(CHN_E_INVALID, W + ": a descriptor array is NULL");
@@ -57,7 +61,7 @@ static int inflate_check_crc(const chn_inflate_crc *c, const char *who) {
 
 static int inflate_run_host(const chn_inflate_job *j, const chn_inflate_crc *c, const char *who) {
     int rc = inflate_check_crc(c, who);
-    if (rc == CHN_OK) rc = inflate_check_job(j, who);
+    if (rc == CHN_OK) rc = inflate_check_job(j, who, true);
     if (rc || j->n_members == 0) return rc;
     const bool want = c && (c->expected || c->crc32);
     InfShared *sh = new (std::nothrow) InfShared;
@@ -150,7 +154,8 @@ static int inflate_issue(chn_inflate *h, InflateSet &st, const chn_inflate_job *
         if (i > first && j->out_offset[i] != j->out_offset[i - 1] + j->out_length[i - 1]) contiguous = false;
         out_bytes += j->out_length[i];
     }
-    st.first = first; st.n = n; st.out_bytes = out_bytes; st.direct = out_pinned && contiguous;
+    st.dev_out = (j->flags & CHN_INFLATE_OUT_DEVICE) != 0;
+    st.first = first; st.n = n; st.out_bytes = out_bytes; st.direct = st.dev_out || (out_pinned && contiguous);
     st.crc = c != nullptr;
     const bool expect = c && c->expected;
     int rc;
@@ -159,7 +164,7 @@ static int inflate_issue(chn_inflate *h, InflateSet &st, const chn_inflate_job *
     const size_t desc_bytes = (size_t)n * (expect ? 28 : 24), status_bytes = (size_t)n * (st.crc ? 8 : 4);
     if ((rc = st.h_desc.ensure(desc_bytes + desc_bytes / 4)) || (rc = st.d_desc.ensure(st.h_desc.cap)) ||
         (rc = st.h_in.ensure((size_t)in_bytes + 2 * INF_PAD + (st.h_in.cap < in_bytes + 2 * INF_PAD ? in_bytes / 4 : 0))) || (rc = st.d_in.ensure(st.h_in.cap)) ||
-        (rc = st.d_out.ensure((size_t)out_bytes + 64 + (st.d_out.cap < out_bytes + 64 ? out_bytes / 4 : 0))) ||
+        (!st.dev_out && (rc = st.d_out.ensure((size_t)out_bytes + 64 + (st.d_out.cap < out_bytes + 64 ? out_bytes / 4 : 0)))) ||
         (rc = st.h_status.ensure(status_bytes + (st.h_status.cap < status_bytes ? status_bytes / 4 : 0))) || (rc = st.d_status.ensure(st.h_status.cap)) || (rc = st.d_cursor.ensure(16)))
         return rc;
     if (!st.direct && (rc = st.h_out.ensure(st.d_out.cap))) return rc;
@@ -171,7 +176,7 @@ static int inflate_issue(chn_inflate *h, InflateSet &st, const chn_inflate_job *
     for (uint64_t k = 0; k < n; ++k) {
         const uint64_t i = first + k;
         in_off[k] = ip; in_len[k] = j->in_length[i];
-        out_off[k] = op; out_len[k] = j->out_length[i];
+        out_off[k] = st.dev_out ? j->out_offset[i] : op; out_len[k] = j->out_length[i];
         if (j->in_length[i]) std::memcpy(stage + ip, j->in + j->in_offset[i], j->in_length[i]);
         ip += ((uint64_t)j->in_length[i] + 15) & ~15ull;
         op += j->out_length[i];
@@ -187,7 +192,7 @@ static int inflate_issue(chn_inflate *h, InflateSet &st, const chn_inflate_job *
     a.in = st.d_in.as<uint8_t>();
     a.in_off = st.d_desc.as<uint64_t>(); a.out_off = a.in_off + n;
     a.in_len = reinterpret_cast<const uint32_t *>(a.out_off + n); a.out_len = a.in_len + n;
-    a.out = st.d_out.as<uint8_t>(); a.status = st.d_status.as<uint32_t>(); a.cursor = st.d_cursor.as<uint32_t>();
+    a.out = st.dev_out ? j->out : st.d_out.as<uint8_t>(); a.status = st.d_status.as<uint32_t>(); a.cursor = st.d_cursor.as<uint32_t>();
     a.n = (uint32_t)n;
     a.expected = expect ? a.out_len + n : nullptr;
     a.crc = st.crc ? a.status + n : nullptr;
@@ -200,7 +205,7 @@ static int inflate_issue(chn_inflate *h, InflateSet &st, const chn_inflate_job *
     HIPCHK(hipEventRecord(st.k1, h->s_run));
     HIPCHK(hipEventRecord(st.done, h->s_run));
     HIPCHK(hipStreamWaitEvent(h->s_down, st.done, 0));
-    if (out_bytes) {
+    if (out_bytes && !st.dev_out) {
         void *dst = st.direct ? static_cast<void *>(j->out + j->out_offset[first]) : st.h_out.p;
         HIPCHK(hipMemcpyAsync(dst, st.d_out.p, out_bytes, hipMemcpyDeviceToHost, h->s_down));
     }
@@ -234,12 +239,17 @@ static int inflate_collect(chn_inflate *h, InflateSet &st, const chn_inflate_job
 static int inflate_run(chn_inflate *h, const chn_inflate_job *j, const chn_inflate_crc *c, const char *who) {
     if (!h) return fail(CHN_E_INVALID, std::string(who) + ": null handle");
     int rc = inflate_check_crc(c, who);
-    if (rc == CHN_OK) rc = inflate_check_job(j, who);
+    if (rc == CHN_OK) rc = inflate_check_job(j, who, false);
     if (rc || j->n_members == 0) return rc;
     if (c && !c->expected && !c->crc32) c = nullptr;  // decode only: the plain kernel
     HIPCHK(hipSetDevice(h->device));
+    const bool dev_out = (j->flags & CHN_INFLATE_OUT_DEVICE) != 0;
+    if (dev_out && j->out_bytes) {  // before anything is launched
+        std::string why;
+        if (!device_memory_of(j->out, j->out_bytes, h->device, why)) return fail(CHN_E_INVALID, std::string(who) + ": CHN_INFLATE_OUT_DEVICE: out " + why);
+    }
     h->kernel_ms = 0;
-    const bool out_pinned = inflate_is_pinned(j->out, j->out_bytes);
+    const bool out_pinned = !dev_out && inflate_is_pinned(j->out, j->out_bytes);
     uint64_t first = 0, g = 0;
     while (first < j->n_members) {
         uint64_t n = 0, ob = 0, ib = 0;

@@ -144,6 +144,7 @@ extern "C" int chn_stream_destroy(chn_stream *s) {
     for (DevBuf *b : bufs) b->release();
     s->big.release();
     s->shx.release();
+    s->tsp.release();
     delete s;
     return CHN_OK;
 }

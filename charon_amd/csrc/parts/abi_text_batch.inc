@@ -5,6 +5,8 @@
 // stream, k_text_pack (text_pack.inc) writes the slot's d_bases / d_nmask / d_mq behind them, and the host waits for the kernel's
 // three words -- N seen, illegal bytes, first read with one -- because the chain is shaped on the host by whether there is an N mask.
 // From there on it is submit_impl with the uploads of those arrays left out.
+// With CHN_TEXT_ON_DEVICE the text is the caller's device memory (the contract of text_split.inc): no staging, no upload, k_text_pack
+// reads the caller's buffer -- it fetches only aligned dwords that hold a wanted byte -- and the wait for its verdict frees the buffer.
 
 static const size_t TEXT_PAD = 64;      // bytes in front of and behind the text on the device
 static const size_t TEXT_MQ_AT = 64;    // the mean-quality column in a slot's h_text, behind k_text_pack's words
@@ -16,7 +18,7 @@ static uint64_t text_pad64(uint64_t x) { return (x + 63) & ~(uint64_t)63; }
 static int text_pack_run(chn_stream *s, Slot &sl, const chn_text_batch *t, const char *who) {
     const std::string W(who);
     if (t->struct_size != sizeof(chn_text_batch)) return fail(CHN_E_INVALID, W + ": bad struct_size");
-    if (t->flags & ~CHN_TEXT_DNA5_RANKS) return fail(CHN_E_INVALID, W + ": unknown flag");
+    if (t->flags & ~(CHN_TEXT_DNA5_RANKS | CHN_TEXT_ON_DEVICE)) return fail(CHN_E_INVALID, W + ": unknown flag");
     const uint64_t n = t->n_reads;
     if (n == 0) return fail(CHN_E_INVALID, "empty batch");
     if (n > s->cfg.max_reads) return fail(CHN_E_CAPACITY, "batch exceeds stream capacity (reads)");
@@ -46,15 +48,17 @@ static int text_pack_run(chn_stream *s, Slot &sl, const chn_text_batch *t, const
     sl.text_n_bases = n_bases;
 
     HIPCHK(hipSetDevice(s->idx->d.device));
+    const bool on_device = (t->flags & CHN_TEXT_ON_DEVICE) != 0;
+    int rc;
+    if (on_device && (rc = device_text_check(t->text, tb, s->idx->d.device, W + ": CHN_TEXT_ON_DEVICE"))) return rc;  // before any launch
     hipStream_t cs = s->stream0;
     const size_t cap_b = (size_t)s->cfg.max_bases, cap_n = (size_t)s->cfg.max_reads;
-    int rc;
     // the slot's batch buffers at the sizes submit_impl reserves for them (they never re-allocate afterwards)
     if ((rc = sl.d_bases.ensure(std::max<size_t>(cap_b / 4, 16))) || (rc = sl.d_nmask.ensure(std::max<size_t>(cap_b / 8, 16))) ||
         (rc = sl.d_mq.ensure(std::max<size_t>(cap_n * 4, 16))) || (rc = sl.d_tctl.ensure(TXT_CTL_WORDS * 4)) ||
         (rc = sl.h_text.ensure(TEXT_MQ_AT + cap_n * 4)))
         return rc;
-    {   // text staging: grow-only, with some slack so that batches of slightly different sizes do not re-allocate
+    if (!on_device) {  // text staging: grow-only, with some slack so that batches of slightly different sizes do not re-allocate
         const size_t need = (size_t)tb + 2 * TEXT_PAD;
         if (need > sl.d_text.cap && (rc = sl.d_text.ensure(need + need / 8)))
             return fail(CHN_E_NOMEM, W + ": no room for " + std::to_string(need >> 20) + " MiB of device text staging (" + g_err + ")");
@@ -62,9 +66,9 @@ static int text_pack_run(chn_stream *s, Slot &sl, const chn_text_batch *t, const
     const bool prof = (s->cfg.flags & CHN_STREAM_PROFILE) != 0;
     if (prof)
         for (int i = 0; i < 4; ++i) if (!sl.tev[i]) HIPCHK(hipEventCreate(&sl.tev[i]));
-    uint8_t *d_text = sl.d_text.as<uint8_t>() + TEXT_PAD;
+    const uint8_t *d_text = on_device ? t->text : sl.d_text.as<uint8_t>() + TEXT_PAD;
     if (prof) HIPCHK(hipEventRecord(sl.tev[0], cs));
-    if (tb) HIPCHK(hipMemcpyAsync(d_text, t->text, tb, hipMemcpyHostToDevice, cs));
+    if (tb && !on_device) HIPCHK(hipMemcpyAsync(sl.d_text.as<uint8_t>() + TEXT_PAD, t->text, tb, hipMemcpyHostToDevice, cs));
     if (prof) HIPCHK(hipEventRecord(sl.tev[1], cs));
     if ((rc = upload(sl.d_off1, sl.h_toff1.data(), n * 8, cs, cap_n * 8)) || (rc = upload(sl.d_len1, t->seq1_length, n * 4, cs, cap_n * 4))) return rc;
     if (paired && ((rc = upload(sl.d_off2, sl.h_toff2.data(), n * 8, cs, cap_n * 8)) || (rc = upload(sl.d_len2, t->seq2_length, n * 4, cs, cap_n * 4)))) return rc;

@@ -1,0 +1,120 @@
+// abi_text_split.inc -- chn_text_split / chn_text_split_host, and the check that a caller's pointer is device memory
+// Part of the single translation unit charon_hip.hip (included in order); not a stand-alone source.
+//
+// chn_text_split queues text_split.inc's kernels on the stream's copy stream and waits twice: once for the three output words (how
+// many records, where they end, how many id bytes -- the sizes of everything that follows), once for the descriptors and the ids,
+// which come down in one batch of copies.  The scratch is the stream's (chn_stream::tsp, grow-only): a word per 4 KiB tile of the
+// text, and line starts, descriptors and id positions by the record bound min(max_records, bytes / 8).
+
+// Is [p, p + bytes) device memory of `device`?  `why` says what it is instead.  (The runtime answers a pageable pointer with an
+// error, which is cleared: it is "not device memory".)
+static bool device_memory_of(const void *p, uint64_t bytes, int device, std::string &why) {
+    for (int k = 0; k < 2; ++k) {
+        const void *q = k == 0 ? p : static_cast<const char *>(p) + (bytes ? bytes - 1 : 0);
+        hipPointerAttribute_t a;
+        std::memset(&a, 0, sizeof a);
+        if (hipPointerGetAttributes(&a, q) != hipSuccess) { (void)hipGetLastError(); why = "is not device memory (pageable host memory, or a pointer the runtime does not know)"; return false; }
+        if (a.type == hipMemoryTypeHost) { why = "is page-locked host memory, not device memory"; return false; }
+        if (a.type != hipMemoryTypeDevice) { why = "is not device memory"; return false; }
+        if (a.device != device) { why = "is memory of device " + std::to_string(a.device) + ", not of device " + std::to_string(device); return false; }
+    }
+    return true;
+}
+
+// the device text contract of chn_text_split and CHN_TEXT_ON_DEVICE
+static int device_text_check(const uint8_t *text, uint64_t text_bytes, int device, const std::string &who) {
+    if (!text_bytes) return CHN_OK;  // nothing is read
+    if (reinterpret_cast<uintptr_t>(text) & 15) return fail(CHN_E_INVALID, who + ": device text must be 16-byte aligned");
+    std::string why;
+    if (!device_memory_of(text, (text_bytes + 15) & ~(uint64_t)15, device, why)) return fail(CHN_E_INVALID, who + ": text " + why);
+    return CHN_OK;
+}
+
+extern "C" int chn_text_split_host(chn_text_split_job *job) {
+    std::string why;
+    const int rc = tsp_host_job(job, why);
+    return rc ? fail(rc, why) : CHN_OK;
+}
+
+extern "C" int chn_text_split(chn_stream *s, chn_text_split_job *j) {
+    const char *who = "chn_text_split";
+    if (!s) return fail(CHN_E_INVALID, "chn_text_split: null stream");
+    std::string why;
+    int rc = tsp_check_job(j, who, why);
+    if (rc) return fail(rc, why);
+    if (s->inflight >= chn_stream::N_SLOTS) return fail(CHN_E_INVALID, "chn_text_split: three batches in flight on the stream: call chn_batch_wait first");
+    const int device = s->idx->d.device;
+    HIPCHK(hipSetDevice(device));
+    if ((rc = device_text_check(j->text, j->text_bytes, device, who))) return rc;
+    const uint64_t start = j->start, end = j->text_bytes, bound64 = tsp_record_bound(j);
+    if (bound64 == 0) {  // nothing to look at, or no room for a record
+        j->n_records = 0; j->consumed = start; j->ids_bytes = 0;
+        return CHN_OK;
+    }
+    const uint32_t bound = (uint32_t)bound64;  // <= 2^28
+    const uint64_t tile0 = start / TSP_TILE;
+    const uint32_t n_tiles = (uint32_t)((end + TSP_TILE - 1) / TSP_TILE - tile0);  // >= 1, <= 2^19
+    const uint32_t cap = 4 * bound;                                                   // <= 2^30 line starts behind the first
+    TextSplitScratch &x = s->tsp;
+    hipStream_t cs = s->stream0;
+    // descriptors in one block: id_off[bound] seq_off[bound] qual_off[bound] (64-bit), id_len[bound] seq_len[bound] (32-bit)
+    if ((rc = x.d_tile.ensure((size_t)n_tiles * 8)) || (rc = x.d_line.ensure(((size_t)cap + 1) * 4)) || (rc = x.d_desc.ensure((size_t)bound * 32)) ||
+        (rc = x.d_idpos.ensure((size_t)bound * 4)) || (rc = x.d_ctl.ensure(TSP_CTL_WORDS * 4)) || (rc = x.h_ctl.ensure(TSP_CTL_WORDS * 4)))
+        return rc;
+    uint32_t *tile_count = x.d_tile.as<uint32_t>(), *tile_off = tile_count + n_tiles, *ctl = x.d_ctl.as<uint32_t>(), *line_start = x.d_line.as<uint32_t>();
+    TspRecArgs a;
+    a.text = j->text; a.line_start = line_start; a.ctl = ctl; a.bound = bound;
+    a.id_off = x.d_desc.as<uint64_t>(); a.seq_off = a.id_off + bound; a.qual_off = a.seq_off + bound;
+    a.id_len = reinterpret_cast<uint32_t *>(a.qual_off + bound); a.seq_len = a.id_len + bound;
+    const uint32_t cus = std::max<uint32_t>(1, s->n_cus);
+    const uint32_t tile_blocks = std::min<uint32_t>((n_tiles + 3) / 4, cus * 8), rec_blocks = std::min<uint32_t>((bound + 255) / 256, cus * 8);
+    const bool prof = (s->cfg.flags & CHN_STREAM_PROFILE) != 0;
+    if (prof) {
+        for (hipEvent_t &e : x.ev) if (!e) HIPCHK(hipEventCreate(&e));
+        HIPCHK(hipEventRecord(x.ev[0], cs));
+    }
+    HIPCHK(hipMemsetAsync(ctl, 0, TSP_CTL_WORDS * 4, cs));
+    HIPCHK(hipMemsetAsync(ctl + TSP_FIRST_BAD, 0xFF, 4, cs));
+    hipLaunchKernelGGL(k_split_count, dim3(tile_blocks), dim3(256), 0, cs, j->text, start, end, tile0, n_tiles, tile_count);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, cs, tile_count, tile_off, (const uint32_t *)nullptr, n_tiles, ctl + TSP_LINES);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_split_lines, dim3(tile_blocks), dim3(256), 0, cs, j->text, start, end, tile0, n_tiles, tile_off, line_start, cap);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_split_records, dim3(rec_blocks), dim3(256), 0, cs, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_split_close, dim3(1), dim3(64), 0, cs, line_start, ctl, bound);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, cs, a.id_len, x.d_idpos.as<uint32_t>(), ctl + TSP_N, bound, ctl + TSP_IDS_BYTES);
+    HIPCHK(hipGetLastError());
+    if (prof) HIPCHK(hipEventRecord(x.ev[1], cs));
+    HIPCHK(hipMemcpyAsync(x.h_ctl.p, ctl, TSP_CTL_WORDS * 4, hipMemcpyDeviceToHost, cs));
+    HIPCHK(hipStreamSynchronize(cs));
+    if (prof) {
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, x.ev[0], x.ev[1]));
+        x.ms += ms; x.calls += 1;
+    }
+    const uint32_t *h = x.h_ctl.as<uint32_t>();
+    const uint64_t n = h[TSP_N], ids_bytes = h[TSP_IDS_BYTES];
+    if (j->ids && ids_bytes > j->ids_capacity) return fail(tsp_ids_too_small(j, ids_bytes, who, why), why);
+    if (n) {
+        if (j->ids && ids_bytes) {
+            if ((rc = x.d_ids.ensure((size_t)ids_bytes + (x.d_ids.cap < ids_bytes ? ids_bytes / 4 : 0)))) return rc;
+            hipLaunchKernelGGL(k_split_ids, dim3(std::min<uint32_t>((uint32_t)((n + 15) / 16), cus * 8)), dim3(256), 0, cs, j->text, a.id_off, a.id_len,
+                               x.d_idpos.as<uint32_t>(), (uint32_t)n, x.d_ids.as<uint8_t>());
+            HIPCHK(hipGetLastError());
+        }
+        hipError_t e = hipMemcpyAsync(j->id_offset, a.id_off, n * 8, hipMemcpyDeviceToHost, cs);
+        if (e == hipSuccess) e = hipMemcpyAsync(j->seq_offset, a.seq_off, n * 8, hipMemcpyDeviceToHost, cs);
+        if (e == hipSuccess) e = hipMemcpyAsync(j->qual_offset, a.qual_off, n * 8, hipMemcpyDeviceToHost, cs);
+        if (e == hipSuccess) e = hipMemcpyAsync(j->id_length, a.id_len, n * 4, hipMemcpyDeviceToHost, cs);
+        if (e == hipSuccess) e = hipMemcpyAsync(j->seq_length, a.seq_len, n * 4, hipMemcpyDeviceToHost, cs);
+        if (e == hipSuccess && j->ids && ids_bytes) e = hipMemcpyAsync(j->ids, x.d_ids.p, ids_bytes, hipMemcpyDeviceToHost, cs);
+        const hipError_t w = hipStreamSynchronize(cs);  // nothing stays queued into the caller's arrays, whatever happened
+        if (e == hipSuccess) e = w;
+        if (e != hipSuccess) return fail(CHN_E_HIP, std::string("chn_text_split: ") + hipGetErrorString(e));
+    }
+    j->n_records = n; j->consumed = h[TSP_CONSUMED]; j->ids_bytes = ids_bytes;
+    return CHN_OK;
+}

@@ -277,13 +277,21 @@ int chn_stream_sync(chn_stream *s);
  * Mean quality of a read: int sum of (signed char)q - 33 over the quality bytes of both mates / their number, one float
  * division, 0.0f where there are none (and for a read without any letter).  A quality string may be longer than its sequence
  * (the reference's reader allows it); every byte of it counts.
- * Every descriptor is checked on the host: offset + length <= text_bytes, else CHN_E_INVALID and nothing is launched. */
+ * Every descriptor is checked on the host: offset + length <= text_bytes, else CHN_E_INVALID and nothing is launched.
+ * CHN_TEXT_ON_DEVICE: `text` is DEVICE memory on the stream's device under the device text contract -- 16-byte aligned, and the
+ * allocation readable up to text_bytes rounded up to 16; every chn_device_malloc result whose size is rounded up to 16 qualifies
+ * (e.g. the `out` of a chn_inflate_run with CHN_INFLATE_OUT_DEVICE).  Nothing is staged or uploaded: k_text_pack reads the caller's
+ * buffer (only aligned dwords that hold a wanted byte).  The descriptor arrays stay HOST arrays and are checked as above; layout,
+ * verdict, chain and results are those of the same bytes in host memory.  A pointer that is not device memory of that device
+ * (page-locked or pageable host memory, another device) or is misaligned is CHN_E_INVALID before anything is launched, and the
+ * stream stays usable.  The buffer may be reused as soon as the call returns.  Combines with CHN_TEXT_DNA5_RANKS. */
 #define CHN_TEXT_DNA5_RANKS 1u
+#define CHN_TEXT_ON_DEVICE 2u
 typedef struct chn_text_batch {
     uint32_t struct_size;
-    uint32_t flags;               /* CHN_TEXT_DNA5_RANKS */
+    uint32_t flags;               /* CHN_TEXT_DNA5_RANKS | CHN_TEXT_ON_DEVICE */
     uint64_t n_reads;
-    const uint8_t *text;          /* HOST memory; page-locked memory (chn_host_alloc) is uploaded asynchronously */
+    const uint8_t *text;          /* HOST memory; page-locked memory (chn_host_alloc) is uploaded asynchronously (CHN_TEXT_ON_DEVICE: DEVICE) */
     uint64_t text_bytes;
     const uint64_t *seq1_offset;  /* [n] bytes into `text` */
     const uint32_t *seq1_length;  /* [n] */
@@ -327,6 +335,54 @@ int chn_text_wait(chn_stream *s, chn_result *r, chn_text_result *t);
  * flight.  Errors as chn_text_submit. */
 int chn_text_pack(chn_stream *s, const chn_text_batch *t, uint32_t *bases2, uint32_t *nmask, uint64_t *seg1_offset,
                   uint64_t *seg2_offset, float *mean_quality, uint64_t *n_bases, uint32_t *has_n);
+
+/* ---- FASTQ records found in a text that lies in device memory (no reference counterpart: the reference parses through seqan3 on
+ * the CPU) ---------------------------------------------------------------------------------------------------------------------
+ * With chn_inflate_run's CHN_INFLATE_OUT_DEVICE in front and CHN_TEXT_ON_DEVICE behind, a caller goes from BGZF members to per-read
+ * calls while the text never leaves device memory: compressed bytes go up; about 40 bytes of descriptors per read, the id bytes and
+ * the results come back.
+ * THE RECORD RULE -- exactly what the front end's parallel FASTQ splitter accepts, applied from `start` one record after another.
+ * A record is taken if and only if
+ *   - its first byte is '@';
+ *   - four line feeds follow inside [start, text_bytes);
+ *   - the sequence line, after dropping one trailing '\r', has length n >= 1 and does not begin with '+';
+ *   - the third line begins with '+';
+ *   - the fourth line, after dropping one trailing '\r', has length n;
+ * and its id is what follows '@' up to the line end, minus one trailing '\r' (it may be empty).  n_records is the number of records
+ * taken before the first place where the rule fails or before max_records is reached, `consumed` the offset behind the last taken
+ * record (`start` if there is none).  A blank line, a wrapped record, an empty read, a last line without a line feed or anything
+ * else ends the run; everything from `consumed` on is the caller's business (typically: carry it in front of the next piece of
+ * text, or hand it to a sequential parser with its own error handling).  `start` must be a record boundary for the result to mean
+ * anything; a caller that processes a file in pieces passes the offset of the tail the piece before left over.
+ * Descriptors: record i has its id at text[id_offset[i] .. + id_length[i]), its sequence at seq_offset[i] with seq_length[i] bytes
+ * and its quality string at qual_offset[i] with the same length -- what chn_text_batch takes as seq1_* / qual1_*.  With `ids` the id
+ * bytes come back to back, id i at the sum of id_length[0 .. i); ids_bytes is their total whether or not `ids` is given.
+ * DEVICE TEXT CONTRACT (as CHN_TEXT_ON_DEVICE): `text` is device memory of the stream's device, 16-byte aligned, the allocation
+ * readable up to text_bytes rounded up to 16.  The descriptor arrays and `ids` are HOST memory.
+ * chn_text_split is SYNCHRONOUS: it runs its kernels on the stream's copy stream (count the line feeds per 4 KiB tile, scan, rank the
+ * line starts, one lane per candidate record, scan and gather the ids), waits for the three output words and then for the descriptors
+ * and ids, which come down in one batch of copies.  Batches in flight on the stream are not disturbed, but there must be fewer than
+ * three.  Its scratch is the stream's, grow-only: 8 bytes per 4 KiB of text, and 52 bytes per record of the bound
+ * min(max_records, (text_bytes - start) / 8) -- size max_records to the records expected, not to the worst case.
+ * chn_text_split_host runs the same rule source on the CPU over HOST text (any alignment) and gives the same outputs.
+ * Errors: CHN_E_INVALID for a wrong struct_size, a flag, start > text_bytes, a NULL descriptor array with max_records > 0, text that
+ * is not device memory of the stream's device or misaligned, three batches in flight; CHN_E_CAPACITY for text_bytes above
+ * CHN_TEXT_SPLIT_MAX_BYTES and for ids_capacity below ids_bytes (the message names the bytes needed).  On an error no output is
+ * defined and nothing stays queued. */
+#define CHN_TEXT_SPLIT_MAX_BYTES (1ull << 31)
+typedef struct chn_text_split_job {
+    uint32_t struct_size, flags;                 /* flags: 0 */
+    const uint8_t *text; uint64_t text_bytes;    /* DEVICE memory on the stream's device (chn_text_split_host: HOST) */
+    uint64_t start;                              /* records are looked for from this byte on; it is a record boundary */
+    uint64_t max_records;                        /* capacity of the arrays below */
+    uint64_t *id_offset;  uint32_t *id_length;   /* [max_records] HOST out; offsets are bytes into `text` */
+    uint64_t *seq_offset; uint32_t *seq_length;  /* the quality string has the sequence's length */
+    uint64_t *qual_offset;
+    uint8_t *ids; uint64_t ids_capacity;         /* HOST out or NULL: the id bytes back to back, id i at sum(id_length[0..i)) */
+    uint64_t n_records, consumed, ids_bytes;     /* out */
+} chn_text_split_job;
+int chn_text_split(chn_stream *s, chn_text_split_job *job);   /* synchronous */
+int chn_text_split_host(chn_text_split_job *job);             /* the same rule source on the CPU; no GPU needed */
 
 /* Model + call only (k_model_call) on per-read counts the caller already holds -- used for reads that the
  * Result state machine cached while the KDE models were still training (include/result.hpp:139-151,181-198)
@@ -409,7 +465,9 @@ int chn_index_emplace(chn_index *idx, const uint64_t *host_values, uint64_t n_va
  * 5 (any stream): *launches = row fetches the last waited batch's minimise+probe kernel issued (h per minimiser; fewer for an index of
  *   at most four bins, whose rows are fetched one at a time and only while the AND so far still has a bin set);
  * 6, 7 (text batches of a CHN_STREAM_PROFILE stream): the host -> device copy of the text / k_text_pack and the mean-quality division,
- *   timed with events on the copy stream; *launches = text batches packed (chn_text_submit and chn_text_pack; reset with which = 7). */
+ *   timed with events on the copy stream; *launches = text batches packed (chn_text_submit and chn_text_pack; reset with which = 7);
+ * 8 (CHN_STREAM_PROFILE streams): chn_text_split's kernels in front of its first wait (count, scan, line starts, records, id scan), timed with
+ *   events on the copy stream; *launches = calls. */
 int chn_stream_profile(chn_stream *s, int which, double *total_ms, uint64_t *launches, int reset);
 /* Algorithmic bytes of the last batch by SURVEY 8(d): sum over reads of ceil(L/4) + M*h*W*8 + (8 + 8C). */
 int chn_stream_last_batch_bytes(chn_stream *s, uint64_t *bytes, uint64_t *total_minimisers);
@@ -427,17 +485,24 @@ int chn_stream_last_batch_bytes(chn_stream *s, uint64_t *bytes, uint64_t *total_
  * (BGZF's end-of-file marker).  chn_inflate_run / chn_inflate_run_host leave the CRC-32 of a member to the caller; the _crc forms take
  * it on the way (below).
  * A chn_inflate owns its streams and staging buffers (grow-only); it is used by ONE thread at a time, different handles may be driven
- * from different threads.  chn_inflate_run is synchronous. */
+ * from different threads.  chn_inflate_run is synchronous.
+ * CHN_INFLATE_OUT_DEVICE (chn_inflate_run / chn_inflate_run_crc only; the _host forms refuse it with CHN_E_INVALID): `out` is DEVICE
+ * memory on the handle's device; out_offset / out_length / out_bytes mean what they mean otherwise.  k_inflate_members writes every
+ * member straight to out + out_offset[i], whatever its alignment, and never outside the member's stretch; no output is staged or
+ * downloaded; statuses (and CRCs) come back as always.  The call stays synchronous: when it returns the bytes are in place for work
+ * on any stream.  `out` is checked before anything is launched: memory that is not device memory of the handle's device (page-locked
+ * or pageable host memory, another device) is CHN_E_INVALID and the message says which.  Any other flag bit is CHN_E_INVALID. */
 #define CHN_INFLATE_MAX_OUT 65536u
+#define CHN_INFLATE_OUT_DEVICE 1u
 /* status[i]: 0 ok | 1 input exhausted | 2 bad block header (type 3, stored LEN/NLEN) | 3 bad code lengths
  * | 4 bad symbol or distance | 5 more output than out_length | 6 stream ended short of out_length */
 typedef struct chn_inflate chn_inflate;
 typedef struct chn_inflate_job {
-    uint32_t struct_size, flags;              /* flags: 0 */
+    uint32_t struct_size, flags;              /* flags: 0 or CHN_INFLATE_OUT_DEVICE */
     uint64_t n_members;
     const uint8_t *in;  uint64_t in_bytes;    /* HOST; pageable (e.g. a mapped file) or page-locked */
     const uint64_t *in_offset; const uint32_t *in_length;    /* [n] raw deflate data of member i */
-    uint8_t *out;  uint64_t out_bytes;        /* HOST */
+    uint8_t *out;  uint64_t out_bytes;        /* HOST (CHN_INFLATE_OUT_DEVICE: DEVICE) */
     const uint64_t *out_offset; const uint32_t *out_length;  /* [n] expected size, <= CHN_INFLATE_MAX_OUT */
     uint32_t *status;                         /* [n] out */
 } chn_inflate_job;
