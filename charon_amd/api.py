@@ -78,6 +78,11 @@ class TextSplitJob(C.Structure):
                 ("n_records", C.c_uint64), ("consumed", C.c_uint64), ("ids_bytes", C.c_uint64)]
 
 
+class TextFetchJob(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("text", C.c_void_p), ("text_bytes", C.c_uint64), ("n_ranges", C.c_uint64),
+                ("offset", C.c_void_p), ("length", C.c_void_p), ("out", C.c_void_p), ("out_capacity", C.c_uint64), ("out_bytes", C.c_uint64)]
+
+
 class TextResult(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("has_n", C.c_uint32), ("n_bases", C.c_uint64), ("mean_quality", C.c_void_p)]
 
@@ -121,7 +126,7 @@ EXPORTS = ["chn_index_create", "chn_index_upload_rows", "chn_index_device_words"
            "chn_model_set", "chn_batch_submit", "chn_batch_wait", "chn_stream_sync", "chn_classify_counts", "chn_classify_counts_raw", "chn_stream_profile",
            "chn_stream_last_batch_bytes", "chn_synth_genomes", "chn_synth_fill_index", "chn_synth_plant", "chn_synth_reads",
            "chn_device_free", "chn_device_download", "chn_device_malloc", "chn_device_upload", "chn_host_alloc", "chn_host_free", "chn_shard_minimise",
-           "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_text_submit", "chn_text_wait", "chn_text_pack", "chn_text_split", "chn_text_split_host", "chn_inflate_create", "chn_inflate_run",
+           "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_text_submit", "chn_text_wait", "chn_text_pack", "chn_text_split", "chn_text_split_host", "chn_text_fetch", "chn_text_fetch_host", "chn_device_copy", "chn_inflate_create", "chn_inflate_run",
            "chn_inflate_run_host", "chn_inflate_destroy", "chn_inflate_kernel_ms", "chn_inflate_run_crc", "chn_inflate_run_host_crc", "chn_deflate_create", "chn_deflate_run", "chn_deflate_run_host",
            "chn_deflate_destroy", "chn_deflate_bound", "chn_deflate_kernel_ms", "chn_deflate_group_members", "chn_last_error", "chn_version"]
 
@@ -176,6 +181,9 @@ _L.chn_text_wait.argtypes = [C.c_void_p, C.POINTER(Result), C.POINTER(TextResult
 _L.chn_text_pack.argtypes = [C.c_void_p, C.POINTER(TextBatch)] + [C.c_void_p] * 5 + [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
 _L.chn_text_split.argtypes = [C.c_void_p, C.POINTER(TextSplitJob)]
 _L.chn_text_split_host.argtypes = [C.POINTER(TextSplitJob)]
+_L.chn_text_fetch.argtypes = [C.c_void_p, C.POINTER(TextFetchJob)]
+_L.chn_text_fetch_host.argtypes = [C.POINTER(TextFetchJob)]
+_L.chn_device_copy.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64]
 _L.chn_inflate_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
 _L.chn_inflate_run.argtypes = [C.c_void_p, C.POINTER(InflateJob)]
 _L.chn_inflate_run_host.argtypes = [C.POINTER(InflateJob)]
@@ -530,6 +538,12 @@ class Stream:
         _chk(_L.chn_text_split(self.h, C.byref(j)))
         return _text_split_results(j, a)
 
+    def text_fetch(self, dev_ptr, nbytes, offsets, lengths, out=None, out_capacity=None):
+        """chn_text_fetch: the byte ranges of device text [0, nbytes) back to back -- see text_fetch_host for what comes back"""
+        j, keep = text_fetch_job(dev_ptr, nbytes, offsets, lengths, out, out_capacity)
+        _chk(_L.chn_text_fetch(self.h, C.byref(j)))
+        return keep[2][:int(j.out_bytes)]
+
     def wait_host(self, text_result=None):
         n, Cn = self._fifo[0][0], self.C
         out = dict(num_hashes=np.zeros(n, np.uint32), counts=np.zeros((n, Cn), np.uint32), unique=np.zeros((n, Cn), np.uint32),
@@ -637,6 +651,34 @@ def text_split_host(data, start=0, max_records=None, want_ids=True, ids_capacity
     j, a = text_split_job(buf.ctypes.data if buf.size else None, nbytes, start, max_records, want_ids, ids_capacity)
     _chk(_L.chn_text_split_host(C.byref(j)))
     return _text_split_results(j, a)
+
+
+# ---- byte ranges of a text (see include/charon_hip.h) ----
+def text_fetch_job(text_ptr, nbytes, offsets, lengths, out=None, out_capacity=None):
+    """the chn_text_fetch_job of ranges (offsets[i], lengths[i]) of the text at `text_ptr`.  `out` is a uint8 array to fill (pageable
+    or from pinned_array) and defaults to a fresh one of the bytes needed; out_capacity defaults to its size.  Returns (job, arrays
+    to keep alive: offsets, lengths, out)."""
+    off, ln = np.ascontiguousarray(offsets, np.uint64), np.ascontiguousarray(lengths, np.uint32)
+    if off.shape != ln.shape or off.ndim != 1:
+        raise ValueError("offsets and lengths must be one-dimensional and of one size")
+    if out_capacity is None:
+        out_capacity = int(ln.sum(dtype=np.uint64)) if out is None else out.size
+    if out is None:
+        out = np.zeros(max(int(out_capacity), 1), np.uint8)
+    j = TextFetchJob()
+    j.struct_size, j.flags, j.text, j.text_bytes, j.n_ranges = C.sizeof(TextFetchJob), 0, text_ptr, int(nbytes), off.size
+    j.offset, j.length, j.out, j.out_capacity = off.ctypes.data, ln.ctypes.data, out.ctypes.data, int(out_capacity)
+    return j, (off, ln, out)
+
+
+def text_fetch_host(data, offsets, lengths, out=None, out_capacity=None, nbytes=None):
+    """chn_text_fetch_host: the copy rule the GPU runs, on the CPU, over `data` (bytes or a uint8 array).  Returns the uint8 array of
+    the ranges back to back (a view of `out` where that is given)."""
+    buf = np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, np.uint8)
+    nbytes = buf.size if nbytes is None else nbytes
+    j, keep = text_fetch_job(buf.ctypes.data if buf.size else None, nbytes, offsets, lengths, out, out_capacity)
+    _chk(_L.chn_text_fetch_host(C.byref(j)))
+    return keep[2][:int(j.out_bytes)]
 
 
 # ---- raw deflate members (see include/charon_hip.h) ----
@@ -914,6 +956,11 @@ def device_upload(device, ptr, arr):
 def device_free(device, ptr):
     if ptr:
         _chk(_L.chn_device_free(device, ptr))
+
+
+def device_copy(device, dst_ptr, src_ptr, nbytes):
+    """chn_device_copy: nbytes from src_ptr to dst_ptr, both device memory of `device`"""
+    _chk(_L.chn_device_copy(device, dst_ptr, src_ptr, int(nbytes)))
 
 
 def device_download(device, ptr, nbytes, dtype):

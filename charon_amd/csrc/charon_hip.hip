@@ -61,6 +61,7 @@
 #include "parts/gzip_tally_long.inc"
 #include "parts/text_pack.inc"
 #include "parts/text_split.inc"
+#include "parts/text_gather.inc"
 #include "parts/inflate_members.inc"
 #include "parts/deflate_members.inc"
 #include "parts/ef_decode.inc"
@@ -69,6 +70,7 @@
 #include "parts/abi_stream_batch.inc"
 #include "parts/abi_shard_wait.inc"
 #include "parts/abi_text_split.inc"
+#include "parts/abi_text_fetch.inc"
 #include "parts/abi_text_batch.inc"
 #include "parts/abi_inflate.inc"
 #include "parts/abi_deflate.inc"

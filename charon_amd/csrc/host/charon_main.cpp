@@ -413,6 +413,18 @@ int main(int argc, char **argv) {
     }
     if (!parse_gpu_inflate_env(&opt)) return 1;  // checked before the index file is opened and before any HIP call
     if (!parse_gpu_deflate_env(opt)) return 1;   // likewise
+    if (const char *e = std::getenv("CHARON_GPU_TEXT")) {
+        // CHARON_GPU_TEXT: 1 = single-end BGZF FASTQ is inflated into device memory and stays there (split, packed and classified on the device of
+        // CHARON_DEVICE, or the one entry of CHARON_DEVICES); 0 or unset = not.  Checked before the index file is opened and before any HIP call.
+        const std::string v(e);
+        if (v != "0" && v != "1") { std::cerr << "charon: CHARON_GPU_TEXT: '" << v << "' is neither 0 nor 1" << std::endl; return 1; }
+        g_gpu_text = v == "1";
+        g_gpu_text_device = opt.devices.empty() ? opt.device : opt.devices[0];
+        if (g_gpu_text && opt.devices.size() > 1) {
+            std::cerr << "charon: CHARON_GPU_TEXT: cannot be set together with a CHARON_DEVICES list of several entries (the text lives on one device)" << std::endl;
+            return 1;
+        }
+    }
     try {
         dehost_main(opt);  // the reference's subcommand callback discards dehost_main's return value (src/dehost_main.cpp:311)
         return 0;

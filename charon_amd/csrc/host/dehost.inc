@@ -92,6 +92,11 @@ struct HostBatch {
     std::vector<uint32_t> ql1, ql2;
     bool text_quals = false, text_from_slab = false;
     WordBuf tcopy;
+    // CHARON_GPU_TEXT=1: the block's text in device memory (so1 / qo1 are offsets into it; the records' seq / qual pointers stay null
+    // until chn_text_fetch has brought a read's letters into `arena`) and the id bytes chn_text_split handed back (the records' ids)
+    std::shared_ptr<DevBlock> dtext;
+    std::unique_ptr<char[]> ids;
+    WordBuf arena;
     ~HostBatch() {
         g_dead_ranges.add(blk1.map_token, blk1.map_begin, blk1.map_len); g_dead_ranges.add(blk2.map_token, blk2.map_begin, blk2.map_len);
         g_slab_pool.give(blk1.buf); g_slab_pool.give(blk2.buf);
@@ -253,8 +258,11 @@ struct HostBatch {
     uint32_t gz_gpu_len = 0;           // longest such read (what chn_batch.gzip_tallies asks for)
     // as_text: lay the batch out and form the host-side gzip ratios as ever, but neither pack the letters nor sum the qualities -- the
     // device does both (chn_text_submit); `slab`: the slab the records are views into, if they all are
+    // resident (with as_text): the letters are in device memory and the caller has filled so1 / qo1 / ql1 from chn_text_split's
+    // descriptors.  No ratio can be formed here, so every read's is "still to come": the device sizes those the routing gives it and
+    // leaves 0 for the others, which finish_rows sizes on the host once their letters are fetched.
     void pack(bool paired, int threads, bool skip_compression, uint32_t gz_gpu_max = 0, bool gz_route_long = false, bool as_text = false,
-              const Slab *slab = nullptr) {
+              const Slab *slab = nullptr, bool resident = false) {
         const size_t nrec = blk1.recs.size();
         keep.clear();
         for (size_t i = 0; i < nrec; ++i) {
@@ -293,12 +301,16 @@ struct HostBatch {
                 const uint64_t L = (uint64_t)len1[i] + (paired ? len2[i] : 0);
                 if (L <= gz_gpu_max) { gz_pending[i] = 1; gz_gpu_len = std::max<uint32_t>(gz_gpu_len, (uint32_t)L); }
             }
+        if (resident && !skip_compression) {  // (a length of 1 when nothing is routed to the device: the compression gate is then finish_rows')
+            gz_pending.assign(n, 1);
+            gz_gpu_len = std::max<uint32_t>(gz_gpu_len, 1);
+        }
         bool saw_n = false, bad = false;
         // Letters -> 2-bit codes + N mask and the quality sums: what seqan3's READER does while it parses (sequence_file_input hands out dna5 ranks and
         // phred values), so it runs on the reader's threads -- `-t`, but never fewer than four -- like the decompression and the record splitting.
         // With the default `-t 1` the main thread used to pack for 3.6 of a 4.8 s read loop (4 M reads of 5 kb).
         const int conv_threads = std::max(threads, g_reader_threads);
-        if (as_text) describe_text(paired, slab, conv_threads);
+        if (as_text && !resident) describe_text(paired, slab, conv_threads);
 #pragma omp parallel num_threads(conv_threads) if (!as_text)
         {
             bool my_n = false, my_bad = false;
@@ -356,6 +368,8 @@ struct BlockQueue {
     }
     void abort() { std::lock_guard<std::mutex> lk(m); aborted = true; q.clear(); cv.notify_all(); }
     void finish(const std::string &err) { std::lock_guard<std::mutex> lk(m); done = true; error = err; cv.notify_all(); }
+    // for a second reader thread, once the first has been aborted and joined
+    void reopen() { std::lock_guard<std::mutex> lk(m); q.clear(); done = aborted = false; error.clear(); }
     std::shared_ptr<HostBatch> pop() {
         std::unique_lock<std::mutex> lk(m);
         cv.wait(lk, [&] { return !q.empty() || done; });
@@ -443,6 +457,7 @@ int dehost_main(DehostArguments &opt) {
     // are released when this function is left, after everything that hands slabs back, while the HIP runtime is certainly still up
     g_pin_slabs = opt.text_batches || g_gpu_inflate;  // (CHARON_GPU_INFLATE=1 downloads straight into the slab)
     struct SlabPoolDrain { ~SlabPoolDrain() { std::lock_guard<std::mutex> lk(g_slab_pool.m); g_slab_pool.v.clear(); } } slab_pool_drain;
+    struct DevTextPoolDrain { ~DevTextPoolDrain() { g_dev_text_pool.drain(); } } dev_text_pool_drain;  // (CHARON_GPU_TEXT=1) likewise
     if (g_gpu_inflate) g_log.info("CHARON_GPU_INFLATE=1: BGZF members are inflated on device " + std::to_string(g_gpu_inflate_device) + " (size and CRC-32 are checked on the device)");
     if (g_gpu_deflate) g_log.info("CHARON_GPU_DEFLATE=1: extract files are compressed on device " + std::to_string(g_gpu_deflate_device) + " (BGZF members of 65280 bytes)");
     if (opt.text_batches) g_log.info("CHARON_TEXT_BATCHES=1: reads go to the device as text (letters -> codes and mean quality on the GPU)");
@@ -451,12 +466,31 @@ int dehost_main(DehostArguments &opt) {
     BlockQueue queue;
     // the readers outlive the reader thread: records of a mapped file are views into the mapping until their rows are printed
     std::unique_ptr<BlockReader> in1p, in2;
-    std::thread reader([&]() {
+    // CHARON_GPU_TEXT=1: the reader hands over blocks of text in device memory while `resident`; when the main thread leaves the mode it
+    // stops this thread and starts it again from `resume_z` of the compressed file with `resume_carry` in front (today's path from there).
+    // A device block is 64 MiB of text (a thousand members per chn_inflate_run: four wavefronts for each of the device's 256 CUs, and
+    // some 13 000 reads of 5 kb per chn_text_split) instead of the 256 MB of a slab: up to seven buffers exist at once.
+    bool resident = false, resumed = false;
+    size_t resume_z = 0;
+    Slab resume_carry;
+    auto reader_body = [&]() {
         try {
             in1p.reset(new BlockReader(opt.read_file));
             BlockReader &in1 = *in1p;
             if (opt.is_paired) in2.reset(new BlockReader(opt.read_file2));
             const size_t max_bytes = (size_t)std::min<uint64_t>(256ULL << 20, std::max<uint64_t>(1 << 20, opt.batch_bases));
+            if (resumed) in1.resume(resume_z, resume_carry);
+            if (resident) {
+                const size_t block_bytes = std::min<size_t>(max_bytes, (size_t)64 << 20);
+                for (;;) {
+                    std::shared_ptr<HostBatch> hb(new HostBatch());
+                    hb->dtext = in1.next_device(block_bytes, g_gpu_text_headroom);
+                    if (!hb->dtext) break;
+                    if (!queue.push(std::move(hb))) return;
+                }
+                queue.finish("");
+                return;
+            }
             for (;;) {
                 std::shared_ptr<HostBatch> hb(new HostBatch());
                 // a batch may hold at most batch_bases padded bases: bound the record count by the byte budget as well
@@ -481,7 +515,25 @@ int dehost_main(DehostArguments &opt) {
         } catch (std::exception &e) {
             queue.finish(e.what());
         }
-    });
+    };
+    if (g_gpu_text) {
+        std::string why;
+        const std::string stem = opt.read_file.substr(0, opt.read_file.size() - std::min<size_t>(3, opt.read_file.size()));
+        if (opt.is_paired) why = "paired input";
+        else if (!ends_with(opt.read_file, ".gz")) why = "not a .gz file";
+        else if (std::getenv("CHARON_NO_BGZF")) why = "CHARON_NO_BGZF is set";
+        else if (!ends_with(stem, ".fastq") && !ends_with(stem, ".fq")) why = "not FASTQ";
+        else if (!BgzfSource().open(opt.read_file)) why = "one deflate stream, not BGZF";
+        resident = why.empty();
+        if (resident) {
+            if (const char *e = std::getenv("CHARON_GPU_TEXT_HEADROOM")) g_gpu_text_headroom = (size_t)std::min<unsigned long long>(1ULL << 30, std::strtoull(e, nullptr, 10));
+            g_log.info("CHARON_GPU_TEXT=1: BGZF text is inflated into the memory of device " + std::to_string(g_gpu_text_device) +
+                       " and stays there (records split and packed on the device; headroom " + std::to_string(g_gpu_text_headroom) + " bytes)");
+        } else {
+            g_log.info("CHARON_GPU_TEXT=1 does not apply to " + opt.read_file + " (" + why + "; single-end BGZF FASTQ only): the run goes on without it");
+        }
+    }
+    std::thread reader(reader_body);
 
     struct ReaderJoin {  // whatever way this function is left: stop the reader and wait for it
         BlockQueue &q; std::thread &t;
@@ -583,6 +635,7 @@ int dehost_main(DehostArguments &opt) {
                 if (dv >= count) throw std::runtime_error("CHARON_DEVICES: device " + std::to_string(dv) + " is not below the device count " + std::to_string(count));
         }
         d.device = devices[0];
+        if (resident && devices.size() > 1) throw std::runtime_error("CHARON_GPU_TEXT: cannot be set together with CHARON_DEVICES=all on several devices (the text lives on one device)");
     }
     {
         std::string list;
@@ -672,6 +725,7 @@ int dehost_main(DehostArguments &opt) {
         HostBatch sub;
         uint32_t version = 0;
         uint64_t seq = 0;  // replica mode: position in input order (the ordered merge releases flights by it)
+        bool resident = false;  // CHARON_GPU_TEXT=1: a text batch whose text is sub.dtext, in device memory
         // what chn_batch_wait fills (per flight: the rows of batch i are written by another thread while batch i + 1 is waited for)
         std::vector<uint32_t> nh, cnt, unq;
         std::vector<double> prob;
@@ -721,7 +775,7 @@ int dehost_main(DehostArguments &opt) {
         const bool tallied = sub.gz_gpu_len != 0;
         if (tallied) { gz_sizes.resize(n); rs.gzip_sizes = gz_sizes.data(); }
         double tt = now();
-        if (opt.text_batches) {  // the mean-quality column comes back with the results
+        if (opt.text_batches || fl.resident) {  // the mean-quality column comes back with the results
             chn_text_result tr;
             std::memset(&tr, 0, sizeof tr);
             tr.struct_size = sizeof tr; tr.mean_quality = sub.mq.data();
@@ -936,7 +990,7 @@ int dehost_main(DehostArguments &opt) {
 
     // a packed batch through chn_batch_submit, or (CHARON_TEXT_BATCHES=1) the text itself through chn_text_submit
     auto submit_flight = [&](chn_stream *st, Flight &fl) {
-        if (!opt.text_batches) {
+        if (!opt.text_batches && !fl.resident) {
             chn_batch bt;
             fill_batch(fl, bt);
             CHN_CHECK(chn_batch_submit(st, &bt));
@@ -955,7 +1009,8 @@ int dehost_main(DehostArguments &opt) {
         tb.compression = sub.comp.data();
         tb.gzip_tallies = sub.gz_gpu_len;
         tb.gzip_output = sub.gz_gpu_len > CHN_GZIP_MAX_LEN ? CHN_GZIP_SIZES_ALL : CHN_GZIP_SIZES;
-        (sub.text_from_slab ? text_slab_batches : text_copy_batches) += 1;
+        if (fl.resident) { tb.flags = CHN_TEXT_ON_DEVICE; tb.text = sub.dtext->buf; tb.text_bytes = sub.dtext->text_bytes; }
+        else (sub.text_from_slab ? text_slab_batches : text_copy_batches) += 1;
         const int rc = chn_text_submit(st, &tb);
         // (the device met a byte that is no IUPAC nucleotide letter: what HostBatch::pack reports for a packed batch)
         if (rc == CHN_E_INVALID && std::strstr(chn_last_error(), "illegal byte"))
@@ -1077,7 +1132,194 @@ int dehost_main(DehostArguments &opt) {
         if (s >= n_rep && (!rp.need_set || rp.need < s - n_rep)) { rp.need = s - n_rep; rp.need_set = true; }
         rp.cv.notify_all();
     };
+
+    // ---- CHARON_GPU_TEXT=1: the read loop while the text stays in device memory ---------------------------------------------------
+    // Everything that touches the stream -- split, submit, wait, fetch -- runs on this thread (one stream per host thread), so the
+    // replica threads are not used: up to two batches are in flight while the next is split and submitted.
+    uint64_t dt_split_records = 0, dt_fetched_records = 0, dt_fetched_bytes = 0;
+    double t_split = 0, t_fetch = 0;
+    // After chn_text_wait: ONE chn_text_fetch for the reads whose letters the host needs -- the sequence of a read the device left
+    // unsized, sequence and quality of every read under --extract (make_entry copies them; without --extract it reads the id alone,
+    // in training too) -- into the flight's arena; the record views point there.  The block's buffer is let go afterwards.
+    auto fetch_letters = [&](Flight &fl) {
+        HostBatch &sub = fl.sub;
+        const size_t n = sub.keep.size();
+        const bool tallied = sub.gz_gpu_len != 0;
+        std::vector<uint64_t> off;
+        std::vector<uint32_t> len, who;
+        uint64_t total = 0;
+        for (size_t i = 0; i < n; ++i) {
+            if (!opt.run_extract && !(tallied && sub.gz_pending[i] && fl.gz_sizes[i] == 0)) continue;
+            who.push_back((uint32_t)i);
+            off.push_back(sub.so1[i]); len.push_back(sub.len1[i]); total += sub.len1[i];
+            if (opt.run_extract) { off.push_back(sub.qo1[i]); len.push_back(sub.ql1[i]); total += sub.ql1[i]; }
+        }
+        if (!who.empty()) {
+            sub.arena.want_pinned = true;
+            sub.arena.assign_raw((size_t)(total / 4) + 1);
+            chn_text_fetch_job job;
+            std::memset(&job, 0, sizeof job);
+            job.struct_size = sizeof job; job.text = sub.dtext->buf; job.text_bytes = sub.dtext->text_bytes;
+            job.n_ranges = off.size(); job.offset = off.data(); job.length = len.data();
+            job.out = reinterpret_cast<uint8_t *>(sub.arena.data()); job.out_capacity = (uint64_t)sub.arena.n * 4;
+            CHN_CHECK(chn_text_fetch(stream, &job));
+            const char *at = reinterpret_cast<const char *>(sub.arena.data());
+            for (uint32_t i : who) {
+                RecView &r = sub.blk1.recs[sub.keep[i]];
+                r.seq = at; at += sub.len1[i];
+                if (opt.run_extract) { r.qual = at; at += sub.ql1[i]; }
+            }
+            dt_fetched_records += who.size(); dt_fetched_bytes += total;
+        }
+        sub.dtext.reset();
+    };
+    auto run_resident = [&]() {
+        std::deque<std::unique_ptr<Flight>> flying;  // submitted, oldest first
+        struct SyncOnThrow {  // the device is done with these flights' arrays before they are freed
+            std::deque<std::unique_ptr<Flight>> &f; chn_stream *s;
+            ~SyncOnThrow() { if (!f.empty()) (void)chn_stream_sync(s); }
+        } sync_on_throw{flying, stream};
+        auto retire_front = [&]() {
+            std::unique_ptr<Flight> f = std::move(flying.front());
+            flying.pop_front();
+            finish_wait(*f, stream, t_wait);
+            const double tk = now();
+            fetch_letters(*f);
+            t_fetch += now() - tk;
+            hand_on(f);
+        };
+        const int dev = g_gpu_text_device;
+        const uint64_t kSplitRecords = 1u << 18;  // per chn_text_split (its scratch is 52 bytes per record of this bound); a block with more takes several
+        std::vector<uint64_t> ido(kSplitRecords), sqo(kSplitRecords), qlo(kSplitRecords), blk_so, blk_qo;
+        std::vector<uint32_t> idl(kSplitRecords), sql(kSplitRecords);
+        std::shared_ptr<DevBlock> prev;  // the block before, while [prev_from, prev->text_bytes) is a tail no record was made of
+        uint64_t prev_from = 0;
+        bool final_pushed = false;
+        for (;;) {
+            const double tp = now();
+            std::shared_ptr<HostBatch> hbp = queue.pop();
+            t_pop += now() - tp;
+            if (!hbp) break;  // (the end of the file, or the reader's error: reported behind the loop below)
+            HostBatch &hb = *hbp;
+            std::shared_ptr<DevBlock> blk = hb.dtext;
+            double tk = now();
+            uint64_t start = blk->member0;
+            if (prev) {
+                const uint64_t tail = prev->text_bytes - prev_from, body = blk->text_bytes - blk->member0;
+                if (tail > blk->member0) {  // a tail longer than the gap (a record longer than the headroom): a buffer for the two
+                    std::shared_ptr<DevBlock> fresh(new DevBlock());
+                    void *p = nullptr;
+                    fresh->cap = (size_t)((tail + body + 15) & ~15ULL);
+                    CHN_CHECK(chn_device_malloc(dev, fresh->cap, &p));
+                    fresh->buf = static_cast<uint8_t *>(p);
+                    fresh->member0 = tail; fresh->text_bytes = tail + body; fresh->file_offset = blk->file_offset;
+                    fresh->z_end = blk->z_end; fresh->last = blk->last;
+                    if (body) CHN_CHECK(chn_device_copy(dev, fresh->buf + tail, blk->buf + blk->member0, body));
+                    blk = fresh;
+                    hb.dtext = fresh;
+                }
+                if (tail) CHN_CHECK(chn_device_copy(dev, blk->buf + blk->member0 - tail, prev->buf + prev_from, tail));
+                start = blk->member0 - tail;
+                prev.reset();
+            }
+            // records: descriptors and id bytes come back, letters and qualities stay where they are
+            const uint64_t end = blk->text_bytes;
+            uint64_t consumed = start, ids_used = 0;
+            hb.ids.reset(new char[end - start + 1]);
+            blk_so.clear(); blk_qo.clear();
+            for (;;) {
+                chn_text_split_job job;
+                std::memset(&job, 0, sizeof job);
+                job.struct_size = sizeof job; job.text = blk->buf; job.text_bytes = end; job.start = consumed; job.max_records = kSplitRecords;
+                job.id_offset = ido.data(); job.id_length = idl.data(); job.seq_offset = sqo.data(); job.seq_length = sql.data(); job.qual_offset = qlo.data();
+                job.ids = reinterpret_cast<uint8_t *>(hb.ids.get()) + ids_used; job.ids_capacity = end - start - ids_used;
+                CHN_CHECK(chn_text_split(stream, &job));
+                const char *id = hb.ids.get() + ids_used;
+                for (uint64_t i = 0; i < job.n_records; ++i) {
+                    RecView r;
+                    r.id = id; r.id_len = idl[i]; r.seq_len = r.qual_len = sql[i];
+                    id += idl[i];
+                    hb.blk1.recs.push_back(r);
+                    blk_so.push_back(sqo[i]); blk_qo.push_back(qlo[i]);
+                }
+                ids_used += job.ids_bytes; consumed = job.consumed;
+                if (job.n_records < kSplitRecords) break;
+            }
+            t_split += now() - tk;
+            const size_t nrec = hb.blk1.recs.size();
+            dt_split_records += nrec;
+            // the block in GPU batches that respect the stream's capacity, as below
+            size_t begin = 0;
+            while (begin < nrec) {
+                uint64_t bases = 0;
+                size_t endi = begin;
+                while (endi < nrec && endi - begin < opt.batch_reads) {
+                    const uint64_t need = HostBatch::pad64(hb.blk1.recs[endi].seq_len);
+                    if (need > opt.batch_bases) throw std::runtime_error("a read is longer than CHARON_BATCH_BASES");
+                    if (bases + need > opt.batch_bases) break;
+                    bases += need; ++endi;
+                }
+                std::unique_ptr<Flight> fl;
+                {
+                    std::lock_guard<std::mutex> lk(pool_m);
+                    if (!flight_pool.empty()) { fl = std::move(flight_pool.back()); flight_pool.pop_back(); }
+                }
+                if (!fl) fl.reset(new Flight());
+                fl->parent = hbp;
+                fl->resident = true;
+                HostBatch &sub = fl->sub;
+                sub.blk1.recs.assign(hb.blk1.recs.begin() + (long)begin, hb.blk1.recs.begin() + (long)endi);
+                tk = now();
+                sub.pack(false, opt.threads, skip_compression, gz_gpu_max, gz_route_long, true, nullptr, true);
+                const size_t n = sub.keep.size();
+                sub.so1.resize(n); sub.qo1.resize(n); sub.so2.clear(); sub.qo2.clear(); sub.ql2.clear();
+                for (size_t i = 0; i < n; ++i) { sub.so1[i] = blk_so[begin + sub.keep[i]]; sub.qo1[i] = blk_qo[begin + sub.keep[i]]; }
+                sub.ql1 = sub.len1;
+                sub.text_quals = true; sub.text_from_slab = false;
+                sub.dtext = blk;
+                t_pack += now() - tk;
+                begin = endi;
+                if (n == 0) { sub.dtext.reset(); continue; }
+                while (flying.size() >= 2) retire_front();
+                // (while the models are in training every batch is retired before the next is submitted, so nothing is in flight here)
+                if (!final_pushed) { result.ensure_device_model(); final_pushed = result.models_final(); }
+                fl->version = result.current_model_version();
+                tk = now();
+                submit_flight(stream, *fl);
+                t_submit += now() - tk;
+                reps[0]->batches += 1; reps[0]->reads += n;
+                flying.push_back(std::move(fl));
+                if (!result.models_final()) retire_front();
+            }
+            // Leaving the mode: no record although four line feeds follow `start` (a wrapped record, a blank line, a damaged record), or
+            // bytes behind the last record at the end of the file (a last line without a line feed).  The text from `consumed` on comes
+            // down once, and it and the rest of the file go through the host's splitter and sequential parser, which produce today's
+            // rows and today's messages.
+            Slab tail_text;
+            bool leave = false;
+            if (consumed < end && (nrec == 0 || blk->last)) {
+                tail_text.resize((size_t)(end - consumed));
+                CHN_CHECK(chn_device_download(dev, tail_text.data(), blk->buf + consumed, end - consumed));
+                leave = blk->last || std::count(tail_text.begin(), tail_text.end(), '\n') >= 4;
+            }
+            if (leave) {
+                while (!flying.empty()) retire_front();
+                g_log.info("CHARON_GPU_TEXT=1: leaving the device-resident path at byte " + std::to_string(blk->file_offset + consumed - blk->member0) +
+                           " of the inflated file (text that is no plain four-line record): the host parser goes on from there");
+                queue.abort();
+                reader.join();
+                queue.reopen();
+                resident = false; resumed = true; resume_z = blk->z_end; resume_carry.swap(tail_text);
+                g_gpu_inflate = true; g_gpu_inflate_device = dev; g_pin_slabs = true;  // inflate as under CHARON_GPU_INFLATE=1 from here on
+                reader = std::thread(reader_body);
+                return;
+            }
+            if (consumed < end) { prev = blk; prev_from = consumed; }
+        }
+        while (!flying.empty()) retire_front();
+    };
     try {
+        if (resident) run_resident();
         for (;;) {
             double tp = now();
             std::shared_ptr<HostBatch> hbp = queue.pop();
@@ -1119,6 +1361,7 @@ int dehost_main(DehostArguments &opt) {
                 }
                 if (!fl) fl.reset(new Flight());
                 fl->parent = hbp;
+                fl->resident = false;
                 HostBatch &sub = fl->sub;
                 sub.bases.want_pinned = sub.nmask.want_pinned = true;  // three of these go round: uploads straight out of them
                 sub.blk1.recs.assign(hb.blk1.recs.begin() + (long)begin, hb.blk1.recs.begin() + (long)endi);
@@ -1177,6 +1420,15 @@ int dehost_main(DehostArguments &opt) {
             std::snprintf(tb, sizeof tb, "timing (reader thread, s): inside chn_inflate_run %.3f (part of inflate)", g_gpu_inflate_s);
             g_log.info(tb);
             std::fprintf(stderr, "charon: %s\n", tb);
+        }
+        if (g_gpu_text && (resident || resumed)) {
+            char tg[512];
+            std::snprintf(tg, sizeof tg, "timing (CHARON_GPU_TEXT=1): records split %llu  records fetched %llu  text bytes inflated %llu  text bytes fetched %llu  "
+                          "seconds in inflate %.3f  seconds in split %.3f  seconds in fetch %.3f",
+                          (unsigned long long)dt_split_records, (unsigned long long)dt_fetched_records, (unsigned long long)g_gpu_text_inflated,
+                          (unsigned long long)dt_fetched_bytes, g_gpu_inflate_s, t_split, t_fetch);
+            g_log.info(tg);
+            std::fprintf(stderr, "charon: %s\n", tg);
         }
         if (g_gpu_deflate) {
             std::snprintf(tb, sizeof tb, "timing (main thread, s): inside chn_deflate_run %.3f (extract files)", g_gpu_deflate_s);

@@ -82,6 +82,59 @@ SlabPool g_slab_pool;
 bool g_gpu_inflate = false;
 int g_gpu_inflate_device = 0;
 double g_gpu_inflate_s = 0;  // reader-thread seconds inside chn_inflate_run_crc (CHARON_TIMING)
+
+// CHARON_GPU_TEXT=1 (single-end BGZF FASTQ): the members of a block are inflated into DEVICE memory (CHN_INFLATE_OUT_DEVICE) and the text
+// stays there; the main thread finds the records (chn_text_split), submits them (CHN_TEXT_ON_DEVICE) and fetches the letters of the few
+// reads the host still needs (chn_text_fetch).  A block's buffer keeps `headroom` bytes free in front of member 0: the tail the block
+// before left over is copied there, device to device, so that it ends exactly where member 0 begins.
+bool g_gpu_text = false;
+int g_gpu_text_device = 0;
+size_t g_gpu_text_headroom = (size_t)4 << 20;  // longer than any read but the rarest (those take a fresh buffer); CHARON_GPU_TEXT_HEADROOM: test hook
+uint64_t g_gpu_text_inflated = 0;              // text bytes inflated into device memory (CHARON_TIMING)
+// The buffers go round: the reader fills one while two wait in the queue, the main thread splits one and up to two batches in flight
+// refer to theirs.  All have one size, so any free one fits; more than four free ones are not kept.
+struct DevTextPool {
+    std::mutex m;
+    std::vector<void *> v;
+    size_t bytes = 0;  // size of every pooled buffer
+    void *take(size_t want) {
+        {
+            std::lock_guard<std::mutex> lk(m);
+            if (bytes != want) { for (void *p : v) (void)chn_device_free(g_gpu_text_device, p); v.clear(); bytes = want; }
+            if (!v.empty()) { void *p = v.back(); v.pop_back(); return p; }
+        }
+        void *p = nullptr;
+        if (chn_device_malloc(g_gpu_text_device, want, &p) != CHN_OK || !p) throw std::runtime_error(std::string("CHARON_GPU_TEXT: ") + chn_last_error());
+        return p;
+    }
+    void give(void *p, size_t n) {
+        {
+            std::lock_guard<std::mutex> lk(m);
+            if (n == bytes && v.size() < 4) { v.push_back(p); return; }
+        }
+        (void)chn_device_free(g_gpu_text_device, p);
+    }
+    void drain() { std::lock_guard<std::mutex> lk(m); for (void *p : v) (void)chn_device_free(g_gpu_text_device, p); v.clear(); }
+};
+DevTextPool g_dev_text_pool;
+// One block of inflated text in device memory: the tail of the block before in [start, member0), this block's members in
+// [member0, text_bytes).  Byte x of it is byte file_offset + (x - member0) of the inflated file.
+struct DevBlock {
+    uint8_t *buf = nullptr;
+    size_t cap = 0;
+    bool pooled = false;
+    uint64_t member0 = 0, text_bytes = 0, file_offset = 0;
+    size_t z_end = 0;   // offset in the compressed file behind this block's last member
+    bool last = false;  // no member follows
+    DevBlock() = default;
+    DevBlock(const DevBlock &) = delete;
+    DevBlock &operator=(const DevBlock &) = delete;
+    ~DevBlock() {
+        if (!buf) return;
+        if (pooled) g_dev_text_pool.give(buf, cap); else (void)chn_device_free(g_gpu_text_device, buf);
+    }
+};
+
 class BgzfSource {
     chn_inflate *gpu_ = nullptr;  // one handle per source, created on first use
     const unsigned char *z_ = nullptr;
@@ -128,10 +181,9 @@ public:
         return true;
     }
     bool at_end() const { return pos_ >= size_; }
-    // Append the next members' data to buf: as many members as fit max_out bytes (at least one non-empty one while there is data).
-    void fill(Slab &buf, size_t max_out) {
-        std::vector<Member> ms;
-        buf.reserve(buf.size() + max_out + 65536);
+    void seek(size_t pos) { pos_ = pos; }  // to a member boundary (DevBlock::z_end)
+    // The next members, as many as fit max_out bytes (at least one non-empty one while there is data); returns the bytes they inflate to.
+    size_t scan(std::vector<Member> &ms, size_t max_out) {
         size_t total = 0;
         while (pos_ < size_) {
             size_t off = 0;
@@ -149,6 +201,50 @@ public:
             ms.push_back(mb);
             pos_ += len;
         }
+        return total;
+    }
+    // CHARON_GPU_TEXT=1: the next members inflated into a device buffer of the pool, member 0 at `headroom`; size and CRC-32 of every
+    // member are checked on the device as under CHARON_GPU_INFLATE=1.  Null when no member is left.
+    std::shared_ptr<DevBlock> fill_device(size_t max_out, size_t headroom, uint64_t file_offset) {
+        if (pos_ >= size_) return nullptr;
+        std::vector<Member> ms;
+        const size_t total = scan(ms, max_out);
+        std::shared_ptr<DevBlock> b(new DevBlock());
+        b->cap = (headroom + max_out + 65536 + 15) & ~(size_t)15;
+        b->buf = static_cast<uint8_t *>(g_dev_text_pool.take(b->cap)); b->pooled = true;
+        b->member0 = headroom; b->text_bytes = headroom + total; b->file_offset = file_offset;
+        b->z_end = pos_; b->last = pos_ >= size_;
+        if (!gpu_ && chn_inflate_create(g_gpu_text_device, &gpu_) != CHN_OK) throw std::runtime_error(std::string("CHARON_GPU_TEXT: ") + chn_last_error());
+        const size_t n = ms.size();
+        std::vector<uint64_t> in_off(n), out_off(n);
+        std::vector<uint32_t> in_len(n), out_len(n), status(n, 0), expected(n);
+        for (size_t i = 0; i < n; ++i) {
+            in_off[i] = (uint64_t)(ms[i].cdata - z_); in_len[i] = ms[i].clen;
+            out_off[i] = headroom + ms[i].out; out_len[i] = ms[i].isize;
+            expected[i] = ms[i].crc;
+        }
+        chn_inflate_job job;
+        std::memset(&job, 0, sizeof job);
+        job.struct_size = sizeof job; job.flags = CHN_INFLATE_OUT_DEVICE; job.n_members = n;
+        job.in = z_; job.in_bytes = size_; job.in_offset = in_off.data(); job.in_length = in_len.data();
+        job.out = b->buf; job.out_bytes = b->text_bytes; job.out_offset = out_off.data(); job.out_length = out_len.data();
+        job.status = status.data();
+        chn_inflate_crc crc;
+        std::memset(&crc, 0, sizeof crc);
+        crc.struct_size = sizeof crc; crc.expected = expected.data();
+        const double t0 = omp_get_wtime();
+        if (chn_inflate_run_crc(gpu_, &job, &crc) != CHN_OK) throw std::runtime_error(std::string("CHARON_GPU_TEXT: ") + chn_last_error());
+        g_gpu_inflate_s += omp_get_wtime() - t0;
+        g_gpu_text_inflated += total;
+        for (size_t i = 0; i < n; ++i)
+            if (status[i] != 0) throw std::runtime_error("gzip read error in " + path_ + ": a BGZF member is corrupt (inflate, size or CRC32 mismatch)");
+        return b;
+    }
+    // Append the next members' data to buf: as many members as fit max_out bytes (at least one non-empty one while there is data).
+    void fill(Slab &buf, size_t max_out) {
+        std::vector<Member> ms;
+        buf.reserve(buf.size() + max_out + 65536);
+        const size_t total = scan(ms, max_out);
         const size_t old = buf.size();
         buf.resize(old + total);
         char *dst = buf.data() + old;
@@ -218,6 +314,7 @@ class BlockReader {
     bool fastq_ = false, eof_ = false;
     Slab carry_;
     double rec_bytes_ = 0;  // bytes of text per record in the last block (sizes the next decode)
+    uint64_t device_offset_ = 0;  // inflated bytes handed out by next_device so far
     std::string path_;
     // Uncompressed files are mapped (MAP_PRIVATE, so that the in-place compaction of multi-line records stays possible): records
     // become views straight into the page cache -- no read() copies, no slab to zero-fill -- and the reader thread only has to find
@@ -490,6 +587,23 @@ public:
     }
     BlockReader(const BlockReader &) = delete;
     BlockReader &operator=(const BlockReader &) = delete;
+
+    // CHARON_GPU_TEXT=1 applies to BGZF input in FASTQ form only
+    bool is_bgzf_fastq() const { return bgzf_ && fastq_; }
+    // the next block of the file as text in device memory (null at the end of the file)
+    std::shared_ptr<DevBlock> next_device(size_t max_bytes, size_t headroom) {
+        const double t0 = omp_get_wtime();
+        std::shared_ptr<DevBlock> b = bgzf_->fill_device(max_bytes, headroom, device_offset_);
+        g_reader_fill_s += omp_get_wtime() - t0;
+        if (b) device_offset_ += b->text_bytes - b->member0;
+        return b;
+    }
+    // go on as next() does from a member boundary of the compressed file, with `carry` (text in front of that member) still to parse
+    void resume(size_t z_pos, Slab &carry) {
+        bgzf_->seek(z_pos);
+        carry_.swap(carry);
+        eof_ = false;
+    }
 
     // Fill `blk` with up to max_recs whole records (reading about max_bytes of new data at a time).  Returns false when
     // the file is exhausted and nothing was produced.

@@ -156,6 +156,20 @@ struct TextSplitScratch {
     }
 };
 
+// chn_text_fetch's staging (abi_text_fetch.inc; allocated with the first call): the range descriptors page-locked and on the device,
+// the gathered bytes on the device and page-locked
+struct TextFetchScratch {
+    DevBuf d_desc, d_out;
+    PinBuf h_desc, h_out;
+    hipEvent_t ev[2] = {nullptr, nullptr};  // profiling streams: around the kernel
+    double ms = 0;
+    uint64_t calls = 0;
+    void release() {
+        d_desc.release(); d_out.release(); h_desc.release(); h_out.release();
+        for (hipEvent_t &e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    }
+};
+
 struct chn_stream {
     chn_index *idx = nullptr;
     chn_stream_cfg cfg;
@@ -213,6 +227,7 @@ struct chn_stream {
     double text_ms[2] = {0, 0};  // text batches of a profiling stream: upload of the text, pack kernels
     uint64_t text_n = 0;
     TextSplitScratch tsp;
+    TextFetchScratch txg;
 };
 
 static uint64_t pow5(unsigned e) { uint64_t p = 1; while (e--) p *= 5; return p; }

@@ -353,7 +353,13 @@ extern "C" int chn_classify_counts(chn_stream *s, uint64_t n, const uint32_t *nu
 }
 
 extern "C" int chn_stream_profile(chn_stream *s, int which, double *total_ms, uint64_t *launches, int reset) {
-    if (!s || which < 0 || which > 8) return fail(CHN_E_INVALID, "chn_stream_profile: bad argument");
+    if (!s || which < 0 || which > 9) return fail(CHN_E_INVALID, "chn_stream_profile: bad argument");
+    if (which == 9) {  // chn_text_fetch: k_text_gather
+        if (total_ms) *total_ms = s->txg.ms;
+        if (launches) *launches = s->txg.calls;
+        if (reset) { s->txg.ms = 0; s->txg.calls = 0; }
+        return CHN_OK;
+    }
     if (which == 8) {  // chn_text_split: its kernels in front of the first wait
         if (total_ms) *total_ms = s->tsp.ms;
         if (launches) *launches = s->tsp.calls;

@@ -145,6 +145,7 @@ extern "C" int chn_stream_destroy(chn_stream *s) {
     s->big.release();
     s->shx.release();
     s->tsp.release();
+    s->txg.release();
     delete s;
     return CHN_OK;
 }

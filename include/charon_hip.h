@@ -384,6 +384,32 @@ typedef struct chn_text_split_job {
 int chn_text_split(chn_stream *s, chn_text_split_job *job);   /* synchronous */
 int chn_text_split_host(chn_text_split_job *job);             /* the same rule source on the CPU; no GPU needed */
 
+/* ---- byte ranges of a text that lies in device memory, fetched into host memory (no reference counterpart) ------------------------
+ * What a caller of the chain above uses for the few records whose letters it needs on the host after all (a gzip ratio the device
+ * left open, a record to be written out): range i is text[offset[i] .. + length[i]) and goes to out + sum(length[0 .. i)), so the
+ * ranges come back to back in the order given.  Ranges may overlap, repeat and have length 0; out_bytes is the sum of the lengths.
+ * `text` follows the DEVICE TEXT CONTRACT above and nothing beyond it is read; offset, length and out are HOST memory, `out` pageable
+ * or page-locked (page-locked memory is downloaded into directly, pageable memory through page-locked staging of the stream's).
+ * chn_text_fetch is SYNCHRONOUS: it uploads 20 bytes per range, runs k_text_gather on the stream's copy stream (one wavefront a range
+ * at a time; whole 16-byte pieces of the destination are single aligned stores built from aligned loads) and waits once for the
+ * bytes.  Batches in flight on the stream are not disturbed, but there must be fewer than three.  Its staging is the stream's,
+ * grow-only: 20 bytes per range, and the gathered bytes on the device and (pageable `out`) page-locked.
+ * chn_text_fetch_host applies the same copy rule on the CPU over HOST text (any alignment).
+ * Errors, all before anything is queued: CHN_E_INVALID for a wrong struct_size, a flag, a NULL range array with n_ranges > 0, a range
+ * with offset[i] + length[i] > text_bytes (the message names it), text that is not device memory of the stream's device or misaligned,
+ * three batches in flight; CHN_E_CAPACITY for out_capacity below the sum of the lengths (the message names the bytes needed).  On an
+ * error nothing has been written and the stream stays usable. */
+typedef struct chn_text_fetch_job {
+    uint32_t struct_size, flags;                 /* flags: 0 */
+    const uint8_t *text; uint64_t text_bytes;    /* DEVICE, device text contract (chn_text_fetch_host: HOST) */
+    uint64_t n_ranges;
+    const uint64_t *offset; const uint32_t *length;  /* [n] HOST; ranges may overlap, repeat, have length 0 */
+    uint8_t *out; uint64_t out_capacity;         /* HOST, pageable or page-locked: range i at sum(length[0..i)) */
+    uint64_t out_bytes;                          /* out: sum of the lengths */
+} chn_text_fetch_job;
+int chn_text_fetch(chn_stream *s, chn_text_fetch_job *job);   /* synchronous */
+int chn_text_fetch_host(chn_text_fetch_job *job);             /* same copy rule on the CPU, no GPU needed */
+
 /* Model + call only (k_model_call) on per-read counts the caller already holds -- used for reads that the
  * Result state machine cached while the KDE models were still training (include/result.hpp:139-151,181-198)
  * and that must be classified with the models as they are later.  All pointers are HOST arrays; outputs as in
@@ -467,7 +493,8 @@ int chn_index_emplace(chn_index *idx, const uint64_t *host_values, uint64_t n_va
  * 6, 7 (text batches of a CHN_STREAM_PROFILE stream): the host -> device copy of the text / k_text_pack and the mean-quality division,
  *   timed with events on the copy stream; *launches = text batches packed (chn_text_submit and chn_text_pack; reset with which = 7);
  * 8 (CHN_STREAM_PROFILE streams): chn_text_split's kernels in front of its first wait (count, scan, line starts, records, id scan), timed with
- *   events on the copy stream; *launches = calls. */
+ *   events on the copy stream; *launches = calls;
+ * 9 (CHN_STREAM_PROFILE streams): chn_text_fetch's k_text_gather, timed with events on the copy stream; *launches = calls. */
 int chn_stream_profile(chn_stream *s, int which, double *total_ms, uint64_t *launches, int reset);
 /* Algorithmic bytes of the last batch by SURVEY 8(d): sum over reads of ceil(L/4) + M*h*W*8 + (8 + 8C). */
 int chn_stream_last_batch_bytes(chn_stream *s, uint64_t *bytes, uint64_t *total_minimisers);
@@ -604,6 +631,9 @@ int chn_device_malloc(int device, uint64_t bytes, void **ptr);
 int chn_device_free(int device, void *ptr);
 int chn_device_upload(int device, void *dev_dst, const void *host_src, uint64_t bytes);
 int chn_device_download(int device, void *host_dst, const void *dev_src, uint64_t bytes);
+/* bytes from one place in device memory to another on the SAME device (e.g. the unconsumed tail of one block of text in front of the
+ * next).  Synchronous.  CHN_E_INVALID if either stretch is not device memory of `device`, or if the two overlap. */
+int chn_device_copy(int device, void *dev_dst, const void *dev_src, uint64_t bytes);
 
 const char *chn_last_error(void);
 const char *chn_version(void);
