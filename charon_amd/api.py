@@ -62,6 +62,7 @@ class Result(C.Structure):
 TEXT_DNA5_RANKS = 1          # chn_text_batch.flags: the text holds seqan3 dna5 ranks (0 A, 1 C, 2 G, 3 N, 4 T), not letters
 TEXT_ON_DEVICE = 2           # chn_text_batch.flags: `text` is device memory (16-byte aligned, readable up to text_bytes rounded up to 16)
 TEXT_SPLIT_MAX_BYTES = 1 << 31   # CHN_TEXT_SPLIT_MAX_BYTES
+TEXT_PAIR_MAX_PAIRS = 1 << 28    # CHN_TEXT_PAIR_MAX_PAIRS
 
 
 class TextBatch(C.Structure):
@@ -69,6 +70,11 @@ class TextBatch(C.Structure):
                 ("text_bytes", C.c_uint64), ("seq1_offset", C.c_void_p), ("seq1_length", C.c_void_p), ("qual1_offset", C.c_void_p),
                 ("qual1_length", C.c_void_p), ("seq2_offset", C.c_void_p), ("seq2_length", C.c_void_p), ("qual2_offset", C.c_void_p),
                 ("qual2_length", C.c_void_p), ("compression", C.c_void_p), ("gzip_tallies", C.c_uint32), ("gzip_output", C.c_uint32)]
+
+
+class TextBatch2(C.Structure):
+    """chn_text_batch2: a chn_text_batch with a second device text behind it (the fields of the batch are named as in TextBatch)"""
+    _fields_ = TextBatch._fields_ + [("text2", C.c_void_p), ("text2_bytes", C.c_uint64)]
 
 
 class TextSplitJob(C.Structure):
@@ -81,6 +87,12 @@ class TextSplitJob(C.Structure):
 class TextFetchJob(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("text", C.c_void_p), ("text_bytes", C.c_uint64), ("n_ranges", C.c_uint64),
                 ("offset", C.c_void_p), ("length", C.c_void_p), ("out", C.c_void_p), ("out_capacity", C.c_uint64), ("out_bytes", C.c_uint64)]
+
+
+class TextPairJob(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("text1", C.c_void_p), ("text1_bytes", C.c_uint64), ("text2", C.c_void_p),
+                ("text2_bytes", C.c_uint64), ("n_pairs", C.c_uint64), ("id1_offset", C.c_void_p), ("id1_length", C.c_void_p),
+                ("id2_offset", C.c_void_p), ("id2_length", C.c_void_p), ("first_mismatch", C.c_uint64)]
 
 
 class TextResult(C.Structure):
@@ -126,7 +138,7 @@ EXPORTS = ["chn_index_create", "chn_index_upload_rows", "chn_index_device_words"
            "chn_model_set", "chn_batch_submit", "chn_batch_wait", "chn_stream_sync", "chn_classify_counts", "chn_classify_counts_raw", "chn_stream_profile",
            "chn_stream_last_batch_bytes", "chn_synth_genomes", "chn_synth_fill_index", "chn_synth_plant", "chn_synth_reads",
            "chn_device_free", "chn_device_download", "chn_device_malloc", "chn_device_upload", "chn_host_alloc", "chn_host_free", "chn_shard_minimise",
-           "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_text_submit", "chn_text_wait", "chn_text_pack", "chn_text_split", "chn_text_split_host", "chn_text_fetch", "chn_text_fetch_host", "chn_device_copy", "chn_inflate_create", "chn_inflate_run",
+           "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_text_submit", "chn_text_wait", "chn_text_pack", "chn_text_split", "chn_text_split_host", "chn_text_fetch", "chn_text_fetch_host", "chn_text_pair_ids", "chn_text_pair_ids_host", "chn_device_copy", "chn_inflate_create", "chn_inflate_run",
            "chn_inflate_run_host", "chn_inflate_destroy", "chn_inflate_kernel_ms", "chn_inflate_run_crc", "chn_inflate_run_host_crc", "chn_deflate_create", "chn_deflate_run", "chn_deflate_run_host",
            "chn_deflate_destroy", "chn_deflate_bound", "chn_deflate_kernel_ms", "chn_deflate_group_members", "chn_last_error", "chn_version"]
 
@@ -176,13 +188,15 @@ _L.chn_index_bin_popcounts.argtypes = [C.c_void_p, C.c_void_p]
 _L.chn_index_replicate.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
 _L.chn_device_count.argtypes = [C.POINTER(C.c_int)]
 _L.chn_device_download.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64]
-_L.chn_text_submit.argtypes = [C.c_void_p, C.POINTER(TextBatch)]
+_L.chn_text_submit.argtypes = [C.c_void_p, C.c_void_p]   # a chn_text_batch or a chn_text_batch2: struct_size says which
 _L.chn_text_wait.argtypes = [C.c_void_p, C.POINTER(Result), C.POINTER(TextResult)]
-_L.chn_text_pack.argtypes = [C.c_void_p, C.POINTER(TextBatch)] + [C.c_void_p] * 5 + [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+_L.chn_text_pack.argtypes = [C.c_void_p, C.c_void_p] + [C.c_void_p] * 5 + [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
 _L.chn_text_split.argtypes = [C.c_void_p, C.POINTER(TextSplitJob)]
 _L.chn_text_split_host.argtypes = [C.POINTER(TextSplitJob)]
 _L.chn_text_fetch.argtypes = [C.c_void_p, C.POINTER(TextFetchJob)]
 _L.chn_text_fetch_host.argtypes = [C.POINTER(TextFetchJob)]
+_L.chn_text_pair_ids.argtypes = [C.c_void_p, C.POINTER(TextPairJob)]
+_L.chn_text_pair_ids_host.argtypes = [C.POINTER(TextPairJob)]
 _L.chn_device_copy.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64]
 _L.chn_inflate_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
 _L.chn_inflate_run.argtypes = [C.c_void_p, C.POINTER(InflateJob)]
@@ -475,12 +489,13 @@ class Stream:
         self._fifo.append((n_reads, None, gzip_tallies, gzip_output))
 
     # ---- text batches (see include/charon_hip.h) ----
-    def _text_batch(self, tb, compression=None, gzip_tallies=0, gzip_output=0, text_device=None):
+    def _text_batch(self, tb, compression=None, gzip_tallies=0, gzip_output=0, text_device=None, text2_device=None):
         """tb: dict from charon_amd.pack.text_batch (text may be any uint8 array, e.g. a pinned_array).  text_device: (device pointer,
-        text_bytes) of the same text in device memory -- CHN_TEXT_ON_DEVICE; tb["text"] is then not looked at"""
-        t = TextBatch()
+        text_bytes) of the same text in device memory -- CHN_TEXT_ON_DEVICE; tb["text"] is then not looked at.  text2_device: (device
+        pointer, text2_bytes) of a second device text that holds mate 2: seq2_offset / qual2_offset are then bytes into it"""
+        t = TextBatch() if text2_device is None else TextBatch2()
         n = len(tb["seq1_length"])
-        t.struct_size, t.flags, t.n_reads = C.sizeof(TextBatch), tb.get("flags", 0) | (TEXT_ON_DEVICE if text_device is not None else 0), n
+        t.struct_size, t.flags, t.n_reads = C.sizeof(t), tb.get("flags", 0) | (TEXT_ON_DEVICE if text_device is not None else 0), n
         keep = []
 
         def ptr(a, dt):
@@ -500,11 +515,14 @@ class Stream:
             setattr(t, k, ptr(tb.get(k), dt))
         t.compression = ptr(compression, np.float32)
         t.gzip_tallies, t.gzip_output = gzip_tallies, gzip_output
+        if text2_device is not None:
+            t.text2, t.text2_bytes = text2_device
         return t, keep, n
 
-    def submit_text(self, tb, compression=None, gzip_tallies=0, gzip_output=0, text_device=None):
-        """chn_text_submit: the text and the descriptor arrays may be reused as soon as this returns.  text_device: see _text_batch"""
-        t, keep, n = self._text_batch(tb, compression, gzip_tallies, gzip_output, text_device)
+    def submit_text(self, tb, compression=None, gzip_tallies=0, gzip_output=0, text_device=None, text2_device=None):
+        """chn_text_submit: the text and the descriptor arrays may be reused as soon as this returns.  text_device, text2_device: see
+        _text_batch"""
+        t, keep, n = self._text_batch(tb, compression, gzip_tallies, gzip_output, text_device, text2_device)
         _chk(_L.chn_text_submit(self.h, C.byref(t)))
         self._fifo.append((n, None, gzip_tallies, gzip_output))
 
@@ -517,10 +535,10 @@ class Stream:
         out["mean_quality"], out["has_n"], out["n_bases"] = mq, int(tr.has_n), int(tr.n_bases)
         return out
 
-    def text_pack(self, tb, text_device=None):
+    def text_pack(self, tb, text_device=None, text2_device=None):
         """chn_text_pack: the packed form of a text batch as the dict pack.pack_reads returns (nmask always an array) plus
-        mean_quality and has_n.  text_device: see _text_batch"""
-        t, keep, n = self._text_batch(tb, text_device=text_device)
+        mean_quality and has_n.  text_device, text2_device: see _text_batch"""
+        t, keep, n = self._text_batch(tb, text_device=text_device, text2_device=text2_device)
         nb, hn = C.c_uint64(), C.c_uint32()
         _chk(_L.chn_text_pack(self.h, C.byref(t), None, None, None, None, None, C.byref(nb), C.byref(hn)))  # layout only: sizes the arrays
         paired = tb.get("seq2_offset") is not None
@@ -543,6 +561,13 @@ class Stream:
         j, keep = text_fetch_job(dev_ptr, nbytes, offsets, lengths, out, out_capacity)
         _chk(_L.chn_text_fetch(self.h, C.byref(j)))
         return keep[2][:int(j.out_bytes)]
+
+    def pair_ids(self, dev1, nbytes1, dev2, nbytes2, id1_offset, id1_length, id2_offset, id2_length):
+        """chn_text_pair_ids: the smallest pair whose ids in the two device texts disagree, the number of pairs if none does -- see
+        pair_ids_host for the rule"""
+        j, keep = text_pair_job(dev1, nbytes1, dev2, nbytes2, id1_offset, id1_length, id2_offset, id2_length)
+        _chk(_L.chn_text_pair_ids(self.h, C.byref(j)))
+        return int(j.first_mismatch)
 
     def wait_host(self, text_result=None):
         n, Cn = self._fifo[0][0], self.C
@@ -679,6 +704,32 @@ def text_fetch_host(data, offsets, lengths, out=None, out_capacity=None, nbytes=
     j, keep = text_fetch_job(buf.ctypes.data if buf.size else None, nbytes, offsets, lengths, out, out_capacity)
     _chk(_L.chn_text_fetch_host(C.byref(j)))
     return keep[2][:int(j.out_bytes)]
+
+
+# ---- the ids of the two mates of every pair (see include/charon_hip.h) ----
+def text_pair_job(text1_ptr, nbytes1, text2_ptr, nbytes2, id1_offset, id1_length, id2_offset, id2_length):
+    """the chn_text_pair_job of pairs whose ids are (id1_offset[i], id1_length[i]) in the text at `text1_ptr` and (id2_offset[i],
+    id2_length[i]) in the text at `text2_ptr`.  Returns (job, arrays to keep alive)."""
+    keep = (np.ascontiguousarray(id1_offset, np.uint64), np.ascontiguousarray(id1_length, np.uint32),
+            np.ascontiguousarray(id2_offset, np.uint64), np.ascontiguousarray(id2_length, np.uint32))
+    if any(a.ndim != 1 or a.size != keep[0].size for a in keep):
+        raise ValueError("the four id arrays must be one-dimensional and of one size")
+    j = TextPairJob()
+    j.struct_size, j.flags, j.n_pairs = C.sizeof(TextPairJob), 0, keep[0].size
+    j.text1, j.text1_bytes, j.text2, j.text2_bytes = text1_ptr, int(nbytes1), text2_ptr, int(nbytes2)
+    j.id1_offset, j.id1_length, j.id2_offset, j.id2_length = (a.ctypes.data for a in keep)
+    j.first_mismatch = 0xDEADBEEF
+    return j, keep
+
+
+def pair_ids_host(data1, data2, id1_offset, id1_length, id2_offset, id2_length):
+    """chn_text_pair_ids_host: the rule the GPU runs, on the CPU, over `data1` and `data2` (bytes or uint8 arrays): both ids of a pair
+    lose their last byte, and what is left must be equal.  Returns the smallest pair that disagrees, the number of pairs if none."""
+    bufs = [np.frombuffer(bytes(d), np.uint8) if isinstance(d, (bytes, bytearray)) else np.ascontiguousarray(d, np.uint8) for d in (data1, data2)]
+    j, keep = text_pair_job(bufs[0].ctypes.data if bufs[0].size else None, bufs[0].size, bufs[1].ctypes.data if bufs[1].size else None, bufs[1].size,
+                            id1_offset, id1_length, id2_offset, id2_length)
+    _chk(_L.chn_text_pair_ids_host(C.byref(j)))
+    return int(j.first_mismatch)
 
 
 # ---- raw deflate members (see include/charon_hip.h) ----

@@ -33,6 +33,7 @@
 #include <chrono>
 #include <functional>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -62,6 +63,7 @@
 #include "parts/text_pack.inc"
 #include "parts/text_split.inc"
 #include "parts/text_gather.inc"
+#include "parts/text_pair.inc"
 #include "parts/inflate_members.inc"
 #include "parts/deflate_members.inc"
 #include "parts/ef_decode.inc"
@@ -71,6 +73,7 @@
 #include "parts/abi_shard_wait.inc"
 #include "parts/abi_text_split.inc"
 #include "parts/abi_text_fetch.inc"
+#include "parts/abi_text_pair.inc"
 #include "parts/abi_text_batch.inc"
 #include "parts/abi_inflate.inc"
 #include "parts/abi_deflate.inc"

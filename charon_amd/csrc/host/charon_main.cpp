@@ -425,6 +425,14 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    if (const char *e = std::getenv("CHARON_GPU_TEXT_PAIRS")) {
+        // CHARON_GPU_TEXT_PAIRS: 1 (only together with CHARON_GPU_TEXT=1) = paired BGZF FASTQ stays in device memory as well: two texts, the
+        // ids of a pair compared on the device; 0 or unset = not.  Checked before the index file is opened and before any HIP call.
+        const std::string v(e);
+        if (v != "0" && v != "1") { std::cerr << "charon: CHARON_GPU_TEXT_PAIRS: '" << v << "' is neither 0 nor 1" << std::endl; return 1; }
+        if (v == "1" && !g_gpu_text) { std::cerr << "charon: CHARON_GPU_TEXT_PAIRS: takes effect only together with CHARON_GPU_TEXT=1, which is not set" << std::endl; return 1; }
+        g_gpu_text_pairs = v == "1";
+    }
     try {
         dehost_main(opt);  // the reference's subcommand callback discards dehost_main's return value (src/dehost_main.cpp:311)
         return 0;

@@ -95,6 +95,7 @@ struct HostBatch {
     // CHARON_GPU_TEXT=1: the block's text in device memory (so1 / qo1 are offsets into it; the records' seq / qual pointers stay null
     // until chn_text_fetch has brought a read's letters into `arena`) and the id bytes chn_text_split handed back (the records' ids)
     std::shared_ptr<DevBlock> dtext;
+    std::shared_ptr<DevBlock> dtext2;  // CHARON_GPU_TEXT_PAIRS=1: the block of file 2 that holds the mates (so2 / qo2 are offsets into it)
     std::unique_ptr<char[]> ids;
     WordBuf arena;
     ~HostBatch() {
@@ -473,6 +474,32 @@ int dehost_main(DehostArguments &opt) {
     bool resident = false, resumed = false;
     size_t resume_z = 0;
     Slab resume_carry;
+    // CHARON_GPU_TEXT_PAIRS=1: while `resident_pairs`, either file has a reader thread and a queue of its own (pair_reader / pair_queue),
+    // each with its own BlockReader, hence its own BgzfSource and inflate handle; this thread is started only when the main thread leaves
+    // the mode, with BOTH files resumed.  Device buffers: each reader fills one while two wait in its queue, the main thread holds one per
+    // side and up to two batches in flight refer to one per side -- at most fourteen exist, eight free ones are kept.
+    bool resident_pairs = false, was_resident_pairs = false, resumed2 = false;
+    size_t resume_z2 = 0;
+    Slab resume_carry2;
+    BlockQueue pair_queue[2];
+    std::thread pair_reader[2];
+    auto pair_reader_body = [&](int k) {
+        BlockQueue &q = pair_queue[k];
+        try {
+            BlockReader in(k ? opt.read_file2 : opt.read_file);
+            const size_t max_bytes = (size_t)std::min<uint64_t>(256ULL << 20, std::max<uint64_t>(1 << 20, opt.batch_bases));
+            const size_t block_bytes = std::min<size_t>(max_bytes, (size_t)64 << 20);
+            for (;;) {
+                std::shared_ptr<HostBatch> hb(new HostBatch());
+                hb->dtext = in.next_device(block_bytes, g_gpu_text_headroom);
+                if (!hb->dtext) break;
+                if (!q.push(std::move(hb))) return;
+            }
+            q.finish("");
+        } catch (std::exception &e) {
+            q.finish(e.what());
+        }
+    };
     auto reader_body = [&]() {
         try {
             in1p.reset(new BlockReader(opt.read_file));
@@ -480,6 +507,7 @@ int dehost_main(DehostArguments &opt) {
             if (opt.is_paired) in2.reset(new BlockReader(opt.read_file2));
             const size_t max_bytes = (size_t)std::min<uint64_t>(256ULL << 20, std::max<uint64_t>(1 << 20, opt.batch_bases));
             if (resumed) in1.resume(resume_z, resume_carry);
+            if (resumed && resumed2) in2->resume(resume_z2, resume_carry2);
             if (resident) {
                 const size_t block_bytes = std::min<size_t>(max_bytes, (size_t)64 << 20);
                 for (;;) {
@@ -516,14 +544,37 @@ int dehost_main(DehostArguments &opt) {
             queue.finish(e.what());
         }
     };
-    if (g_gpu_text) {
+    // why CHARON_GPU_TEXT=1 cannot take `f` (empty: it can)
+    auto not_resident_because = [](const std::string &f) -> std::string {
+        const std::string stem = f.substr(0, f.size() - std::min<size_t>(3, f.size()));
+        if (!ends_with(f, ".gz")) return "not a .gz file";
+        if (std::getenv("CHARON_NO_BGZF")) return "CHARON_NO_BGZF is set";
+        if (!ends_with(stem, ".fastq") && !ends_with(stem, ".fq")) return "not FASTQ";
+        if (!BgzfSource().open(f)) return "one deflate stream, not BGZF";
+        return "";
+    };
+    if (g_gpu_text && g_gpu_text_pairs) {
+        if (!opt.is_paired) {
+            g_log.info("CHARON_GPU_TEXT_PAIRS=1 does not apply to " + opt.read_file + " (single-end input): CHARON_GPU_TEXT=1 alone decides");
+        } else {
+            std::string why = not_resident_because(opt.read_file), file = opt.read_file;
+            if (why.empty()) { why = not_resident_because(opt.read_file2); file = opt.read_file2; }
+            resident_pairs = was_resident_pairs = why.empty();
+            if (resident_pairs) {
+                if (const char *e = std::getenv("CHARON_GPU_TEXT_HEADROOM")) g_gpu_text_headroom = (size_t)std::min<unsigned long long>(1ULL << 30, std::strtoull(e, nullptr, 10));
+                g_dev_text_pool.keep = 8;
+                g_log.info("CHARON_GPU_TEXT=1: BGZF text is inflated into the memory of device " + std::to_string(g_gpu_text_device) +
+                           " and stays there (records split and packed on the device; headroom " + std::to_string(g_gpu_text_headroom) + " bytes)");
+                g_log.info("CHARON_GPU_TEXT_PAIRS=1: both files of the pair stay in device memory (two texts a batch; the ids of a pair are compared on the device)");
+            } else {
+                g_log.info("CHARON_GPU_TEXT_PAIRS=1 does not apply to " + file + " (" + why + "; both files must be BGZF FASTQ): the run goes on without it");
+            }
+        }
+    }
+    if (g_gpu_text && !resident_pairs) {
         std::string why;
-        const std::string stem = opt.read_file.substr(0, opt.read_file.size() - std::min<size_t>(3, opt.read_file.size()));
         if (opt.is_paired) why = "paired input";
-        else if (!ends_with(opt.read_file, ".gz")) why = "not a .gz file";
-        else if (std::getenv("CHARON_NO_BGZF")) why = "CHARON_NO_BGZF is set";
-        else if (!ends_with(stem, ".fastq") && !ends_with(stem, ".fq")) why = "not FASTQ";
-        else if (!BgzfSource().open(opt.read_file)) why = "one deflate stream, not BGZF";
+        else why = not_resident_because(opt.read_file);
         resident = why.empty();
         if (resident) {
             if (const char *e = std::getenv("CHARON_GPU_TEXT_HEADROOM")) g_gpu_text_headroom = (size_t)std::min<unsigned long long>(1ULL << 30, std::strtoull(e, nullptr, 10));
@@ -533,12 +584,14 @@ int dehost_main(DehostArguments &opt) {
             g_log.info("CHARON_GPU_TEXT=1 does not apply to " + opt.read_file + " (" + why + "; single-end BGZF FASTQ only): the run goes on without it");
         }
     }
-    std::thread reader(reader_body);
+    std::thread reader;
+    if (resident_pairs) for (int k = 0; k < 2; ++k) pair_reader[k] = std::thread(pair_reader_body, k);
+    else reader = std::thread(reader_body);
 
     struct ReaderJoin {  // whatever way this function is left: stop the reader and wait for it
         BlockQueue &q; std::thread &t;
         ~ReaderJoin() { if (t.joinable()) { q.abort(); t.join(); } }
-    } reader_join{queue, reader};
+    } reader_join{queue, reader}, pair_reader_join0{pair_queue[0], pair_reader[0]}, pair_reader_join1{pair_queue[1], pair_reader[1]};
     // the HIP runtime takes 0.1-0.2 s to come up: let it do so while this thread reads the index file
     std::thread warm([]() { void *p = nullptr; if (chn_host_alloc(64, &p) == CHN_OK) chn_host_free(p); });
     struct WarmJoin { std::thread &t; ~WarmJoin() { if (t.joinable()) t.join(); } } warm_join{warm};
@@ -635,7 +688,7 @@ int dehost_main(DehostArguments &opt) {
                 if (dv >= count) throw std::runtime_error("CHARON_DEVICES: device " + std::to_string(dv) + " is not below the device count " + std::to_string(count));
         }
         d.device = devices[0];
-        if (resident && devices.size() > 1) throw std::runtime_error("CHARON_GPU_TEXT: cannot be set together with CHARON_DEVICES=all on several devices (the text lives on one device)");
+        if ((resident || resident_pairs) && devices.size() > 1) throw std::runtime_error("CHARON_GPU_TEXT: cannot be set together with CHARON_DEVICES=all on several devices (the text lives on one device)");
     }
     {
         std::string list;
@@ -722,6 +775,7 @@ int dehost_main(DehostArguments &opt) {
     // One GPU batch on its way through the pipeline: its host arrays stay alive until chn_batch_wait has returned.
     struct Flight {
         std::shared_ptr<HostBatch> parent;  // owns the slabs the record views point into
+        std::shared_ptr<HostBatch> parent2; // CHARON_GPU_TEXT_PAIRS=1: owns the id bytes of the mates' records (file 2's block)
         HostBatch sub;
         uint32_t version = 0;
         uint64_t seq = 0;  // replica mode: position in input order (the ordered merge releases flights by it)
@@ -903,6 +957,7 @@ int dehost_main(DehostArguments &opt) {
     std::mutex pool_m;
     auto recycle = [&](std::unique_ptr<Flight> &f) {
         f->parent.reset();
+        f->parent2.reset();
         std::lock_guard<std::mutex> lk(pool_m);
         flight_pool.push_back(std::move(f));
     };
@@ -997,8 +1052,9 @@ int dehost_main(DehostArguments &opt) {
             return;
         }
         HostBatch &sub = fl.sub;
-        chn_text_batch tb;
-        std::memset(&tb, 0, sizeof tb);
+        chn_text_batch2 tb2;  // (a chn_text_batch with the text of file 2 behind it: used as such by paired resident batches only)
+        std::memset(&tb2, 0, sizeof tb2);
+        chn_text_batch &tb = tb2.batch;
         tb.struct_size = sizeof tb; tb.n_reads = sub.keep.size(); tb.text = sub.text; tb.text_bytes = sub.text_bytes;
         tb.seq1_offset = sub.so1.data(); tb.seq1_length = sub.len1.data();
         if (sub.text_quals) { tb.qual1_offset = sub.qo1.data(); tb.qual1_length = sub.ql1.data(); }
@@ -1010,6 +1066,7 @@ int dehost_main(DehostArguments &opt) {
         tb.gzip_tallies = sub.gz_gpu_len;
         tb.gzip_output = sub.gz_gpu_len > CHN_GZIP_MAX_LEN ? CHN_GZIP_SIZES_ALL : CHN_GZIP_SIZES;
         if (fl.resident) { tb.flags = CHN_TEXT_ON_DEVICE; tb.text = sub.dtext->buf; tb.text_bytes = sub.dtext->text_bytes; }
+        if (fl.resident && sub.dtext2) { tb.struct_size = sizeof tb2; tb2.text2 = sub.dtext2->buf; tb2.text2_bytes = sub.dtext2->text_bytes; }
         else (sub.text_from_slab ? text_slab_batches : text_copy_batches) += 1;
         const int rc = chn_text_submit(st, &tb);
         // (the device met a byte that is no IUPAC nucleotide letter: what HostBatch::pack reports for a packed batch)
@@ -1138,6 +1195,8 @@ int dehost_main(DehostArguments &opt) {
     // replica threads are not used: up to two batches are in flight while the next is split and submitted.
     uint64_t dt_split_records = 0, dt_fetched_records = 0, dt_fetched_bytes = 0;
     double t_split = 0, t_fetch = 0;
+    uint64_t dp_pairs_checked = 0, dp_id2_bytes = 0;  // CHARON_GPU_TEXT_PAIRS=1: pairs through chn_text_pair_ids; id bytes of file 2 that came down
+    double t_pair = 0;
     // After chn_text_wait: ONE chn_text_fetch for the reads whose letters the host needs -- the sequence of a read the device left
     // unsized, sequence and quality of every read under --extract (make_entry copies them; without --extract it reads the id alone,
     // in training too) -- into the flight's arena; the record views point there.  The block's buffer is let go afterwards.
@@ -1153,6 +1212,39 @@ int dehost_main(DehostArguments &opt) {
             who.push_back((uint32_t)i);
             off.push_back(sub.so1[i]); len.push_back(sub.len1[i]); total += sub.len1[i];
             if (opt.run_extract) { off.push_back(sub.qo1[i]); len.push_back(sub.ql1[i]); total += sub.ql1[i]; }
+        }
+        if (sub.dtext2) {  // pairs over two texts: the same reads' mates out of file 2's block, behind mate 1's bytes in the arena -- one fetch per text
+            std::vector<uint64_t> off2;
+            std::vector<uint32_t> len2;
+            uint64_t total2 = 0;
+            for (uint32_t i : who) {
+                off2.push_back(sub.so2[i]); len2.push_back(sub.len2[i]); total2 += sub.len2[i];
+                if (opt.run_extract) { off2.push_back(sub.qo2[i]); len2.push_back(sub.ql2[i]); total2 += sub.ql2[i]; }
+            }
+            if (!who.empty()) {
+                sub.arena.want_pinned = true;
+                sub.arena.assign_raw((size_t)((total + total2) / 4) + 2);
+                uint8_t *arena = reinterpret_cast<uint8_t *>(sub.arena.data());
+                for (int k = 0; k < 2; ++k) {
+                    chn_text_fetch_job job;
+                    std::memset(&job, 0, sizeof job);
+                    const DevBlock &blk = k ? *sub.dtext2 : *sub.dtext;
+                    job.struct_size = sizeof job; job.text = blk.buf; job.text_bytes = blk.text_bytes;
+                    job.n_ranges = k ? off2.size() : off.size(); job.offset = k ? off2.data() : off.data(); job.length = k ? len2.data() : len.data();
+                    job.out = arena + (k ? total : 0); job.out_capacity = k ? total2 : total;
+                    CHN_CHECK(chn_text_fetch(stream, &job));
+                }
+                const char *at = reinterpret_cast<const char *>(arena), *at2 = at + total;
+                for (uint32_t i : who) {
+                    RecView &r = sub.blk1.recs[sub.keep[i]], &m = sub.blk2.recs[sub.keep[i]];
+                    r.seq = at; at += sub.len1[i];
+                    m.seq = at2; at2 += sub.len2[i];
+                    if (opt.run_extract) { r.qual = at; at += sub.ql1[i]; m.qual = at2; at2 += sub.ql2[i]; }
+                }
+                dt_fetched_records += who.size(); dt_fetched_bytes += total + total2;
+            }
+            sub.dtext.reset(); sub.dtext2.reset();
+            return;
         }
         if (!who.empty()) {
             sub.arena.want_pinned = true;
@@ -1173,28 +1265,105 @@ int dehost_main(DehostArguments &opt) {
         }
         sub.dtext.reset();
     };
-    auto run_resident = [&]() {
-        std::deque<std::unique_ptr<Flight>> flying;  // submitted, oldest first
-        struct SyncOnThrow {  // the device is done with these flights' arrays before they are freed
-            std::deque<std::unique_ptr<Flight>> &f; chn_stream *s;
-            ~SyncOnThrow() { if (!f.empty()) (void)chn_stream_sync(s); }
-        } sync_on_throw{flying, stream};
-        auto retire_front = [&]() {
-            std::unique_ptr<Flight> f = std::move(flying.front());
-            flying.pop_front();
-            finish_wait(*f, stream, t_wait);
-            const double tk = now();
-            fetch_letters(*f);
-            t_fetch += now() - tk;
-            hand_on(f);
-        };
+    // What the single-end loop and the paired loop (CHARON_GPU_TEXT_PAIRS=1) share:
+    typedef std::deque<std::unique_ptr<Flight>> Flying;  // submitted, oldest first
+    struct SyncOnThrow {  // the device is done with these flights' arrays before they are freed
+        Flying &f; chn_stream *s;
+        ~SyncOnThrow() { if (!f.empty()) (void)chn_stream_sync(s); }
+    };
+    auto retire_front = [&](Flying &flying) {
+        std::unique_ptr<Flight> f = std::move(flying.front());
+        flying.pop_front();
+        finish_wait(*f, stream, t_wait);
+        const double tk = now();
+        fetch_letters(*f);
+        t_fetch += now() - tk;
+        hand_on(f);
+    };
+    auto take_flight = [&]() {
+        std::unique_ptr<Flight> fl;
+        {
+            std::lock_guard<std::mutex> lk(pool_m);
+            if (!flight_pool.empty()) { fl = std::move(flight_pool.back()); flight_pool.pop_back(); }
+        }
+        if (!fl) fl.reset(new Flight());
+        return fl;
+    };
+    // a packed resident flight on its way: at most two in flight, the models pushed while they train, one batch at a time until they are final
+    bool final_pushed = false;
+    auto submit_resident = [&](Flying &flying, std::unique_ptr<Flight> &fl) {
+        const size_t n = fl->sub.keep.size();
+        while (flying.size() >= 2) retire_front(flying);
+        // (while the models are in training every batch is retired before the next is submitted, so nothing is in flight here)
+        if (!final_pushed) { result.ensure_device_model(); final_pushed = result.models_final(); }
+        fl->version = result.current_model_version();
+        const double tk = now();
+        submit_flight(stream, *fl);
+        t_submit += now() - tk;
+        reps[0]->batches += 1; reps[0]->reads += n;
+        flying.push_back(std::move(fl));
+        if (!result.models_final()) retire_front(flying);
+    };
+    // The tail [prev_from, prev->text_bytes) of the block before copied in front of member 0 of `blk`, so that it ends where member 0
+    // begins; a tail longer than the gap (a record longer than the headroom) gets a fresh buffer for the two, which replaces `blk` (and
+    // hb.dtext).  Returns where the text of `blk` now starts.
+    auto carry_tail = [&](const std::shared_ptr<DevBlock> &prev, uint64_t prev_from, std::shared_ptr<DevBlock> &blk, HostBatch &hb) -> uint64_t {
         const int dev = g_gpu_text_device;
-        const uint64_t kSplitRecords = 1u << 18;  // per chn_text_split (its scratch is 52 bytes per record of this bound); a block with more takes several
-        std::vector<uint64_t> ido(kSplitRecords), sqo(kSplitRecords), qlo(kSplitRecords), blk_so, blk_qo;
-        std::vector<uint32_t> idl(kSplitRecords), sql(kSplitRecords);
+        const uint64_t tail = prev->text_bytes - prev_from, body = blk->text_bytes - blk->member0;
+        if (tail > blk->member0) {
+            std::shared_ptr<DevBlock> fresh(new DevBlock());
+            void *p = nullptr;
+            fresh->cap = (size_t)((tail + body + 15) & ~15ULL);
+            CHN_CHECK(chn_device_malloc(dev, fresh->cap, &p));
+            fresh->buf = static_cast<uint8_t *>(p);
+            fresh->member0 = tail; fresh->text_bytes = tail + body; fresh->file_offset = blk->file_offset;
+            fresh->z_end = blk->z_end; fresh->last = blk->last;
+            if (body) CHN_CHECK(chn_device_copy(dev, fresh->buf + tail, blk->buf + blk->member0, body));
+            blk = fresh;
+            hb.dtext = fresh;
+        }
+        if (tail) CHN_CHECK(chn_device_copy(dev, blk->buf + blk->member0 - tail, prev->buf + prev_from, tail));
+        return blk->member0 - tail;
+    };
+    // The records of blk's text from `start` on: descriptors and (want_ids) id bytes come back, letters and qualities stay where they
+    // are.  The id bytes go to hb.ids; `sink` gets every record: its id bytes (null without want_ids), id length, sequence length, and
+    // the offsets of id, sequence and quality string in the text.  Returns the offset behind the last record; *ids_bytes the id bytes
+    // that came down.
+    const uint64_t kSplitRecords = 1u << 18;  // per chn_text_split (its scratch is 52 bytes per record of this bound); a block with more takes several
+    std::vector<uint64_t> ido, sqo, qlo;  // (sized by the first call: a run that is not resident never pays for them)
+    std::vector<uint32_t> idl, sql;
+    auto split_block = [&](const DevBlock &blk, uint64_t start, bool want_ids, HostBatch &hb,
+                           const std::function<void(const char *, uint32_t, uint32_t, uint64_t, uint64_t, uint64_t)> &sink, uint64_t *ids_bytes) -> uint64_t {
+        const uint64_t end = blk.text_bytes;
+        uint64_t consumed = start, ids_used = 0;
+        if (want_ids) hb.ids.reset(new char[end - start + 1]);
+        if (ido.empty()) { ido.resize(kSplitRecords); sqo.resize(kSplitRecords); qlo.resize(kSplitRecords); idl.resize(kSplitRecords); sql.resize(kSplitRecords); }
+        for (;;) {
+            chn_text_split_job job;
+            std::memset(&job, 0, sizeof job);
+            job.struct_size = sizeof job; job.text = blk.buf; job.text_bytes = end; job.start = consumed; job.max_records = kSplitRecords;
+            job.id_offset = ido.data(); job.id_length = idl.data(); job.seq_offset = sqo.data(); job.seq_length = sql.data(); job.qual_offset = qlo.data();
+            if (want_ids) { job.ids = reinterpret_cast<uint8_t *>(hb.ids.get()) + ids_used; job.ids_capacity = end - start - ids_used; }
+            CHN_CHECK(chn_text_split(stream, &job));
+            const char *id = want_ids ? hb.ids.get() + ids_used : nullptr;
+            for (uint64_t i = 0; i < job.n_records; ++i) {
+                sink(id, idl[i], sql[i], ido[i], sqo[i], qlo[i]);
+                if (id) id += idl[i];
+            }
+            if (want_ids) ids_used += job.ids_bytes;
+            consumed = job.consumed;
+            if (job.n_records < kSplitRecords) break;
+        }
+        if (ids_bytes) *ids_bytes = ids_used;
+        return consumed;
+    };
+    auto run_resident = [&]() {
+        Flying flying;
+        SyncOnThrow sync_on_throw{flying, stream};
+        const int dev = g_gpu_text_device;
+        std::vector<uint64_t> blk_so, blk_qo;
         std::shared_ptr<DevBlock> prev;  // the block before, while [prev_from, prev->text_bytes) is a tail no record was made of
         uint64_t prev_from = 0;
-        bool final_pushed = false;
         for (;;) {
             const double tp = now();
             std::shared_ptr<HostBatch> hbp = queue.pop();
@@ -1205,46 +1374,17 @@ int dehost_main(DehostArguments &opt) {
             double tk = now();
             uint64_t start = blk->member0;
             if (prev) {
-                const uint64_t tail = prev->text_bytes - prev_from, body = blk->text_bytes - blk->member0;
-                if (tail > blk->member0) {  // a tail longer than the gap (a record longer than the headroom): a buffer for the two
-                    std::shared_ptr<DevBlock> fresh(new DevBlock());
-                    void *p = nullptr;
-                    fresh->cap = (size_t)((tail + body + 15) & ~15ULL);
-                    CHN_CHECK(chn_device_malloc(dev, fresh->cap, &p));
-                    fresh->buf = static_cast<uint8_t *>(p);
-                    fresh->member0 = tail; fresh->text_bytes = tail + body; fresh->file_offset = blk->file_offset;
-                    fresh->z_end = blk->z_end; fresh->last = blk->last;
-                    if (body) CHN_CHECK(chn_device_copy(dev, fresh->buf + tail, blk->buf + blk->member0, body));
-                    blk = fresh;
-                    hb.dtext = fresh;
-                }
-                if (tail) CHN_CHECK(chn_device_copy(dev, blk->buf + blk->member0 - tail, prev->buf + prev_from, tail));
-                start = blk->member0 - tail;
+                start = carry_tail(prev, prev_from, blk, hb);
                 prev.reset();
             }
-            // records: descriptors and id bytes come back, letters and qualities stay where they are
             const uint64_t end = blk->text_bytes;
-            uint64_t consumed = start, ids_used = 0;
-            hb.ids.reset(new char[end - start + 1]);
             blk_so.clear(); blk_qo.clear();
-            for (;;) {
-                chn_text_split_job job;
-                std::memset(&job, 0, sizeof job);
-                job.struct_size = sizeof job; job.text = blk->buf; job.text_bytes = end; job.start = consumed; job.max_records = kSplitRecords;
-                job.id_offset = ido.data(); job.id_length = idl.data(); job.seq_offset = sqo.data(); job.seq_length = sql.data(); job.qual_offset = qlo.data();
-                job.ids = reinterpret_cast<uint8_t *>(hb.ids.get()) + ids_used; job.ids_capacity = end - start - ids_used;
-                CHN_CHECK(chn_text_split(stream, &job));
-                const char *id = hb.ids.get() + ids_used;
-                for (uint64_t i = 0; i < job.n_records; ++i) {
-                    RecView r;
-                    r.id = id; r.id_len = idl[i]; r.seq_len = r.qual_len = sql[i];
-                    id += idl[i];
-                    hb.blk1.recs.push_back(r);
-                    blk_so.push_back(sqo[i]); blk_qo.push_back(qlo[i]);
-                }
-                ids_used += job.ids_bytes; consumed = job.consumed;
-                if (job.n_records < kSplitRecords) break;
-            }
+            const uint64_t consumed = split_block(*blk, start, true, hb, [&](const char *id, uint32_t id_len, uint32_t seq_len, uint64_t, uint64_t so, uint64_t qo) {
+                RecView r;
+                r.id = id; r.id_len = id_len; r.seq_len = r.qual_len = seq_len;
+                hb.blk1.recs.push_back(r);
+                blk_so.push_back(so); blk_qo.push_back(qo);
+            }, nullptr);
             t_split += now() - tk;
             const size_t nrec = hb.blk1.recs.size();
             dt_split_records += nrec;
@@ -1259,12 +1399,7 @@ int dehost_main(DehostArguments &opt) {
                     if (bases + need > opt.batch_bases) break;
                     bases += need; ++endi;
                 }
-                std::unique_ptr<Flight> fl;
-                {
-                    std::lock_guard<std::mutex> lk(pool_m);
-                    if (!flight_pool.empty()) { fl = std::move(flight_pool.back()); flight_pool.pop_back(); }
-                }
-                if (!fl) fl.reset(new Flight());
+                std::unique_ptr<Flight> fl = take_flight();
                 fl->parent = hbp;
                 fl->resident = true;
                 HostBatch &sub = fl->sub;
@@ -1280,16 +1415,7 @@ int dehost_main(DehostArguments &opt) {
                 t_pack += now() - tk;
                 begin = endi;
                 if (n == 0) { sub.dtext.reset(); continue; }
-                while (flying.size() >= 2) retire_front();
-                // (while the models are in training every batch is retired before the next is submitted, so nothing is in flight here)
-                if (!final_pushed) { result.ensure_device_model(); final_pushed = result.models_final(); }
-                fl->version = result.current_model_version();
-                tk = now();
-                submit_flight(stream, *fl);
-                t_submit += now() - tk;
-                reps[0]->batches += 1; reps[0]->reads += n;
-                flying.push_back(std::move(fl));
-                if (!result.models_final()) retire_front();
+                submit_resident(flying, fl);
             }
             // Leaving the mode: no record although four line feeds follow `start` (a wrapped record, a blank line, a damaged record), or
             // bytes behind the last record at the end of the file (a last line without a line feed).  The text from `consumed` on comes
@@ -1303,7 +1429,7 @@ int dehost_main(DehostArguments &opt) {
                 leave = blk->last || std::count(tail_text.begin(), tail_text.end(), '\n') >= 4;
             }
             if (leave) {
-                while (!flying.empty()) retire_front();
+                while (!flying.empty()) retire_front(flying);
                 g_log.info("CHARON_GPU_TEXT=1: leaving the device-resident path at byte " + std::to_string(blk->file_offset + consumed - blk->member0) +
                            " of the inflated file (text that is no plain four-line record): the host parser goes on from there");
                 queue.abort();
@@ -1316,10 +1442,183 @@ int dehost_main(DehostArguments &opt) {
             }
             if (consumed < end) { prev = blk; prev_from = consumed; }
         }
-        while (!flying.empty()) retire_front();
+        while (!flying.empty()) retire_front(flying);
+    };
+    // ---- CHARON_GPU_TEXT_PAIRS=1: the same loop over two files -------------------------------------------------------------------------
+    // Each side (file) keeps its current block, the descriptors of the records that are split but not yet paired, and `consumed`.  A side
+    // with no unpaired record left takes its next block (carry and headroom as above); a side that still has some does not, so files
+    // with records of unequal size never pile up text and no record is split twice.  The pairs at hand -- the shorter of the two lists
+    // -- therefore lie in ONE block of either file, and a batch of them is a chn_text_batch2 over those two blocks.  The ids of a batch
+    // are compared on the device before the submit; the ids of file 2 come down with the split under --extract only.
+    auto run_resident_pairs = [&]() {
+        Flying flying;
+        SyncOnThrow sync_on_throw{flying, stream};
+        const int dev = g_gpu_text_device;
+        struct Side {
+            std::shared_ptr<HostBatch> hb;   // the block's holder: owns the id bytes its records' views point into
+            std::shared_ptr<DevBlock> blk;   // the current block (kept at the end of the file: leaving the mode resumes behind it)
+            std::vector<uint64_t> id_off, seq_off, qual_off;  // records split from `blk`; those from `head` on are not yet paired
+            std::vector<uint32_t> id_len, seq_len;
+            std::vector<const char *> id;    // the id bytes (null where they did not come down)
+            size_t head = 0;
+            uint64_t consumed = 0;           // behind the last split record
+            uint64_t paired_end = 0;         // behind the last PAIRED record
+            bool eof = false;
+            size_t unpaired() const { return id_off.size() - head; }
+        } side[2];
+        std::string reader_failure;
+        // leaving the mode: every flight retired, either side's text from behind its last paired record downloaded, both readers stopped,
+        // and today's one-thread paired reader started with both files resumed
+        auto leave = [&](int k) {
+            while (!flying.empty()) retire_front(flying);
+            Slab carry[2];
+            size_t z[2] = {0, 0};
+            for (int s = 0; s < 2; ++s) {
+                Side &sd = side[s];
+                if (!sd.blk) continue;  // (no block of this file was taken: it starts from its first member)
+                z[s] = sd.blk->z_end;
+                const uint64_t from = sd.paired_end, end = sd.blk->text_bytes;
+                carry[s].resize((size_t)(end - from));
+                if (end > from) CHN_CHECK(chn_device_download(dev, carry[s].data(), sd.blk->buf + from, end - from));
+            }
+            const Side &sk = side[k];
+            g_log.info("CHARON_GPU_TEXT=1: leaving the device-resident path at byte " + std::to_string(sk.blk->file_offset + sk.consumed - sk.blk->member0) +
+                       " of the inflated file " + (k ? opt.read_file2 : opt.read_file) + " (text that is no plain four-line record): the host parser goes on from there");
+            for (int s = 0; s < 2; ++s) pair_queue[s].abort();
+            for (int s = 0; s < 2; ++s) if (pair_reader[s].joinable()) pair_reader[s].join();
+            for (int s = 0; s < 2; ++s) { side[s].hb.reset(); side[s].blk.reset(); }
+            resident_pairs = false; resumed = resumed2 = true;
+            resume_z = z[0]; resume_carry.swap(carry[0]); resume_z2 = z[1]; resume_carry2.swap(carry[1]);
+            g_gpu_inflate = true; g_gpu_inflate_device = dev; g_pin_slabs = true;  // inflate as under CHARON_GPU_INFLATE=1 from here on
+            reader = std::thread(reader_body);
+        };
+        // the next block of side k, the tail of the block before in front of it, split into records.  true: the mode has to be left
+        auto take_block = [&](int k) -> bool {
+            Side &sd = side[k];
+            const double tp = now();
+            std::shared_ptr<HostBatch> hbp = pair_queue[k].pop();
+            t_pop += now() - tp;
+            if (!hbp) {  // the end of the file, or the reader's error
+                sd.eof = true;
+                if (!pair_queue[k].error.empty()) reader_failure = pair_queue[k].error;
+                return false;
+            }
+            HostBatch &hb = *hbp;
+            std::shared_ptr<DevBlock> blk = hb.dtext;
+            double tk = now();
+            uint64_t start = blk->member0;
+            // (every record of the block before is paired: its tail is [consumed, text_bytes))
+            if (sd.blk) start = carry_tail(sd.blk, sd.consumed, blk, hb);
+            const uint64_t end = blk->text_bytes;
+            const bool want_ids = k == 0 || opt.run_extract;  // the TSV prints the id of mate 1; mate 2's is written under --extract only
+            sd.id_off.clear(); sd.seq_off.clear(); sd.qual_off.clear(); sd.id_len.clear(); sd.seq_len.clear(); sd.id.clear(); sd.head = 0;
+            uint64_t ids_bytes = 0;
+            const uint64_t consumed = split_block(*blk, start, want_ids, hb, [&](const char *id, uint32_t id_len, uint32_t seq_len, uint64_t io, uint64_t so, uint64_t qo) {
+                sd.id.push_back(id); sd.id_len.push_back(id_len); sd.seq_len.push_back(seq_len);
+                sd.id_off.push_back(io); sd.seq_off.push_back(so); sd.qual_off.push_back(qo);
+            }, &ids_bytes);
+            if (k == 1) dp_id2_bytes += ids_bytes;
+            t_split += now() - tk;
+            dt_split_records += sd.id_off.size();
+            sd.hb = hbp; sd.blk = blk; sd.consumed = consumed; sd.paired_end = start;
+            // no record although four line feeds follow `start`, or bytes behind the last record at the end of the file
+            if (consumed < end && (sd.id_off.empty() || blk->last)) {
+                if (blk->last) return true;
+                Slab tail_text((size_t)(end - consumed));
+                CHN_CHECK(chn_device_download(dev, tail_text.data(), blk->buf + consumed, end - consumed));
+                if (std::count(tail_text.begin(), tail_text.end(), '\n') >= 4) return true;
+            }
+            return false;
+        };
+        for (;;) {
+            bool left = false;
+            for (int k = 0; k < 2 && !left; ++k)
+                while (side[k].unpaired() == 0 && !side[k].eof)  // (a block may end inside its first record and yield none)
+                    if (take_block(k)) { leave(k); left = true; break; }
+            if (left) return;
+            if (side[0].unpaired() == 0 || side[1].unpaired() == 0) break;  // one file has run out: the pairs made so far are all there are
+            Side &s1 = side[0], &s2 = side[1];
+            size_t avail = std::min(s1.unpaired(), s2.unpaired());
+            while (avail) {
+                uint64_t bases = 0;
+                size_t cnt = 0;
+                while (cnt < avail && cnt < opt.batch_reads) {
+                    const uint64_t need = HostBatch::pad64(s1.seq_len[s1.head + cnt]) + HostBatch::pad64(s2.seq_len[s2.head + cnt]);
+                    if (need > opt.batch_bases) throw std::runtime_error("a read is longer than CHARON_BATCH_BASES");
+                    if (bases + need > opt.batch_bases) break;
+                    bases += need; ++cnt;
+                }
+                // the ids of the batch's pairs must agree after dropping the last character (src/dehost_main.cpp:423-430): on the device
+                double tk = now();
+                chn_text_pair_job pj;
+                std::memset(&pj, 0, sizeof pj);
+                pj.struct_size = sizeof pj; pj.text1 = s1.blk->buf; pj.text1_bytes = s1.blk->text_bytes; pj.text2 = s2.blk->buf; pj.text2_bytes = s2.blk->text_bytes;
+                pj.n_pairs = cnt; pj.id1_offset = s1.id_off.data() + s1.head; pj.id1_length = s1.id_len.data() + s1.head;
+                pj.id2_offset = s2.id_off.data() + s2.head; pj.id2_length = s2.id_len.data() + s2.head;
+                CHN_CHECK(chn_text_pair_ids(stream, &pj));
+                t_pair += now() - tk;
+                dp_pairs_checked += cnt;
+                if (pj.first_mismatch < cnt) {
+                    const size_t a = s1.head + (size_t)pj.first_mismatch, b = s2.head + (size_t)pj.first_mismatch;
+                    while (!flying.empty()) retire_front(flying);
+                    if (writer.t.joinable()) writer_drain();
+                    const uint32_t la = s1.id_len[a] ? s1.id_len[a] - 1 : 0, lb = s2.id_len[b] ? s2.id_len[b] - 1 : 0;
+                    std::string id2(lb, '\0');
+                    if (lb) {  // the one id of file 2 this run needs on the host
+                        chn_text_fetch_job job;
+                        std::memset(&job, 0, sizeof job);
+                        const uint64_t o = s2.id_off[b];
+                        job.struct_size = sizeof job; job.text = s2.blk->buf; job.text_bytes = s2.blk->text_bytes;
+                        job.n_ranges = 1; job.offset = &o; job.length = &lb;
+                        job.out = reinterpret_cast<uint8_t *>(&id2[0]); job.out_capacity = lb;
+                        CHN_CHECK(chn_text_fetch(stream, &job));
+                    }
+                    std::cout.flush();
+                    std::cout << std::string(s1.id[a], la) << " " << id2;
+                    std::cout.flush();
+                    std::fprintf(stderr, "terminate called after throwing an instance of 'std::runtime_error'\n  what():  Your pairs don't match for read ids.\n");
+                    std::abort();
+                }
+                std::unique_ptr<Flight> fl = take_flight();
+                fl->parent = s1.hb; fl->parent2 = s2.hb;
+                fl->resident = true;
+                HostBatch &sub = fl->sub;
+                sub.blk1.recs.resize(cnt); sub.blk2.recs.resize(cnt);
+                for (size_t i = 0; i < cnt; ++i) {
+                    RecView r, m;
+                    r.id = s1.id[s1.head + i]; r.id_len = s1.id_len[s1.head + i]; r.seq_len = r.qual_len = s1.seq_len[s1.head + i];
+                    m.id = s2.id[s2.head + i]; m.id_len = m.id ? s2.id_len[s2.head + i] : 0; m.seq_len = m.qual_len = s2.seq_len[s2.head + i];
+                    sub.blk1.recs[i] = r; sub.blk2.recs[i] = m;
+                }
+                tk = now();
+                sub.pack(true, opt.threads, skip_compression, gz_gpu_max, gz_route_long, true, nullptr, true);
+                const size_t n = sub.keep.size();
+                sub.so1.resize(n); sub.qo1.resize(n); sub.so2.resize(n); sub.qo2.resize(n);
+                for (size_t i = 0; i < n; ++i) {
+                    const size_t a = s1.head + sub.keep[i], b = s2.head + sub.keep[i];
+                    sub.so1[i] = s1.seq_off[a]; sub.qo1[i] = s1.qual_off[a]; sub.so2[i] = s2.seq_off[b]; sub.qo2[i] = s2.qual_off[b];
+                }
+                sub.ql1 = sub.len1; sub.ql2 = sub.len2;
+                sub.text_quals = true; sub.text_from_slab = false;
+                sub.dtext = s1.blk; sub.dtext2 = s2.blk;
+                t_pack += now() - tk;
+                s1.head += cnt; s2.head += cnt; avail -= cnt;
+                for (Side *sd : {&s1, &s2}) sd->paired_end = sd->unpaired() ? sd->id_off[sd->head] - 1 : sd->consumed;  // ('@' stands in front of an id)
+                if (n == 0) { sub.dtext.reset(); sub.dtext2.reset(); continue; }
+                submit_resident(flying, fl);
+            }
+        }
+        while (!flying.empty()) retire_front(flying);
+        // nothing was left: both readers are done with (one may still wait to hand over a block nobody wants), and the loop below,
+        // which reads the one-thread reader's queue, finds it finished -- with the error a reader met, if one did
+        for (int s = 0; s < 2; ++s) pair_queue[s].abort();
+        for (int s = 0; s < 2; ++s) if (pair_reader[s].joinable()) pair_reader[s].join();
+        for (int s = 0; s < 2; ++s) { side[s].hb.reset(); side[s].blk.reset(); }
+        queue.finish(reader_failure);
     };
     try {
         if (resident) run_resident();
+        if (resident_pairs) run_resident_pairs();
         for (;;) {
             double tp = now();
             std::shared_ptr<HostBatch> hbp = queue.pop();
@@ -1403,7 +1702,7 @@ int dehost_main(DehostArguments &opt) {
         queue.abort();  // the reader thread stops at its next block
         stop_replicas();
     }
-    reader.join();
+    if (reader.joinable()) reader.join();
     if (!failure.empty()) { std::cout.flush(); throw std::runtime_error(failure); }
     result.complete();
     std::cout.flush();
@@ -1421,7 +1720,7 @@ int dehost_main(DehostArguments &opt) {
             g_log.info(tb);
             std::fprintf(stderr, "charon: %s\n", tb);
         }
-        if (g_gpu_text && (resident || resumed)) {
+        if (g_gpu_text && (resident || resumed || was_resident_pairs)) {
             char tg[512];
             std::snprintf(tg, sizeof tg, "timing (CHARON_GPU_TEXT=1): records split %llu  records fetched %llu  text bytes inflated %llu  text bytes fetched %llu  "
                           "seconds in inflate %.3f  seconds in split %.3f  seconds in fetch %.3f",
@@ -1429,6 +1728,12 @@ int dehost_main(DehostArguments &opt) {
                           (unsigned long long)dt_fetched_bytes, g_gpu_inflate_s, t_split, t_fetch);
             g_log.info(tg);
             std::fprintf(stderr, "charon: %s\n", tg);
+        }
+        if (was_resident_pairs) {
+            std::snprintf(tb, sizeof tb, "timing (CHARON_GPU_TEXT_PAIRS=1): pairs checked %llu  id bytes of file 2 downloaded %llu  seconds in pair check %.3f",
+                          (unsigned long long)dp_pairs_checked, (unsigned long long)dp_id2_bytes, t_pair);
+            g_log.info(tb);
+            std::fprintf(stderr, "charon: %s\n", tb);
         }
         if (g_gpu_deflate) {
             std::snprintf(tb, sizeof tb, "timing (main thread, s): inside chn_deflate_run %.3f (extract files)", g_gpu_deflate_s);

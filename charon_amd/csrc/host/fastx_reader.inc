@@ -91,12 +91,17 @@ bool g_gpu_text = false;
 int g_gpu_text_device = 0;
 size_t g_gpu_text_headroom = (size_t)4 << 20;  // longer than any read but the rarest (those take a fresh buffer); CHARON_GPU_TEXT_HEADROOM: test hook
 uint64_t g_gpu_text_inflated = 0;              // text bytes inflated into device memory (CHARON_TIMING)
+// CHARON_GPU_TEXT_PAIRS=1 (with CHARON_GPU_TEXT=1; paired BGZF FASTQ): each file has a reader thread of its own that fills device
+// buffers, so the counters the readers add to are guarded, and twice as many buffers exist (below)
+bool g_gpu_text_pairs = false;
+std::mutex g_reader_stat_m;
 // The buffers go round: the reader fills one while two wait in the queue, the main thread splits one and up to two batches in flight
 // refer to theirs.  All have one size, so any free one fits; more than four free ones are not kept.
 struct DevTextPool {
     std::mutex m;
     std::vector<void *> v;
     size_t bytes = 0;  // size of every pooled buffer
+    size_t keep = 4;   // free buffers kept (eight with two readers: CHARON_GPU_TEXT_PAIRS=1)
     void *take(size_t want) {
         {
             std::lock_guard<std::mutex> lk(m);
@@ -110,7 +115,7 @@ struct DevTextPool {
     void give(void *p, size_t n) {
         {
             std::lock_guard<std::mutex> lk(m);
-            if (n == bytes && v.size() < 4) { v.push_back(p); return; }
+            if (n == bytes && v.size() < keep) { v.push_back(p); return; }
         }
         (void)chn_device_free(g_gpu_text_device, p);
     }
@@ -234,8 +239,11 @@ public:
         crc.struct_size = sizeof crc; crc.expected = expected.data();
         const double t0 = omp_get_wtime();
         if (chn_inflate_run_crc(gpu_, &job, &crc) != CHN_OK) throw std::runtime_error(std::string("CHARON_GPU_TEXT: ") + chn_last_error());
-        g_gpu_inflate_s += omp_get_wtime() - t0;
-        g_gpu_text_inflated += total;
+        {
+            std::lock_guard<std::mutex> lk(g_reader_stat_m);
+            g_gpu_inflate_s += omp_get_wtime() - t0;
+            g_gpu_text_inflated += total;
+        }
         for (size_t i = 0; i < n; ++i)
             if (status[i] != 0) throw std::runtime_error("gzip read error in " + path_ + ": a BGZF member is corrupt (inflate, size or CRC32 mismatch)");
         return b;
@@ -594,7 +602,7 @@ public:
     std::shared_ptr<DevBlock> next_device(size_t max_bytes, size_t headroom) {
         const double t0 = omp_get_wtime();
         std::shared_ptr<DevBlock> b = bgzf_->fill_device(max_bytes, headroom, device_offset_);
-        g_reader_fill_s += omp_get_wtime() - t0;
+        { std::lock_guard<std::mutex> lk(g_reader_stat_m); g_reader_fill_s += omp_get_wtime() - t0; }
         if (b) device_offset_ += b->text_bytes - b->member0;
         return b;
     }

@@ -170,6 +170,20 @@ struct TextFetchScratch {
     }
 };
 
+// chn_text_pair_ids' staging (abi_text_pair.inc; allocated with the first call): the id descriptors of both files page-locked and on
+// the device, the kernel's one word on the device and page-locked
+struct TextPairScratch {
+    DevBuf d_desc, d_first;
+    PinBuf h_desc, h_first;
+    hipEvent_t ev[2] = {nullptr, nullptr};  // profiling streams: around the kernel
+    double ms = 0;
+    uint64_t calls = 0;
+    void release() {
+        d_desc.release(); d_first.release(); h_desc.release(); h_first.release();
+        for (hipEvent_t &e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    }
+};
+
 struct chn_stream {
     chn_index *idx = nullptr;
     chn_stream_cfg cfg;
@@ -228,6 +242,7 @@ struct chn_stream {
     uint64_t text_n = 0;
     TextSplitScratch tsp;
     TextFetchScratch txg;
+    TextPairScratch tpi;
 };
 
 static uint64_t pow5(unsigned e) { uint64_t p = 1; while (e--) p *= 5; return p; }

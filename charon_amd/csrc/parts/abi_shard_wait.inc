@@ -353,7 +353,13 @@ extern "C" int chn_classify_counts(chn_stream *s, uint64_t n, const uint32_t *nu
 }
 
 extern "C" int chn_stream_profile(chn_stream *s, int which, double *total_ms, uint64_t *launches, int reset) {
-    if (!s || which < 0 || which > 9) return fail(CHN_E_INVALID, "chn_stream_profile: bad argument");
+    if (!s || which < 0 || which > 11 || which == 10) return fail(CHN_E_INVALID, "chn_stream_profile: bad argument");
+    if (which == 11) {  // chn_text_pair_ids: k_pair_ids
+        if (total_ms) *total_ms = s->tpi.ms;
+        if (launches) *launches = s->tpi.calls;
+        if (reset) { s->tpi.ms = 0; s->tpi.calls = 0; }
+        return CHN_OK;
+    }
     if (which == 9) {  // chn_text_fetch: k_text_gather
         if (total_ms) *total_ms = s->txg.ms;
         if (launches) *launches = s->txg.calls;

@@ -146,6 +146,7 @@ extern "C" int chn_stream_destroy(chn_stream *s) {
     s->shx.release();
     s->tsp.release();
     s->txg.release();
+    s->tpi.release();
     delete s;
     return CHN_OK;
 }

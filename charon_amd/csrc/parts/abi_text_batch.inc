@@ -17,7 +17,11 @@ static uint64_t text_pad64(uint64_t x) { return (x + 63) & ~(uint64_t)63; }
 // words and the mean quality in sl.h_text.  A failure leaves nothing queued that matters (the copy stream drains on its own).
 static int text_pack_run(chn_stream *s, Slot &sl, const chn_text_batch *t, const char *who) {
     const std::string W(who);
-    if (t->struct_size != sizeof(chn_text_batch)) return fail(CHN_E_INVALID, W + ": bad struct_size");
+    // chn_text_batch is the form without text2 (nothing behind gzip_output is read), chn_text_batch2 the form with it
+    static_assert(offsetof(chn_text_batch2, text2) == sizeof(chn_text_batch), "text2 lies right behind the batch");
+    if (t->struct_size != sizeof(chn_text_batch) && t->struct_size != sizeof(chn_text_batch2)) return fail(CHN_E_INVALID, W + ": bad struct_size");
+    const chn_text_batch2 *t2 = t->struct_size == sizeof(chn_text_batch2) ? reinterpret_cast<const chn_text_batch2 *>(t) : nullptr;
+    const uint8_t *text2 = t2 ? t2->text2 : nullptr;
     if (t->flags & ~(CHN_TEXT_DNA5_RANKS | CHN_TEXT_ON_DEVICE)) return fail(CHN_E_INVALID, W + ": unknown flag");
     const uint64_t n = t->n_reads;
     if (n == 0) return fail(CHN_E_INVALID, "empty batch");
@@ -29,17 +33,20 @@ static int text_pack_run(chn_stream *s, Slot &sl, const chn_text_batch *t, const
     if ((t->qual2_offset == nullptr) != (t->qual2_length == nullptr)) return fail(CHN_E_INVALID, W + ": qual2_offset / qual2_length must both be set or both NULL");
     if (t->qual2_offset && !t->seq2_offset) return fail(CHN_E_INVALID, W + ": qual2_* without seq2_*");
     const bool paired = t->seq2_offset != nullptr;
+    if (text2 && !(t->flags & CHN_TEXT_ON_DEVICE)) return fail(CHN_E_INVALID, W + ": text2 needs CHN_TEXT_ON_DEVICE");
+    if (text2 && !paired) return fail(CHN_E_INVALID, W + ": text2 without seq2_*");
     const bool q1 = t->qual1_offset != nullptr, q2 = t->qual2_offset != nullptr;
     // range check of every descriptor and the segment layout (pack.py::pack_reads, HostBatch::pack)
-    const uint64_t tb = t->text_bytes;
+    const uint64_t tb = t->text_bytes, tb2 = text2 ? t2->text2_bytes : tb;  // mate 2 lies in text2 where there is one
     auto inside = [tb](uint64_t o, uint32_t l) { return o <= tb && l <= tb - o; };
+    auto inside2 = [tb2](uint64_t o, uint32_t l) { return o <= tb2 && l <= tb2 - o; };
     sl.h_toff1.resize(n);
     if (paired) sl.h_toff2.resize(n); else sl.h_toff2.clear();
     uint64_t cur = 0;
     for (uint64_t i = 0; i < n; ++i) {
         if (!inside(t->seq1_offset[i], t->seq1_length[i]) || (q1 && !inside(t->qual1_offset[i], t->qual1_length[i])) ||
-            (paired && !inside(t->seq2_offset[i], t->seq2_length[i])) || (q2 && !inside(t->qual2_offset[i], t->qual2_length[i])))
-            return fail(CHN_E_INVALID, W + ": a stretch of read " + std::to_string(i) + " reaches beyond text_bytes");
+            (paired && !inside2(t->seq2_offset[i], t->seq2_length[i])) || (q2 && !inside2(t->qual2_offset[i], t->qual2_length[i])))
+            return fail(CHN_E_INVALID, W + ": a stretch of read " + std::to_string(i) + " reaches beyond " + (text2 ? "text_bytes / text2_bytes" : "text_bytes"));
         sl.h_toff1[i] = cur; cur += text_pad64(t->seq1_length[i]);
         if (paired) { sl.h_toff2[i] = cur; cur += text_pad64(t->seq2_length[i]); }
     }
@@ -51,6 +58,7 @@ static int text_pack_run(chn_stream *s, Slot &sl, const chn_text_batch *t, const
     const bool on_device = (t->flags & CHN_TEXT_ON_DEVICE) != 0;
     int rc;
     if (on_device && (rc = device_text_check(t->text, tb, s->idx->d.device, W + ": CHN_TEXT_ON_DEVICE"))) return rc;  // before any launch
+    if (text2 && (rc = device_text_check(text2, tb2, s->idx->d.device, W + ": CHN_TEXT_ON_DEVICE: text2"))) return rc;
     hipStream_t cs = s->stream0;
     const size_t cap_b = (size_t)s->cfg.max_bases, cap_n = (size_t)s->cfg.max_reads;
     // the slot's batch buffers at the sizes submit_impl reserves for them (they never re-allocate afterwards)
@@ -92,7 +100,7 @@ static int text_pack_run(chn_stream *s, Slot &sl, const chn_text_batch *t, const
 
     TextPackArgs a;
     std::memset(&a, 0, sizeof a);
-    a.text = d_text;
+    a.text = d_text; a.text2 = text2 ? text2 : d_text;
     a.off1 = sl.d_off1.as<uint64_t>(); a.len1 = sl.d_len1.as<uint32_t>();
     a.off2 = paired ? sl.d_off2.as<uint64_t>() : nullptr; a.len2 = paired ? sl.d_len2.as<uint32_t>() : nullptr;
     a.so1 = d_o; a.qo1 = q1 ? d_o + cap_n : nullptr; a.so2 = paired ? d_o + 2 * cap_n : nullptr; a.qo2 = q2 ? d_o + 3 * cap_n : nullptr;

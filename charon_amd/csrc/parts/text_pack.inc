@@ -11,6 +11,8 @@
 // A read's letters start at any byte offset: a lane fetches the (at most five) ALIGNED dwords that cover its 16 bytes and shifts
 // them into place (v_alignbit), so it touches at most 3 bytes before and behind its stretch -- the text buffer carries 64 bytes
 // of padding at both ends.  Descriptors are range-checked on the host before the launch.
+// Two texts (chn_text_batch2.text2: the two files of paired input in two device buffers): mate 2's letters and qualities are read from
+// TextPackArgs.text2, which the host sets to `text` for a batch with one text -- one code path, the mate picks the base pointer.
 // Qualities: the lane of bases [p, p + 16) of a mate sums the quality bytes [p, p + 16) of that mate; a quality string longer than
 // its sequence (or one without a sequence) is finished by the read's first lane, byte by byte.  The partial sums of a read are
 // added up over the lanes of the wavefront that hold it (segmented shuffle reduction) before the one integer atomic per read and
@@ -18,6 +20,7 @@
 
 struct TextPackArgs {
     const uint8_t *text;                 // 4-byte aligned, 64 bytes of padding before and behind
+    const uint8_t *text2;                // the text that holds mate 2: `text` again unless the batch has two texts
     const uint64_t *off1, *off2;         // padded segment offsets in bases (off2 NULL: single-end)
     const uint32_t *len1, *len2;
     const uint64_t *so1, *so2;           // byte offsets of the letters
@@ -76,11 +79,12 @@ __global__ __launch_bounds__(256) void k_text_pack(const TextPackArgs a) {
     if (a.off2 && b >= a.off2[r]) { so = a.off2[r]; to = a.so2[r]; L = a.len2[r]; mate = 1; }
     const uint64_t p = b - so;  // a multiple of 16; >= L in the padding
     const uint32_t count = active && p < L ? (L - p < 16 ? (uint32_t)(L - p) : 16u) : 0u;
+    const uint8_t *tx = mate ? a.text2 : a.text;  // the text this lane's mate lies in
 
     uint32_t codes = 0, nb = 0, bad = 0;
     if (count) {
         uint32_t w[4];
-        text_fetch16(a.text, to + p, count, w);
+        text_fetch16(tx, to + p, count, w);
 #pragma unroll
         for (uint32_t j = 0; j < 16; ++j) {
             const uint32_t c = (w[j >> 2] >> (8 * (j & 3))) & 0xffu;
@@ -118,7 +122,7 @@ __global__ __launch_bounds__(256) void k_text_pack(const TextPackArgs a) {
     const uint32_t nq = count && p < Q ? (Q - p < 16 ? (uint32_t)(Q - p) : 16u) : 0u;
     if (nq) {
         uint32_t w[4];
-        text_fetch16(a.text, qo[r] + p, nq, w);
+        text_fetch16(tx, qo[r] + p, nq, w);
 #pragma unroll
         for (uint32_t j = 0; j < 16; ++j)
             if (j < nq) sum += (int)(signed char)((w[j >> 2] >> (8 * (j & 3))) & 0xffu) - 33;
@@ -130,7 +134,7 @@ __global__ __launch_bounds__(256) void k_text_pack(const TextPackArgs a) {
             if (!xo) continue;
             const uint32_t xq = (m ? a.ql2 : a.ql1)[r], xl = (m ? a.len2 : a.len1)[r];
             const uint64_t covered = ((uint64_t)xl + 15) & ~(uint64_t)15;
-            const uint8_t *q = a.text + xo[r];
+            const uint8_t *q = (m ? a.text2 : a.text) + xo[r];
             for (uint64_t j = covered; j < xq; ++j) sum += (int)(signed char)q[j] - 33;
         }
     }

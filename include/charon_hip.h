@@ -284,7 +284,17 @@ int chn_stream_sync(chn_stream *s);
  * buffer (only aligned dwords that hold a wanted byte).  The descriptor arrays stay HOST arrays and are checked as above; layout,
  * verdict, chain and results are those of the same bytes in host memory.  A pointer that is not device memory of that device
  * (page-locked or pageable host memory, another device) or is misaligned is CHN_E_INVALID before anything is launched, and the
- * stream stays usable.  The buffer may be reused as soon as the call returns.  Combines with CHN_TEXT_DNA5_RANKS. */
+ * stream stays usable.  The buffer may be reused as soon as the call returns.  Combines with CHN_TEXT_DNA5_RANKS.
+ * TWO TEXTS (the two files of paired input, each inflated into a device buffer of its own): chn_text_batch2 is a chn_text_batch with
+ * `text2` and `text2_bytes` appended, and the calls below take either -- struct_size says which.  With text2 != NULL mate 1 stays in
+ * `text` and seq2_offset / qual2_offset are bytes into `text2`, a second device buffer under the same contract, checked in the same
+ * way before anything is launched; every mate-2 stretch is range-checked against text2_bytes.  Layout, verdict, chain and results are
+ * those of the same bytes in one text.  CHN_E_INVALID before any launch, the stream staying usable: text2 without
+ * CHN_TEXT_ON_DEVICE, text2 without seq2_*, text2 that is not device memory of the stream's device or is misaligned, a mate-2 stretch
+ * beyond text2_bytes.  text2 == NULL is a batch with one text (text2_bytes is not looked at).
+ * struct_size: sizeof(chn_text_batch) (== offsetof(chn_text_batch2, text2)) means "no text2" and nothing behind gzip_output is read,
+ * so a caller built before text2 existed keeps working; sizeof(chn_text_batch2) is the form with text2.  Any other value is
+ * CHN_E_INVALID. */
 #define CHN_TEXT_DNA5_RANKS 1u
 #define CHN_TEXT_ON_DEVICE 2u
 typedef struct chn_text_batch {
@@ -305,6 +315,13 @@ typedef struct chn_text_batch {
     uint32_t gzip_tallies;        /* as chn_batch.gzip_tallies */
     uint32_t gzip_output;         /* as chn_batch.gzip_output */
 } chn_text_batch;
+/* the batch with a second text behind it (TWO TEXTS above): hand &t.batch to chn_text_submit / chn_text_pack with
+ * t.batch.struct_size = sizeof(chn_text_batch2) */
+typedef struct chn_text_batch2 {
+    chn_text_batch batch;
+    const uint8_t *text2;         /* NULL, or DEVICE memory that holds mate 2 (needs CHN_TEXT_ON_DEVICE and seq2_*) */
+    uint64_t text2_bytes;
+} chn_text_batch2;
 typedef struct chn_text_result {
     uint32_t struct_size;
     uint32_t has_n;               /* out: 1 if any base of the batch is N */
@@ -410,6 +427,40 @@ typedef struct chn_text_fetch_job {
 int chn_text_fetch(chn_stream *s, chn_text_fetch_job *job);   /* synchronous */
 int chn_text_fetch_host(chn_text_fetch_job *job);             /* same copy rule on the CPU, no GPU needed */
 
+/* ---- do the ids of the mates of every pair agree?  Two texts that lie in device memory (replaces the id comparison of the
+ * reference's paired loop, src/dehost_main.cpp:423-430, for a caller whose two files are device-resident) ------------------------------
+ * What a caller of the chain above uses on paired input, so that the ids of file 2 need not come down (the output names a pair by the
+ * id of mate 1): pair i has its ids at text1[id1_offset[i] .. + id1_length[i]) and text2[id2_offset[i] .. + id2_length[i]) -- what
+ * chn_text_split gave for the two files.
+ * THE RULE (the front end's): both ids lose their LAST byte, the mate number of "name/1" and "name/2": la = id1_length ? id1_length - 1
+ * : 0, lb likewise; the pair agrees if and only if la == lb and the first la bytes are equal.  The dropped byte never counts; two
+ * empty ids agree, and so do an empty id and a one-byte id.  first_mismatch is the smallest i whose ids disagree, n_pairs if there is
+ * none.  An id may have any uint32_t length.
+ * text1 and text2 follow the DEVICE TEXT CONTRACT above (they may be the same buffer) and nothing beyond it is read; the id arrays are
+ * HOST memory.
+ * chn_text_pair_ids is SYNCHRONOUS: it uploads 24 bytes per pair, runs k_pair_ids on the stream's copy stream (one lane per pair;
+ * aligned dwords that hold a wanted byte, shifted into place; the lowest disagreeing lane of a ballot, one atomicMin per wavefront)
+ * and waits once for the one word.  Batches in flight on the stream are not disturbed, but there must be fewer than three.  Its
+ * staging is the stream's, grow-only: 24 bytes per pair page-locked and on the device.  n_pairs == 0 is a no-op: first_mismatch = 0.
+ * chn_text_pair_ids_host applies the same rule source on the CPU over HOST texts (any alignment).
+ * Errors, all before anything is queued: CHN_E_INVALID for a wrong struct_size, a flag, n_pairs above CHN_TEXT_PAIR_MAX_PAIRS (2^28,
+ * the record bound of chn_text_split; no array is looked at), a NULL id array with n_pairs > 0, an id with
+ * offset + length > text1_bytes / text2_bytes (the whole id, dropped byte included; the message names pair and file), a text that is
+ * not device memory of the stream's device or misaligned, three batches in flight.  On an error first_mismatch is not defined and
+ * the stream stays usable. */
+#define CHN_TEXT_PAIR_MAX_PAIRS (1ull << 28)
+typedef struct chn_text_pair_job {
+    uint32_t struct_size, flags;                        /* flags: 0 */
+    const uint8_t *text1; uint64_t text1_bytes;         /* DEVICE, device text contract (chn_text_pair_ids_host: HOST, any alignment) */
+    const uint8_t *text2; uint64_t text2_bytes;
+    uint64_t n_pairs;
+    const uint64_t *id1_offset; const uint32_t *id1_length;   /* [n] HOST: what chn_text_split gave for file 1 */
+    const uint64_t *id2_offset; const uint32_t *id2_length;   /* [n] HOST: ... for file 2 */
+    uint64_t first_mismatch;                            /* out: smallest i whose ids disagree, n_pairs if none */
+} chn_text_pair_job;
+int chn_text_pair_ids(chn_stream *s, chn_text_pair_job *job);   /* synchronous */
+int chn_text_pair_ids_host(chn_text_pair_job *job);             /* same rule source on the CPU, no GPU needed */
+
 /* Model + call only (k_model_call) on per-read counts the caller already holds -- used for reads that the
  * Result state machine cached while the KDE models were still training (include/result.hpp:139-151,181-198)
  * and that must be classified with the models as they are later.  All pointers are HOST arrays; outputs as in
@@ -494,7 +545,9 @@ int chn_index_emplace(chn_index *idx, const uint64_t *host_values, uint64_t n_va
  *   timed with events on the copy stream; *launches = text batches packed (chn_text_submit and chn_text_pack; reset with which = 7);
  * 8 (CHN_STREAM_PROFILE streams): chn_text_split's kernels in front of its first wait (count, scan, line starts, records, id scan), timed with
  *   events on the copy stream; *launches = calls;
- * 9 (CHN_STREAM_PROFILE streams): chn_text_fetch's k_text_gather, timed with events on the copy stream; *launches = calls. */
+ * 9 (CHN_STREAM_PROFILE streams): chn_text_fetch's k_text_gather, timed with events on the copy stream; *launches = calls;
+ * 11 (CHN_STREAM_PROFILE streams): chn_text_pair_ids' k_pair_ids, timed with events on the copy stream; *launches = calls that ran
+ *   it (n_pairs > 0).  10 is not a slot: it is refused with CHN_E_INVALID like every other value. */
 int chn_stream_profile(chn_stream *s, int which, double *total_ms, uint64_t *launches, int reset);
 /* Algorithmic bytes of the last batch by SURVEY 8(d): sum over reads of ceil(L/4) + M*h*W*8 + (8 + 8C). */
 int chn_stream_last_batch_bytes(chn_stream *s, uint64_t *bytes, uint64_t *total_minimisers);

@@ -7,7 +7,11 @@ and a nanopore-like set (500 b .. 50 kb, log-uniform) -- at every -t, in alterna
     CHARON_GPU_TEXT=1      this build, text stays in device memory
 The sha256 of the TSV must be the same in every run of a file.  Prints, and writes to the output file, min-max reads/s per build and -t
 and the CHARON_TIMING lines of the last round.  "unset" must lie inside the parent's range.
-usage: python tools/gpu_text_resident_bench.py [reads=400000] [work dir] [rounds=3] [out=profiles/r09/gpu_text_resident.txt] [-t values...]"""
+usage: python tools/gpu_text_resident_bench.py [reads=400000] [work dir] [rounds=3] [out=profiles/r09/gpu_text_resident.txt] [-t values...]
+
+The paired leg (CHARON_GPU_TEXT_PAIRS=1): two BGZF files of 2 x 150 b pairs, in alternated rounds of parent, unset and
+CHARON_GPU_TEXT=1 CHARON_GPU_TEXT_PAIRS=1; the same checks, pairs/s instead of reads/s.
+usage: python tools/gpu_text_resident_bench.py pairs [pairs=4000000] [work dir] [rounds=3] [out=profiles/r10/gpu_text_pairs.txt] [-t values...]"""
 import hashlib
 import importlib.util
 import os
@@ -19,7 +23,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-SWITCHES = ("CHARON_GPU_TEXT", "CHARON_GPU_INFLATE", "CHARON_TEXT_BATCHES", "CHARON_GPU_DEFLATE")
+SWITCHES = ("CHARON_GPU_TEXT", "CHARON_GPU_TEXT_PAIRS", "CHARON_GPU_INFLATE", "CHARON_TEXT_BATCHES", "CHARON_GPU_DEFLATE")
 
 
 def write_nanopore_like(path, letters, genomes, seed=2):
@@ -42,11 +46,39 @@ def write_nanopore_like(path, letters, genomes, seed=2):
     return n
 
 
+def write_pairs(paths, n, genomes, length=150, seed=3, chunk=20000):
+    """n pairs of 2 x `length` letters: mate 1 and the reverse strand's start of a 400 b fragment, 3 % substitutions; ids p<i>/1, p<i>/2"""
+    r = np.random.default_rng(seed)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    comp = np.zeros(256, np.uint8)
+    comp[list(b"ACGT")] = list(b"TGCA")
+    gsa = [np.frombuffer(g, np.uint8) for g in genomes]
+    with open(paths[0], "wb") as f1, open(paths[1], "wb") as f2:
+        for lo in range(0, n, chunk):
+            m = min(chunk, n - lo)
+            out = ([], [])
+            for i in range(m):
+                g = gsa[(lo + i) % len(gsa)]
+                at = int(r.integers(0, len(g) - 400))
+                frag = g[at:at + 400]
+                for k, s in ((0, frag[:length].copy()), (1, comp[frag[::-1][:length]])):
+                    hit = r.random(length) < 0.03
+                    s[hit] = acgt[r.integers(0, 4, int(hit.sum()))]
+                    q = (r.integers(5, 41, length) + 33).astype(np.uint8)
+                    out[k].append(b"@p%09d/%d\n" % (lo + i, k + 1) + s.tobytes() + b"\n+\n" + q.tobytes() + b"\n")
+            f1.write(b"".join(out[0]))
+            f2.write(b"".join(out[1]))
+
+
 def main():
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 400000
+    paired = len(sys.argv) > 1 and sys.argv[1] == "pairs"
+    if paired:
+        del sys.argv[1]
+    n = int(sys.argv[1]) if len(sys.argv) > 1 else (4000000 if paired else 400000)
     work = sys.argv[2] if len(sys.argv) > 2 else "/tmp/charon_gpu_text_resident"
     rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 3
-    report = sys.argv[4] if len(sys.argv) > 4 else os.path.join(ROOT, "profiles", "r09", "gpu_text_resident.txt")
+    report = sys.argv[4] if len(sys.argv) > 4 else (os.path.join(ROOT, "profiles", "r10", "gpu_text_pairs.txt") if paired else
+                                                     os.path.join(ROOT, "profiles", "r09", "gpu_text_resident.txt"))
     threads = [int(x) for x in sys.argv[5:]] or [1, 16]
     spec = importlib.util.spec_from_file_location("cli_steady_state", os.path.join(ROOT, "tools", "cli_steady_state.py"))
     css = importlib.util.module_from_spec(spec)
@@ -76,7 +108,18 @@ def main():
         lines.append(s)
 
     files = []
-    for label in ("5 kb reads", "nanopore-like reads"):
+    unit = "pairs/s" if paired else "reads/s"
+    if paired:
+        fqs = [os.path.join(work, "pairs_%d.fastq" % k) for k in (1, 2)]
+        write_pairs(fqs, n, gs)
+        for fq in fqs:
+            subprocess.run([sys.executable, os.path.join(ROOT, "tools", "make_bgzf.py"), fq, fq + ".gz", "6", "16"], check=True)
+        say("2 x 150 b pairs: %d pairs, %.2f GB of text, %.2f GB as BGZF" % (n, sum(os.path.getsize(fq) for fq in fqs) / 1e9,
+                                                                            sum(os.path.getsize(fq + ".gz") for fq in fqs) / 1e9))
+        for fq in fqs:
+            os.remove(fq)
+        files.append(("2 x 150 b pairs", [fq + ".gz" for fq in fqs], n))
+    for label in (() if paired else ("5 kb reads", "nanopore-like reads")):
         fq = os.path.join(work, "reads%d.fastq" % len(files))
         if not files:
             css.write_fastq(fq, n, gs)
@@ -86,11 +129,13 @@ def main():
         subprocess.run([sys.executable, os.path.join(ROOT, "tools", "make_bgzf.py"), fq, fq + ".gz", "6", "16"], check=True)
         say("%s: %d reads, %.2f GB of text, %.2f GB as BGZF" % (label, count, os.path.getsize(fq) / 1e9, os.path.getsize(fq + ".gz") / 1e9))
         os.remove(fq)
-        files.append((label, fq + ".gz", count))
+        files.append((label, [fq + ".gz"], count))
 
     parent = os.environ.get("PARENT_CHARON")
     configs = (([("parent", parent, {})] if parent else []) +
-               [("unset", exe, {}), ("CHARON_GPU_INFLATE=1", exe, {"CHARON_GPU_INFLATE": "1"}), ("CHARON_GPU_TEXT=1", exe, {"CHARON_GPU_TEXT": "1"})])
+               [("unset", exe, {})] +
+               ([("CHARON_GPU_TEXT_PAIRS=1", exe, {"CHARON_GPU_TEXT": "1", "CHARON_GPU_TEXT_PAIRS": "1"})] if paired else
+                [("CHARON_GPU_INFLATE=1", exe, {"CHARON_GPU_INFLATE": "1"}), ("CHARON_GPU_TEXT=1", exe, {"CHARON_GPU_TEXT": "1"})]))
     ok = True
     for label, bgzf, count in files:
         digests, rates, timing = set(), {}, {}
@@ -103,7 +148,7 @@ def main():
                     out = os.path.join(work, "out.tsv")
                     t0 = time.time()
                     with open(out, "wb") as fo:
-                        p = subprocess.run([binary, "dehost", "--db", os.path.join(work, "bench.idx"), "-t", str(t), "--log", os.path.join(work, "c.log"), bgzf],
+                        p = subprocess.run([binary, "dehost", "--db", os.path.join(work, "bench.idx"), "-t", str(t), "--log", os.path.join(work, "c.log")] + bgzf,
                                            stdout=fo, stderr=subprocess.PIPE, env=env, timeout=900)
                     dt = time.time() - t0
                     if p.returncode:
@@ -116,19 +161,19 @@ def main():
                     digests.add(hsh.hexdigest())
                     rates.setdefault((name, t), []).append(count / dt)
                     timing[(name, t)] = [ln.strip() for ln in p.stderr.decode().splitlines() if "timing (reader" in ln or "timing (main" in ln or "timing (CHARON_GPU_TEXT" in ln]
-                    print("%s round %d %-20s -t %2d: %.2f s -> %.0f reads/s  sha256 %s" % (label, rnd, name, t, dt, count / dt, hsh.hexdigest()[:16]), flush=True)
+                    print("%s round %d %-24s -t %2d: %.2f s -> %.0f %s  sha256 %s" % (label, rnd, name, t, dt, count / dt, unit, hsh.hexdigest()[:16]), flush=True)
         say("")
         say("%s: TSV identical across runs: %s" % (label, len(digests) == 1))
         ok = ok and len(digests) == 1
         for (name, t), v in sorted(rates.items(), key=lambda kv: (kv[0][1], kv[0][0])):
-            say("%-20s -t %2d: %.0f - %.0f reads/s over %d runs" % (name, t, min(v), max(v), len(v)))
+            say("%-24s -t %2d: %.0f - %.0f %s over %d runs" % (name, t, min(v), max(v), unit, len(v)))
         for t in threads:
             if parent:
                 u, pr = rates[("unset", t)], rates[("parent", t)]
                 say("-t %d: unset inside the parent's range: %s" % (t, min(pr) <= max(u) and min(u) <= max(pr)))
             for name, _, _ in configs:
                 for ln in timing[(name, t)]:
-                    say("   %-20s -t %2d %s" % (name, t, ln))
+                    say("   %-24s -t %2d %s" % (name, t, ln))
     os.makedirs(os.path.dirname(report), exist_ok=True)
     with open(report, "w") as f:
         f.write("\n".join(lines) + "\n")
