@@ -127,6 +127,13 @@ class DeflateJob(C.Structure):
                 ("out_offset", C.c_void_p), ("out_length", C.c_void_p), ("out_used", C.c_void_p), ("crc32", C.c_void_p)]
 
 
+class ExtractJob(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("text", C.c_void_p), ("text_bytes", C.c_uint64), ("n_records", C.c_uint64),
+                ("id_offset", C.c_void_p), ("id_length", C.c_void_p), ("seq_offset", C.c_void_p), ("seq_length", C.c_void_p),
+                ("qual_offset", C.c_void_p), ("qual_length", C.c_void_p), ("out", C.c_void_p), ("out_capacity", C.c_uint64),
+                ("out_used", C.c_uint64)]
+
+
 class SynthReadsOut(C.Structure):
     _fields_ = [("bases2", C.c_void_p), ("seg1_offset", C.c_void_p), ("seg1_length", C.c_void_p), ("mean_quality", C.c_void_p),
                 ("compression", C.c_void_p), ("n_bases", C.c_uint64)]
@@ -140,7 +147,9 @@ EXPORTS = ["chn_index_create", "chn_index_upload_rows", "chn_index_device_words"
            "chn_device_free", "chn_device_download", "chn_device_malloc", "chn_device_upload", "chn_host_alloc", "chn_host_free", "chn_shard_minimise",
            "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_text_submit", "chn_text_wait", "chn_text_pack", "chn_text_split", "chn_text_split_host", "chn_text_fetch", "chn_text_fetch_host", "chn_text_pair_ids", "chn_text_pair_ids_host", "chn_device_copy", "chn_inflate_create", "chn_inflate_run",
            "chn_inflate_run_host", "chn_inflate_destroy", "chn_inflate_kernel_ms", "chn_inflate_run_crc", "chn_inflate_run_host_crc", "chn_deflate_create", "chn_deflate_run", "chn_deflate_run_host",
-           "chn_deflate_destroy", "chn_deflate_bound", "chn_deflate_kernel_ms", "chn_deflate_group_members", "chn_last_error", "chn_version"]
+           "chn_deflate_destroy", "chn_deflate_bound", "chn_deflate_kernel_ms", "chn_deflate_group_members", "chn_extract_create", "chn_extract_destroy",
+           "chn_extract_bound", "chn_extract_append_records", "chn_extract_append_bytes", "chn_extract_finish", "chn_extract_records_host",
+           "chn_extract_kernel_ms", "chn_last_error", "chn_version"]
 
 _L.chn_last_error.restype = C.c_char_p
 _L.chn_version.restype = C.c_char_p
@@ -212,6 +221,14 @@ _L.chn_deflate_destroy.argtypes = [C.c_void_p]
 _L.chn_deflate_bound.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
 _L.chn_deflate_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
 _L.chn_deflate_group_members.argtypes = [C.c_void_p, C.c_uint32]
+_L.chn_extract_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
+_L.chn_extract_destroy.argtypes = [C.c_void_p]
+_L.chn_extract_bound.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+_L.chn_extract_append_records.argtypes = [C.c_void_p, C.POINTER(ExtractJob)]
+_L.chn_extract_append_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+_L.chn_extract_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+_L.chn_extract_records_host.argtypes = [C.POINTER(ExtractJob), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+_L.chn_extract_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
 
 
 class ChnError(RuntimeError):
@@ -948,6 +965,114 @@ class Deflater:
     def destroy(self):
         if self.h:
             _L.chn_deflate_destroy(self.h)
+            self.h = None
+
+
+# ---- the records of an --extract file formed and deflated on the device (see include/charon_hip.h) ----
+def extract_job(text_ptr, nbytes, id_offset, id_length, seq_offset, seq_length, qual_offset, qual_length, out=None, out_capacity=None):
+    """the chn_extract_job of records whose id, sequence and quality string are the given ranges of the text at `text_ptr`.  `out`:
+    a uint8 array for the members (pageable or from pinned_array), out_capacity defaults to its size.  Returns (job, arrays to keep
+    alive)."""
+    keep = [np.ascontiguousarray(id_offset, np.uint64), np.ascontiguousarray(id_length, np.uint32),
+            np.ascontiguousarray(seq_offset, np.uint64), np.ascontiguousarray(seq_length, np.uint32),
+            np.ascontiguousarray(qual_offset, np.uint64), np.ascontiguousarray(qual_length, np.uint32)]
+    if any(a.ndim != 1 or a.size != keep[0].size for a in keep):
+        raise ValueError("the six descriptor arrays must be one-dimensional and of one size")
+    j = ExtractJob()
+    j.struct_size, j.flags, j.text, j.text_bytes, j.n_records = C.sizeof(ExtractJob), 0, text_ptr, int(nbytes), keep[0].size
+    j.id_offset, j.id_length, j.seq_offset, j.seq_length, j.qual_offset, j.qual_length = (a.ctypes.data for a in keep)
+    if out is not None:
+        j.out, j.out_capacity = out.ctypes.data, out.size if out_capacity is None else int(out_capacity)
+    else:
+        j.out, j.out_capacity = None, int(out_capacity or 0)
+    j.out_used = 0xDEADBEEF
+    return j, keep + [out]
+
+
+def extract_record_bytes(id_length, seq_length, qual_length):
+    """the bytes the records of these lengths have altogether: id + sequence + quality string + 6 each"""
+    return int(sum(int(np.asarray(a, np.uint64).sum(dtype=np.uint64)) for a in (id_length, seq_length, qual_length))) + 6 * len(id_length)
+
+
+def extract_records_host(data, id_offset, id_length, seq_offset, seq_length, qual_offset, qual_length, nbytes=None, capacity=None):
+    """chn_extract_records_host: the record rule the GPU runs, on the CPU, over `data` (bytes or a uint8 array).  Returns the records
+    back to back as bytes."""
+    buf = np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, np.uint8)
+    nbytes = buf.size if nbytes is None else nbytes
+    j, keep = extract_job(buf.ctypes.data if buf.size else None, nbytes, id_offset, id_length, seq_offset, seq_length, qual_offset, qual_length)
+    cap = extract_record_bytes(keep[1], keep[3], keep[5]) if capacity is None else int(capacity)
+    out = np.full(cap + 16, 0xA5, np.uint8)
+    got = C.c_uint64(0xDEADBEEF)
+    _chk(_L.chn_extract_records_host(C.byref(j), out.ctypes.data, cap, C.byref(got)))
+    assert bytes(out[got.value:]) == b"\xa5" * (out.size - got.value), "chn_extract_records_host wrote behind the records"
+    return out[:got.value].tobytes()
+
+
+class Extractor:
+    """chn_extract: ONE extract file.  Records formed out of a device text (append_records) and host bytes (append_bytes) make up the
+    file's text; every call returns the BGZF members of the whole 65 280-byte pieces that became complete, finish() the last, shorter
+    one (no end-of-file marker).  One thread at a time per object."""
+
+    def __init__(self, device=0):
+        self.h = C.c_void_p()
+        _chk(_L.chn_extract_create(device, C.byref(self.h)))
+
+    def bound(self, appended_bytes):
+        """bytes `out` must have for an append of appended_bytes now; with 0, what finish() needs"""
+        b = C.c_uint64()
+        _chk(_L.chn_extract_bound(self.h, int(appended_bytes), C.byref(b)))
+        return b.value
+
+    def _out(self, need, out, guard):
+        if out is None:
+            out = np.empty(need + 2 * guard, np.uint8)
+        out[:] = 0xA5
+        return out
+
+    def append_records(self, text_ptr, nbytes, id_offset, id_length, seq_offset, seq_length, qual_offset, qual_length, out=None, guard=16):
+        """chn_extract_append_records.  `out`: a uint8 array of at least bound + 2 * guard bytes (e.g. a pinned_array); the members go
+        to out[guard:], and the bytes around them must stay 0xA5.  Returns the members as bytes."""
+        need = self.bound(extract_record_bytes(id_length, seq_length, qual_length))
+        out = self._out(need, out, guard)
+        j, keep = extract_job(text_ptr, nbytes, id_offset, id_length, seq_offset, seq_length, qual_offset, qual_length, out[guard:], need)
+        _chk(_L.chn_extract_append_records(self.h, C.byref(j)))
+        return self._taken(out, guard, int(j.out_used), need)
+
+    def append_job(self, job):
+        """chn_extract_append_records on a prepared ExtractJob (extract_job)"""
+        _chk(_L.chn_extract_append_records(self.h, C.byref(job)))
+        return int(job.out_used)
+
+    def append_bytes(self, data, out=None, guard=16, capacity=None):
+        buf = np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, np.uint8)
+        need = self.bound(buf.size) if capacity is None else int(capacity)
+        out = self._out(need, out, guard)
+        used = C.c_uint64(0xDEADBEEF)
+        _chk(_L.chn_extract_append_bytes(self.h, buf.ctypes.data if buf.size else None, buf.size, out[guard:].ctypes.data, need, C.byref(used)))
+        return self._taken(out, guard, used.value, need)
+
+    def finish(self, out=None, guard=16, capacity=None):
+        need = self.bound(0) if capacity is None else int(capacity)
+        out = self._out(need, out, guard)
+        used = C.c_uint64(0xDEADBEEF)
+        _chk(_L.chn_extract_finish(self.h, out[guard:].ctypes.data, need, C.byref(used)))
+        return self._taken(out, guard, used.value, need)
+
+    @staticmethod
+    def _taken(out, guard, used, need):
+        assert used <= need, "more bytes than chn_extract_bound gave"
+        assert bytes(out[:guard]) == b"\xa5" * guard and bytes(out[guard + used:]) == b"\xa5" * (out.size - guard - used), \
+            "bytes outside the returned members were written"
+        return out[guard:guard + used].tobytes()
+
+    def kernel_ms(self):
+        ms = C.c_double()
+        _chk(_L.chn_extract_kernel_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def destroy(self):
+        if self.h:
+            _L.chn_extract_destroy(self.h)
             self.h = None
 
 

@@ -64,6 +64,7 @@
 #include "parts/text_split.inc"
 #include "parts/text_gather.inc"
 #include "parts/text_pair.inc"
+#include "parts/extract_records.inc"
 #include "parts/inflate_members.inc"
 #include "parts/deflate_members.inc"
 #include "parts/ef_decode.inc"
@@ -77,5 +78,6 @@
 #include "parts/abi_text_batch.inc"
 #include "parts/abi_inflate.inc"
 #include "parts/abi_deflate.inc"
+#include "parts/abi_extract.inc"
 #include "parts/abi_shardx.inc"
 #include "parts/abi_synth_memory.inc"

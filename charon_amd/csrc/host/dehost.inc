@@ -90,6 +90,8 @@ struct HostBatch {
     uint64_t text_bytes = 0;
     std::vector<uint64_t> so1, qo1, so2, qo2;
     std::vector<uint32_t> ql1, ql2;
+    std::vector<uint64_t> io1, io2;    // CHARON_GPU_EXTRACT=1: where the ids lie in dtext / dtext2, and their lengths (mate 2's ids do not come down)
+    std::vector<uint32_t> il1, il2;
     bool text_quals = false, text_from_slab = false;
     WordBuf tcopy;
     // CHARON_GPU_TEXT=1: the block's text in device memory (so1 / qo1 are offsets into it; the records' seq / qual pointers stay null
@@ -584,6 +586,17 @@ int dehost_main(DehostArguments &opt) {
             g_log.info("CHARON_GPU_TEXT=1 does not apply to " + opt.read_file + " (" + why + "; single-end BGZF FASTQ only): the run goes on without it");
         }
     }
+    if (g_gpu_extract) {
+        if (opt.category_to_extract.empty()) {
+            g_log.info("CHARON_GPU_EXTRACT=1 does nothing without --extract: the run goes on without it");
+            g_gpu_extract = false;
+        } else if (!resident && !resident_pairs) {
+            g_log.info("CHARON_GPU_EXTRACT=1 does not apply (the input is not taken by the device-resident loop of CHARON_GPU_TEXT=1): the run goes on without it");
+            g_gpu_extract = false;
+        } else {
+            g_log.info("CHARON_GPU_EXTRACT=1: the records of the extract files are formed and compressed in the memory of device " + std::to_string(g_gpu_text_device));
+        }
+    }
     std::thread reader;
     if (resident_pairs) for (int k = 0; k < 2; ++k) pair_reader[k] = std::thread(pair_reader_body, k);
     else reader = std::thread(reader_body);
@@ -780,6 +793,7 @@ int dehost_main(DehostArguments &opt) {
         uint32_t version = 0;
         uint64_t seq = 0;  // replica mode: position in input order (the ordered merge releases flights by it)
         bool resident = false;  // CHARON_GPU_TEXT=1: a text batch whose text is sub.dtext, in device memory
+        bool device_records = false;  // CHARON_GPU_EXTRACT=1: the records of its called reads are formed on the device (decided after the wait)
         // what chn_batch_wait fills (per flight: the rows of batch i are written by another thread while batch i + 1 is waited for)
         std::vector<uint32_t> nh, cnt, unq;
         std::vector<double> prob;
@@ -890,7 +904,9 @@ int dehost_main(DehostArguments &opt) {
             e.prob.assign(prob.begin() + i * C, prob.begin() + (i + 1) * C);
             e.call = call[i]; e.conf = conf[i]; e.model_version = version; e.row_version = version;
             format_row(meta, e, e.row);
-            if (opt.run_extract) {
+            if (fl.device_records) {
+                e.rec_index = (uint32_t)i;  // Result::extract notes the index; the letters stay on the device
+            } else if (opt.run_extract) {
                 e.rec_id.assign(a.id, a.id_len); e.rec_seq.assign(a.seq, a.seq_len); e.rec_qual.assign(a.qual ? a.qual : "", a.qual_len);
                 if (opt.is_paired) {
                     const RecView &b = sub.blk2.recs[sub.keep[i]];
@@ -946,9 +962,25 @@ int dehost_main(DehostArguments &opt) {
         for (long i = 0; i < (long)n; ++i) make_entry((size_t)i, entries[(size_t)i]);
         // ... then critical(add_read_to_results): serial, in input order (what the reference does at -t 1).  When a model finishes
         // training in the middle of the batch, the rest of the batch is brought up to date in one device call.
+        if (fl.device_records) result.begin_device_records();
         for (size_t i = 0; i < n; ++i) {
             if (result.models_final() && entries[i].model_version != result.current_model_version()) result.refresh(entries, i);
             result.add_read(entries[i]);
+        }
+        if (fl.device_records) {
+            // every read went through classify_read at once (the models are final and this flight's version is current): one
+            // chn_extract_append_records per extract file that got records, mate 1's out of the flight's text, mate 2's out of its second
+            Result::DeviceRecords dr;
+            dr.text[0] = sub.dtext->buf; dr.text_bytes[0] = sub.dtext->text_bytes;
+            dr.id_off[0] = sub.io1.data(); dr.id_len[0] = sub.il1.data(); dr.seq_off[0] = sub.so1.data(); dr.seq_len[0] = sub.len1.data();
+            dr.qual_off[0] = sub.qo1.data(); dr.qual_len[0] = sub.ql1.data();
+            if (sub.dtext2) {
+                dr.text[1] = sub.dtext2->buf; dr.text_bytes[1] = sub.dtext2->text_bytes;
+                dr.id_off[1] = sub.io2.data(); dr.id_len[1] = sub.il2.data(); dr.seq_off[1] = sub.so2.data(); dr.seq_len[1] = sub.len2.data();
+                dr.qual_off[1] = sub.qo2.data(); dr.qual_len[1] = sub.ql2.data();
+            }
+            struct LetGo { HostBatch &s; ~LetGo() { s.dtext.reset(); s.dtext2.reset(); } } let_go{sub};  // the blocks' buffers, once the calls have returned
+            result.append_device_records(dr);
         }
     };
 
@@ -958,6 +990,7 @@ int dehost_main(DehostArguments &opt) {
     auto recycle = [&](std::unique_ptr<Flight> &f) {
         f->parent.reset();
         f->parent2.reset();
+        f->device_records = false;
         std::lock_guard<std::mutex> lk(pool_m);
         flight_pool.push_back(std::move(f));
     };
@@ -1204,14 +1237,17 @@ int dehost_main(DehostArguments &opt) {
         HostBatch &sub = fl.sub;
         const size_t n = sub.keep.size();
         const bool tallied = sub.gz_gpu_len != 0;
+        // under --extract, sequence and quality of every read -- unless the flight's records are formed on the device (CHARON_GPU_EXTRACT=1)
+        const bool letters = opt.run_extract && !fl.device_records;
+        const bool ids2 = letters && g_gpu_extract && sub.dtext2;  // the ids of mate 2 did not come down with the split: with the letters, then
         std::vector<uint64_t> off;
         std::vector<uint32_t> len, who;
         uint64_t total = 0;
         for (size_t i = 0; i < n; ++i) {
-            if (!opt.run_extract && !(tallied && sub.gz_pending[i] && fl.gz_sizes[i] == 0)) continue;
+            if (!letters && !(tallied && sub.gz_pending[i] && fl.gz_sizes[i] == 0)) continue;
             who.push_back((uint32_t)i);
             off.push_back(sub.so1[i]); len.push_back(sub.len1[i]); total += sub.len1[i];
-            if (opt.run_extract) { off.push_back(sub.qo1[i]); len.push_back(sub.ql1[i]); total += sub.ql1[i]; }
+            if (letters) { off.push_back(sub.qo1[i]); len.push_back(sub.ql1[i]); total += sub.ql1[i]; }
         }
         if (sub.dtext2) {  // pairs over two texts: the same reads' mates out of file 2's block, behind mate 1's bytes in the arena -- one fetch per text
             std::vector<uint64_t> off2;
@@ -1219,7 +1255,8 @@ int dehost_main(DehostArguments &opt) {
             uint64_t total2 = 0;
             for (uint32_t i : who) {
                 off2.push_back(sub.so2[i]); len2.push_back(sub.len2[i]); total2 += sub.len2[i];
-                if (opt.run_extract) { off2.push_back(sub.qo2[i]); len2.push_back(sub.ql2[i]); total2 += sub.ql2[i]; }
+                if (letters) { off2.push_back(sub.qo2[i]); len2.push_back(sub.ql2[i]); total2 += sub.ql2[i]; }
+                if (ids2) { off2.push_back(sub.io2[i]); len2.push_back(sub.il2[i]); total2 += sub.il2[i]; dp_id2_bytes += sub.il2[i]; }
             }
             if (!who.empty()) {
                 sub.arena.want_pinned = true;
@@ -1239,11 +1276,12 @@ int dehost_main(DehostArguments &opt) {
                     RecView &r = sub.blk1.recs[sub.keep[i]], &m = sub.blk2.recs[sub.keep[i]];
                     r.seq = at; at += sub.len1[i];
                     m.seq = at2; at2 += sub.len2[i];
-                    if (opt.run_extract) { r.qual = at; at += sub.ql1[i]; m.qual = at2; at2 += sub.ql2[i]; }
+                    if (letters) { r.qual = at; at += sub.ql1[i]; m.qual = at2; at2 += sub.ql2[i]; }
+                    if (ids2) { m.id = at2; m.id_len = sub.il2[i]; at2 += sub.il2[i]; }
                 }
                 dt_fetched_records += who.size(); dt_fetched_bytes += total + total2;
             }
-            sub.dtext.reset(); sub.dtext2.reset();
+            if (!fl.device_records) { sub.dtext.reset(); sub.dtext2.reset(); }
             return;
         }
         if (!who.empty()) {
@@ -1259,11 +1297,11 @@ int dehost_main(DehostArguments &opt) {
             for (uint32_t i : who) {
                 RecView &r = sub.blk1.recs[sub.keep[i]];
                 r.seq = at; at += sub.len1[i];
-                if (opt.run_extract) { r.qual = at; at += sub.ql1[i]; }
+                if (letters) { r.qual = at; at += sub.ql1[i]; }
             }
             dt_fetched_records += who.size(); dt_fetched_bytes += total;
         }
-        sub.dtext.reset();
+        if (!fl.device_records) sub.dtext.reset();
     };
     // What the single-end loop and the paired loop (CHARON_GPU_TEXT_PAIRS=1) share:
     typedef std::deque<std::unique_ptr<Flight>> Flying;  // submitted, oldest first
@@ -1275,6 +1313,9 @@ int dehost_main(DehostArguments &opt) {
         std::unique_ptr<Flight> f = std::move(flying.front());
         flying.pop_front();
         finish_wait(*f, stream, t_wait);
+        // CHARON_GPU_EXTRACT=1: with final models and a current version every read of the flight is classified and written at once, so
+        // its records can be formed where the text is; otherwise (training, or a version the models have moved on from) today's path
+        f->device_records = g_gpu_extract && opt.run_extract && result.models_final() && result.current_model_version() == f->version;
         const double tk = now();
         fetch_letters(*f);
         t_fetch += now() - tk;
@@ -1361,7 +1402,7 @@ int dehost_main(DehostArguments &opt) {
         Flying flying;
         SyncOnThrow sync_on_throw{flying, stream};
         const int dev = g_gpu_text_device;
-        std::vector<uint64_t> blk_so, blk_qo;
+        std::vector<uint64_t> blk_so, blk_qo, blk_io;
         std::shared_ptr<DevBlock> prev;  // the block before, while [prev_from, prev->text_bytes) is a tail no record was made of
         uint64_t prev_from = 0;
         for (;;) {
@@ -1378,12 +1419,13 @@ int dehost_main(DehostArguments &opt) {
                 prev.reset();
             }
             const uint64_t end = blk->text_bytes;
-            blk_so.clear(); blk_qo.clear();
-            const uint64_t consumed = split_block(*blk, start, true, hb, [&](const char *id, uint32_t id_len, uint32_t seq_len, uint64_t, uint64_t so, uint64_t qo) {
+            blk_so.clear(); blk_qo.clear(); blk_io.clear();
+            const uint64_t consumed = split_block(*blk, start, true, hb, [&](const char *id, uint32_t id_len, uint32_t seq_len, uint64_t io, uint64_t so, uint64_t qo) {
                 RecView r;
                 r.id = id; r.id_len = id_len; r.seq_len = r.qual_len = seq_len;
                 hb.blk1.recs.push_back(r);
                 blk_so.push_back(so); blk_qo.push_back(qo);
+                if (g_gpu_extract) blk_io.push_back(io);
             }, nullptr);
             t_split += now() - tk;
             const size_t nrec = hb.blk1.recs.size();
@@ -1410,6 +1452,10 @@ int dehost_main(DehostArguments &opt) {
                 sub.so1.resize(n); sub.qo1.resize(n); sub.so2.clear(); sub.qo2.clear(); sub.ql2.clear();
                 for (size_t i = 0; i < n; ++i) { sub.so1[i] = blk_so[begin + sub.keep[i]]; sub.qo1[i] = blk_qo[begin + sub.keep[i]]; }
                 sub.ql1 = sub.len1;
+                if (g_gpu_extract) {
+                    sub.io1.resize(n); sub.il1.resize(n);
+                    for (size_t i = 0; i < n; ++i) { sub.io1[i] = blk_io[begin + sub.keep[i]]; sub.il1[i] = sub.blk1.recs[sub.keep[i]].id_len; }
+                }
                 sub.text_quals = true; sub.text_from_slab = false;
                 sub.dtext = blk;
                 t_pack += now() - tk;
@@ -1510,7 +1556,9 @@ int dehost_main(DehostArguments &opt) {
             // (every record of the block before is paired: its tail is [consumed, text_bytes))
             if (sd.blk) start = carry_tail(sd.blk, sd.consumed, blk, hb);
             const uint64_t end = blk->text_bytes;
-            const bool want_ids = k == 0 || opt.run_extract;  // the TSV prints the id of mate 1; mate 2's is written under --extract only
+            // the TSV prints the id of mate 1; mate 2's is written under --extract only -- and under CHARON_GPU_EXTRACT=1 out of the device
+            // text, or (a flight on the host path) fetched with its letters
+            const bool want_ids = k == 0 || (opt.run_extract && !g_gpu_extract);
             sd.id_off.clear(); sd.seq_off.clear(); sd.qual_off.clear(); sd.id_len.clear(); sd.seq_len.clear(); sd.id.clear(); sd.head = 0;
             uint64_t ids_bytes = 0;
             const uint64_t consumed = split_block(*blk, start, want_ids, hb, [&](const char *id, uint32_t id_len, uint32_t seq_len, uint64_t io, uint64_t so, uint64_t qo) {
@@ -1599,6 +1647,13 @@ int dehost_main(DehostArguments &opt) {
                     sub.so1[i] = s1.seq_off[a]; sub.qo1[i] = s1.qual_off[a]; sub.so2[i] = s2.seq_off[b]; sub.qo2[i] = s2.qual_off[b];
                 }
                 sub.ql1 = sub.len1; sub.ql2 = sub.len2;
+                if (g_gpu_extract) {
+                    sub.io1.resize(n); sub.il1.resize(n); sub.io2.resize(n); sub.il2.resize(n);
+                    for (size_t i = 0; i < n; ++i) {
+                        const size_t a = s1.head + sub.keep[i], b = s2.head + sub.keep[i];
+                        sub.io1[i] = s1.id_off[a]; sub.il1[i] = s1.id_len[a]; sub.io2[i] = s2.id_off[b]; sub.il2[i] = s2.id_len[b];
+                    }
+                }
                 sub.text_quals = true; sub.text_from_slab = false;
                 sub.dtext = s1.blk; sub.dtext2 = s2.blk;
                 t_pack += now() - tk;
@@ -1737,6 +1792,13 @@ int dehost_main(DehostArguments &opt) {
         }
         if (g_gpu_deflate) {
             std::snprintf(tb, sizeof tb, "timing (main thread, s): inside chn_deflate_run %.3f (extract files)", g_gpu_deflate_s);
+            g_log.info(tb);
+            std::fprintf(stderr, "charon: %s\n", tb);
+        }
+        if (g_gpu_extract) {
+            std::snprintf(tb, sizeof tb, "timing (CHARON_GPU_EXTRACT=1): records formed on the device %llu  bytes appended from the host %llu  compressed bytes down %llu  "
+                          "seconds in chn_extract calls %.3f", (unsigned long long)g_gpu_extract_records, (unsigned long long)g_gpu_extract_host_bytes,
+                          (unsigned long long)g_gpu_extract_down, g_gpu_extract_s);
             g_log.info(tb);
             std::fprintf(stderr, "charon: %s\n", tb);
         }

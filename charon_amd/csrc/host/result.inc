@@ -15,6 +15,7 @@ struct Entry {
     uint32_t model_version = 0;  // version of the KDE models the device used for prob/call/conf
     std::string row;             // TSV row formatted (in parallel) for model_version; empty if not formatted yet
     std::string rec_id, rec_seq, rec_qual, rec2_id, rec2_seq, rec2_qual;  // only kept when --extract is given
+    uint32_t rec_index = 0;      // CHARON_GPU_EXTRACT=1, a flight whose records are formed on the device: the read's index in the flight
     uint32_t row_version = 0;
 };
 
@@ -126,6 +127,15 @@ void format_row(const IndexMeta &meta, const Entry &e, std::string &out);
 bool g_gpu_deflate = false;
 int g_gpu_deflate_device = 0;
 double g_gpu_deflate_s = 0;  // main-thread seconds inside chn_deflate_run (CHARON_TIMING)
+// CHARON_GPU_EXTRACT=1 (with CHARON_GPU_TEXT=1, CHARON_GPU_DEFLATE=1 and --extract): every FASTQ extract file is a chn_extract on the
+// device of the resident text.  The records of a flight that is classified at once are formed there out of the flight's text
+// (chn_extract_append_records); the bytes the host forms itself -- reads handled while the models train, the host parser's after the
+// resident mode was left -- go up through chn_extract_append_bytes, in the order of add_read.  Only BGZF members come down.  The file's
+// bytes are those of flush_extract_gpu: its text cut at multiples of CHN_DEFLATE_MAX_IN from its start.  Set in main(); dehost_main
+// clears it where it does not apply.
+bool g_gpu_extract = false;
+uint64_t g_gpu_extract_records = 0, g_gpu_extract_host_bytes = 0, g_gpu_extract_down = 0;  // CHARON_TIMING
+double g_gpu_extract_s = 0;  // main-thread seconds inside the chn_extract calls
 
 // Result (include/result.hpp): cache while training, classify, print, count
 class Result {
@@ -151,7 +161,10 @@ class Result {
         bool fastq = false, wrote = false;
         std::string path, pending;
         std::vector<size_t> cuts;  // record boundaries in `pending`, about 1 MB apart
+        chn_extract *gx = nullptr;         // CHARON_GPU_EXTRACT=1: the file on the device, created with the first bytes
+        std::vector<uint32_t> picked;      // ... and the reads of the flight at hand that go to this file (Entry::rec_index)
     };
+    bool picking_ = false;  // CHARON_GPU_EXTRACT=1: between begin_device_records and append_device_records, extract() notes indices
     std::map<uint8_t, std::vector<ExtractFile>> extract_;
     chn_deflate *deflater_ = nullptr;  // CHARON_GPU_DEFLATE=1: created with the first piece
     std::vector<uint8_t> deflated_;
@@ -202,7 +215,36 @@ class Result {
         x.wrote = true;
         x.pending.erase(0, take);
     }
+    bool on_device(const ExtractFile &x) const { return g_gpu_extract && x.fastq; }
+    void gx_write(ExtractFile &x, uint64_t used) {
+        g_gpu_extract_down += used;
+        if (used && std::fwrite(deflated_.data(), 1, used, x.f) != used) throw std::runtime_error("write to extract file " + x.path + " failed");
+        if (used) x.wrote = true;
+    }
+    // room in deflated_ for what an append of `bytes` (0: chn_extract_finish) may return
+    void gx_room(ExtractFile &x, uint64_t bytes) {
+        uint64_t bound = 0;
+        bool ok = x.gx || chn_extract_create(g_gpu_deflate_device, &x.gx) == CHN_OK;
+        ok = ok && chn_extract_bound(x.gx, bytes, &bound) == CHN_OK;
+        if (!ok) throw std::runtime_error("compressing the extract file " + x.path + " failed: " + chn_last_error());
+        if (deflated_.size() < bound) deflated_.resize(bound);
+    }
+    // CHARON_GPU_EXTRACT=1: the bytes the host formed, behind everything appended so far
+    void flush_extract_gx(ExtractFile &x) {
+        x.cuts.clear();
+        if (x.pending.empty()) return;
+        gx_room(x, x.pending.size());
+        uint64_t used = 0;
+        const double t0 = omp_get_wtime();
+        const bool ok = chn_extract_append_bytes(x.gx, reinterpret_cast<const uint8_t *>(x.pending.data()), x.pending.size(), deflated_.data(), deflated_.size(), &used) == CHN_OK;
+        g_gpu_extract_s += omp_get_wtime() - t0;
+        if (!ok) throw std::runtime_error("compressing the extract file " + x.path + " failed: " + chn_last_error());
+        g_gpu_extract_host_bytes += x.pending.size();
+        x.pending.clear();
+        gx_write(x, used);
+    }
     void flush_extract(ExtractFile &x) {
+        if (on_device(x)) { flush_extract_gx(x); return; }
         if (g_gpu_deflate) { flush_extract_gpu(x, false); return; }
         if (x.pending.empty()) return;
         std::vector<size_t> b(1, 0);
@@ -228,7 +270,22 @@ class Result {
     void close_extract(ExtractFile &x) {
         if (!x.f) return;
         if (g_gpu_deflate) {  // every file ends with BGZF's end-of-file marker; one that got no record is the marker alone
-            flush_extract_gpu(x, true);
+            if (on_device(x)) {
+                flush_extract_gx(x);
+                if (x.gx) {
+                    gx_room(x, 0);
+                    uint64_t used = 0;
+                    const double t0 = omp_get_wtime();
+                    const bool done = chn_extract_finish(x.gx, deflated_.data(), deflated_.size(), &used) == CHN_OK;
+                    g_gpu_extract_s += omp_get_wtime() - t0;
+                    if (!done) throw std::runtime_error("compressing the extract file " + x.path + " failed: " + chn_last_error());
+                    gx_write(x, used);
+                    (void)chn_extract_destroy(x.gx);
+                    x.gx = nullptr;
+                }
+            } else {
+                flush_extract_gpu(x, true);
+            }
             static const unsigned char eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
             const bool ok = std::fwrite(eof, 1, sizeof eof, x.f) == sizeof eof;
             if (std::fclose(x.f) != 0 || !ok) { x.f = nullptr; throw std::runtime_error("write to extract file " + x.path + " failed"); }
@@ -268,6 +325,10 @@ class Result {
     void extract(const Entry &e) {  // extract_read / extract_paired_read (include/result.hpp:118-128)
         auto it = extract_.find(e.call);
         if (it == extract_.end()) return;
+        if (picking_) {  // the record is formed on the device at the end of the flight
+            for (ExtractFile &x : it->second) x.picked.push_back(e.rec_index);
+            return;
+        }
         write_record(it->second[0], e.rec_id, e.rec_seq, e.rec_qual);
         if (it->second.size() > 1) write_record(it->second[1], e.rec2_id, e.rec2_seq, e.rec2_qual);
     }
@@ -363,8 +424,54 @@ public:
         for (auto &kv : extract_)
             for (ExtractFile &x : kv.second) {
                 try { close_extract(x); } catch (...) { if (x.f) std::fclose(x.f); x.f = nullptr; }
+                if (x.gx) (void)chn_extract_destroy(x.gx);
             }
         if (deflater_) (void)chn_deflate_destroy(deflater_);
+    }
+    // CHARON_GPU_EXTRACT=1: the texts and descriptor arrays of a resident flight, by the read's index in the flight; [0] mate 1 / the
+    // read, [1] mate 2 (paired input: the second file of a category takes its records from there)
+    struct DeviceRecords {
+        const uint8_t *text[2] = {nullptr, nullptr};
+        uint64_t text_bytes[2] = {0, 0};
+        const uint64_t *id_off[2] = {nullptr, nullptr}, *seq_off[2] = {nullptr, nullptr}, *qual_off[2] = {nullptr, nullptr};
+        const uint32_t *id_len[2] = {nullptr, nullptr}, *seq_len[2] = {nullptr, nullptr}, *qual_len[2] = {nullptr, nullptr};
+    };
+    // every add_read up to append_device_records is of a flight whose records are formed on the device (the models are final, so
+    // each goes through classify_read at once and in order)
+    void begin_device_records() { picking_ = true; }
+    void append_device_records(const DeviceRecords &dr) {
+        picking_ = false;
+        std::vector<uint64_t> o[3];
+        std::vector<uint32_t> l[3];
+        for (auto &kv : extract_)
+            for (size_t m = 0; m < kv.second.size(); ++m) {
+                ExtractFile &x = kv.second[m];
+                if (x.picked.empty()) continue;
+                struct Clear { std::vector<uint32_t> &v; ~Clear() { v.clear(); } } clear{x.picked};
+                const size_t k = m ? 1 : 0, n = x.picked.size();
+                flush_extract_gx(x);  // what the host formed before this flight comes first
+                uint64_t bytes = 0;
+                for (int a = 0; a < 3; ++a) { o[a].resize(n); l[a].resize(n); }
+                for (size_t i = 0; i < n; ++i) {
+                    const uint32_t r = x.picked[i];
+                    o[0][i] = dr.id_off[k][r]; l[0][i] = dr.id_len[k][r]; o[1][i] = dr.seq_off[k][r]; l[1][i] = dr.seq_len[k][r];
+                    o[2][i] = dr.qual_off[k][r]; l[2][i] = dr.qual_len[k][r];
+                    bytes += (uint64_t)l[0][i] + l[1][i] + l[2][i] + 6;
+                }
+                gx_room(x, bytes);
+                chn_extract_job job;
+                std::memset(&job, 0, sizeof job);
+                job.struct_size = sizeof job; job.text = dr.text[k]; job.text_bytes = dr.text_bytes[k]; job.n_records = n;
+                job.id_offset = o[0].data(); job.id_length = l[0].data(); job.seq_offset = o[1].data(); job.seq_length = l[1].data();
+                job.qual_offset = o[2].data(); job.qual_length = l[2].data();
+                job.out = deflated_.data(); job.out_capacity = deflated_.size();
+                const double t0 = omp_get_wtime();
+                const bool ok = chn_extract_append_records(x.gx, &job) == CHN_OK;
+                g_gpu_extract_s += omp_get_wtime() - t0;
+                if (!ok) throw std::runtime_error("forming the records of the extract file " + x.path + " on the device failed: " + chn_last_error());
+                g_gpu_extract_records += n;
+                gx_write(x, job.out_used);
+            }
     }
     Result(const Result &) = delete;
     Result &operator=(const Result &) = delete;

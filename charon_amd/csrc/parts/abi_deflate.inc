@@ -149,45 +149,23 @@ extern "C" int chn_deflate_group_members(chn_deflate *h, uint32_t members) {
 // the results of a group in one block: out_off[n + 1] (64-bit), out_len[n], crc[n]
 static size_t deflate_res_bytes(uint64_t n) { return (size_t)(n + 1) * 8 + (size_t)n * 8; }
 
-// pack, upload and compress members [first, first + n) in set `st`, and start the download of their sizes
-static int deflate_issue(chn_deflate *h, DeflateSet &st, const chn_deflate_job *j, uint64_t first, uint64_t n) {
-    uint64_t in_bytes = 0, in_total = 0;
-    for (uint64_t i = first; i < first + n; ++i) { in_bytes += ((uint64_t)j->in_length[i] + 15) & ~15ull; in_total += j->in_length[i]; }
-    st.first = first; st.n = n;
+// compress the n pieces that lie in device memory at d_in + in_off[k] (in_off / in_len: d_desc, uploaded on s_up like the pieces and
+// the zeroed cursor, in front of the event st.up that the caller has recorded) in set `st`, and start the download of their sizes.
+// `d_in` is the set's own staging (chn_deflate_run) or a buffer of the caller's that is already in place (chn_extract).
+static int deflate_launch(chn_deflate *h, DeflateSet &st, const uint8_t *d_in, uint64_t n, uint64_t in_total, uint32_t flags) {
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(n, (uint64_t)std::max(1, h->cus) * 2);
-    const size_t desc_bytes = (size_t)n * 12, res_bytes = deflate_res_bytes(n);
-    const size_t packed_bytes = (size_t)deflate_bound(n, in_total, j->flags) + 16;
-    int rc;
-    if ((rc = st.h_desc.ensure(desc_bytes)) || (rc = st.d_desc.ensure(st.h_desc.cap)) ||
-        (rc = st.h_in.ensure((size_t)in_bytes + 16 + (st.h_in.cap < in_bytes + 16 ? in_bytes / 4 : 0))) || (rc = st.d_in.ensure(st.h_in.cap)) ||
-        (rc = st.d_slots.ensure((size_t)n * DFL_SLOT + 16)) || (rc = st.h_res.ensure(res_bytes)) || (rc = st.d_res.ensure(st.h_res.cap)) ||
-        (rc = st.d_packed.ensure(packed_bytes + (st.d_packed.cap < packed_bytes ? packed_bytes / 4 : 0))) || (rc = st.d_cursor.ensure(16)) ||
-        (rc = h->d_tokens.ensure((size_t)std::max(1, h->cus) * 2 * DFL_MAX_IN * 4)))  // (for the widest grid at once: a kernel may be running on it)
-        return rc;
-    uint64_t *in_off = st.h_desc.as<uint64_t>();
-    uint32_t *in_len = reinterpret_cast<uint32_t *>(in_off + n);
-    uint8_t *stage = st.h_in.as<uint8_t>();
-    uint64_t ip = 0;
-    for (uint64_t k = 0; k < n; ++k) {
-        const uint64_t i = first + k;
-        in_off[k] = ip; in_len[k] = j->in_length[i];
-        if (j->in_length[i]) std::memcpy(stage + ip, j->in + j->in_offset[i], j->in_length[i]);
-        ip += ((uint64_t)j->in_length[i] + 15) & ~15ull;
-    }
-    HIPCHK(hipMemcpyAsync(st.d_in.p, stage, ip + 16, hipMemcpyHostToDevice, h->s_up));
-    HIPCHK(hipMemcpyAsync(st.d_desc.p, st.h_desc.p, desc_bytes, hipMemcpyHostToDevice, h->s_up));
-    HIPCHK(hipMemsetAsync(st.d_cursor.p, 0, 4, h->s_up));
-    HIPCHK(hipEventRecord(st.up, h->s_up));
+    const size_t res_bytes = deflate_res_bytes(n);
+    const size_t packed_bytes = (size_t)deflate_bound(n, in_total, flags) + 16;
     HIPCHK(hipStreamWaitEvent(h->s_run, st.up, 0));
     DeflateArgs a;
-    a.in = st.d_in.as<uint8_t>();
+    a.in = d_in;
     a.in_off = st.d_desc.as<uint64_t>();
     a.in_len = reinterpret_cast<const uint32_t *>(a.in_off + n);
     a.slots = st.d_slots.as<uint8_t>();
     uint64_t *d_off = st.d_res.as<uint64_t>();
     a.out_len = reinterpret_cast<uint32_t *>(d_off + n + 1); a.crc = a.out_len + n;
     a.tokens = h->d_tokens.as<uint32_t>(); a.cursor = st.d_cursor.as<uint32_t>();
-    a.n = (uint32_t)n; a.flags = j->flags;
+    a.n = (uint32_t)n; a.flags = flags;
     // a looping grid: two workgroups of one wavefront fit a CU's LDS; the cursor hands out members
     HIPCHK(hipEventRecord(st.k0, h->s_run));
     hipLaunchKernelGGL(k_deflate_members, dim3(blocks), dim3(WAVE), 0, h->s_run, a);
@@ -203,6 +181,46 @@ static int deflate_issue(chn_deflate *h, DeflateSet &st, const chn_deflate_job *
     HIPCHK(hipEventRecord(st.sized, h->s_down));
     st.busy = true;
     return CHN_OK;
+}
+
+// the set's buffers for n pieces of in_total bytes altogether, all but the staging of the pieces themselves
+static int deflate_ensure(chn_deflate *h, DeflateSet &st, uint64_t n, uint64_t in_total, uint32_t flags) {
+    const size_t desc_bytes = (size_t)n * 12, res_bytes = deflate_res_bytes(n);
+    const size_t packed_bytes = (size_t)deflate_bound(n, in_total, flags) + 16;
+    int rc;
+    if ((rc = st.h_desc.ensure(desc_bytes)) || (rc = st.d_desc.ensure(st.h_desc.cap)) ||
+        (rc = st.d_slots.ensure((size_t)n * DFL_SLOT + 16)) || (rc = st.h_res.ensure(res_bytes)) || (rc = st.d_res.ensure(st.h_res.cap)) ||
+        (rc = st.d_packed.ensure(packed_bytes + (st.d_packed.cap < packed_bytes ? packed_bytes / 4 : 0))) || (rc = st.d_cursor.ensure(16)) ||
+        (rc = h->d_tokens.ensure((size_t)std::max(1, h->cus) * 2 * DFL_MAX_IN * 4)))  // (for the widest grid at once: a kernel may be running on it)
+        return rc;
+    return CHN_OK;
+}
+
+// pack, upload and compress members [first, first + n) in set `st`, and start the download of their sizes
+static int deflate_issue(chn_deflate *h, DeflateSet &st, const chn_deflate_job *j, uint64_t first, uint64_t n) {
+    uint64_t in_bytes = 0, in_total = 0;
+    for (uint64_t i = first; i < first + n; ++i) { in_bytes += ((uint64_t)j->in_length[i] + 15) & ~15ull; in_total += j->in_length[i]; }
+    st.first = first; st.n = n;
+    const size_t desc_bytes = (size_t)n * 12;
+    int rc;
+    if ((rc = deflate_ensure(h, st, n, in_total, j->flags)) ||
+        (rc = st.h_in.ensure((size_t)in_bytes + 16 + (st.h_in.cap < in_bytes + 16 ? in_bytes / 4 : 0))) || (rc = st.d_in.ensure(st.h_in.cap)))
+        return rc;
+    uint64_t *in_off = st.h_desc.as<uint64_t>();
+    uint32_t *in_len = reinterpret_cast<uint32_t *>(in_off + n);
+    uint8_t *stage = st.h_in.as<uint8_t>();
+    uint64_t ip = 0;
+    for (uint64_t k = 0; k < n; ++k) {
+        const uint64_t i = first + k;
+        in_off[k] = ip; in_len[k] = j->in_length[i];
+        if (j->in_length[i]) std::memcpy(stage + ip, j->in + j->in_offset[i], j->in_length[i]);
+        ip += ((uint64_t)j->in_length[i] + 15) & ~15ull;
+    }
+    HIPCHK(hipMemcpyAsync(st.d_in.p, stage, ip + 16, hipMemcpyHostToDevice, h->s_up));
+    HIPCHK(hipMemcpyAsync(st.d_desc.p, st.h_desc.p, desc_bytes, hipMemcpyHostToDevice, h->s_up));
+    HIPCHK(hipMemsetAsync(st.d_cursor.p, 0, 4, h->s_up));
+    HIPCHK(hipEventRecord(st.up, h->s_up));
+    return deflate_launch(h, st, st.d_in.as<uint8_t>(), n, in_total, j->flags);
 }
 
 // wait for the group in set `st`, download its members behind `*used` and hand offsets, sizes and CRCs to the caller

@@ -647,6 +647,58 @@ int chn_deflate_kernel_ms(chn_deflate *h, double *ms);
 /* testing and measurement aid: at most `members` (1 .. 1024, the default) members in one group of chn_deflate_run's pipeline */
 int chn_deflate_group_members(chn_deflate *h, uint32_t members);
 
+/* ---- the records of an --extract file formed and deflated on the device (no reference counterpart: the reference forms them on the
+ * CPU and writes through zlib's gzFile) ------------------------------------------------------------------------------------------
+ * What a caller of the device-resident chain (chn_inflate_run's CHN_INFLATE_OUT_DEVICE, chn_text_split, CHN_TEXT_ON_DEVICE) uses to
+ * write reads out as BGZF FASTQ without bringing their letters down: a chn_extract stands for ONE output file.
+ * THE RECORD RULE: record i is  '@' id '\n' SEQ '\n' '+' '\n' qual '\n'  with id = text[id_offset[i] .. + id_length[i]) and
+ * qual = text[qual_offset[i] .. + qual_length[i]) as they stand and SEQ = text[seq_offset[i] .. + seq_length[i]) with every byte
+ * through the front end's letter map: A C G T in either case become upper case, U / u become T, every other byte (the IUPAC letters;
+ * a byte that is no letter cannot be in a read chn_text_submit accepted) becomes N.  It has id_length + seq_length + qual_length + 6
+ * bytes; the records of a job follow one another in the order given.
+ * THE FILE'S TEXT is everything appended to the handle, in order -- records formed on the device by chn_extract_append_records from
+ * a device text, and host bytes the caller formed itself, uploaded by chn_extract_append_bytes.  It is cut into pieces of
+ * CHN_DEFLATE_MAX_IN bytes at multiples of that size from the file's start, whatever the appends were.  Every append writes its bytes
+ * behind the handle's pending tail in device memory, compresses every whole piece that is there then (k_deflate_members under
+ * CHN_DEFLATE_BGZF, reading the pending buffer in place), brings the members down back to back into `out` (*out_used bytes, possibly
+ * 0) and keeps the fewer than CHN_DEFLATE_MAX_IN bytes behind the last piece as the new tail.  chn_extract_finish compresses a
+ * non-empty tail as one last, shorter member and leaves the handle empty, ready for another file; it writes NO end-of-file marker.
+ * THE PIN: for any sequence of appends, the bytes the handle returned, chn_extract_finish's included, are those of chn_deflate_run_host
+ * under CHN_DEFLATE_BGZF over the file's text cut at multiples of CHN_DEFLATE_MAX_IN.
+ * chn_extract_bound gives the bytes `out` must have for an append of appended_bytes to the handle as it stands (appended_bytes is the
+ * sum of the records' lengths, or n); with appended_bytes == 0, what chn_extract_finish needs.
+ * `text` follows the DEVICE TEXT CONTRACT (device memory of the handle's device, 16-byte aligned, readable up to text_bytes rounded up
+ * to 16) and nothing beyond it is read; the descriptor arrays, `bytes` and `out` are HOST memory, `out` pageable or page-locked.
+ * Every call is SYNCHRONOUS: when it returns, nothing of it is queued and `text` is no longer needed.  A chn_extract owns its streams,
+ * its staging and a grow-only device buffer of pending text; ONE thread at a time per handle, no chn_stream.  n_records == 0 and
+ * n == 0 are no-ops (out_used = 0).
+ * chn_extract_records_host applies the record rule on the CPU over HOST text of any alignment: the records of `job` (its out fields
+ * are not looked at) back to back into text_out, *bytes their total; CHN_E_CAPACITY if capacity is below it.
+ * Errors, all before anything is queued, the handle staying usable and nothing appended: CHN_E_INVALID for a wrong struct_size, a
+ * flag, a NULL descriptor array with n_records > 0, an id, sequence or quality string that ends behind text_bytes (the message names
+ * the record), text that is not device memory of the handle's device or misaligned; CHN_E_CAPACITY for out_capacity below
+ * chn_extract_bound for this append (the message names the bytes needed).  After CHN_E_HIP the handle can only be destroyed. */
+typedef struct chn_extract chn_extract;
+typedef struct chn_extract_job {
+    uint32_t struct_size, flags;                 /* flags: 0 */
+    const uint8_t *text; uint64_t text_bytes;    /* DEVICE, device text contract (chn_extract_records_host: HOST) */
+    uint64_t n_records;
+    const uint64_t *id_offset;   const uint32_t *id_length;    /* [n] HOST: what chn_text_split gave */
+    const uint64_t *seq_offset;  const uint32_t *seq_length;
+    const uint64_t *qual_offset; const uint32_t *qual_length;
+    uint8_t *out; uint64_t out_capacity;         /* HOST, pageable or page-locked: the BGZF members of the whole pieces */
+    uint64_t out_used;                           /* out */
+} chn_extract_job;
+int chn_extract_create(int32_t device, chn_extract **out);
+int chn_extract_destroy(chn_extract *h);
+int chn_extract_bound(const chn_extract *h, uint64_t appended_bytes, uint64_t *out_bytes);
+int chn_extract_append_records(chn_extract *h, chn_extract_job *job);     /* synchronous */
+int chn_extract_append_bytes(chn_extract *h, const uint8_t *bytes, uint64_t n, uint8_t *out, uint64_t out_capacity, uint64_t *out_used);
+int chn_extract_finish(chn_extract *h, uint8_t *out, uint64_t out_capacity, uint64_t *out_used);
+int chn_extract_records_host(chn_extract_job *job, uint8_t *text_out, uint64_t capacity, uint64_t *bytes);
+/* measurement aid: device time of the kernels of the handle's last call (k_extract_records and the compressor's), from events around them */
+int chn_extract_kernel_ms(chn_extract *h, double *ms);
+
 /* ---- synthetic workload fabrication on the device (bench / tests; no reference counterpart) ---------- */
 /* Measurement aid: the rate this device sustains for NOTHING BUT the index's probe pattern -- independent uniformly random row
  * fetches of 8 * bin_words bytes from THIS index's words (one load per thread in flight, 32 wavefronts per CU, `nt` cache policy if

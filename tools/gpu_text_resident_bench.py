@@ -11,7 +11,12 @@ usage: python tools/gpu_text_resident_bench.py [reads=400000] [work dir] [rounds
 
 The paired leg (CHARON_GPU_TEXT_PAIRS=1): two BGZF files of 2 x 150 b pairs, in alternated rounds of parent, unset and
 CHARON_GPU_TEXT=1 CHARON_GPU_TEXT_PAIRS=1; the same checks, pairs/s instead of reads/s.
-usage: python tools/gpu_text_resident_bench.py pairs [pairs=4000000] [work dir] [rounds=3] [out=profiles/r10/gpu_text_pairs.txt] [-t values...]"""
+usage: python tools/gpu_text_resident_bench.py pairs [pairs=4000000] [work dir] [rounds=3] [out=profiles/r10/gpu_text_pairs.txt] [-t values...]
+
+The extract leg (CHARON_GPU_EXTRACT=1): `charon dehost --extract all` on the 7d file, in alternated rounds of the parent build
+and this build with CHARON_GPU_TEXT=1 CHARON_GPU_DEFLATE=1, and this build with CHARON_GPU_EXTRACT=1 added.  The TSV and every extract
+file must have one sha256 across the three.
+usage: python tools/gpu_text_resident_bench.py extract [reads=400000] [work dir] [rounds=3] [out=profiles/r11/gpu_extract.txt] [-t values...]"""
 import hashlib
 import importlib.util
 import os
@@ -23,7 +28,15 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-SWITCHES = ("CHARON_GPU_TEXT", "CHARON_GPU_TEXT_PAIRS", "CHARON_GPU_INFLATE", "CHARON_TEXT_BATCHES", "CHARON_GPU_DEFLATE")
+SWITCHES = ("CHARON_GPU_TEXT", "CHARON_GPU_TEXT_PAIRS", "CHARON_GPU_INFLATE", "CHARON_TEXT_BATCHES", "CHARON_GPU_DEFLATE", "CHARON_GPU_EXTRACT")
+
+
+def sha256_of(path):
+    hsh = hashlib.sha256()
+    with open(path, "rb") as fi:
+        for chunk in iter(lambda: fi.read(1 << 24), b""):
+            hsh.update(chunk)
+    return hsh.hexdigest()
 
 
 def write_nanopore_like(path, letters, genomes, seed=2):
@@ -72,12 +85,14 @@ def write_pairs(paths, n, genomes, length=150, seed=3, chunk=20000):
 
 def main():
     paired = len(sys.argv) > 1 and sys.argv[1] == "pairs"
-    if paired:
+    extract = len(sys.argv) > 1 and sys.argv[1] == "extract"
+    if paired or extract:
         del sys.argv[1]
     n = int(sys.argv[1]) if len(sys.argv) > 1 else (4000000 if paired else 400000)
     work = sys.argv[2] if len(sys.argv) > 2 else "/tmp/charon_gpu_text_resident"
     rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 3
     report = sys.argv[4] if len(sys.argv) > 4 else (os.path.join(ROOT, "profiles", "r10", "gpu_text_pairs.txt") if paired else
+                                                     os.path.join(ROOT, "profiles", "r11", "gpu_extract.txt") if extract else
                                                      os.path.join(ROOT, "profiles", "r09", "gpu_text_resident.txt"))
     threads = [int(x) for x in sys.argv[5:]] or [1, 16]
     spec = importlib.util.spec_from_file_location("cli_steady_state", os.path.join(ROOT, "tools", "cli_steady_state.py"))
@@ -119,7 +134,7 @@ def main():
         for fq in fqs:
             os.remove(fq)
         files.append(("2 x 150 b pairs", [fq + ".gz" for fq in fqs], n))
-    for label in (() if paired else ("5 kb reads", "nanopore-like reads")):
+    for label in (() if paired else ("5 kb reads", ) if extract else ("5 kb reads", "nanopore-like reads")):
         fq = os.path.join(work, "reads%d.fastq" % len(files))
         if not files:
             css.write_fastq(fq, n, gs)
@@ -132,7 +147,10 @@ def main():
         files.append((label, [fq + ".gz"], count))
 
     parent = os.environ.get("PARENT_CHARON")
-    configs = (([("parent", parent, {})] if parent else []) +
+    base = {"CHARON_GPU_TEXT": "1", "CHARON_GPU_DEFLATE": "1"}
+    configs = ([("parent, TEXT + DEFLATE", parent, base)] if parent else []) + [("TEXT + DEFLATE", exe, base), ("CHARON_GPU_EXTRACT=1", exe, dict(base, CHARON_GPU_EXTRACT="1"))]
+    more = ["--extract", "all", "-p", os.path.join(work, "ex")] if extract else []
+    configs = configs if extract else (([("parent", parent, {})] if parent else []) +
                [("unset", exe, {})] +
                ([("CHARON_GPU_TEXT_PAIRS=1", exe, {"CHARON_GPU_TEXT": "1", "CHARON_GPU_TEXT_PAIRS": "1"})] if paired else
                 [("CHARON_GPU_INFLATE=1", exe, {"CHARON_GPU_INFLATE": "1"}), ("CHARON_GPU_TEXT=1", exe, {"CHARON_GPU_TEXT": "1"})]))
@@ -148,27 +166,28 @@ def main():
                     out = os.path.join(work, "out.tsv")
                     t0 = time.time()
                     with open(out, "wb") as fo:
-                        p = subprocess.run([binary, "dehost", "--db", os.path.join(work, "bench.idx"), "-t", str(t), "--log", os.path.join(work, "c.log")] + bgzf,
+                        p = subprocess.run([binary, "dehost", "--db", os.path.join(work, "bench.idx"), "-t", str(t), "--log", os.path.join(work, "c.log")] + more + bgzf,
                                            stdout=fo, stderr=subprocess.PIPE, env=env, timeout=900)
                     dt = time.time() - t0
                     if p.returncode:
                         sys.exit("charon dehost failed (%s): %s" % (name, p.stderr.decode()[-800:]))
-                    hsh = hashlib.sha256()
-                    with open(out, "rb") as fi:
-                        for chunk in iter(lambda: fi.read(1 << 24), b""):
-                            hsh.update(chunk)
+                    digest = sha256_of(out)
                     os.remove(out)
-                    digests.add(hsh.hexdigest())
+                    for x in sorted(os.listdir(work)) if extract else ():  # the extract files: <prefix>_<category>.fastq.gz
+                        if x.startswith("ex_") and x.endswith(".gz"):
+                            digest += " " + x + ":" + sha256_of(os.path.join(work, x))
+                            os.remove(os.path.join(work, x))
+                    digests.add(digest)
                     rates.setdefault((name, t), []).append(count / dt)
-                    timing[(name, t)] = [ln.strip() for ln in p.stderr.decode().splitlines() if "timing (reader" in ln or "timing (main" in ln or "timing (CHARON_GPU_TEXT" in ln]
-                    print("%s round %d %-24s -t %2d: %.2f s -> %.0f %s  sha256 %s" % (label, rnd, name, t, dt, count / dt, unit, hsh.hexdigest()[:16]), flush=True)
+                    timing[(name, t)] = [ln.strip() for ln in p.stderr.decode().splitlines() if "timing (reader" in ln or "timing (main" in ln or "timing (CHARON_GPU_" in ln]
+                    print("%s round %d %-24s -t %2d: %.2f s -> %.0f %s  sha256 %s" % (label, rnd, name, t, dt, count / dt, unit, digest[:16]), flush=True)
         say("")
-        say("%s: TSV identical across runs: %s" % (label, len(digests) == 1))
+        say("%s: TSV%s identical across runs: %s" % (label, " and extract files" if extract else "", len(digests) == 1))
         ok = ok and len(digests) == 1
         for (name, t), v in sorted(rates.items(), key=lambda kv: (kv[0][1], kv[0][0])):
             say("%-24s -t %2d: %.0f - %.0f %s over %d runs" % (name, t, min(v), max(v), unit, len(v)))
         for t in threads:
-            if parent:
+            if parent and not extract:
                 u, pr = rates[("unset", t)], rates[("parent", t)]
                 say("-t %d: unset inside the parent's range: %s" % (t, min(pr) <= max(u) and min(u) <= max(pr)))
             for name, _, _ in configs:
