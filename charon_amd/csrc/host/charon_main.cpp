@@ -27,6 +27,7 @@
 #include <mutex>
 #include <thread>
 #include <cmath>
+#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -80,6 +81,7 @@ bool g_gzip_emulator = true;
 #include "fastx_reader.inc"
 #include "result.inc"
 #include "ordered_merge.inc"
+#include "host_batch.inc"
 #include "dehost.inc"
 #include "index_builder.inc"
 

@@ -1,388 +1,6 @@
-// dehost.inc -- host batches (2-bit packing, quality, gzip column), reader queue, reference-file self-check, dehost_main (src/dehost_main.cpp:314-550)
+// dehost.inc -- reference-file self-check, dehost_main (src/dehost_main.cpp:314-550)
 // Part of the single translation unit charon_main.cpp (included inside its anonymous namespace, in order); not a
 // stand-alone header.
-
-// ---------------------------------------------------------------------------------------------------
-// batching: pack reads into the 2-bit layout of include/charon_hip.h
-// ---------------------------------------------------------------------------------------------------
-#if defined(__x86_64__)
-const bool g_has_avx2 = __builtin_cpu_supports("avx2");
-#endif
-// Zero-filled array of 32-bit words; page-locked on request (chn_host_alloc), so that chn_batch_submit's upload of it is an asynchronous
-// DMA instead of a staged copy on the caller's thread.  Grows, never shrinks (batches go round).
-struct WordBuf {
-    uint32_t *p = nullptr;
-    size_t n = 0, cap = 0;
-    bool pinned = false, want_pinned = false;
-    WordBuf() = default;
-    WordBuf(const WordBuf &) = delete;
-    WordBuf &operator=(const WordBuf &) = delete;
-    ~WordBuf() { release(); }
-    void release() {
-        if (p) { if (pinned) (void)chn_host_free(p); else std::free(p); }
-        p = nullptr; n = cap = 0;
-    }
-    // room for `count` words, contents undefined (the packing loop writes every word of a read's span itself, thread by thread: clearing
-    // 50 MB per batch on the main thread first was 0.75 s of a 1.2 s packing phase on 4 M reads)
-    void assign_raw(size_t count) {
-        if (count > cap) {
-            release();
-            const size_t c = count + count / 8 + 16;
-            void *q = nullptr;
-            if (want_pinned && chn_host_alloc(c * 4, &q) == CHN_OK && q) pinned = true;
-            else { q = std::malloc(c * 4); pinned = false; if (!q) throw std::bad_alloc(); }
-            p = static_cast<uint32_t *>(q); cap = c;
-        }
-        n = count;
-    }
-    void assign_zero(size_t count) {
-        if (count > cap) {
-            release();
-            const size_t c = count + count / 8 + 16;
-            void *q = nullptr;
-            if (want_pinned && chn_host_alloc(c * 4, &q) == CHN_OK && q) pinned = true;
-            else { q = std::malloc(c * 4); pinned = false; if (!q) throw std::bad_alloc(); }
-            p = static_cast<uint32_t *>(q); cap = c;
-        }
-        n = count;
-        std::memset(p, 0, count * 4);
-    }
-    uint32_t *data() { return p; }
-    const uint32_t *data() const { return p; }
-};
-
-// The default routing of reads beyond CHN_GZIP_MAX_LEN letters (CHN_GZIP_SIZES_ALL): the device sizes every read of the batch of at
-// most the returned length (0: none of them).  One wavefront walks one such read, at about DEV_NS per letter (a lone wavefront's
-// deflate_slow: 0.1-0.2 ms per kb, profiles/r03/sq_gzip_tally.txt), and the device holds WAVES of them at once; the host emulator
-// takes HOST_NS per letter on one thread (about 70 us per 5 kb, DESIGN 6b).  A long read only pays on the device when its walk hides
-// under what the batch costs anyway: the batch's other device work (BATCH_NS per letter of the batch) or the host time of the long
-// reads the device takes off `threads` threads.  So a batch of short reads never waits for one lone 2 Mb read (0.3 s on the device,
-// 28 ms on one host thread), while a batch with many ultra-long reads sends them to the device at -t 1.  Applied only where every read
-// up to CHN_GZIP_MAX_LEN is sized on the device already (fewer than 12 threads): the routing never moves a read below that length.
-static uint32_t gzip_long_device_limit(std::vector<uint32_t> long_lens, uint64_t batch_letters, int threads) {
-    const double DEV_NS = 150.0, HOST_NS = 14.0, BATCH_NS = 0.1, WAVES = 512.0;
-    std::sort(long_lens.begin(), long_lens.end());
-    double rest = 0;  // letters of the reads at most long_lens[i]
-    std::vector<double> upto(long_lens.size());
-    for (size_t i = 0; i < long_lens.size(); ++i) upto[i] = rest += long_lens[i];
-    for (size_t i = long_lens.size(); i-- > 0;) {  // the longest limit that pays
-        const double dev = DEV_NS * std::max<double>(long_lens[i], upto[i] / WAVES);
-        const double hidden = std::max(BATCH_NS * (double)batch_letters, HOST_NS * upto[i] / std::max(1, threads));
-        if (dev <= hidden) return long_lens[i];
-    }
-    return 0;
-}
-
-struct HostBatch {
-    RawBlock blk1, blk2;               // records of this batch (views into the blocks' slabs)
-    std::vector<Slab> extra;  // further slabs of mate records when one block did not hold enough of them
-    std::vector<uint32_t> keep;        // indices of the records that are classified (zero-length reads are skipped)
-    WordBuf bases, nmask;              // 2-bit codes, N mask
-    std::vector<uint32_t> len1, len2;
-    std::vector<uint64_t> off1, off2;
-    std::vector<float> mq, comp;
-    bool any_n = false;
-    uint64_t n_bases = 0;
-    // CHARON_TEXT_BATCHES=1: the batch as chn_text_batch describes it -- `text` is the stretch of the block's slab that holds the kept
-    // records (single-end input that was decoded into a slab: nothing is copied) or `tcopy`, a page-locked copy of the letters and
-    // qualities alone (mapped files, whose pages cannot be page-locked, and pairs, whose mates live in two slabs)
-    const uint8_t *text = nullptr;
-    uint64_t text_bytes = 0;
-    std::vector<uint64_t> so1, qo1, so2, qo2;
-    std::vector<uint32_t> ql1, ql2;
-    std::vector<uint64_t> io1, io2;    // CHARON_GPU_EXTRACT=1: where the ids lie in dtext / dtext2, and their lengths (mate 2's ids do not come down)
-    std::vector<uint32_t> il1, il2;
-    bool text_quals = false, text_from_slab = false;
-    WordBuf tcopy;
-    // CHARON_GPU_TEXT=1: the block's text in device memory (so1 / qo1 are offsets into it; the records' seq / qual pointers stay null
-    // until chn_text_fetch has brought a read's letters into `arena`) and the id bytes chn_text_split handed back (the records' ids)
-    std::shared_ptr<DevBlock> dtext;
-    std::shared_ptr<DevBlock> dtext2;  // CHARON_GPU_TEXT_PAIRS=1: the block of file 2 that holds the mates (so2 / qo2 are offsets into it)
-    std::unique_ptr<char[]> ids;
-    WordBuf arena;
-    ~HostBatch() {
-        g_dead_ranges.add(blk1.map_token, blk1.map_begin, blk1.map_len); g_dead_ranges.add(blk2.map_token, blk2.map_begin, blk2.map_len);
-        g_slab_pool.give(blk1.buf); g_slab_pool.give(blk2.buf);
-        for (auto &e : extra) g_slab_pool.give(e);
-    }
-
-    static uint64_t pad64(uint64_t x) { return (x + 63) & ~63ULL; }
-    // returns false on an illegal character
-    bool put(const RecView &r, uint64_t off, bool &saw_n) {
-        uint32_t *bw = bases.data() + (off >> 4);
-        uint32_t *nw = nmask.data() + (off >> 5);
-        // the segment's span (a multiple of 64 letters) is this call's to initialise: the N mask is OR-ed into, the code words behind the
-        // last letter are never written below
-        std::memset(nw, 0, (size_t)(pad64(r.seq_len) >> 5) * 4);
-        for (uint64_t wdx = ((uint64_t)r.seq_len + 15) >> 4; wdx < (pad64(r.seq_len) >> 4); ++wdx) bw[wdx] = 0;
-        const unsigned char *sq = reinterpret_cast<const unsigned char *>(r.seq);
-        bool ok = true;
-        uint32_t i = 0;
-#if defined(__x86_64__)
-        if (g_has_avx2) i = put_avx2(sq, r.seq_len, bw, nw, ok, saw_n);
-#endif
-        for (; i < r.seq_len; i += 16) {
-            uint32_t w = 0, nb = 0;
-            const uint32_t m = std::min<uint32_t>(16, r.seq_len - i);
-            for (uint32_t j = 0; j < m; ++j) {
-                const uint8_t c = g_codes.t[sq[i + j]];
-                if (c < 4) w |= (uint32_t)c << (2 * j);
-                else if (c == 4) nb |= 1u << j;
-                else ok = false;
-            }
-            bw[i >> 4] = w;
-            if (nb) { nw[i >> 5] |= nb << (i & 16); saw_n = true; }
-        }
-        return ok;
-    }
-#if defined(__x86_64__)
-    // 32 letters per step: A/C/G/T in either case pack by arithmetic ((c >> 1) & 3 gives A0 C1 T2 G3; x ^ (x >> 1) swaps the last
-    // two); a chunk holding anything else goes through the table.  Returns the number of letters done (a multiple of 32).
-    __attribute__((target("avx2"))) static uint32_t put_avx2(const unsigned char *sq, uint32_t len, uint32_t *bw, uint32_t *nw, bool &ok, bool &saw_n) {
-        const __m256i upper = _mm256_set1_epi8((char)0xDF), three = _mm256_set1_epi8(3), one = _mm256_set1_epi8(1);
-        const __m256i lA = _mm256_set1_epi8('A'), lC = _mm256_set1_epi8('C'), lG = _mm256_set1_epi8('G'), lT = _mm256_set1_epi8('T');
-        const __m256i w16 = _mm256_set1_epi16(0x0401), w32 = _mm256_set1_epi32(0x00100001);
-        const __m256i pick = _mm256_setr_epi8(0, 4, 8, 12, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, 0, 4, 8, 12, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1);
-        uint32_t i = 0;
-        for (; i + 32 <= len; i += 32) {
-            const __m256i c = _mm256_loadu_si256(reinterpret_cast<const __m256i *>(sq + i));
-            const __m256i u = _mm256_and_si256(c, upper);
-            const __m256i valid = _mm256_or_si256(_mm256_or_si256(_mm256_cmpeq_epi8(u, lA), _mm256_cmpeq_epi8(u, lC)),
-                                                  _mm256_or_si256(_mm256_cmpeq_epi8(u, lG), _mm256_cmpeq_epi8(u, lT)));
-            if (_mm256_movemask_epi8(valid) != -1) {  // N, other IUPAC letters, U, or an illegal character somewhere in the chunk
-                for (uint32_t h = 0; h < 32; h += 16) {
-                    uint32_t w = 0, nb = 0;
-                    for (uint32_t j = 0; j < 16; ++j) {
-                        const uint8_t cc = g_codes.t[sq[i + h + j]];
-                        if (cc < 4) w |= (uint32_t)cc << (2 * j);
-                        else if (cc == 4) nb |= 1u << j;
-                        else ok = false;
-                    }
-                    bw[(i + h) >> 4] = w;
-                    if (nb) { nw[i >> 5] |= nb << h; saw_n = true; }
-                }
-                continue;
-            }
-            const __m256i t = _mm256_and_si256(_mm256_srli_epi16(c, 1), three);
-            const __m256i code = _mm256_xor_si256(t, _mm256_and_si256(_mm256_srli_epi16(t, 1), one));
-            const __m256i b4 = _mm256_madd_epi16(_mm256_maddubs_epi16(code, w16), w32);  // one byte (four letters) per 32-bit lane
-            const __m256i packed = _mm256_shuffle_epi8(b4, pick);
-            bw[i >> 4] = (uint32_t)_mm256_extract_epi32(packed, 0);
-            bw[(i >> 4) + 1] = (uint32_t)_mm256_extract_epi32(packed, 4);
-        }
-        return i;
-    }
-    // sum of the bytes of p read as SIGNED chars (what `(int)qual[j]` sees; bytes above 127 do not occur in a valid FASTQ)
-    __attribute__((target("avx2,popcnt"))) static int64_t char_sum_avx2(const char *q, size_t n) {
-        const unsigned char *p = reinterpret_cast<const unsigned char *>(q);
-        __m256i acc = _mm256_setzero_si256();
-        size_t i = 0;
-        int64_t high = 0;
-        for (; i + 32 <= n; i += 32) {
-            const __m256i v = _mm256_loadu_si256(reinterpret_cast<const __m256i *>(p + i));
-            acc = _mm256_add_epi64(acc, _mm256_sad_epu8(v, _mm256_setzero_si256()));
-            high += __builtin_popcount((unsigned)_mm256_movemask_epi8(v));
-        }
-        int64_t s = (int64_t)((uint64_t)_mm256_extract_epi64(acc, 0) + (uint64_t)_mm256_extract_epi64(acc, 1) + (uint64_t)_mm256_extract_epi64(acc, 2) + (uint64_t)_mm256_extract_epi64(acc, 3)) - 256 * high;
-        for (; i < n; ++i) s += (int)q[i];
-        return s;
-    }
-#endif
-    // sum of (phred character - 33) over a quality string, as the int the reference accumulates (src/dehost_main.cpp:355-360)
-    static int phred_sum(const char *q, uint32_t n) {
-#if defined(__x86_64__)
-        if (g_has_avx2) return (int)(char_sum_avx2(q, n) - 33 * (int64_t)n);
-#endif
-        int sum = 0;
-        for (uint32_t j = 0; j < n; ++j) sum += (int)q[j] - 33;
-        return sum;
-    }
-    // the kept records as (offset, length) pairs into one buffer
-    void describe_text(bool paired, const Slab *slab, int copy_threads) {
-        const size_t n = keep.size();
-        so1.assign(n, 0); qo1.assign(n, 0); ql1.assign(n, 0);
-        if (paired) { so2.assign(n, 0); qo2.assign(n, 0); ql2.assign(n, 0); } else { so2.clear(); qo2.clear(); ql2.clear(); }
-        text_quals = false;
-        for (size_t i = 0; i < n && !text_quals; ++i) text_quals = blk1.recs[keep[i]].qual_len != 0 || (paired && blk2.recs[keep[i]].qual_len != 0);
-        text = nullptr; text_bytes = 0; text_from_slab = false;
-        if (n == 0) return;
-        if (!paired && slab && !slab->empty()) {
-            // the slab as it stands: from the first kept stretch to the end of the last (ids and `+` lines ride along)
-            const char *lo = slab->data() + slab->size(), *hi = slab->data();
-            bool inside = true;
-            for (size_t i = 0; i < n; ++i) {
-                const RecView &a = blk1.recs[keep[i]];
-                lo = std::min(lo, a.seq); hi = std::max(hi, a.seq + a.seq_len);
-                if (a.qual_len) { lo = std::min(lo, a.qual); hi = std::max(hi, a.qual + a.qual_len); }
-            }
-            inside = lo >= slab->data() && hi <= slab->data() + slab->size() && lo <= hi;
-            if (inside) {
-                for (size_t i = 0; i < n; ++i) {
-                    const RecView &a = blk1.recs[keep[i]];
-                    so1[i] = (uint64_t)(a.seq - lo);
-                    if (a.qual_len) { qo1[i] = (uint64_t)(a.qual - lo); ql1[i] = a.qual_len; }
-                }
-                text = reinterpret_cast<const uint8_t *>(lo); text_bytes = (uint64_t)(hi - lo); text_from_slab = true;
-                return;
-            }
-        }
-        // a copy of the letters and qualities alone: per read sequence, quality, mate sequence, mate quality
-        uint64_t cur = 0;
-        for (size_t i = 0; i < n; ++i) {
-            const RecView &a = blk1.recs[keep[i]];
-            so1[i] = cur; cur += a.seq_len;
-            qo1[i] = cur; ql1[i] = a.qual_len; cur += a.qual_len;
-            if (paired) {
-                const RecView &b = blk2.recs[keep[i]];
-                so2[i] = cur; cur += b.seq_len;
-                qo2[i] = cur; ql2[i] = b.qual_len; cur += b.qual_len;
-            }
-        }
-        tcopy.want_pinned = true;
-        tcopy.assign_raw((size_t)((cur + 3) / 4) + 1);
-        char *dst = reinterpret_cast<char *>(tcopy.data());
-#pragma omp parallel for num_threads(copy_threads) schedule(dynamic, 64)
-        for (long i = 0; i < (long)n; ++i) {
-            const RecView &a = blk1.recs[keep[i]];
-            std::memcpy(dst + so1[i], a.seq, a.seq_len);
-            if (a.qual_len) std::memcpy(dst + qo1[i], a.qual, a.qual_len);
-            if (paired) {
-                const RecView &b = blk2.recs[keep[i]];
-                std::memcpy(dst + so2[i], b.seq, b.seq_len);
-                if (b.qual_len) std::memcpy(dst + qo2[i], b.qual, b.qual_len);
-            }
-        }
-        text = reinterpret_cast<const uint8_t *>(dst); text_bytes = cur;
-    }
-    // layout + parallel packing, mean quality and gzip ratio of the records in blk1 (/blk2)
-    // gz_gpu_max > 0: reads of at most that many letters get their gzip size from the device (finish_compression); gz_route_long: and
-    // the reads beyond CHN_GZIP_MAX_LEN that gzip_long_device_limit gives the device in this batch
-    std::vector<uint8_t> gz_pending;   // per kept read: its compression ratio is still to come
-    uint32_t gz_gpu_len = 0;           // longest such read (what chn_batch.gzip_tallies asks for)
-    // as_text: lay the batch out and form the host-side gzip ratios as ever, but neither pack the letters nor sum the qualities -- the
-    // device does both (chn_text_submit); `slab`: the slab the records are views into, if they all are
-    // resident (with as_text): the letters are in device memory and the caller has filled so1 / qo1 / ql1 from chn_text_split's
-    // descriptors.  No ratio can be formed here, so every read's is "still to come": the device sizes those the routing gives it and
-    // leaves 0 for the others, which finish_rows sizes on the host once their letters are fetched.
-    void pack(bool paired, int threads, bool skip_compression, uint32_t gz_gpu_max = 0, bool gz_route_long = false, bool as_text = false,
-              const Slab *slab = nullptr, bool resident = false) {
-        const size_t nrec = blk1.recs.size();
-        keep.clear();
-        for (size_t i = 0; i < nrec; ++i) {
-            const uint64_t L = (uint64_t)blk1.recs[i].seq_len + (paired ? blk2.recs[i].seq_len : 0);
-            if (L == 0) { g_log.warn("Ignoring read " + std::string(blk1.recs[i].id, blk1.recs[i].id_len) + " as has zero length!"); continue; }  // src/dehost_main.cpp:351-354
-            if (L > std::numeric_limits<uint32_t>::max()) { g_log.warn("Ignoring read as too long!"); continue; }
-            keep.push_back((uint32_t)i);
-        }
-        const size_t n = keep.size();
-        off1.assign(n, 0); len1.assign(n, 0); mq.assign(n, 0); comp.assign(n, 0);
-        if (paired) { off2.assign(n, 0); len2.assign(n, 0); }
-        uint64_t cur = 0;
-        for (size_t i = 0; i < n; ++i) {
-            const uint32_t k = keep[i];
-            off1[i] = cur; len1[i] = blk1.recs[k].seq_len; cur += pad64(len1[i]);
-            if (paired) { off2[i] = cur; len2[i] = blk2.recs[k].seq_len; cur += pad64(len2[i]); }
-        }
-        n_bases = std::max<uint64_t>(cur, 64);
-        if (as_text) {}
-        else if (cur == 0) { bases.assign_zero(n_bases / 16); nmask.assign_zero(n_bases / 32); }
-        else { bases.assign_raw(n_bases / 16); nmask.assign_raw(n_bases / 32); }
-        gz_pending.assign(n, 0); gz_gpu_len = 0;
-        // (only where every read up to CHN_GZIP_MAX_LEN goes to the device already: the device then sizes every read up to the limit)
-        if (gz_gpu_max >= CHN_GZIP_MAX_LEN && gz_route_long && !skip_compression) {
-            std::vector<uint32_t> long_lens;
-            uint64_t letters = 0;
-            for (size_t i = 0; i < n; ++i) {
-                const uint64_t L = (uint64_t)len1[i] + (paired ? len2[i] : 0);
-                letters += L;
-                if (L > CHN_GZIP_MAX_LEN) long_lens.push_back((uint32_t)L);
-            }
-            gz_gpu_max = std::max(gz_gpu_max, gzip_long_device_limit(long_lens, letters, threads));
-        }
-        if (gz_gpu_max && !skip_compression)
-            for (size_t i = 0; i < n; ++i) {
-                const uint64_t L = (uint64_t)len1[i] + (paired ? len2[i] : 0);
-                if (L <= gz_gpu_max) { gz_pending[i] = 1; gz_gpu_len = std::max<uint32_t>(gz_gpu_len, (uint32_t)L); }
-            }
-        if (resident && !skip_compression) {  // (a length of 1 when nothing is routed to the device: the compression gate is then finish_rows')
-            gz_pending.assign(n, 1);
-            gz_gpu_len = std::max<uint32_t>(gz_gpu_len, 1);
-        }
-        bool saw_n = false, bad = false;
-        // Letters -> 2-bit codes + N mask and the quality sums: what seqan3's READER does while it parses (sequence_file_input hands out dna5 ranks and
-        // phred values), so it runs on the reader's threads -- `-t`, but never fewer than four -- like the decompression and the record splitting.
-        // With the default `-t 1` the main thread used to pack for 3.6 of a 4.8 s read loop (4 M reads of 5 kb).
-        const int conv_threads = std::max(threads, g_reader_threads);
-        if (as_text && !resident) describe_text(paired, slab, conv_threads);
-#pragma omp parallel num_threads(conv_threads) if (!as_text)
-        {
-            bool my_n = false, my_bad = false;
-#pragma omp for schedule(dynamic, 16)
-            for (long i = 0; i < (long)(as_text ? 0 : n); ++i) {
-                const RecView &a = blk1.recs[keep[i]];
-                const RecView *b = paired ? &blk2.recs[keep[i]] : nullptr;
-                if (!put(a, off1[i], my_n)) my_bad = true;
-                if (b && !put(*b, off2[i], my_n)) my_bad = true;
-                // mean quality (src/dehost_main.cpp:355-360 / :441-450): int sum of phred (char - 33) / count, as float
-                int sum = phred_sum(a.qual, a.qual_len);
-                size_t cnt = a.qual_len;
-                if (b) { cnt += b->qual_len; sum += phred_sum(b->qual, b->qual_len); }
-                mq[i] = cnt ? static_cast<float>(sum) / static_cast<float>(cnt) : 0.0f;
-            }
-#pragma omp critical(batch_flags)
-            { saw_n = saw_n || my_n; bad = bad || my_bad; }
-        }
-        // the gzip ratio of the reads the device does not size (src/dehost_main.cpp:363): per-read work of the reference's loop, on the -t threads
-        bool host_gzip = false;
-        if (!skip_compression && !bad)
-            for (size_t i = 0; i < n && !host_gzip; ++i) host_gzip = !gz_pending[i];
-        if (host_gzip) {
-#pragma omp parallel num_threads(threads)
-            {
-                Deflater defl;
-#pragma omp for schedule(dynamic, 16)
-                for (long i = 0; i < (long)n; ++i)
-                    if (!gz_pending[i]) comp[i] = defl.ratio(blk1.recs[keep[i]], paired ? &blk2.recs[keep[i]] : nullptr);
-            }
-        }
-        any_n = saw_n;
-        if (bad) throw std::runtime_error("parse error: illegal character in a sequence (only IUPAC nucleotide letters are accepted)");
-    }
-};
-
-// a fault of the input (as opposed to one of the device or the program): reported without naming the replica that met it
-struct InputError : std::runtime_error { using std::runtime_error::runtime_error; };
-
-// bounded hand-over of parsed blocks from the reader thread
-struct BlockQueue {
-    std::mutex m;
-    std::condition_variable cv;
-    std::deque<std::shared_ptr<HostBatch>> q;
-    bool done = false, aborted = false;
-    std::string error;
-    // false: the consumer has gone away (an error before or inside the read loop); the reader stops
-    bool push(std::shared_ptr<HostBatch> b) {
-        std::unique_lock<std::mutex> lk(m);
-        cv.wait(lk, [&] { return q.size() < 2 || aborted; });
-        if (aborted) return false;
-        q.push_back(std::move(b));
-        cv.notify_all();
-        return true;
-    }
-    void abort() { std::lock_guard<std::mutex> lk(m); aborted = true; q.clear(); cv.notify_all(); }
-    void finish(const std::string &err) { std::lock_guard<std::mutex> lk(m); done = true; error = err; cv.notify_all(); }
-    // for a second reader thread, once the first has been aborted and joined
-    void reopen() { std::lock_guard<std::mutex> lk(m); q.clear(); done = aborted = false; error.clear(); }
-    std::shared_ptr<HostBatch> pop() {
-        std::unique_lock<std::mutex> lk(m);
-        cv.wait(lk, [&] { return !q.empty() || done; });
-        if (q.empty()) return nullptr;
-        std::shared_ptr<HostBatch> b = std::move(q.front());
-        q.pop_front();
-        cv.notify_all();
-        return b;
-    }
-};
 
 // loader self-check (v), SURVEY 8(c): if a reference FASTA recorded in the index (filepath_to_bin) is still readable, every
 // minimiser of it must be found in its bin.  This is the first-contact test for the third-party behaviour this build
@@ -443,6 +61,27 @@ void self_check_reference_files(const IndexMeta &meta, chn_stream *stream, const
     if (checked) g_log.info("self-check: minimisers of " + std::to_string(checked) + " reference file(s) all found in their bins");
 }
 
+// The ids of a pair differ after dropping their last characters (src/dehost_main.cpp:423-430): the two ids behind the rows printed so
+// far, and the end the reference's uncaught exception gives.  The caller has drained whatever still had rows to print.
+[[noreturn]] void pairs_do_not_match(const char *id1, size_t len1, const char *id2, size_t len2) {
+    std::cout.flush();
+    std::cout << std::string(id1, len1) << " " << std::string(id2, len2);
+    std::cout.flush();
+    std::fprintf(stderr, "terminate called after throwing an instance of 'std::runtime_error'\n  what():  Your pairs don't match for read ids.\n");
+    std::abort();
+}
+
+// CHARON_TIMING=1: one line to the log and, behind "charon: ", to stderr
+__attribute__((format(printf, 1, 2))) void timing_line(const char *fmt, ...) {
+    char tb[512];
+    va_list ap;
+    va_start(ap, fmt);
+    std::vsnprintf(tb, sizeof tb, fmt, ap);
+    va_end(ap);
+    g_log.info(tb);
+    std::fprintf(stderr, "charon: %s\n", tb);
+}
+
 int dehost_main(DehostArguments &opt) {
     const double t_entry = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
     g_log.open(opt.log_file, opt.verbosity);
@@ -469,24 +108,22 @@ int dehost_main(DehostArguments &opt) {
     BlockQueue queue;
     // the readers outlive the reader thread: records of a mapped file are views into the mapping until their rows are printed
     std::unique_ptr<BlockReader> in1p, in2;
-    // CHARON_GPU_TEXT=1: the reader hands over blocks of text in device memory while `resident`; when the main thread leaves the mode it
-    // stops this thread and starts it again from `resume_z` of the compressed file with `resume_carry` in front (today's path from there).
+    // CHARON_GPU_TEXT=1: while the run is device-resident, each of its `n_sides` files (one, or with CHARON_GPU_TEXT_PAIRS=1 the two of
+    // a pair) has a reader thread and a queue of its own (side_reader / side_queue), each with its own BlockReader, hence its own
+    // BgzfSource and inflate handle, which hand over blocks of text in device memory.  The host reader (reader_body) is then started
+    // only when the main thread leaves the mode: from `resume_z` of either compressed file with `resume_carry` in front.
     // A device block is 64 MiB of text (a thousand members per chn_inflate_run: four wavefronts for each of the device's 256 CUs, and
-    // some 13 000 reads of 5 kb per chn_text_split) instead of the 256 MB of a slab: up to seven buffers exist at once.
-    bool resident = false, resumed = false;
-    size_t resume_z = 0;
-    Slab resume_carry;
-    // CHARON_GPU_TEXT_PAIRS=1: while `resident_pairs`, either file has a reader thread and a queue of its own (pair_reader / pair_queue),
-    // each with its own BlockReader, hence its own BgzfSource and inflate handle; this thread is started only when the main thread leaves
-    // the mode, with BOTH files resumed.  Device buffers: each reader fills one while two wait in its queue, the main thread holds one per
-    // side and up to two batches in flight refer to one per side -- at most fourteen exist, eight free ones are kept.
-    bool resident_pairs = false, was_resident_pairs = false, resumed2 = false;
-    size_t resume_z2 = 0;
-    Slab resume_carry2;
-    BlockQueue pair_queue[2];
-    std::thread pair_reader[2];
-    auto pair_reader_body = [&](int k) {
-        BlockQueue &q = pair_queue[k];
+    // some 13 000 reads of 5 kb per chn_text_split) instead of the 256 MB of a slab.  Device buffers: each reader fills one while two
+    // wait in its queue, the main thread holds one per side and up to two batches in flight refer to one per side -- at most seven
+    // exist per side; of a pair's fourteen, eight free ones are kept.
+    int n_sides = 0;
+    bool resumed[2] = {false, false};
+    size_t resume_z[2] = {0, 0};
+    Slab resume_carry[2];
+    BlockQueue side_queue[2];
+    std::thread side_reader[2];
+    auto side_reader_body = [&](int k) {
+        BlockQueue &q = side_queue[k];
         try {
             BlockReader in(k ? opt.read_file2 : opt.read_file);
             const size_t max_bytes = (size_t)std::min<uint64_t>(256ULL << 20, std::max<uint64_t>(1 << 20, opt.batch_bases));
@@ -508,19 +145,8 @@ int dehost_main(DehostArguments &opt) {
             BlockReader &in1 = *in1p;
             if (opt.is_paired) in2.reset(new BlockReader(opt.read_file2));
             const size_t max_bytes = (size_t)std::min<uint64_t>(256ULL << 20, std::max<uint64_t>(1 << 20, opt.batch_bases));
-            if (resumed) in1.resume(resume_z, resume_carry);
-            if (resumed && resumed2) in2->resume(resume_z2, resume_carry2);
-            if (resident) {
-                const size_t block_bytes = std::min<size_t>(max_bytes, (size_t)64 << 20);
-                for (;;) {
-                    std::shared_ptr<HostBatch> hb(new HostBatch());
-                    hb->dtext = in1.next_device(block_bytes, g_gpu_text_headroom);
-                    if (!hb->dtext) break;
-                    if (!queue.push(std::move(hb))) return;
-                }
-                queue.finish("");
-                return;
-            }
+            if (resumed[0]) in1.resume(resume_z[0], resume_carry[0]);
+            if (resumed[1]) in2->resume(resume_z[1], resume_carry[1]);
             for (;;) {
                 std::shared_ptr<HostBatch> hb(new HostBatch());
                 // a batch may hold at most batch_bases padded bases: bound the record count by the byte budget as well
@@ -555,33 +181,25 @@ int dehost_main(DehostArguments &opt) {
         if (!BgzfSource().open(f)) return "one deflate stream, not BGZF";
         return "";
     };
-    if (g_gpu_text && g_gpu_text_pairs) {
-        if (!opt.is_paired) {
+    // no side, one (single-end input) or two (CHARON_GPU_TEXT_PAIRS=1 and a pair of files)
+    if (g_gpu_text) {
+        bool two = false;
+        if (g_gpu_text_pairs && !opt.is_paired)
             g_log.info("CHARON_GPU_TEXT_PAIRS=1 does not apply to " + opt.read_file + " (single-end input): CHARON_GPU_TEXT=1 alone decides");
-        } else {
+        if (g_gpu_text_pairs && opt.is_paired) {
             std::string why = not_resident_because(opt.read_file), file = opt.read_file;
             if (why.empty()) { why = not_resident_because(opt.read_file2); file = opt.read_file2; }
-            resident_pairs = was_resident_pairs = why.empty();
-            if (resident_pairs) {
-                if (const char *e = std::getenv("CHARON_GPU_TEXT_HEADROOM")) g_gpu_text_headroom = (size_t)std::min<unsigned long long>(1ULL << 30, std::strtoull(e, nullptr, 10));
-                g_dev_text_pool.keep = 8;
-                g_log.info("CHARON_GPU_TEXT=1: BGZF text is inflated into the memory of device " + std::to_string(g_gpu_text_device) +
-                           " and stays there (records split and packed on the device; headroom " + std::to_string(g_gpu_text_headroom) + " bytes)");
-                g_log.info("CHARON_GPU_TEXT_PAIRS=1: both files of the pair stay in device memory (two texts a batch; the ids of a pair are compared on the device)");
-            } else {
-                g_log.info("CHARON_GPU_TEXT_PAIRS=1 does not apply to " + file + " (" + why + "; both files must be BGZF FASTQ): the run goes on without it");
-            }
+            two = why.empty();
+            if (!two) g_log.info("CHARON_GPU_TEXT_PAIRS=1 does not apply to " + file + " (" + why + "; both files must be BGZF FASTQ): the run goes on without it");
         }
-    }
-    if (g_gpu_text && !resident_pairs) {
-        std::string why;
-        if (opt.is_paired) why = "paired input";
-        else why = not_resident_because(opt.read_file);
-        resident = why.empty();
-        if (resident) {
+        const std::string why = two ? "" : opt.is_paired ? "paired input" : not_resident_because(opt.read_file);
+        if (why.empty()) {
+            n_sides = two ? 2 : 1;
             if (const char *e = std::getenv("CHARON_GPU_TEXT_HEADROOM")) g_gpu_text_headroom = (size_t)std::min<unsigned long long>(1ULL << 30, std::strtoull(e, nullptr, 10));
+            if (two) g_dev_text_pool.keep = 8;
             g_log.info("CHARON_GPU_TEXT=1: BGZF text is inflated into the memory of device " + std::to_string(g_gpu_text_device) +
                        " and stays there (records split and packed on the device; headroom " + std::to_string(g_gpu_text_headroom) + " bytes)");
+            if (two) g_log.info("CHARON_GPU_TEXT_PAIRS=1: both files of the pair stay in device memory (two texts a batch; the ids of a pair are compared on the device)");
         } else {
             g_log.info("CHARON_GPU_TEXT=1 does not apply to " + opt.read_file + " (" + why + "; single-end BGZF FASTQ only): the run goes on without it");
         }
@@ -590,7 +208,7 @@ int dehost_main(DehostArguments &opt) {
         if (opt.category_to_extract.empty()) {
             g_log.info("CHARON_GPU_EXTRACT=1 does nothing without --extract: the run goes on without it");
             g_gpu_extract = false;
-        } else if (!resident && !resident_pairs) {
+        } else if (!n_sides) {
             g_log.info("CHARON_GPU_EXTRACT=1 does not apply (the input is not taken by the device-resident loop of CHARON_GPU_TEXT=1): the run goes on without it");
             g_gpu_extract = false;
         } else {
@@ -598,13 +216,13 @@ int dehost_main(DehostArguments &opt) {
         }
     }
     std::thread reader;
-    if (resident_pairs) for (int k = 0; k < 2; ++k) pair_reader[k] = std::thread(pair_reader_body, k);
-    else reader = std::thread(reader_body);
+    for (int k = 0; k < n_sides; ++k) side_reader[k] = std::thread(side_reader_body, k);
+    if (!n_sides) reader = std::thread(reader_body);
 
     struct ReaderJoin {  // whatever way this function is left: stop the reader and wait for it
         BlockQueue &q; std::thread &t;
         ~ReaderJoin() { if (t.joinable()) { q.abort(); t.join(); } }
-    } reader_join{queue, reader}, pair_reader_join0{pair_queue[0], pair_reader[0]}, pair_reader_join1{pair_queue[1], pair_reader[1]};
+    } reader_join{queue, reader}, side_reader_join0{side_queue[0], side_reader[0]}, side_reader_join1{side_queue[1], side_reader[1]};
     // the HIP runtime takes 0.1-0.2 s to come up: let it do so while this thread reads the index file
     std::thread warm([]() { void *p = nullptr; if (chn_host_alloc(64, &p) == CHN_OK) chn_host_free(p); });
     struct WarmJoin { std::thread &t; ~WarmJoin() { if (t.joinable()) t.join(); } } warm_join{warm};
@@ -701,7 +319,7 @@ int dehost_main(DehostArguments &opt) {
                 if (dv >= count) throw std::runtime_error("CHARON_DEVICES: device " + std::to_string(dv) + " is not below the device count " + std::to_string(count));
         }
         d.device = devices[0];
-        if ((resident || resident_pairs) && devices.size() > 1) throw std::runtime_error("CHARON_GPU_TEXT: cannot be set together with CHARON_DEVICES=all on several devices (the text lives on one device)");
+        if (n_sides && devices.size() > 1) throw std::runtime_error("CHARON_GPU_TEXT: cannot be set together with CHARON_DEVICES=all on several devices (the text lives on one device)");
     }
     {
         std::string list;
@@ -994,6 +612,28 @@ int dehost_main(DehostArguments &opt) {
         std::lock_guard<std::mutex> lk(pool_m);
         flight_pool.push_back(std::move(f));
     };
+    auto take_flight = [&]() {
+        std::unique_ptr<Flight> fl;
+        {
+            std::lock_guard<std::mutex> lk(pool_m);
+            if (!flight_pool.empty()) { fl = std::move(flight_pool.back()); flight_pool.pop_back(); }
+        }
+        if (!fl) fl.reset(new Flight());
+        return fl;
+    };
+    // The end of the GPU batch that starts at record `begin` of `limit`: at most batch_reads records and batch_bases padded bases, the
+    // stream's capacity (need_of(i): the padded bases of record i, both mates of a pair)
+    auto cut_batch = [&](size_t begin, size_t limit, auto need_of) -> size_t {
+        uint64_t bases = 0;
+        size_t end = begin;
+        while (end < limit && end - begin < opt.batch_reads) {
+            const uint64_t need = need_of(end);
+            if (need > opt.batch_bases) throw std::runtime_error("a read is longer than CHARON_BATCH_BASES");
+            if (bases + need > opt.batch_bases) break;
+            bases += need; ++end;
+        }
+        return end;
+    };
     // The rows of a batch are formatted and written by a thread of their own once the models are final and nothing is extracted (every plain
     // `charon dehost` run after its first read): the main thread packs and submits batch i + 1 meanwhile -- with the default -t 1 it used to
     // alternate between packing (1.2 s of a 2.1 s loop on 4 M reads) and rows (0.8 s).  Batches go through in order; at most two wait.
@@ -1239,71 +879,49 @@ int dehost_main(DehostArguments &opt) {
         const bool tallied = sub.gz_gpu_len != 0;
         // under --extract, sequence and quality of every read -- unless the flight's records are formed on the device (CHARON_GPU_EXTRACT=1)
         const bool letters = opt.run_extract && !fl.device_records;
-        const bool ids2 = letters && g_gpu_extract && sub.dtext2;  // the ids of mate 2 did not come down with the split: with the letters, then
-        std::vector<uint64_t> off;
-        std::vector<uint32_t> len, who;
-        uint64_t total = 0;
+        const bool two = sub.dtext2 != nullptr;  // pairs over two texts: the same reads' mates out of file 2's block -- one fetch per text
+        const bool ids2 = letters && g_gpu_extract && two;  // the ids of mate 2 did not come down with the split: with the letters, then
+        std::vector<uint64_t> off[2];
+        std::vector<uint32_t> len[2], who;
+        uint64_t total[2] = {0, 0};
+        auto range = [&](int k, uint64_t o, uint32_t l) { off[k].push_back(o); len[k].push_back(l); total[k] += l; };
         for (size_t i = 0; i < n; ++i) {
             if (!letters && !(tallied && sub.gz_pending[i] && fl.gz_sizes[i] == 0)) continue;
             who.push_back((uint32_t)i);
-            off.push_back(sub.so1[i]); len.push_back(sub.len1[i]); total += sub.len1[i];
-            if (letters) { off.push_back(sub.qo1[i]); len.push_back(sub.ql1[i]); total += sub.ql1[i]; }
-        }
-        if (sub.dtext2) {  // pairs over two texts: the same reads' mates out of file 2's block, behind mate 1's bytes in the arena -- one fetch per text
-            std::vector<uint64_t> off2;
-            std::vector<uint32_t> len2;
-            uint64_t total2 = 0;
-            for (uint32_t i : who) {
-                off2.push_back(sub.so2[i]); len2.push_back(sub.len2[i]); total2 += sub.len2[i];
-                if (letters) { off2.push_back(sub.qo2[i]); len2.push_back(sub.ql2[i]); total2 += sub.ql2[i]; }
-                if (ids2) { off2.push_back(sub.io2[i]); len2.push_back(sub.il2[i]); total2 += sub.il2[i]; dp_id2_bytes += sub.il2[i]; }
-            }
-            if (!who.empty()) {
-                sub.arena.want_pinned = true;
-                sub.arena.assign_raw((size_t)((total + total2) / 4) + 2);
-                uint8_t *arena = reinterpret_cast<uint8_t *>(sub.arena.data());
-                for (int k = 0; k < 2; ++k) {
-                    chn_text_fetch_job job;
-                    std::memset(&job, 0, sizeof job);
-                    const DevBlock &blk = k ? *sub.dtext2 : *sub.dtext;
-                    job.struct_size = sizeof job; job.text = blk.buf; job.text_bytes = blk.text_bytes;
-                    job.n_ranges = k ? off2.size() : off.size(); job.offset = k ? off2.data() : off.data(); job.length = k ? len2.data() : len.data();
-                    job.out = arena + (k ? total : 0); job.out_capacity = k ? total2 : total;
-                    CHN_CHECK(chn_text_fetch(stream, &job));
-                }
-                const char *at = reinterpret_cast<const char *>(arena), *at2 = at + total;
-                for (uint32_t i : who) {
-                    RecView &r = sub.blk1.recs[sub.keep[i]], &m = sub.blk2.recs[sub.keep[i]];
-                    r.seq = at; at += sub.len1[i];
-                    m.seq = at2; at2 += sub.len2[i];
-                    if (letters) { r.qual = at; at += sub.ql1[i]; m.qual = at2; at2 += sub.ql2[i]; }
-                    if (ids2) { m.id = at2; m.id_len = sub.il2[i]; at2 += sub.il2[i]; }
-                }
-                dt_fetched_records += who.size(); dt_fetched_bytes += total + total2;
-            }
-            if (!fl.device_records) { sub.dtext.reset(); sub.dtext2.reset(); }
-            return;
+            range(0, sub.so1[i], sub.len1[i]);
+            if (letters) range(0, sub.qo1[i], sub.ql1[i]);
+            if (two) range(1, sub.so2[i], sub.len2[i]);
+            if (two && letters) range(1, sub.qo2[i], sub.ql2[i]);
+            if (ids2) { range(1, sub.io2[i], sub.il2[i]); dp_id2_bytes += sub.il2[i]; }
         }
         if (!who.empty()) {
             sub.arena.want_pinned = true;
-            sub.arena.assign_raw((size_t)(total / 4) + 1);
-            chn_text_fetch_job job;
-            std::memset(&job, 0, sizeof job);
-            job.struct_size = sizeof job; job.text = sub.dtext->buf; job.text_bytes = sub.dtext->text_bytes;
-            job.n_ranges = off.size(); job.offset = off.data(); job.length = len.data();
-            job.out = reinterpret_cast<uint8_t *>(sub.arena.data()); job.out_capacity = (uint64_t)sub.arena.n * 4;
-            CHN_CHECK(chn_text_fetch(stream, &job));
-            const char *at = reinterpret_cast<const char *>(sub.arena.data());
+            sub.arena.assign_raw((size_t)((total[0] + total[1]) / 4) + 2);
+            uint8_t *arena = reinterpret_cast<uint8_t *>(sub.arena.data());
+            for (int k = 0; k < (two ? 2 : 1); ++k) {  // mate 2's bytes behind mate 1's
+                chn_text_fetch_job job;
+                std::memset(&job, 0, sizeof job);
+                const DevBlock &blk = k ? *sub.dtext2 : *sub.dtext;
+                job.struct_size = sizeof job; job.text = blk.buf; job.text_bytes = blk.text_bytes;
+                job.n_ranges = off[k].size(); job.offset = off[k].data(); job.length = len[k].data();
+                job.out = arena + (k ? total[0] : 0); job.out_capacity = total[k];
+                CHN_CHECK(chn_text_fetch(stream, &job));
+            }
+            const char *at = reinterpret_cast<const char *>(arena), *at2 = at + total[0];
             for (uint32_t i : who) {
                 RecView &r = sub.blk1.recs[sub.keep[i]];
                 r.seq = at; at += sub.len1[i];
                 if (letters) { r.qual = at; at += sub.ql1[i]; }
+                if (!two) continue;
+                RecView &m = sub.blk2.recs[sub.keep[i]];
+                m.seq = at2; at2 += sub.len2[i];
+                if (letters) { m.qual = at2; at2 += sub.ql2[i]; }
+                if (ids2) { m.id = at2; m.id_len = sub.il2[i]; at2 += sub.il2[i]; }
             }
-            dt_fetched_records += who.size(); dt_fetched_bytes += total;
+            dt_fetched_records += who.size(); dt_fetched_bytes += total[0] + total[1];
         }
-        if (!fl.device_records) sub.dtext.reset();
+        if (!fl.device_records) { sub.dtext.reset(); sub.dtext2.reset(); }
     };
-    // What the single-end loop and the paired loop (CHARON_GPU_TEXT_PAIRS=1) share:
     typedef std::deque<std::unique_ptr<Flight>> Flying;  // submitted, oldest first
     struct SyncOnThrow {  // the device is done with these flights' arrays before they are freed
         Flying &f; chn_stream *s;
@@ -1320,15 +938,6 @@ int dehost_main(DehostArguments &opt) {
         fetch_letters(*f);
         t_fetch += now() - tk;
         hand_on(f);
-    };
-    auto take_flight = [&]() {
-        std::unique_ptr<Flight> fl;
-        {
-            std::lock_guard<std::mutex> lk(pool_m);
-            if (!flight_pool.empty()) { fl = std::move(flight_pool.back()); flight_pool.pop_back(); }
-        }
-        if (!fl) fl.reset(new Flight());
-        return fl;
     };
     // a packed resident flight on its way: at most two in flight, the models pushed while they train, one batch at a time until they are final
     bool final_pushed = false;
@@ -1398,108 +1007,17 @@ int dehost_main(DehostArguments &opt) {
         if (ids_bytes) *ids_bytes = ids_used;
         return consumed;
     };
+    // The loop over `n_sides` files: one (single-end) or two (CHARON_GPU_TEXT_PAIRS=1).  Each side (file) keeps its current block, the
+    // descriptors of the records that are split but not yet in a batch, and `consumed`.  A side with no such record left takes its next
+    // block (the tail of the block before carried in front of it); a side that still has some does not, so files with records of unequal
+    // size never pile up text and no record is split twice.  The records at hand -- with two sides the pairs: the shorter of the two
+    // lists -- therefore lie in ONE block of either file, and a batch of them is a chn_text_batch (chn_text_batch2) over it (them).  The
+    // ids of a batch of pairs are compared on the device before the submit; the ids of file 2 come down with the split under --extract only.
     auto run_resident = [&]() {
         Flying flying;
         SyncOnThrow sync_on_throw{flying, stream};
         const int dev = g_gpu_text_device;
-        std::vector<uint64_t> blk_so, blk_qo, blk_io;
-        std::shared_ptr<DevBlock> prev;  // the block before, while [prev_from, prev->text_bytes) is a tail no record was made of
-        uint64_t prev_from = 0;
-        for (;;) {
-            const double tp = now();
-            std::shared_ptr<HostBatch> hbp = queue.pop();
-            t_pop += now() - tp;
-            if (!hbp) break;  // (the end of the file, or the reader's error: reported behind the loop below)
-            HostBatch &hb = *hbp;
-            std::shared_ptr<DevBlock> blk = hb.dtext;
-            double tk = now();
-            uint64_t start = blk->member0;
-            if (prev) {
-                start = carry_tail(prev, prev_from, blk, hb);
-                prev.reset();
-            }
-            const uint64_t end = blk->text_bytes;
-            blk_so.clear(); blk_qo.clear(); blk_io.clear();
-            const uint64_t consumed = split_block(*blk, start, true, hb, [&](const char *id, uint32_t id_len, uint32_t seq_len, uint64_t io, uint64_t so, uint64_t qo) {
-                RecView r;
-                r.id = id; r.id_len = id_len; r.seq_len = r.qual_len = seq_len;
-                hb.blk1.recs.push_back(r);
-                blk_so.push_back(so); blk_qo.push_back(qo);
-                if (g_gpu_extract) blk_io.push_back(io);
-            }, nullptr);
-            t_split += now() - tk;
-            const size_t nrec = hb.blk1.recs.size();
-            dt_split_records += nrec;
-            // the block in GPU batches that respect the stream's capacity, as below
-            size_t begin = 0;
-            while (begin < nrec) {
-                uint64_t bases = 0;
-                size_t endi = begin;
-                while (endi < nrec && endi - begin < opt.batch_reads) {
-                    const uint64_t need = HostBatch::pad64(hb.blk1.recs[endi].seq_len);
-                    if (need > opt.batch_bases) throw std::runtime_error("a read is longer than CHARON_BATCH_BASES");
-                    if (bases + need > opt.batch_bases) break;
-                    bases += need; ++endi;
-                }
-                std::unique_ptr<Flight> fl = take_flight();
-                fl->parent = hbp;
-                fl->resident = true;
-                HostBatch &sub = fl->sub;
-                sub.blk1.recs.assign(hb.blk1.recs.begin() + (long)begin, hb.blk1.recs.begin() + (long)endi);
-                tk = now();
-                sub.pack(false, opt.threads, skip_compression, gz_gpu_max, gz_route_long, true, nullptr, true);
-                const size_t n = sub.keep.size();
-                sub.so1.resize(n); sub.qo1.resize(n); sub.so2.clear(); sub.qo2.clear(); sub.ql2.clear();
-                for (size_t i = 0; i < n; ++i) { sub.so1[i] = blk_so[begin + sub.keep[i]]; sub.qo1[i] = blk_qo[begin + sub.keep[i]]; }
-                sub.ql1 = sub.len1;
-                if (g_gpu_extract) {
-                    sub.io1.resize(n); sub.il1.resize(n);
-                    for (size_t i = 0; i < n; ++i) { sub.io1[i] = blk_io[begin + sub.keep[i]]; sub.il1[i] = sub.blk1.recs[sub.keep[i]].id_len; }
-                }
-                sub.text_quals = true; sub.text_from_slab = false;
-                sub.dtext = blk;
-                t_pack += now() - tk;
-                begin = endi;
-                if (n == 0) { sub.dtext.reset(); continue; }
-                submit_resident(flying, fl);
-            }
-            // Leaving the mode: no record although four line feeds follow `start` (a wrapped record, a blank line, a damaged record), or
-            // bytes behind the last record at the end of the file (a last line without a line feed).  The text from `consumed` on comes
-            // down once, and it and the rest of the file go through the host's splitter and sequential parser, which produce today's
-            // rows and today's messages.
-            Slab tail_text;
-            bool leave = false;
-            if (consumed < end && (nrec == 0 || blk->last)) {
-                tail_text.resize((size_t)(end - consumed));
-                CHN_CHECK(chn_device_download(dev, tail_text.data(), blk->buf + consumed, end - consumed));
-                leave = blk->last || std::count(tail_text.begin(), tail_text.end(), '\n') >= 4;
-            }
-            if (leave) {
-                while (!flying.empty()) retire_front(flying);
-                g_log.info("CHARON_GPU_TEXT=1: leaving the device-resident path at byte " + std::to_string(blk->file_offset + consumed - blk->member0) +
-                           " of the inflated file (text that is no plain four-line record): the host parser goes on from there");
-                queue.abort();
-                reader.join();
-                queue.reopen();
-                resident = false; resumed = true; resume_z = blk->z_end; resume_carry.swap(tail_text);
-                g_gpu_inflate = true; g_gpu_inflate_device = dev; g_pin_slabs = true;  // inflate as under CHARON_GPU_INFLATE=1 from here on
-                reader = std::thread(reader_body);
-                return;
-            }
-            if (consumed < end) { prev = blk; prev_from = consumed; }
-        }
-        while (!flying.empty()) retire_front(flying);
-    };
-    // ---- CHARON_GPU_TEXT_PAIRS=1: the same loop over two files -------------------------------------------------------------------------
-    // Each side (file) keeps its current block, the descriptors of the records that are split but not yet paired, and `consumed`.  A side
-    // with no unpaired record left takes its next block (carry and headroom as above); a side that still has some does not, so files
-    // with records of unequal size never pile up text and no record is split twice.  The pairs at hand -- the shorter of the two lists
-    // -- therefore lie in ONE block of either file, and a batch of them is a chn_text_batch2 over those two blocks.  The ids of a batch
-    // are compared on the device before the submit; the ids of file 2 come down with the split under --extract only.
-    auto run_resident_pairs = [&]() {
-        Flying flying;
-        SyncOnThrow sync_on_throw{flying, stream};
-        const int dev = g_gpu_text_device;
+        const bool two = n_sides == 2;
         struct Side {
             std::shared_ptr<HostBatch> hb;   // the block's holder: owns the id bytes its records' views point into
             std::shared_ptr<DevBlock> blk;   // the current block (kept at the end of the file: leaving the mode resumes behind it)
@@ -1508,33 +1026,37 @@ int dehost_main(DehostArguments &opt) {
             std::vector<const char *> id;    // the id bytes (null where they did not come down)
             size_t head = 0;
             uint64_t consumed = 0;           // behind the last split record
-            uint64_t paired_end = 0;         // behind the last PAIRED record
+            uint64_t paired_end = 0;         // behind the last PAIRED record (one side: the last record in a batch)
             bool eof = false;
             size_t unpaired() const { return id_off.size() - head; }
         } side[2];
+        Side &s1 = side[0], &s2 = side[1];
         std::string reader_failure;
-        // leaving the mode: every flight retired, either side's text from behind its last paired record downloaded, both readers stopped,
-        // and today's one-thread paired reader started with both files resumed
+        // the side readers are done with (one may still wait to hand over a block nobody wants)
+        auto stop_side_readers = [&]() {
+            for (int s = 0; s < n_sides; ++s) side_queue[s].abort();
+            for (int s = 0; s < n_sides; ++s) if (side_reader[s].joinable()) side_reader[s].join();
+            for (int s = 0; s < n_sides; ++s) { side[s].hb.reset(); side[s].blk.reset(); }
+        };
+        // Leaving the mode because of side k: every flight retired, each side's text from behind its last paired record downloaded, the
+        // side readers stopped, and the host reader started with every file resumed.  That text and the rest of the files go through the
+        // host's splitter and sequential parser, which produce today's rows and today's messages.
         auto leave = [&](int k) {
             while (!flying.empty()) retire_front(flying);
-            Slab carry[2];
-            size_t z[2] = {0, 0};
-            for (int s = 0; s < 2; ++s) {
+            for (int s = 0; s < n_sides; ++s) {
                 Side &sd = side[s];
+                resumed[s] = true;
                 if (!sd.blk) continue;  // (no block of this file was taken: it starts from its first member)
-                z[s] = sd.blk->z_end;
+                resume_z[s] = sd.blk->z_end;
                 const uint64_t from = sd.paired_end, end = sd.blk->text_bytes;
-                carry[s].resize((size_t)(end - from));
-                if (end > from) CHN_CHECK(chn_device_download(dev, carry[s].data(), sd.blk->buf + from, end - from));
+                resume_carry[s].resize((size_t)(end - from));
+                if (end > from) CHN_CHECK(chn_device_download(dev, resume_carry[s].data(), sd.blk->buf + from, end - from));
             }
             const Side &sk = side[k];
             g_log.info("CHARON_GPU_TEXT=1: leaving the device-resident path at byte " + std::to_string(sk.blk->file_offset + sk.consumed - sk.blk->member0) +
-                       " of the inflated file " + (k ? opt.read_file2 : opt.read_file) + " (text that is no plain four-line record): the host parser goes on from there");
-            for (int s = 0; s < 2; ++s) pair_queue[s].abort();
-            for (int s = 0; s < 2; ++s) if (pair_reader[s].joinable()) pair_reader[s].join();
-            for (int s = 0; s < 2; ++s) { side[s].hb.reset(); side[s].blk.reset(); }
-            resident_pairs = false; resumed = resumed2 = true;
-            resume_z = z[0]; resume_carry.swap(carry[0]); resume_z2 = z[1]; resume_carry2.swap(carry[1]);
+                       " of the inflated file " + (two ? (k ? opt.read_file2 : opt.read_file) + " " : "") +
+                       "(text that is no plain four-line record): the host parser goes on from there");
+            stop_side_readers();
             g_gpu_inflate = true; g_gpu_inflate_device = dev; g_pin_slabs = true;  // inflate as under CHARON_GPU_INFLATE=1 from here on
             reader = std::thread(reader_body);
         };
@@ -1542,11 +1064,11 @@ int dehost_main(DehostArguments &opt) {
         auto take_block = [&](int k) -> bool {
             Side &sd = side[k];
             const double tp = now();
-            std::shared_ptr<HostBatch> hbp = pair_queue[k].pop();
+            std::shared_ptr<HostBatch> hbp = side_queue[k].pop();
             t_pop += now() - tp;
             if (!hbp) {  // the end of the file, or the reader's error
                 sd.eof = true;
-                if (!pair_queue[k].error.empty()) reader_failure = pair_queue[k].error;
+                if (!side_queue[k].error.empty()) reader_failure = side_queue[k].error;
                 return false;
             }
             HostBatch &hb = *hbp;
@@ -1569,7 +1091,8 @@ int dehost_main(DehostArguments &opt) {
             t_split += now() - tk;
             dt_split_records += sd.id_off.size();
             sd.hb = hbp; sd.blk = blk; sd.consumed = consumed; sd.paired_end = start;
-            // no record although four line feeds follow `start`, or bytes behind the last record at the end of the file
+            // no record although four line feeds follow `start` (a wrapped record, a blank line, a damaged record), or bytes behind the
+            // last record at the end of the file (a last line without a line feed)
             if (consumed < end && (sd.id_off.empty() || blk->last)) {
                 if (blk->last) return true;
                 Slab tail_text((size_t)(end - consumed));
@@ -1578,102 +1101,108 @@ int dehost_main(DehostArguments &opt) {
             }
             return false;
         };
-        for (;;) {
-            bool left = false;
-            for (int k = 0; k < 2 && !left; ++k)
-                while (side[k].unpaired() == 0 && !side[k].eof)  // (a block may end inside its first record and yield none)
-                    if (take_block(k)) { leave(k); left = true; break; }
-            if (left) return;
-            if (side[0].unpaired() == 0 || side[1].unpaired() == 0) break;  // one file has run out: the pairs made so far are all there are
-            Side &s1 = side[0], &s2 = side[1];
-            size_t avail = std::min(s1.unpaired(), s2.unpaired());
-            while (avail) {
-                uint64_t bases = 0;
-                size_t cnt = 0;
-                while (cnt < avail && cnt < opt.batch_reads) {
-                    const uint64_t need = HostBatch::pad64(s1.seq_len[s1.head + cnt]) + HostBatch::pad64(s2.seq_len[s2.head + cnt]);
-                    if (need > opt.batch_bases) throw std::runtime_error("a read is longer than CHARON_BATCH_BASES");
-                    if (bases + need > opt.batch_bases) break;
-                    bases += need; ++cnt;
-                }
-                // the ids of the batch's pairs must agree after dropping the last character (src/dehost_main.cpp:423-430): on the device
-                double tk = now();
-                chn_text_pair_job pj;
-                std::memset(&pj, 0, sizeof pj);
-                pj.struct_size = sizeof pj; pj.text1 = s1.blk->buf; pj.text1_bytes = s1.blk->text_bytes; pj.text2 = s2.blk->buf; pj.text2_bytes = s2.blk->text_bytes;
-                pj.n_pairs = cnt; pj.id1_offset = s1.id_off.data() + s1.head; pj.id1_length = s1.id_len.data() + s1.head;
-                pj.id2_offset = s2.id_off.data() + s2.head; pj.id2_length = s2.id_len.data() + s2.head;
-                CHN_CHECK(chn_text_pair_ids(stream, &pj));
-                t_pair += now() - tk;
-                dp_pairs_checked += cnt;
-                if (pj.first_mismatch < cnt) {
-                    const size_t a = s1.head + (size_t)pj.first_mismatch, b = s2.head + (size_t)pj.first_mismatch;
-                    while (!flying.empty()) retire_front(flying);
-                    if (writer.t.joinable()) writer_drain();
-                    const uint32_t la = s1.id_len[a] ? s1.id_len[a] - 1 : 0, lb = s2.id_len[b] ? s2.id_len[b] - 1 : 0;
-                    std::string id2(lb, '\0');
-                    if (lb) {  // the one id of file 2 this run needs on the host
-                        chn_text_fetch_job job;
-                        std::memset(&job, 0, sizeof job);
-                        const uint64_t o = s2.id_off[b];
-                        job.struct_size = sizeof job; job.text = s2.blk->buf; job.text_bytes = s2.blk->text_bytes;
-                        job.n_ranges = 1; job.offset = &o; job.length = &lb;
-                        job.out = reinterpret_cast<uint8_t *>(&id2[0]); job.out_capacity = lb;
-                        CHN_CHECK(chn_text_fetch(stream, &job));
-                    }
-                    std::cout.flush();
-                    std::cout << std::string(s1.id[a], la) << " " << id2;
-                    std::cout.flush();
-                    std::fprintf(stderr, "terminate called after throwing an instance of 'std::runtime_error'\n  what():  Your pairs don't match for read ids.\n");
-                    std::abort();
-                }
-                std::unique_ptr<Flight> fl = take_flight();
-                fl->parent = s1.hb; fl->parent2 = s2.hb;
-                fl->resident = true;
-                HostBatch &sub = fl->sub;
-                sub.blk1.recs.resize(cnt); sub.blk2.recs.resize(cnt);
+        // the ids of the next `cnt` pairs must agree after dropping the last character (src/dehost_main.cpp:423-430): on the device
+        auto check_pair_ids = [&](size_t cnt) {
+            const double tk = now();
+            chn_text_pair_job pj;
+            std::memset(&pj, 0, sizeof pj);
+            pj.struct_size = sizeof pj; pj.text1 = s1.blk->buf; pj.text1_bytes = s1.blk->text_bytes; pj.text2 = s2.blk->buf; pj.text2_bytes = s2.blk->text_bytes;
+            pj.n_pairs = cnt; pj.id1_offset = s1.id_off.data() + s1.head; pj.id1_length = s1.id_len.data() + s1.head;
+            pj.id2_offset = s2.id_off.data() + s2.head; pj.id2_length = s2.id_len.data() + s2.head;
+            CHN_CHECK(chn_text_pair_ids(stream, &pj));
+            t_pair += now() - tk;
+            dp_pairs_checked += cnt;
+            if (pj.first_mismatch >= cnt) return;
+            const size_t a = s1.head + (size_t)pj.first_mismatch, b = s2.head + (size_t)pj.first_mismatch;
+            while (!flying.empty()) retire_front(flying);
+            if (writer.t.joinable()) writer_drain();
+            const uint32_t la = s1.id_len[a] ? s1.id_len[a] - 1 : 0, lb = s2.id_len[b] ? s2.id_len[b] - 1 : 0;
+            std::string id2(lb, '\0');
+            if (lb) {  // the one id of file 2 this run needs on the host
+                chn_text_fetch_job job;
+                std::memset(&job, 0, sizeof job);
+                const uint64_t o = s2.id_off[b];
+                job.struct_size = sizeof job; job.text = s2.blk->buf; job.text_bytes = s2.blk->text_bytes;
+                job.n_ranges = 1; job.offset = &o; job.length = &lb;
+                job.out = reinterpret_cast<uint8_t *>(&id2[0]); job.out_capacity = lb;
+                CHN_CHECK(chn_text_fetch(stream, &job));
+            }
+            pairs_do_not_match(s1.id[a], la, id2.data(), lb);
+        };
+        // The next `cnt` records of every side as one flight: record views and pack, then where their letters, qualities and ids lie in
+        // the texts (with one side the second halves stay cleared); every side moves on by `cnt`.
+        auto fill_flight = [&](Flight &fl, size_t cnt) {
+            fl.parent = s1.hb;
+            if (two) fl.parent2 = s2.hb;
+            fl.resident = true;
+            HostBatch &sub = fl.sub;
+            auto views = [&](const Side &sd, std::vector<RecView> &recs) {
+                recs.resize(cnt);
                 for (size_t i = 0; i < cnt; ++i) {
-                    RecView r, m;
-                    r.id = s1.id[s1.head + i]; r.id_len = s1.id_len[s1.head + i]; r.seq_len = r.qual_len = s1.seq_len[s1.head + i];
-                    m.id = s2.id[s2.head + i]; m.id_len = m.id ? s2.id_len[s2.head + i] : 0; m.seq_len = m.qual_len = s2.seq_len[s2.head + i];
-                    sub.blk1.recs[i] = r; sub.blk2.recs[i] = m;
+                    RecView r;
+                    r.id = sd.id[sd.head + i]; r.id_len = r.id ? sd.id_len[sd.head + i] : 0; r.seq_len = r.qual_len = sd.seq_len[sd.head + i];
+                    recs[i] = r;
                 }
-                tk = now();
-                sub.pack(true, opt.threads, skip_compression, gz_gpu_max, gz_route_long, true, nullptr, true);
-                const size_t n = sub.keep.size();
-                sub.so1.resize(n); sub.qo1.resize(n); sub.so2.resize(n); sub.qo2.resize(n);
+            };
+            views(s1, sub.blk1.recs);
+            if (two) views(s2, sub.blk2.recs);
+            const double tk = now();
+            sub.pack(two, opt.threads, skip_compression, gz_gpu_max, gz_route_long, true, nullptr, true);
+            const size_t n = sub.keep.size();
+            auto columns = [&](const Side &sd, const std::vector<uint32_t> &len, std::vector<uint64_t> &so, std::vector<uint64_t> &qo, std::vector<uint32_t> &ql,
+                               std::vector<uint64_t> &io, std::vector<uint32_t> &il) {
+                so.resize(n); qo.resize(n); ql = len;
+                if (g_gpu_extract) { io.resize(n); il.resize(n); }
                 for (size_t i = 0; i < n; ++i) {
-                    const size_t a = s1.head + sub.keep[i], b = s2.head + sub.keep[i];
-                    sub.so1[i] = s1.seq_off[a]; sub.qo1[i] = s1.qual_off[a]; sub.so2[i] = s2.seq_off[b]; sub.qo2[i] = s2.qual_off[b];
+                    const size_t a = sd.head + sub.keep[i];
+                    so[i] = sd.seq_off[a]; qo[i] = sd.qual_off[a];
+                    if (g_gpu_extract) { io[i] = sd.id_off[a]; il[i] = sd.id_len[a]; }
                 }
-                sub.ql1 = sub.len1; sub.ql2 = sub.len2;
-                if (g_gpu_extract) {
-                    sub.io1.resize(n); sub.il1.resize(n); sub.io2.resize(n); sub.il2.resize(n);
-                    for (size_t i = 0; i < n; ++i) {
-                        const size_t a = s1.head + sub.keep[i], b = s2.head + sub.keep[i];
-                        sub.io1[i] = s1.id_off[a]; sub.il1[i] = s1.id_len[a]; sub.io2[i] = s2.id_off[b]; sub.il2[i] = s2.id_len[b];
-                    }
-                }
-                sub.text_quals = true; sub.text_from_slab = false;
-                sub.dtext = s1.blk; sub.dtext2 = s2.blk;
-                t_pack += now() - tk;
-                s1.head += cnt; s2.head += cnt; avail -= cnt;
-                for (Side *sd : {&s1, &s2}) sd->paired_end = sd->unpaired() ? sd->id_off[sd->head] - 1 : sd->consumed;  // ('@' stands in front of an id)
-                if (n == 0) { sub.dtext.reset(); sub.dtext2.reset(); continue; }
+            };
+            columns(s1, sub.len1, sub.so1, sub.qo1, sub.ql1, sub.io1, sub.il1);
+            if (two) columns(s2, sub.len2, sub.so2, sub.qo2, sub.ql2, sub.io2, sub.il2);
+            else { sub.so2.clear(); sub.qo2.clear(); sub.ql2.clear(); }
+            sub.text_quals = true; sub.text_from_slab = false;
+            sub.dtext = s1.blk;
+            if (two) sub.dtext2 = s2.blk;
+            t_pack += now() - tk;
+            for (int k = 0; k < n_sides; ++k) {
+                Side &sd = side[k];
+                sd.head += cnt;
+                sd.paired_end = sd.unpaired() ? sd.id_off[sd.head] - 1 : sd.consumed;  // ('@' stands in front of an id)
+            }
+        };
+        for (;;) {
+            // Leaving the mode is noted here and done once the records at hand are submitted: side `leaving` met text the device cannot
+            // go on splitting.
+            int leaving = -1;
+            for (int k = 0; k < n_sides && leaving < 0; ++k)
+                while (side[k].unpaired() == 0 && !side[k].eof)  // (a block may end inside its first record and yield none)
+                    if (take_block(k)) { leaving = k; break; }
+            size_t avail = two ? std::min(s1.unpaired(), s2.unpaired()) : s1.unpaired();
+            if (avail == 0 && leaving < 0) break;  // a file has run out: the records submitted so far are all there are
+            while (avail) {
+                // GPU batches that respect the stream's capacity, as below
+                const size_t cnt = cut_batch(0, avail, [&](size_t i) {
+                    return HostBatch::pad64(s1.seq_len[s1.head + i]) + (two ? HostBatch::pad64(s2.seq_len[s2.head + i]) : 0);
+                });
+                if (two) check_pair_ids(cnt);
+                std::unique_ptr<Flight> fl = take_flight();
+                fill_flight(*fl, cnt);
+                avail -= cnt;
+                if (fl->sub.keep.empty()) { fl->sub.dtext.reset(); fl->sub.dtext2.reset(); continue; }
                 submit_resident(flying, fl);
             }
+            if (leaving >= 0) { leave(leaving); return; }
         }
         while (!flying.empty()) retire_front(flying);
-        // nothing was left: both readers are done with (one may still wait to hand over a block nobody wants), and the loop below,
-        // which reads the one-thread reader's queue, finds it finished -- with the error a reader met, if one did
-        for (int s = 0; s < 2; ++s) pair_queue[s].abort();
-        for (int s = 0; s < 2; ++s) if (pair_reader[s].joinable()) pair_reader[s].join();
-        for (int s = 0; s < 2; ++s) { side[s].hb.reset(); side[s].blk.reset(); }
+        // nothing was left: the loop below, which reads the host reader's queue, finds it finished -- with the error a side reader met,
+        // if one did
+        stop_side_readers();
         queue.finish(reader_failure);
     };
     try {
-        if (resident) run_resident();
-        if (resident_pairs) run_resident_pairs();
+        if (n_sides) run_resident();
         for (;;) {
             double tp = now();
             std::shared_ptr<HostBatch> hbp = queue.pop();
@@ -1688,32 +1217,18 @@ int dehost_main(DehostArguments &opt) {
                     if (la != lb || std::memcmp(a.id, b.id, la) != 0) {
                         if (dealing) drain_replicas();
                         if (writer.t.joinable()) writer_drain();
-                        std::cout.flush();
-                        std::cout << std::string(a.id, la) << " " << std::string(b.id, lb);
-                        std::cout.flush();
-                        std::fprintf(stderr, "terminate called after throwing an instance of 'std::runtime_error'\n  what():  Your pairs don't match for read ids.\n");
-                        std::abort();
+                        pairs_do_not_match(a.id, la, b.id, lb);
                     }
                 }
             }
             // split the block into GPU batches that respect the stream's capacity
             size_t begin = 0;
             while (begin < nrec) {
-                uint64_t bases = 0;
-                size_t endi = begin;
-                while (endi < nrec && endi - begin < opt.batch_reads) {
-                    const uint64_t need = HostBatch::pad64(hb.blk1.recs[endi].seq_len) + (opt.is_paired ? HostBatch::pad64(hb.blk2.recs[endi].seq_len) : 0);
-                    if (need > opt.batch_bases) throw std::runtime_error("a read is longer than CHARON_BATCH_BASES");
-                    if (bases + need > opt.batch_bases) break;
-                    bases += need; ++endi;
-                }
+                const size_t endi = cut_batch(begin, nrec, [&](size_t i) {
+                    return HostBatch::pad64(hb.blk1.recs[i].seq_len) + (opt.is_paired ? HostBatch::pad64(hb.blk2.recs[i].seq_len) : 0);
+                });
                 if (dealing) release_ready();
-                std::unique_ptr<Flight> fl;
-                {
-                    std::lock_guard<std::mutex> lk(pool_m);
-                    if (!flight_pool.empty()) { fl = std::move(flight_pool.back()); flight_pool.pop_back(); }
-                }
-                if (!fl) fl.reset(new Flight());
+                std::unique_ptr<Flight> fl = take_flight();
                 fl->parent = hbp;
                 fl->resident = false;
                 HostBatch &sub = fl->sub;
@@ -1762,64 +1277,33 @@ int dehost_main(DehostArguments &opt) {
     result.complete();
     std::cout.flush();
     if (timing) {
-        char tb[256];
-        std::snprintf(tb, sizeof tb, "timing (main thread, s): wait-for-reader %.3f  pack %.3f  submit %.3f  wait-for-gpu %.3f  tallies->sizes %.3f  rows %.3f",
-                      t_pop, t_pack, t_submit, t_wait, t_gz, t_rows);
-        g_log.info(tb);
-        std::fprintf(stderr, "charon: %s\n", tb);
-        std::snprintf(tb, sizeof tb, "timing (reader thread, s): inflate %.3f  record splitting %.3f", g_reader_fill_s, g_reader_parse_s);
-        g_log.info(tb);
-        std::fprintf(stderr, "charon: %s\n", tb);
-        if (g_gpu_inflate) {
-            std::snprintf(tb, sizeof tb, "timing (reader thread, s): inside chn_inflate_run %.3f (part of inflate)", g_gpu_inflate_s);
-            g_log.info(tb);
-            std::fprintf(stderr, "charon: %s\n", tb);
-        }
-        if (g_gpu_text && (resident || resumed || was_resident_pairs)) {
-            char tg[512];
-            std::snprintf(tg, sizeof tg, "timing (CHARON_GPU_TEXT=1): records split %llu  records fetched %llu  text bytes inflated %llu  text bytes fetched %llu  "
-                          "seconds in inflate %.3f  seconds in split %.3f  seconds in fetch %.3f",
-                          (unsigned long long)dt_split_records, (unsigned long long)dt_fetched_records, (unsigned long long)g_gpu_text_inflated,
-                          (unsigned long long)dt_fetched_bytes, g_gpu_inflate_s, t_split, t_fetch);
-            g_log.info(tg);
-            std::fprintf(stderr, "charon: %s\n", tg);
-        }
-        if (was_resident_pairs) {
-            std::snprintf(tb, sizeof tb, "timing (CHARON_GPU_TEXT_PAIRS=1): pairs checked %llu  id bytes of file 2 downloaded %llu  seconds in pair check %.3f",
-                          (unsigned long long)dp_pairs_checked, (unsigned long long)dp_id2_bytes, t_pair);
-            g_log.info(tb);
-            std::fprintf(stderr, "charon: %s\n", tb);
-        }
-        if (g_gpu_deflate) {
-            std::snprintf(tb, sizeof tb, "timing (main thread, s): inside chn_deflate_run %.3f (extract files)", g_gpu_deflate_s);
-            g_log.info(tb);
-            std::fprintf(stderr, "charon: %s\n", tb);
-        }
-        if (g_gpu_extract) {
-            std::snprintf(tb, sizeof tb, "timing (CHARON_GPU_EXTRACT=1): records formed on the device %llu  bytes appended from the host %llu  compressed bytes down %llu  "
-                          "seconds in chn_extract calls %.3f", (unsigned long long)g_gpu_extract_records, (unsigned long long)g_gpu_extract_host_bytes,
-                          (unsigned long long)g_gpu_extract_down, g_gpu_extract_s);
-            g_log.info(tb);
-            std::fprintf(stderr, "charon: %s\n", tb);
-        }
-        std::snprintf(tb, sizeof tb, "timing (start-up, s): index file read %.3f  device + index create %.3f  index decode, stream, models %.3f (of which reference self-check %.3f)  read loop %.3f",
-                      t_meta - t_entry, t_hip - t_meta, t_ready - t_hip, t_ready - t_sc0, now() - t_ready);
-        g_log.info(tb);
-        std::fprintf(stderr, "charon: %s\n", tb);
-        std::snprintf(tb, sizeof tb, "timing (index decode, s): select blocks checked %.3f  page-locked staging %.3f  slices staged %.3f  waited for the device %.3f  bin popcounts %.3f",
-                      file.t_verify, file.t_stage_alloc, file.t_stage_fill, file.t_device_wait, file.t_popcounts);
-        g_log.info(tb);
-        std::fprintf(stderr, "charon: %s\n", tb);
+        timing_line("timing (main thread, s): wait-for-reader %.3f  pack %.3f  submit %.3f  wait-for-gpu %.3f  tallies->sizes %.3f  rows %.3f",
+                    t_pop, t_pack, t_submit, t_wait, t_gz, t_rows);
+        timing_line("timing (reader thread, s): inflate %.3f  record splitting %.3f", g_reader_fill_s, g_reader_parse_s);
+        if (g_gpu_inflate) timing_line("timing (reader thread, s): inside chn_inflate_run %.3f (part of inflate)", g_gpu_inflate_s);
+        if (n_sides)
+            timing_line("timing (CHARON_GPU_TEXT=1): records split %llu  records fetched %llu  text bytes inflated %llu  text bytes fetched %llu  "
+                        "seconds in inflate %.3f  seconds in split %.3f  seconds in fetch %.3f",
+                        (unsigned long long)dt_split_records, (unsigned long long)dt_fetched_records, (unsigned long long)g_gpu_text_inflated,
+                        (unsigned long long)dt_fetched_bytes, g_gpu_inflate_s, t_split, t_fetch);
+        if (n_sides == 2)
+            timing_line("timing (CHARON_GPU_TEXT_PAIRS=1): pairs checked %llu  id bytes of file 2 downloaded %llu  seconds in pair check %.3f",
+                        (unsigned long long)dp_pairs_checked, (unsigned long long)dp_id2_bytes, t_pair);
+        if (g_gpu_deflate) timing_line("timing (main thread, s): inside chn_deflate_run %.3f (extract files)", g_gpu_deflate_s);
+        if (g_gpu_extract)
+            timing_line("timing (CHARON_GPU_EXTRACT=1): records formed on the device %llu  bytes appended from the host %llu  compressed bytes down %llu  "
+                        "seconds in chn_extract calls %.3f", (unsigned long long)g_gpu_extract_records, (unsigned long long)g_gpu_extract_host_bytes,
+                        (unsigned long long)g_gpu_extract_down, g_gpu_extract_s);
+        timing_line("timing (start-up, s): index file read %.3f  device + index create %.3f  index decode, stream, models %.3f (of which reference self-check %.3f)  read loop %.3f",
+                    t_meta - t_entry, t_hip - t_meta, t_ready - t_hip, t_ready - t_sc0, now() - t_ready);
+        timing_line("timing (index decode, s): select blocks checked %.3f  page-locked staging %.3f  slices staged %.3f  waited for the device %.3f  bin popcounts %.3f",
+                    file.t_verify, file.t_stage_alloc, file.t_stage_fill, file.t_device_wait, file.t_popcounts);
     }
     for (auto &rp : reps) {
         g_log.info("replica " + std::to_string(rp->index) + " (device " + std::to_string(rp->device) + "): " + std::to_string(rp->batches) + " batches, " +
                    std::to_string(rp->reads) + " reads");
-        if (timing && dealing) {
-            char tb[160];
-            std::snprintf(tb, sizeof tb, "timing (replica %zu, device %d, s): submit %.3f  wait-for-gpu %.3f", rp->index, rp->device, rp->t_submit, rp->t_wait);
-            g_log.info(tb);
-            std::fprintf(stderr, "charon: %s\n", tb);
-        }
+        if (timing && dealing)
+            timing_line("timing (replica %zu, device %d, s): submit %.3f  wait-for-gpu %.3f", rp->index, rp->device, rp->t_submit, rp->t_wait);
     }
     if (opt.text_batches)
         g_log.info("text batches: " + std::to_string(text_slab_batches.load()) + " sent as the block's slab, " + std::to_string(text_copy_batches.load()) +

@@ -198,6 +198,30 @@ def test_pairs_leave_the_mode(tmp_path):
     assert log_of(tmp_path, "d_on").count(LEFT) == 1
 
 
+def test_pairs_file_1_leaves_while_mates_are_at_hand(tmp_path):
+    # Mates half as long as the reads, blocks of 1 MiB: a block of file 2 holds about twice the records of one of file 1, so when file
+    # 1's side takes its last block -- a wrapped record near its end: the mode must be left -- the other side still holds mates that
+    # are split and not yet paired.  They are paired with the records in front of the wrapped one and submitted before the mode is
+    # left; either file then comes down from behind its last paired record.
+    r = util.rng(60)
+    gs = genomes()
+    reads, mates = util.sample_reads(r, gs, 6000, (200, 400), sub_rate=0.03), util.sample_reads(r, gs, 6000, (80, 150), sub_rate=0.03)
+    a, b = pair_records(reads, mates, r)
+    s, q = a[5900].split(b"\n")[1], a[5900].split(b"\n")[3]
+    a[5900] = b"@read5900/1\n" + s[:60] + b"\n" + s[60:] + b"\n+\n" + q[:60] + b"\n" + q[60:] + b"\n"
+    # file 1: the wrapped record lies in its fourth block; file 2: two blocks, the second taken long before that
+    assert len(b"".join(a[:5900])) > (3 << 20) + (1 << 18) and (2 << 20) - (1 << 18) > len(b"".join(b)) > (1 << 20) + (1 << 18)
+    f = write_pair(tmp_path, "m", a, b, r=r, lo=3000, hi=9000)
+    env = {"CHARON_BATCH_READS": "37", "CHARON_BATCH_BASES": str(1 << 20), "CHARON_TIMING": "1"}
+    out = both(tmp_path, ["--db", IDX, "-t", "4"] + f, env, tag="m", rows=5990)
+    log = log_of(tmp_path, "m_on")
+    assert "read5999/1\t" in out and log.count(LEFT) == 1
+    # submit, then leave: every pair in front of the wrapped record went through the id check on the device, those of file 1's last
+    # block included (leaving at once would have handed them to the host parser unchecked)
+    m = re.search(r"timing \(CHARON_GPU_TEXT_PAIRS=1\): pairs checked (\d+)  ", log)
+    assert m and int(m.group(1)) == 5900, m and m.groups()
+
+
 def test_pairs_corrupt_member_in_file_2(tmp_path):
     r = util.rng(58)
     a, b = pair_records(*sample_pairs(r, 600), r)

@@ -16,7 +16,11 @@ usage: python tools/gpu_text_resident_bench.py pairs [pairs=4000000] [work dir] 
 The extract leg (CHARON_GPU_EXTRACT=1): `charon dehost --extract all` on the 7d file, in alternated rounds of the parent build
 and this build with CHARON_GPU_TEXT=1 CHARON_GPU_DEFLATE=1, and this build with CHARON_GPU_EXTRACT=1 added.  The TSV and every extract
 file must have one sha256 across the three.
-usage: python tools/gpu_text_resident_bench.py extract [reads=400000] [work dir] [rounds=3] [out=profiles/r11/gpu_extract.txt] [-t values...]"""
+usage: python tools/gpu_text_resident_bench.py extract [reads=400000] [work dir] [rounds=3] [out=profiles/r11/gpu_extract.txt] [-t values...]
+
+--parent-switches (anywhere on the command line, with PARENT_CHARON set): every build with switches gets a twin "parent, <name>", the
+parent binary under the same switches, and per -t a line saying whether this build's range overlaps its twin's -- or, where it lies
+below, by how much of the twin's own min-max width.  For a change that claims only to be no slower than the parent in every mode."""
 import hashlib
 import importlib.util
 import os
@@ -84,6 +88,9 @@ def write_pairs(paths, n, genomes, length=150, seed=3, chunk=20000):
 
 
 def main():
+    twins = "--parent-switches" in sys.argv
+    if twins:
+        sys.argv.remove("--parent-switches")
     paired = len(sys.argv) > 1 and sys.argv[1] == "pairs"
     extract = len(sys.argv) > 1 and sys.argv[1] == "extract"
     if paired or extract:
@@ -154,6 +161,9 @@ def main():
                [("unset", exe, {})] +
                ([("CHARON_GPU_TEXT_PAIRS=1", exe, {"CHARON_GPU_TEXT": "1", "CHARON_GPU_TEXT_PAIRS": "1"})] if paired else
                 [("CHARON_GPU_INFLATE=1", exe, {"CHARON_GPU_INFLATE": "1"}), ("CHARON_GPU_TEXT=1", exe, {"CHARON_GPU_TEXT": "1"})]))
+    if twins and parent:
+        configs = [c for name, binary, extra in configs
+                   for c in ([("parent, " + name, parent, extra)] if extra and binary == exe and ("parent, " + name, parent, extra) not in configs else []) + [(name, binary, extra)]]
     ok = True
     for label, bgzf, count in files:
         digests, rates, timing = set(), {}, {}
@@ -190,6 +200,19 @@ def main():
             if parent and not extract:
                 u, pr = rates[("unset", t)], rates[("parent", t)]
                 say("-t %d: unset inside the parent's range: %s" % (t, min(pr) <= max(u) and min(u) <= max(pr)))
+            for name, _, _ in configs if twins and parent else ():
+                if ("parent, " + name, t) in rates:
+                    v, pv = rates[(name, t)], rates[("parent, " + name, t)]
+                    width = max(pv) - min(pv)
+                    if min(pv) <= max(v) and min(v) <= max(pv):
+                        say("-t %d: %s overlaps its parent twin's range: True" % (t, name))
+                    elif min(v) > max(pv):
+                        say("-t %d: %s overlaps its parent twin's range: False (faster throughout: its minimum lies %.0f %s above the twin's maximum)"
+                            % (t, name, min(v) - max(pv), unit))
+                    else:
+                        gap = min(pv) - max(v)
+                        say("-t %d: %s overlaps its parent twin's range: False (its maximum lies %.0f %s below the twin's minimum; the twin's width is %.0f: %s)"
+                            % (t, name, gap, unit, width, "within" if gap <= width else "NOT within"))
             for name, _, _ in configs:
                 for ln in timing[(name, t)]:
                     say("   %-24s -t %2d %s" % (name, t, ln))
