@@ -17,6 +17,7 @@ _L = C.CDLL(LIB_PATH)
 MINIMISER_SEED = 0x8F3F73B5CF1C9ADE
 STREAM_PROFILE = 1
 STREAM_TINY_LOG = 2
+STREAM_NO_PROBE_GATE = 4
 # chn_batch.gzip_output (include/charon_hip.h)
 GZIP_TALLIES, GZIP_SIZES, GZIP_BOTH = 0, 1, 2
 GZIP_SIZES_ALL = 3           # the gzip size of every read of 1 .. gzip_tallies letters, any length, any number of deflate blocks
@@ -383,11 +384,13 @@ def default_model(num_categories, host_index, paired=False, dist="kde", pos_para
 
 
 class Stream:
-    def __init__(self, index, max_reads, max_bases, profile=False, tiny_log=False, split_bucket=0):
-        """split_bucket (testing): length class from which single-end reads are cut over the 64 lanes of a wavefront
+    def __init__(self, index, max_reads, max_bases, profile=False, tiny_log=False, split_bucket=0, probe_gate=True):
+        """probe_gate=False (testing): CHN_STREAM_NO_PROBE_GATE, consecutive probe grids share the device from their first workgroup on.
+        split_bucket (testing): length class from which single-end reads are cut over the 64 lanes of a wavefront
         (CHN_STREAM_SPLIT_BUCKET: 0 = default, 32 768 bases; 64 = 1 024 bases; 255 = never)"""
         self.index = index
-        cfg = StreamCfg(C.sizeof(StreamCfg), (STREAM_PROFILE if profile else 0) | (STREAM_TINY_LOG if tiny_log else 0) | ((split_bucket & 0xff) << 8),
+        cfg = StreamCfg(C.sizeof(StreamCfg), (STREAM_PROFILE if profile else 0) | (STREAM_TINY_LOG if tiny_log else 0) | (0 if probe_gate else STREAM_NO_PROBE_GATE) |
+                        ((split_bucket & 0xff) << 8),
                         max_reads, max_bases)
         self.h = C.c_void_p()
         _chk(_L.chn_stream_create(index.h, C.byref(cfg), C.byref(self.h)))

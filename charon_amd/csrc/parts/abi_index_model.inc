@@ -219,6 +219,12 @@ struct chn_stream {
     int inflight = 0;  // batches submitted and not yet waited for (FIFO)
     uint64_t batch_seq = 0;  // whole-chain batches submitted so far: batch i's probe kernel runs on probe stream i & 1
     bool last_had_long = false;  // the batch waited for last had reads for the SPLIT launch: while that is so, every batch takes the first probe stream
+    // The probe gate: a batch's ordinary launch waits in its queue (hipStreamWaitValue64) until *gate_signal has reached the value of the
+    // gated batch before it, which that batch's grid writes when its last workgroup has started and a one-thread kernel behind the grid
+    // writes again.  Every wait names a value whose writers this thread has already enqueued on this chn_stream.
+    unsigned long long *gate_signal = nullptr;  // signal memory, zero at creation; null: no gate (no device support, CHN_STREAM_NO_PROBE_GATE)
+    uint64_t gate_seq = 0;                      // value of the last gated batch whose writers are enqueued (0: none yet)
+    uint64_t gated_batches = 0;                 // launches queued behind a gate wait (chn_stream_profile, which = 13)
     HostModel model;
     K3Args k3;
     // chn_classify_counts(_raw): inputs and outputs of k_model_call on the caller's counts.  A set of its own (allocated on first use,

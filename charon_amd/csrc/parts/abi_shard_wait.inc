@@ -171,6 +171,7 @@ static int rerun_worst_case(chn_stream *s, Slot &sl) {
     int rc = s->big.ensure(total, (n + WAVE - 1) / WAVE + std::min<uint64_t>(sl.split_bound, total / len_bucket_floor(std::min(s->long_bucket, 247u)) + 1), (uint32_t)d.bin_words, 65536, 0, nw);
     if (rc) return rc;
     K1Args a = sl.k1;
+    a.gate_started = a.gate_signal = nullptr;  // no probe gate: the slot's counter has counted this grid once already, and nothing waits for it
     fill_k1_log(a, sl, s->big, true);
     const size_t lds = k1_lds_bytes(a.wn, d.num_categories, MODE_ROWS, a.h, (uint32_t)d.bin_words, (uint32_t)d.bins);
     hipError_t e = launch_k1_mode(MODE_ROWS, (uint32_t)d.bin_words, a, lds, s->stream);
@@ -353,7 +354,13 @@ extern "C" int chn_classify_counts(chn_stream *s, uint64_t n, const uint32_t *nu
 }
 
 extern "C" int chn_stream_profile(chn_stream *s, int which, double *total_ms, uint64_t *launches, int reset) {
-    if (!s || which < 0 || which > 11 || which == 10) return fail(CHN_E_INVALID, "chn_stream_profile: bad argument");
+    if (!s || which < 0 || which > 13 || which == 10 || which == 12) return fail(CHN_E_INVALID, "chn_stream_profile: bad argument");
+    if (which == 13) {  // batches whose ordinary probe launch was queued behind a probe-gate wait
+        if (total_ms) *total_ms = s->gate_signal ? 1.0 : 0.0;  // (no time: whether this stream gates at all)
+        if (launches) *launches = s->gated_batches;
+        if (reset) s->gated_batches = 0;
+        return CHN_OK;
+    }
     if (which == 11) {  // chn_text_pair_ids: k_pair_ids
         if (total_ms) *total_ms = s->tpi.ms;
         if (launches) *launches = s->tpi.calls;

@@ -54,6 +54,18 @@ extern "C" int chn_stream_create(chn_index *idx, const chn_stream_cfg *cfg, chn_
         s->long_bucket = ob == 0 ? LONG_BUCKET_DEFAULT : ob == 255 ? 256u : std::max(64u, ob);
     }
     if (e != hipSuccess) { chn_stream_destroy(s); return fail(CHN_E_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e)); }
+    {   // The probe gate's signal word (chn_stream::gate_signal), where the device's queues can wait for a value in memory.  Without it, or
+        // with CHN_STREAM_NO_PROBE_GATE, consecutive probe grids share the device from their first workgroup on.  Diagnostics builds:
+        // CHN_PROBE_GATE=0 does the same, for the A/B.
+        int can_wait = 0;
+        const char *off = diag_env("CHN_PROBE_GATE");
+        if (!(cfg->flags & CHN_STREAM_NO_PROBE_GATE) && !(off && std::atoi(off) == 0) &&
+            hipDeviceGetAttribute(&can_wait, hipDeviceAttributeCanUseStreamWaitValue, idx->d.device) == hipSuccess && can_wait) {
+            e = hipExtMallocWithFlags((void **)&s->gate_signal, 8, hipMallocSignalMemory);
+            if (e == hipSuccess) e = hipMemset(s->gate_signal, 0, 8);
+            if (e != hipSuccess) { chn_stream_destroy(s); return fail(CHN_E_HIP, std::string("probe gate signal: ") + hipGetErrorString(e)); }
+        }
+    }
     const uint64_t n = cfg->max_reads, C = idx->d.num_categories;
     int rc = CHN_OK;
     const bool sharded = idx->d.row_begin != 0 || idx->d.row_end != idx->d.bin_size;
@@ -119,6 +131,7 @@ extern "C" int chn_stream_destroy(chn_stream *s) {
     if (s->stream4) { (void)hipStreamSynchronize(s->stream4); (void)hipStreamDestroy(s->stream4); }
     if (s->stream5) { (void)hipStreamSynchronize(s->stream5); (void)hipStreamDestroy(s->stream5); }
     if (s->stream) (void)hipStreamDestroy(s->stream);
+    if (s->gate_signal) (void)hipFree(s->gate_signal);
     for (hipEvent_t a : s->prof_anchor) if (a) (void)hipEventDestroy(a);
     for (Slot &sl : s->slot) {
         for (int i = 0; i < 8; ++i) if (sl.ev[i]) (void)hipEventDestroy(sl.ev[i]);
@@ -664,9 +677,24 @@ static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind, bool bo
         if (e4 != hipSuccess) return fail(CHN_E_HIP, std::string("k_minimise_probe (split) launch: ") + hipGetErrorString(e4));
         HIPCHK(hipEventRecord(sl.split_done, s->stream4));
     }
+    // The probe gate.  A batch that alternates no longer starts beside its predecessor's grid for that grid's whole life (both then run at
+    // half speed for twice as long, and the predecessor's side kernels starve under two grids): its launch waits, in its queue and not on a
+    // CU, until the gated batch before it has dispatched its last workgroup, and so fills that grid's thinning last generation.  It still
+    // queues behind batch i - 2 by stream order.  The value waited for is the last one whose writers (the grid, and k_gate_release behind
+    // it) are already enqueued: batches that launch no gated grid -- list modes, long-read batches on the first stream, re-runs --
+    // write nothing and use up no value, and this batch's own value counts only once its launch has succeeded.
+    const bool gated = !list_mode && alternate && s->gate_signal != nullptr;
+    if (gated) {
+        if (s->gate_seq) {
+            HIPCHK(hipStreamWaitValue64(ps, s->gate_signal, s->gate_seq, hipStreamWaitValueGte, ~0ull));
+            s->gated_batches += 1;
+        }
+        a.gate_started = ctl + CTL_GATE; a.gate_signal = s->gate_signal; a.gate_value = s->gate_seq + 1;
+    }
     if (prof) { HIPCHK(hipEventRecord(sl.ev[0], ps)); }
     hipError_t e = launch_k1_mode(mode, W, a, lds, ps);
     if (e != hipSuccess) return fail(CHN_E_HIP, std::string("k_minimise_probe launch: ") + hipGetErrorString(e));
+    if (gated) s->gate_seq += 1;
     if (prof) {
         // (profiling streams: the probe kernel's time is the time until BOTH its launches are done -- with long reads in the batch the SPLIT launch may
         //  carry most of the bases)
@@ -685,6 +713,10 @@ static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind, bool bo
     HIPCHK(hipEventRecord(sl.k1_done, ps));
     HIPCHK(hipStreamWaitEvent(s->stream2, sl.k1_done, 0));
     if (sl.split_bound) HIPCHK(hipStreamWaitEvent(s->stream2, sl.split_done, 0));
+    if (gated) {  // the backstop: a grid that died still releases its successor (a max: the successor's grid may have written already)
+        hipLaunchKernelGGL(k_gate_release, dim3(1), dim3(1), 0, ps, s->gate_signal, (unsigned long long)s->gate_seq);
+        HIPCHK(hipGetLastError());
+    }
     int rc = launch_tail(s, sl, sl.lb, s->stream2);
     if (rc) return rc;
     if (diag_sub) std::fprintf(stderr, "submit: validate + uploads %.2f ms, deflate tallies %.2f, ordering + probe launch %.2f, tail %.2f\n",

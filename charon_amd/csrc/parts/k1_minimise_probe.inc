@@ -62,7 +62,21 @@ struct K1Args {
     const unsigned long long *n_long_ptr;  // nullptr: no read is split
     uint32_t wave_slot0;
     unsigned long long *fetches;           // (may be null) += row fetches issued: h per minimiser, fewer with conditional probing
+    // The probe gate (ordinary launch only; both pointers null: no gate).  Every workgroup counts itself in at *gate_started (a control
+    // word of the slot, zeroed with the others); the one that finds all the others there -- the grid has no workgroup left to
+    // dispatch -- raises *gate_signal, the stream's signal word, to gate_value, this batch's sequence number.  The next batch's launch
+    // waits in its queue for exactly that (abi_stream_batch.inc).
+    unsigned long long *gate_started, *gate_signal;
+    unsigned long long gate_value;
 };
+// What a gated launch is followed by in its stream: whatever became of the grid, the signal reaches the batch's value.
+// (The signal word is host memory behind the bus, which carries add, swap and compare-and-swap only: the attribute has the compiler
+//  form the max from a compare-and-swap loop, not from an atomic the far side may never carry out.)
+__global__ void k_gate_release(unsigned long long *signal, unsigned long long value) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) [[clang::atomic(remote_memory, fine_grained_memory)]] {
+        (void)__hip_atomic_fetch_max(signal, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
 
 // Does the first window (wn canonical k-mer values) of the sequence starting at base `o` hold its minimum more than once?
 // Same rolling arithmetic as the kernel body.  A piece of a long read may start cold at `o` only if it does not (SURVEY H3).
@@ -180,6 +194,13 @@ __device__ __forceinline__ void wait_vmcnt(uint32_t n) {
 template <int W, int MODE, int WN_T, bool SPLIT = false, bool COND_T = false>
 __global__ __launch_bounds__(WAVE) void k_minimise_probe(const K1Args a) {
     extern __shared__ __align__(16) unsigned char smem[];
+    // Probe gate: arrivals are counted (workgroups are dealt round-robin over the XCDs: the last index starting says nothing about the
+    // others); max and not store, so the signal never moves backwards.  Done with before the first load the kernel counts itself.
+    if (!SPLIT && a.gate_started && threadIdx.x == 0) {
+        if (atomicAdd(a.gate_started, 1ULL) == (unsigned long long)gridDim.x - 1) [[clang::atomic(remote_memory, fine_grained_memory)]] {
+            (void)__hip_atomic_fetch_max(a.gate_signal, a.gate_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
     const uint32_t n_long = a.n_long_ptr ? (uint32_t)__builtin_nontemporal_load(a.n_long_ptr) : 0u;
     uint32_t item = blockIdx.x;
     if (SPLIT && item >= n_long) return;

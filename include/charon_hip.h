@@ -159,6 +159,10 @@ typedef struct chn_stream_cfg {
 #define CHN_STREAM_PROFILE 1u   /* bracket every kernel with HIP events (chn_stream_profile) */
 #define CHN_STREAM_TINY_LOG 2u  /* testing only: start with a deliberately undersized row log so that every batch takes the
                                  * overflow -> worst-case re-run path of chn_batch_wait */
+#define CHN_STREAM_NO_PROBE_GATE 4u /* testing only: never hold a batch's minimise+probe launch back until its predecessor has
+                                     * dispatched its last workgroup (the probe gate); consecutive batches' probe kernels then share
+                                     * the device from their first workgroup on, as they also do on a device without stream-wait-value
+                                     * support */
 /* A single-end read of 32 768 bases or more is rolled by the 64 lanes of one wavefront at once, in pieces that overlap by w - 1
  * bases (exact: a piece starts only where the window minimum is unique); shorter reads take one lane each.  Testing only:
  * CHN_STREAM_SPLIT_BUCKET(b) moves that limit to length class b (8 classes per octave: class = 8 (floor(log2 L) - 2) + the three
@@ -537,7 +541,9 @@ int chn_index_emplace(chn_index *idx, const uint64_t *host_values, uint64_t n_va
  *   several, the total is the time during which some probe kernel was running (the union of their intervals, never more than the wall
  *   time around them) and total / launches is what a batch adds to it.  *launches counts batches.  reset forgets the previous end.
  *   1, 2 and 3 are event-bracketed times of each batch on its own; 3 runs from the batch's turn on its probe stream to the end of its
- *   model+call kernel and so contains the time its probe kernel shares the device with its neighbour's;
+ *   model+call kernel and so contains the time its launch waits at the probe gate (until the batch before it has dispatched its last
+ *   workgroup: about one kernel length with three in flight) and the time its probe kernel shares the device with its neighbour's; the
+ *   brackets of 0 start behind that wait;
  * 4 (any stream): *launches = number of batches chn_batch_wait re-ran on worst-case buffers after a row-log overflow;
  * 5 (any stream): *launches = row fetches the last waited batch's minimise+probe kernel issued (h per minimiser; fewer for an index of
  *   at most four bins, whose rows are fetched one at a time and only while the AND so far still has a bin set);
@@ -547,7 +553,11 @@ int chn_index_emplace(chn_index *idx, const uint64_t *host_values, uint64_t n_va
  *   events on the copy stream; *launches = calls;
  * 9 (CHN_STREAM_PROFILE streams): chn_text_fetch's k_text_gather, timed with events on the copy stream; *launches = calls;
  * 11 (CHN_STREAM_PROFILE streams): chn_text_pair_ids' k_pair_ids, timed with events on the copy stream; *launches = calls that ran
- *   it (n_pairs > 0).  10 is not a slot: it is refused with CHN_E_INVALID like every other value. */
+ *   it (n_pairs > 0).  10 and 12 are not slots: they are refused with CHN_E_INVALID like every other value;
+ * 13 (any stream): *launches = batches whose minimise+probe launch was queued behind a probe-gate wait, i.e. held in its queue until the
+ *   batch before it had no workgroup left to dispatch (0 on a CHN_STREAM_NO_PROBE_GATE stream, on a device without stream-wait-value
+ *   support, and for batches that take the first probe stream because of long reads).  *total_ms is no time here: 1 if the stream
+ *   gates at all (the device can wait for a value in memory and the stream was not created with CHN_STREAM_NO_PROBE_GATE), else 0. */
 int chn_stream_profile(chn_stream *s, int which, double *total_ms, uint64_t *launches, int reset);
 /* Algorithmic bytes of the last batch by SURVEY 8(d): sum over reads of ceil(L/4) + M*h*W*8 + (8 + 8C). */
 int chn_stream_last_batch_bytes(chn_stream *s, uint64_t *bytes, uint64_t *total_minimisers);

@@ -7,6 +7,7 @@
 #   tools/diag/libcharon_hip_CHN_DIAG.so    -DCHN_DIAG: the library reads the CHN_* environment switches (a product build reads none), e.g.
 #       CHN_PROBE_STREAMS=1   every batch's probe kernel on one stream, as before the two probe streams (A/B of the overlap)
 #       CHN_PROBE_STREAMS=2   the two probe streams alternately for every batch, also while batches hold reads for the SPLIT launch
+#       CHN_PROBE_GATE=0      alternate without the probe gate: consecutive probe grids share the device from their first workgroup on (A/B of the gate)
 # Use with CHARON_HIP_LIB=<path> python bench.py ...
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
