@@ -85,6 +85,17 @@ class TextSplitJob(C.Structure):
                 ("n_records", C.c_uint64), ("consumed", C.c_uint64), ("ids_bytes", C.c_uint64)]
 
 
+FASTA_SPLIT_END_OF_INPUT = 1     # CHN_FASTA_SPLIT_END_OF_INPUT
+
+
+class FastaSplitJob(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("text", C.c_void_p), ("text_bytes", C.c_uint64), ("start", C.c_uint64),
+                ("max_records", C.c_uint64), ("id_offset", C.c_void_p), ("id_length", C.c_void_p), ("seq_offset", C.c_void_p),
+                ("seq_length", C.c_void_p), ("seq_text", C.c_void_p), ("seq_capacity", C.c_uint64), ("ids", C.c_void_p),
+                ("ids_capacity", C.c_uint64), ("n_records", C.c_uint64), ("consumed", C.c_uint64), ("ids_bytes", C.c_uint64),
+                ("seq_bytes", C.c_uint64)]
+
+
 class TextFetchJob(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("text", C.c_void_p), ("text_bytes", C.c_uint64), ("n_ranges", C.c_uint64),
                 ("offset", C.c_void_p), ("length", C.c_void_p), ("out", C.c_void_p), ("out_capacity", C.c_uint64), ("out_bytes", C.c_uint64)]
@@ -146,7 +157,7 @@ EXPORTS = ["chn_index_create", "chn_index_upload_rows", "chn_index_device_words"
            "chn_model_set", "chn_batch_submit", "chn_batch_wait", "chn_stream_sync", "chn_classify_counts", "chn_classify_counts_raw", "chn_stream_profile",
            "chn_stream_last_batch_bytes", "chn_synth_genomes", "chn_synth_fill_index", "chn_synth_plant", "chn_synth_reads",
            "chn_device_free", "chn_device_download", "chn_device_malloc", "chn_device_upload", "chn_host_alloc", "chn_host_free", "chn_shard_minimise",
-           "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_text_submit", "chn_text_wait", "chn_text_pack", "chn_text_split", "chn_text_split_host", "chn_text_fetch", "chn_text_fetch_host", "chn_text_pair_ids", "chn_text_pair_ids_host", "chn_device_copy", "chn_inflate_create", "chn_inflate_run",
+           "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_text_submit", "chn_text_wait", "chn_text_pack", "chn_text_split", "chn_text_split_host", "chn_fasta_split", "chn_fasta_split_host", "chn_text_fetch", "chn_text_fetch_host", "chn_text_pair_ids", "chn_text_pair_ids_host", "chn_device_copy", "chn_inflate_create", "chn_inflate_run",
            "chn_inflate_run_host", "chn_inflate_destroy", "chn_inflate_kernel_ms", "chn_inflate_run_crc", "chn_inflate_run_host_crc", "chn_deflate_create", "chn_deflate_run", "chn_deflate_run_host",
            "chn_deflate_destroy", "chn_deflate_bound", "chn_deflate_kernel_ms", "chn_deflate_group_members", "chn_extract_create", "chn_extract_destroy",
            "chn_extract_bound", "chn_extract_append_records", "chn_extract_append_bytes", "chn_extract_finish", "chn_extract_records_host",
@@ -203,6 +214,8 @@ _L.chn_text_wait.argtypes = [C.c_void_p, C.POINTER(Result), C.POINTER(TextResult
 _L.chn_text_pack.argtypes = [C.c_void_p, C.c_void_p] + [C.c_void_p] * 5 + [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
 _L.chn_text_split.argtypes = [C.c_void_p, C.POINTER(TextSplitJob)]
 _L.chn_text_split_host.argtypes = [C.POINTER(TextSplitJob)]
+_L.chn_fasta_split.argtypes = [C.c_void_p, C.POINTER(FastaSplitJob)]
+_L.chn_fasta_split_host.argtypes = [C.POINTER(FastaSplitJob)]
 _L.chn_text_fetch.argtypes = [C.c_void_p, C.POINTER(TextFetchJob)]
 _L.chn_text_fetch_host.argtypes = [C.POINTER(TextFetchJob)]
 _L.chn_text_pair_ids.argtypes = [C.c_void_p, C.POINTER(TextPairJob)]
@@ -576,6 +589,13 @@ class Stream:
         _chk(_L.chn_text_split(self.h, C.byref(j)))
         return _text_split_results(j, a)
 
+    def fasta_split(self, dev_ptr, nbytes, seq_ptr, seq_capacity, start=0, max_records=None, want_ids=True, ids_capacity=None, end_of_input=False):
+        """chn_fasta_split: the FASTA records of device text [start, nbytes), their letters unwrapped into the device buffer at seq_ptr
+        -- see fasta_split_host for what comes back (seq_text stays on the device and is not part of it)"""
+        j, a = fasta_split_job(dev_ptr, nbytes, seq_ptr, seq_capacity, start, max_records, want_ids, ids_capacity, end_of_input)
+        _chk(_L.chn_fasta_split(self.h, C.byref(j)))
+        return _fasta_split_results(j, a)
+
     def text_fetch(self, dev_ptr, nbytes, offsets, lengths, out=None, out_capacity=None):
         """chn_text_fetch: the byte ranges of device text [0, nbytes) back to back -- see text_fetch_host for what comes back"""
         j, keep = text_fetch_job(dev_ptr, nbytes, offsets, lengths, out, out_capacity)
@@ -696,6 +716,58 @@ def text_split_host(data, start=0, max_records=None, want_ids=True, ids_capacity
     j, a = text_split_job(buf.ctypes.data if buf.size else None, nbytes, start, max_records, want_ids, ids_capacity)
     _chk(_L.chn_text_split_host(C.byref(j)))
     return _text_split_results(j, a)
+
+
+# ---- FASTA records of a text (see include/charon_hip.h) ----
+FASTA_KEYS = ("id_offset", "id_length", "seq_offset", "seq_length")
+
+
+def fasta_split_job(text_ptr, nbytes, seq_ptr, seq_capacity, start=0, max_records=None, want_ids=True, ids_capacity=None, end_of_input=False):
+    """the chn_fasta_split_job of the text at `text_ptr` with the letters going to `seq_ptr`.  max_records defaults to the most records
+    the text can hold (one per 3 bytes: callers with large texts pass what they expect), ids_capacity to the bytes behind `start`.
+    Returns (job, arrays)."""
+    nbytes, start = int(nbytes), int(start)
+    if max_records is None:
+        max_records = max(nbytes - start, 0) // 3
+    m = max(int(max_records), 1)
+    a = dict(id_offset=np.zeros(m, np.uint64), id_length=np.zeros(m, np.uint32), seq_offset=np.zeros(m, np.uint64),
+             seq_length=np.zeros(m, np.uint32), ids=None)
+    j = FastaSplitJob()
+    j.struct_size, j.flags, j.text, j.text_bytes = C.sizeof(FastaSplitJob), FASTA_SPLIT_END_OF_INPUT if end_of_input else 0, text_ptr, nbytes
+    j.start, j.max_records, j.seq_text, j.seq_capacity = start, int(max_records), seq_ptr, int(seq_capacity)
+    for k in FASTA_KEYS:
+        setattr(j, k, a[k].ctypes.data)
+    if want_ids:
+        cap = max(nbytes - start, 0) if ids_capacity is None else int(ids_capacity)
+        a["ids"] = np.zeros(max(cap, 1), np.uint8)
+        j.ids, j.ids_capacity = a["ids"].ctypes.data, cap
+    return j, a
+
+
+def _fasta_split_results(j, a):
+    n = int(j.n_records)
+    out = {k: a[k][:n].copy() for k in FASTA_KEYS}
+    out.update(n_records=n, consumed=int(j.consumed), ids_bytes=int(j.ids_bytes), seq_bytes=int(j.seq_bytes),
+               ids=a["ids"][:int(j.ids_bytes)].tobytes() if a["ids"] is not None else None)
+    return out
+
+
+def fasta_split_host(data, start=0, max_records=None, want_ids=True, ids_capacity=None, nbytes=None, end_of_input=False, seq_capacity=None):
+    """chn_fasta_split_host: the rule the GPU runs, on the CPU, over `data` (bytes or a uint8 array).  Returns a dict: n_records,
+    consumed, ids_bytes, seq_bytes, the descriptor arrays id_offset / id_length / seq_offset / seq_length cut to n_records, ids (the id
+    bytes back to back, None without want_ids), seq_text (the letters of the taken records back to back, as bytes) and seq_tail_untouched."""
+    buf = np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, np.uint8)
+    nbytes = buf.size if nbytes is None else nbytes
+    if seq_capacity is None:
+        seq_capacity = (max(nbytes - start, 0) + 15) & ~15
+    seq = np.full(max(int(seq_capacity), 1), 0xA5, np.uint8)
+    j, a = fasta_split_job(buf.ctypes.data if buf.size else None, nbytes, seq.ctypes.data, seq_capacity, start, max_records, want_ids, ids_capacity,
+                           end_of_input)
+    _chk(_L.chn_fasta_split_host(C.byref(j)))
+    out = _fasta_split_results(j, a)
+    out["seq_text"] = seq[:out["seq_bytes"]].tobytes()
+    out["seq_tail_untouched"] = bool((seq[out["seq_bytes"]:] == 0xA5).all())  # the buffer was filled with 0xA5: nothing behind the letters is written
+    return out
 
 
 # ---- byte ranges of a text (see include/charon_hip.h) ----

@@ -62,6 +62,7 @@
 #include "parts/gzip_tally_long.inc"
 #include "parts/text_pack.inc"
 #include "parts/text_split.inc"
+#include "parts/fasta_split.inc"
 #include "parts/text_gather.inc"
 #include "parts/text_pair.inc"
 #include "parts/extract_records.inc"
@@ -73,6 +74,7 @@
 #include "parts/abi_stream_batch.inc"
 #include "parts/abi_shard_wait.inc"
 #include "parts/abi_text_split.inc"
+#include "parts/abi_fasta_split.inc"
 #include "parts/abi_text_fetch.inc"
 #include "parts/abi_text_pair.inc"
 #include "parts/abi_text_batch.inc"

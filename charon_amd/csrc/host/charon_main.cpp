@@ -435,6 +435,14 @@ int main(int argc, char **argv) {
         if (v == "1" && !g_gpu_text) { std::cerr << "charon: CHARON_GPU_TEXT_PAIRS: takes effect only together with CHARON_GPU_TEXT=1, which is not set" << std::endl; return 1; }
         g_gpu_text_pairs = v == "1";
     }
+    if (const char *e = std::getenv("CHARON_GPU_TEXT_FASTA")) {
+        // CHARON_GPU_TEXT_FASTA: 1 (only together with CHARON_GPU_TEXT=1) = single-end BGZF FASTA stays in device memory as well: records
+        // found and unwrapped by chn_fasta_split; 0 or unset = not.  Checked before the index file is opened and before any HIP call.
+        const std::string v(e);
+        if (v != "0" && v != "1") { std::cerr << "charon: CHARON_GPU_TEXT_FASTA: '" << v << "' is neither 0 nor 1" << std::endl; return 1; }
+        if (v == "1" && !g_gpu_text) { std::cerr << "charon: CHARON_GPU_TEXT_FASTA: takes effect only together with CHARON_GPU_TEXT=1, which is not set" << std::endl; return 1; }
+        g_gpu_text_fasta = v == "1";
+    }
     if (const char *e = std::getenv("CHARON_GPU_EXTRACT")) {
         // CHARON_GPU_EXTRACT: 1 (only together with CHARON_GPU_TEXT=1 and CHARON_GPU_DEFLATE=1) = under --extract the records of the reads the
         // device-resident loop calls are formed and compressed in device memory (chn_extract); 0 or unset = not.  Checked before the index

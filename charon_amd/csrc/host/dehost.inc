@@ -122,12 +122,14 @@ int dehost_main(DehostArguments &opt) {
     Slab resume_carry[2];
     BlockQueue side_queue[2];
     std::thread side_reader[2];
+    // (CHARON_GPU_TEXT_BLOCK: test hook, a smaller block -- down to one BGZF member's 64 KiB)
+    size_t resident_block_bytes = std::min<size_t>((size_t)std::min<uint64_t>(256ULL << 20, std::max<uint64_t>(1 << 20, opt.batch_bases)), (size_t)64 << 20);
+    if (const char *e = std::getenv("CHARON_GPU_TEXT_BLOCK")) resident_block_bytes = (size_t)std::min<unsigned long long>(resident_block_bytes, std::max<unsigned long long>(65536, std::strtoull(e, nullptr, 10)));
     auto side_reader_body = [&](int k) {
         BlockQueue &q = side_queue[k];
         try {
             BlockReader in(k ? opt.read_file2 : opt.read_file);
-            const size_t max_bytes = (size_t)std::min<uint64_t>(256ULL << 20, std::max<uint64_t>(1 << 20, opt.batch_bases));
-            const size_t block_bytes = std::min<size_t>(max_bytes, (size_t)64 << 20);
+            const size_t block_bytes = resident_block_bytes;
             for (;;) {
                 std::shared_ptr<HostBatch> hb(new HostBatch());
                 hb->dtext = in.next_device(block_bytes, g_gpu_text_headroom);
@@ -181,6 +183,18 @@ int dehost_main(DehostArguments &opt) {
         if (!BgzfSource().open(f)) return "one deflate stream, not BGZF";
         return "";
     };
+    // why CHARON_GPU_TEXT_FASTA=1 cannot take `f` (empty: it can): FASTA by name, as BlockReader decides it
+    auto not_resident_fasta_because = [](const std::string &f) -> std::string {
+        const std::string stem = f.substr(0, f.size() - std::min<size_t>(3, f.size()));
+        if (!ends_with(f, ".gz")) return "not a .gz file";
+        if (std::getenv("CHARON_NO_BGZF")) return "CHARON_NO_BGZF is set";
+        bool fasta = false;
+        for (const char *x : {".fasta", ".fa", ".fna", ".ffn", ".faa", ".frn", ".fas"}) fasta = fasta || ends_with(stem, x);
+        if (!fasta) return "not FASTA";
+        if (!BgzfSource().open(f)) return "one deflate stream, not BGZF";
+        return "";
+    };
+    bool fasta_side = false;  // CHARON_GPU_TEXT_FASTA=1 took the input: the one side is a FASTA file
     // no side, one (single-end input) or two (CHARON_GPU_TEXT_PAIRS=1 and a pair of files)
     if (g_gpu_text) {
         bool two = false;
@@ -192,13 +206,20 @@ int dehost_main(DehostArguments &opt) {
             two = why.empty();
             if (!two) g_log.info("CHARON_GPU_TEXT_PAIRS=1 does not apply to " + file + " (" + why + "; both files must be BGZF FASTQ): the run goes on without it");
         }
-        const std::string why = two ? "" : opt.is_paired ? "paired input" : not_resident_because(opt.read_file);
+        std::string why = two ? "" : opt.is_paired ? "paired input" : not_resident_because(opt.read_file);
+        if (g_gpu_text_fasta) {
+            const std::string fwhy = opt.is_paired ? "paired input" : not_resident_fasta_because(opt.read_file);
+            fasta_side = fwhy.empty();
+            if (fasta_side) why.clear();
+            else g_log.info("CHARON_GPU_TEXT_FASTA=1 does not apply to " + opt.read_file + " (" + fwhy + "; single-end BGZF FASTA only): the run goes on as under CHARON_GPU_TEXT=1 alone");
+        }
         if (why.empty()) {
             n_sides = two ? 2 : 1;
             if (const char *e = std::getenv("CHARON_GPU_TEXT_HEADROOM")) g_gpu_text_headroom = (size_t)std::min<unsigned long long>(1ULL << 30, std::strtoull(e, nullptr, 10));
-            if (two) g_dev_text_pool.keep = 8;
+            if (two || fasta_side) g_dev_text_pool.keep = 8;
             g_log.info("CHARON_GPU_TEXT=1: BGZF text is inflated into the memory of device " + std::to_string(g_gpu_text_device) +
                        " and stays there (records split and packed on the device; headroom " + std::to_string(g_gpu_text_headroom) + " bytes)");
+            if (fasta_side) g_log.info("CHARON_GPU_TEXT_FASTA=1: FASTA records are found and unwrapped on the device (a second buffer per block holds the letters)");
             if (two) g_log.info("CHARON_GPU_TEXT_PAIRS=1: both files of the pair stay in device memory (two texts a batch; the ids of a pair are compared on the device)");
         } else {
             g_log.info("CHARON_GPU_TEXT=1 does not apply to " + opt.read_file + " (" + why + "; single-end BGZF FASTQ only): the run goes on without it");
@@ -210,6 +231,9 @@ int dehost_main(DehostArguments &opt) {
             g_gpu_extract = false;
         } else if (!n_sides) {
             g_log.info("CHARON_GPU_EXTRACT=1 does not apply (the input is not taken by the device-resident loop of CHARON_GPU_TEXT=1): the run goes on without it");
+            g_gpu_extract = false;
+        } else if (fasta_side) {
+            g_log.info("CHARON_GPU_EXTRACT=1 does not apply (FASTA input: extract records are formed on the device for FASTQ only): the run goes on without it");
             g_gpu_extract = false;
         } else {
             g_log.info("CHARON_GPU_EXTRACT=1: the records of the extract files are formed and compressed in the memory of device " + std::to_string(g_gpu_text_device));
@@ -1007,6 +1031,41 @@ int dehost_main(DehostArguments &opt) {
         if (ids_bytes) *ids_bytes = ids_used;
         return consumed;
     };
+    // The same for a FASTA block (CHARON_GPU_TEXT_FASTA=1): chn_fasta_split unwraps the letters of the records it takes into `letters`,
+    // a buffer of blk's capacity, and `sink` gets sequence offsets into THAT buffer (and no quality offset).  A block with more than
+    // kSplitRecords records takes several calls; each writes behind the letters of the one before, from the next multiple of 16 on.
+    // (Room: a call that stops at the bound has dropped at least ">\n" of each of its 2^18 records, so the letters end more than
+    // 512 KiB below the text they came from.)  `eoi`: no text follows, the end counts as the last record's end.
+    auto split_fasta_block = [&](const DevBlock &blk, DevBlock &letters, uint64_t start, bool eoi, HostBatch &hb,
+                                 const std::function<void(const char *, uint32_t, uint32_t, uint64_t, uint64_t, uint64_t)> &sink, uint64_t *ids_bytes) -> uint64_t {
+        const uint64_t end = blk.text_bytes;
+        uint64_t consumed = start, ids_used = 0, base = 0;
+        hb.ids.reset(new char[end - start + 1]);
+        if (ido.empty()) { ido.resize(kSplitRecords); sqo.resize(kSplitRecords); qlo.resize(kSplitRecords); idl.resize(kSplitRecords); sql.resize(kSplitRecords); }
+        letters.text_bytes = 0;
+        for (;;) {
+            chn_fasta_split_job job;
+            std::memset(&job, 0, sizeof job);
+            job.struct_size = sizeof job; job.flags = eoi ? CHN_FASTA_SPLIT_END_OF_INPUT : 0;
+            job.text = blk.buf; job.text_bytes = end; job.start = consumed; job.max_records = kSplitRecords;
+            job.id_offset = ido.data(); job.id_length = idl.data(); job.seq_offset = sqo.data(); job.seq_length = sql.data();
+            job.seq_text = letters.buf + base; job.seq_capacity = letters.cap - base;
+            job.ids = reinterpret_cast<uint8_t *>(hb.ids.get()) + ids_used; job.ids_capacity = end - start - ids_used;
+            CHN_CHECK(chn_fasta_split(stream, &job));
+            const char *id = hb.ids.get() + ids_used;
+            for (uint64_t i = 0; i < job.n_records; ++i) {
+                sink(id, idl[i], sql[i], ido[i], base + sqo[i], 0);
+                id += idl[i];
+            }
+            ids_used += job.ids_bytes;
+            consumed = job.consumed;
+            letters.text_bytes = base + job.seq_bytes;
+            base += (job.seq_bytes + 15) & ~15ULL;
+            if (job.n_records < kSplitRecords) break;
+        }
+        if (ids_bytes) *ids_bytes = ids_used;
+        return consumed;
+    };
     // The loop over `n_sides` files: one (single-end) or two (CHARON_GPU_TEXT_PAIRS=1).  Each side (file) keeps its current block, the
     // descriptors of the records that are split but not yet in a batch, and `consumed`.  A side with no such record left takes its next
     // block (the tail of the block before carried in front of it); a side that still has some does not, so files with records of unequal
@@ -1021,6 +1080,7 @@ int dehost_main(DehostArguments &opt) {
         struct Side {
             std::shared_ptr<HostBatch> hb;   // the block's holder: owns the id bytes its records' views point into
             std::shared_ptr<DevBlock> blk;   // the current block (kept at the end of the file: leaving the mode resumes behind it)
+            std::shared_ptr<DevBlock> letters;  // CHARON_GPU_TEXT_FASTA=1: the unwrapped letters of blk's records; seq_off are offsets into it
             std::vector<uint64_t> id_off, seq_off, qual_off;  // records split from `blk`; those from `head` on are not yet paired
             std::vector<uint32_t> id_len, seq_len;
             std::vector<const char *> id;    // the id bytes (null where they did not come down)
@@ -1036,7 +1096,7 @@ int dehost_main(DehostArguments &opt) {
         auto stop_side_readers = [&]() {
             for (int s = 0; s < n_sides; ++s) side_queue[s].abort();
             for (int s = 0; s < n_sides; ++s) if (side_reader[s].joinable()) side_reader[s].join();
-            for (int s = 0; s < n_sides; ++s) { side[s].hb.reset(); side[s].blk.reset(); }
+            for (int s = 0; s < n_sides; ++s) { side[s].hb.reset(); side[s].blk.reset(); side[s].letters.reset(); }
         };
         // Leaving the mode because of side k: every flight retired, each side's text from behind its last paired record downloaded, the
         // side readers stopped, and the host reader started with every file resumed.  That text and the rest of the files go through the
@@ -1055,7 +1115,8 @@ int dehost_main(DehostArguments &opt) {
             const Side &sk = side[k];
             g_log.info("CHARON_GPU_TEXT=1: leaving the device-resident path at byte " + std::to_string(sk.blk->file_offset + sk.consumed - sk.blk->member0) +
                        " of the inflated file " + (two ? (k ? opt.read_file2 : opt.read_file) + " " : "") +
-                       "(text that is no plain four-line record): the host parser goes on from there");
+                       (fasta_side ? "(text that is no FASTA record the device takes, or a record longer than a block)" : "(text that is no plain four-line record)") +
+                       ": the host parser goes on from there");
             stop_side_readers();
             g_gpu_inflate = true; g_gpu_inflate_device = dev; g_pin_slabs = true;  // inflate as under CHARON_GPU_INFLATE=1 from here on
             reader = std::thread(reader_body);
@@ -1083,14 +1144,40 @@ int dehost_main(DehostArguments &opt) {
             const bool want_ids = k == 0 || (opt.run_extract && !g_gpu_extract);
             sd.id_off.clear(); sd.seq_off.clear(); sd.qual_off.clear(); sd.id_len.clear(); sd.seq_len.clear(); sd.id.clear(); sd.head = 0;
             uint64_t ids_bytes = 0;
-            const uint64_t consumed = split_block(*blk, start, want_ids, hb, [&](const char *id, uint32_t id_len, uint32_t seq_len, uint64_t io, uint64_t so, uint64_t qo) {
+            const auto sink = [&](const char *id, uint32_t id_len, uint32_t seq_len, uint64_t io, uint64_t so, uint64_t qo) {
                 sd.id.push_back(id); sd.id_len.push_back(id_len); sd.seq_len.push_back(seq_len);
                 sd.id_off.push_back(io); sd.seq_off.push_back(so); sd.qual_off.push_back(qo);
-            }, &ids_bytes);
+            };
+            if (fasta_side) {  // a buffer of the block's size for the letters: of the pool where the block's is
+                sd.letters.reset(new DevBlock());
+                DevBlock &lt = *sd.letters;
+                lt.cap = blk->cap;
+                if (blk->pooled) { lt.buf = static_cast<uint8_t *>(g_dev_text_pool.take(lt.cap)); lt.pooled = true; }
+                else { void *p = nullptr; CHN_CHECK(chn_device_malloc(dev, lt.cap, &p)); lt.buf = static_cast<uint8_t *>(p); }
+            }
+            const uint64_t consumed = fasta_side ? split_fasta_block(*blk, *sd.letters, start, blk->last, hb, sink, &ids_bytes)
+                                                 : split_block(*blk, start, want_ids, hb, sink, &ids_bytes);
             if (k == 1) dp_id2_bytes += ids_bytes;
             t_split += now() - tk;
             dt_split_records += sd.id_off.size();
             sd.hb = hbp; sd.blk = blk; sd.consumed = consumed; sd.paired_end = start;
+            if (fasta_side) {
+                // At the end of the file everything is taken unless the rule failed.  Before it, text is left over behind the last record
+                // taken (at least its successor's header), which the next block completes -- unless no record was taken at all: then
+                // the text at `consumed` is no header line, or its record is empty (a second header line follows), or the record does
+                // not end in this text; that one is carried on while it is shorter than a block
+                if (consumed >= end) return false;
+                if (blk->last) return true;
+                if (!sd.id_off.empty()) return false;
+                Slab tail_text((size_t)(end - consumed));
+                CHN_CHECK(chn_device_download(dev, tail_text.data(), blk->buf + consumed, end - consumed));
+                const char *t = tail_text.data(), *te = t + tail_text.size();
+                if (*t != '>' && *t != ';') return true;
+                for (const char *nl = static_cast<const char *>(std::memchr(t, '\n', (size_t)(te - t))); nl && nl + 1 < te;
+                     nl = static_cast<const char *>(std::memchr(nl + 1, '\n', (size_t)(te - nl - 1))))
+                    if (nl[1] == '>' || nl[1] == ';') return true;
+                return end - consumed >= resident_block_bytes;
+            }
             // no record although four line feeds follow `start` (a wrapped record, a blank line, a damaged record), or bytes behind the
             // last record at the end of the file (a last line without a line feed)
             if (consumed < end && (sd.id_off.empty() || blk->last)) {
@@ -1140,7 +1227,8 @@ int dehost_main(DehostArguments &opt) {
                 recs.resize(cnt);
                 for (size_t i = 0; i < cnt; ++i) {
                     RecView r;
-                    r.id = sd.id[sd.head + i]; r.id_len = r.id ? sd.id_len[sd.head + i] : 0; r.seq_len = r.qual_len = sd.seq_len[sd.head + i];
+                    r.id = sd.id[sd.head + i]; r.id_len = r.id ? sd.id_len[sd.head + i] : 0; r.seq_len = sd.seq_len[sd.head + i];
+                    r.qual_len = fasta_side ? 0 : r.seq_len;
                     recs[i] = r;
                 }
             };
@@ -1162,8 +1250,9 @@ int dehost_main(DehostArguments &opt) {
             columns(s1, sub.len1, sub.so1, sub.qo1, sub.ql1, sub.io1, sub.il1);
             if (two) columns(s2, sub.len2, sub.so2, sub.qo2, sub.ql2, sub.io2, sub.il2);
             else { sub.so2.clear(); sub.qo2.clear(); sub.ql2.clear(); }
-            sub.text_quals = true; sub.text_from_slab = false;
-            sub.dtext = s1.blk;
+            sub.text_quals = !fasta_side; sub.text_from_slab = false;
+            if (fasta_side) sub.ql1.assign(n, 0);  // (no quality string: the ranges fetch_letters asks for them are empty)
+            sub.dtext = fasta_side ? s1.letters : s1.blk;
             if (two) sub.dtext2 = s2.blk;
             t_pack += now() - tk;
             for (int k = 0; k < n_sides; ++k) {

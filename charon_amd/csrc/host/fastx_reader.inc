@@ -94,6 +94,9 @@ uint64_t g_gpu_text_inflated = 0;              // text bytes inflated into devic
 // CHARON_GPU_TEXT_PAIRS=1 (with CHARON_GPU_TEXT=1; paired BGZF FASTQ): each file has a reader thread of its own that fills device
 // buffers, so the counters the readers add to are guarded, and twice as many buffers exist (below)
 bool g_gpu_text_pairs = false;
+// CHARON_GPU_TEXT_FASTA=1 (with CHARON_GPU_TEXT=1; single-end BGZF FASTA): the same loop with chn_fasta_split in place of chn_text_split.
+// Every block has a second buffer of the pool for the unwrapped letters, which is the text the batches are submitted and fetched from.
+bool g_gpu_text_fasta = false;
 std::mutex g_reader_stat_m;
 // The buffers go round: the reader fills one while two wait in the queue, the main thread splits one and up to two batches in flight
 // refer to theirs.  All have one size, so any free one fits; more than four free ones are not kept.

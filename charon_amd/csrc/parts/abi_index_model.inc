@@ -247,6 +247,7 @@ struct chn_stream {
     double text_ms[2] = {0, 0};  // text batches of a profiling stream: upload of the text, pack kernels
     uint64_t text_n = 0;
     TextSplitScratch tsp;
+    TextSplitScratch fsp;  // chn_fasta_split's (abi_fasta_split.inc): tile summaries and sums in d_tile, header ranks in d_line
     TextFetchScratch txg;
     TextPairScratch tpi;
 };

@@ -354,7 +354,13 @@ extern "C" int chn_classify_counts(chn_stream *s, uint64_t n, const uint32_t *nu
 }
 
 extern "C" int chn_stream_profile(chn_stream *s, int which, double *total_ms, uint64_t *launches, int reset) {
-    if (!s || which < 0 || which > 13 || which == 10 || which == 12) return fail(CHN_E_INVALID, "chn_stream_profile: bad argument");
+    if (!s || which < 0 || which > 14 || which == 10 || which == 12) return fail(CHN_E_INVALID, "chn_stream_profile: bad argument");
+    if (which == 14) {  // chn_fasta_split: its kernels in front of the first wait
+        if (total_ms) *total_ms = s->fsp.ms;
+        if (launches) *launches = s->fsp.calls;
+        if (reset) { s->fsp.ms = 0; s->fsp.calls = 0; }
+        return CHN_OK;
+    }
     if (which == 13) {  // batches whose ordinary probe launch was queued behind a probe-gate wait
         if (total_ms) *total_ms = s->gate_signal ? 1.0 : 0.0;  // (no time: whether this stream gates at all)
         if (launches) *launches = s->gated_batches;

@@ -158,6 +158,7 @@ extern "C" int chn_stream_destroy(chn_stream *s) {
     s->big.release();
     s->shx.release();
     s->tsp.release();
+    s->fsp.release();
     s->txg.release();
     s->tpi.release();
     delete s;

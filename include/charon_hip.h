@@ -405,6 +405,58 @@ typedef struct chn_text_split_job {
 int chn_text_split(chn_stream *s, chn_text_split_job *job);   /* synchronous */
 int chn_text_split_host(chn_text_split_job *job);             /* the same rule source on the CPU; no GPU needed */
 
+/* ---- FASTA records found and unwrapped in a text that lies in device memory (no reference counterpart: the reference parses
+ * through seqan3 on the CPU) -------------------------------------------------------------------------------------------------------
+ * What chn_text_split is for FASTQ, for FASTA: with chn_inflate_run's CHN_INFLATE_OUT_DEVICE in front and CHN_TEXT_ON_DEVICE behind,
+ * the text never leaves device memory.  A FASTA sequence is spread over many lines, so besides finding the records the call UNWRAPS
+ * them: the letters of the taken records are written back to back into a second device buffer, `seq_text`, which is what the caller
+ * then submits as the text of a CHN_TEXT_ON_DEVICE batch (seq_offset / seq_length as seq1_*, no quality arrays).
+ * THE RECORD RULE -- exactly what the front end's BlockReader::parse_fasta produces from a record boundary on (and with it what
+ * seqan3::sequence_file_input gives the reference for a FASTA file: lines starting with '>' or ';' are id lines, blanks and digits
+ * inside sequence lines are skipped).  Lines end at '\n' inside [start, text_bytes).
+ *   - A HEADER LINE is a line whose first byte is '>' or ';'.  Record i runs from header line i up to the next header line.
+ *   - The id is what follows the first byte up to the line feed, minus one trailing '\r' (it may be empty).
+ *   - The sequence is the bytes of the lines between the two header lines, in order, without '\n', '\r', ' ', '\t' and '0' .. '9'.
+ *   - A record is taken if and only if its first byte begins a header line, the header's line feed lies in the text, the next header
+ *     line begins inside the text, and the compacted sequence has length >= 1.
+ * With CHN_FASTA_SPLIT_END_OF_INPUT the end of the text counts as a following header line, and as the line end of a last line that
+ * has no line feed: the last record of a file is taken too (parse_fasta at the end of its file).
+ * Records are taken from `start` one after another until the rule fails or max_records is reached.  An empty record, a text that does
+ * not begin with a header (leading blank lines included) and a record with no header behind it end the run; everything from
+ * `consumed` on is the caller's business, as with chn_text_split.  `consumed` is the offset of the first record not taken
+ * (text_bytes if everything was taken under the flag, `start` if nothing was).
+ * Descriptors: record i has its id at text[id_offset[i] .. + id_length[i]) and its letters at seq_text[seq_offset[i] .. +
+ * seq_length[i]); seq_offset[0] = 0, seq_offset[i + 1] = seq_offset[i] + seq_length[i], seq_bytes is the total.  Ids come back as
+ * from chn_text_split.
+ * `text` follows the DEVICE TEXT CONTRACT above.  So does `seq_text`: device memory of the stream's device, 16-byte aligned,
+ * seq_capacity a multiple of 16 and at least text_bytes - start rounded up to 16 (a smaller one is CHN_E_CAPACITY); it must not
+ * overlap `text`.  Nothing at or behind seq_bytes rounded up to 16 is written.  The descriptor arrays and `ids` are HOST memory.
+ * chn_fasta_split is SYNCHRONOUS and keeps chn_text_split's conventions: its kernels run on the stream's copy stream (a summary per
+ * 4 KiB tile, a one-workgroup scan that resolves the line running into every tile, header ranks, one lane per candidate record, the
+ * compaction of the letters through LDS into aligned 16-byte stores, id scan and gather), it waits for the four output words and then
+ * for the descriptors and ids.  Batches in flight on the stream are not disturbed, but there must be fewer than three.  Its scratch is
+ * the stream's, grow-only: 52 bytes per 4 KiB of text, and 40 bytes per record of the bound min(max_records, (text_bytes - start) / 3).
+ * chn_fasta_split_host runs the same rule source sequentially on the CPU over HOST text and a HOST seq_text of any alignment.
+ * Errors: CHN_E_INVALID for a wrong struct_size, an unknown flag, start > text_bytes, a NULL descriptor array with max_records > 0,
+ * seq_text overlapping text, text or seq_text that is not device memory of the stream's device or misaligned, a seq_capacity that is
+ * no multiple of 16 (device call), three batches in flight; CHN_E_CAPACITY for text_bytes above CHN_TEXT_SPLIT_MAX_BYTES, a
+ * seq_capacity below text_bytes - start rounded up to 16, and ids_capacity below ids_bytes (the message names the bytes needed).  On an
+ * error no output is defined and nothing stays queued. */
+#define CHN_FASTA_SPLIT_END_OF_INPUT 1u
+typedef struct chn_fasta_split_job {
+    uint32_t struct_size, flags;                 /* flags: 0 or CHN_FASTA_SPLIT_END_OF_INPUT */
+    const uint8_t *text; uint64_t text_bytes;    /* DEVICE memory on the stream's device (chn_fasta_split_host: HOST) */
+    uint64_t start;                              /* records are looked for from this byte on; it is a record boundary */
+    uint64_t max_records;                        /* capacity of the arrays below */
+    uint64_t *id_offset;  uint32_t *id_length;   /* [max_records] HOST out; offsets are bytes into `text` */
+    uint64_t *seq_offset; uint32_t *seq_length;  /* [max_records] HOST out; offsets are bytes into `seq_text` */
+    uint8_t *seq_text; uint64_t seq_capacity;    /* DEVICE out (chn_fasta_split_host: HOST): the letters of the taken records back to back */
+    uint8_t *ids; uint64_t ids_capacity;         /* HOST out or NULL: the id bytes back to back, id i at sum(id_length[0..i)) */
+    uint64_t n_records, consumed, ids_bytes, seq_bytes;   /* out */
+} chn_fasta_split_job;
+int chn_fasta_split(chn_stream *s, chn_fasta_split_job *job);   /* synchronous */
+int chn_fasta_split_host(chn_fasta_split_job *job);             /* the same rule source on the CPU; no GPU needed */
+
 /* ---- byte ranges of a text that lies in device memory, fetched into host memory (no reference counterpart) ------------------------
  * What a caller of the chain above uses for the few records whose letters it needs on the host after all (a gzip ratio the device
  * left open, a record to be written out): range i is text[offset[i] .. + length[i]) and goes to out + sum(length[0 .. i)), so the
@@ -557,7 +609,9 @@ int chn_index_emplace(chn_index *idx, const uint64_t *host_values, uint64_t n_va
  * 13 (any stream): *launches = batches whose minimise+probe launch was queued behind a probe-gate wait, i.e. held in its queue until the
  *   batch before it had no workgroup left to dispatch (0 on a CHN_STREAM_NO_PROBE_GATE stream, on a device without stream-wait-value
  *   support, and for batches that take the first probe stream because of long reads).  *total_ms is no time here: 1 if the stream
- *   gates at all (the device can wait for a value in memory and the stream was not created with CHN_STREAM_NO_PROBE_GATE), else 0. */
+ *   gates at all (the device can wait for a value in memory and the stream was not created with CHN_STREAM_NO_PROBE_GATE), else 0;
+ * 14 (CHN_STREAM_PROFILE streams): chn_fasta_split's kernels in front of its first wait (tiles, resolve, scans, headers, records,
+ *   compaction, id scan), timed with events on the copy stream; *launches = calls. */
 int chn_stream_profile(chn_stream *s, int which, double *total_ms, uint64_t *launches, int reset);
 /* Algorithmic bytes of the last batch by SURVEY 8(d): sum over reads of ceil(L/4) + M*h*W*8 + (8 + 8C). */
 int chn_stream_last_batch_bytes(chn_stream *s, uint64_t *bytes, uint64_t *total_minimisers);
