@@ -1,6 +1,7 @@
 """The member set of the inflate tests (tests/test_inflate_cpu.py, tests/test_gpu_inflate.py): small raw deflate members made with
 Python's zlib or a bit writer, and the yardstick that says which of them a decoder must accept -- Python's zlib, never the code under
-test.  Everything is seeded, so both test files see the same bytes."""
+test.  Everything is seeded, so both test files see the same bytes.  crafted_set / crafted_sweep / foreign_set further down are the
+members zlib's deflate never writes: made with tests/deflate_writer.py, or by libdeflate (tests/golden/foreign_members.bin)."""
 import functools
 import random
 import zlib
@@ -179,6 +180,276 @@ def sweep_cases():
 @functools.lru_cache(maxsize=None)
 def sweep_verdicts():
     return [yardstick(m, s) for m, s in sweep_cases()]
+
+
+# ---- members zlib's deflate never writes (tests/deflate_writer.py) ----------------------------------------------------------------------
+STORED_ALIGN_N = (0, 1, 2, 3, 4, 5, 7, 8, 9)
+STORED_IN_N = (1023, 1024, 1025, 2047, 2048, 2049)
+
+
+def _rbytes(r, n):
+    return bytes(r.randrange(256) for _ in range(n))
+
+
+def _all_symbols(dw):
+    """a non-final stored block of 32 768 random bytes, then one dynamic block of 286 + 30 codes, most of them 14 and 15 bits long, that
+    uses every one of them: the 256 literals; every distance symbol with its smallest and largest extra value; every length symbol with
+    its smallest and largest extra value at distance 64, 63 and 65 (lengths over 64), L, L - 1, 2 and 1 -- in front of each such group
+    66 bytes copied out of the random block, so that a copy from the wrong place shows in the bytes"""
+    r = random.Random(4242)
+    first = _rbytes(r, 32768)
+    ll_lens = [1, 2, 3, 4, 5, 6] + [14] * 232 + [15] * 48
+    dd_lens = list(range(1, 11)) + [14] * 12 + [15] * 8
+    r.shuffle(ll_lens); r.shuffle(dd_lens)
+    assert dw.kraft(ll_lens) == 32768 and dw.kraft(dd_lens) == 32768 and len(ll_lens) == 286 and len(dd_lens) == 30
+    tokens = list(range(256))
+    r.shuffle(tokens)
+    at = 32768 + 256
+    for d in range(30):
+        for dx in sorted({0, (1 << dw.DIST_EXTRA[d]) - 1}):
+            ls = 257 + r.randrange(8)
+            tokens.append((dw.MATCH, ls, 0, d, dx))
+            at += dw.LEN_BASE[ls - 257]
+    for i in range(29):
+        for lx in sorted({0, (1 << dw.LEN_EXTRA[i]) - 1}):
+            length = dw.LEN_BASE[i] + lx
+            tokens.append(dw.match(66, at - r.randrange(max(0, at - 32768), 32768 - 66)))
+            at += 66
+            dists = [64] + ([63, 65] if length > 64 else []) + [length, length - 1, 2, 1]
+            for dist in sorted(set(dists), key=dists.index):
+                tokens.append((dw.MATCH, 257 + i, lx) + dw.dist_token(dist))
+                at += length
+    tokens.append(dw.EOB)
+    return [dw.stored(first), dw.dynamic(tokens, ll_lens, dd_lens)]
+
+
+def _many_blocks(dw):
+    """200 dynamic blocks, each with fresh random tables of 286 + 30 codes of up to 15 bits, 20 literals and one match"""
+    r = random.Random(303)
+    blocks, at = [], 0
+    for _ in range(200):
+        ll_lens, dd_lens = dw.random_complete(r, range(286), 15, 286), dw.random_complete(r, range(30), 15, 30)
+        i = r.randrange(29)
+        m = (dw.MATCH, 257 + i, r.randrange(1 << dw.LEN_EXTRA[i])) + dw.dist_token(r.randint(1, min(at + 20, 32768)))
+        blocks.append(dw.dynamic([r.randrange(256) for _ in range(20)] + [m, dw.EOB], ll_lens, dd_lens))
+        at += 20 + dw.match_length(m)
+    return blocks
+
+
+def _lens(n, of):
+    """n code lengths, zero except for of = {symbol: length}"""
+    return [of.get(s, 0) for s in range(n)]
+
+
+@functools.lru_cache(maxsize=None)
+def _crafted():
+    """(good, bad) lists of (name, blocks): see crafted_set"""
+    from tests import deflate_writer as dw
+    M, S, B, EOB = dw.MATCH, dw.SYM, dw.BITS, dw.EOB
+    r = random.Random(808)
+    A, Bb = 65, 66
+    one_ll = dw.random_complete(r, [A, Bb, 256, 257, 264, 284, 285], 15, 286)
+    lit_ll = dw.random_complete(r, sorted(set(b"no distance code at all")) + [256], 15, 257)
+    lit257_ll = dw.random_complete(r, [A, Bb, 256, 257], 15, 258)
+    # a, 256, 257, 258 at 1, 2, 3, 3 bits and distance symbols 0 .. 5 at 3, 3, 3, 3, 2, 2: one code 16 writes the 3 of 258 and of distance symbols 0 .. 3
+    r16_ll, r16_dd = _lens(259, {97: 1, 256: 2, 257: 3, 258: 3}), [3, 3, 3, 3, 2, 2]
+    r16_cl = dw.with_run(r16_ll + r16_dd, 258, 16, 5)
+    # 259 .. 261 and distance symbols 0, 1 have no code: one code 17 writes those five zeros
+    r17_ll, r17_dd = _lens(262, {97: 1, 256: 2, 257: 3, 258: 3}), [0, 0, 1, 1]
+    r17_cl = dw.with_run(r17_ll + r17_dd, 259, 17, 5)
+    plain_ll, plain_dd = _lens(258, {97: 1, 256: 2, 257: 2}), [1, 1]
+    ten = _rbytes(r, 10)
+    good = [
+        ("all_symbols", _all_symbols(dw)),
+        ("one_dist_code", [dw.dynamic([A, Bb, (M, 257, 0, 0, 0), Bb, (M, 285, 0, 0, 0), A, (M, 284, 31, 0, 0), (M, 264, 0, 0, 0), EOB], one_ll, [1])]),
+        ("empty_dist", [dw.dynamic(list(b"no distance code at all") + [EOB], lit_ll, [0])]),
+        ("only_eob", [dw.dynamic([EOB], _lens(257, {256: 1}), [0])]),
+        ("rep16_crosses", [dw.dynamic([97, 97, 97, dw.match(4, 1), dw.match(3, 6), 97, dw.match(4, 5), dw.match(3, 7), EOB], r16_ll, r16_dd, r16_cl)]),
+        ("rep17_crosses", [dw.dynamic([97, 97, 97, dw.match(3, 3), 97, dw.match(4, 4), EOB], r17_ll, r17_dd, r17_cl)]),
+        ("dist_10_of_10", [dw.stored(ten), dw.fixed([dw.match(20, 10), EOB])]),
+        ("many_blocks", _many_blocks(dw)),
+    ]
+    for k in range(8):  # 3 + 9 k + 7 bits of fixed block in front of the stored header: bit (2 + k) mod 8
+        for n in STORED_ALIGN_N:
+            good.append(("stored_align%d_%d" % (k, n), [dw.fixed([144 + r.randrange(112) for _ in range(k)] + [EOB]), dw.stored(_rbytes(r, n))]))
+    for n in STORED_IN_N:
+        good.append(("stored_in%d" % n, [dw.stored(_rbytes(r, n - 5))]))
+    pad = (B, 0, 16)
+    bad = [
+        ("one_dist_code_unused_bit", [dw.dynamic([A, Bb, (S, "ll", 257), (B, 1, 1), A, EOB, pad], one_ll, [1])]),
+        ("empty_dist_used", [dw.dynamic([A, Bb, (S, "ll", 257), pad, EOB], lit257_ll, [0])]),
+        ("only_eob_unused_bit", [dw.dynamic([(B, 1, 1), pad], _lens(257, {256: 1}), [0])]),
+        ("first_is_16", [dw.dynamic([97, EOB], plain_ll, plain_dd, [(16, 3)] + (plain_ll + plain_dd)[3:])]),
+        ("repeat_overruns", [dw.dynamic([97, EOB], plain_ll, plain_dd, (plain_ll + plain_dd)[:-2] + [(18, 11)])]),
+        ("no_eob", [dw.dynamic([97, 98, pad], _lens(257, {97: 1, 98: 1}), [1, 1])]),
+        ("incomplete_ll", [dw.dynamic([97, EOB, pad], _lens(257, {97: 2, 256: 2}), [1, 1])]),
+        ("oversub_ll", [dw.dynamic([97, EOB, pad], _lens(257, {97: 1, 98: 1, 256: 1}), [1, 1])]),
+        ("fixed_286", [dw.fixed([A, (S, "ll", 286), pad, EOB])]),
+        ("fixed_dist30", [dw.fixed([A, Bb, A, (S, "ll", 257), (S, "dd", 30), pad, EOB])]),
+        ("dist_11_of_10", [dw.stored(ten), dw.fixed([dw.match(20, 11), EOB])]),
+        ("hdist_31", [dw.dynamic([97, EOB, pad], plain_ll, dw.random_complete(r, range(31), 15, 31))]),
+    ]
+    return good, bad
+
+
+def _first_coded_byte(dw, blocks):
+    """the byte in which the first block that is not stored begins (0 if all are)"""
+    starts = []
+    dw.write(blocks, starts)
+    return next((s >> 3 for s, b in zip(starts, blocks) if b[0] != "stored"), 0)
+
+
+@functools.lru_cache(maxsize=None)
+def crafted_set():
+    """(good, bad) lists of (name, data, size) made with tests/deflate_writer.py: streams that are valid (or precisely not) by RFC 1951
+    but that zlib's deflate does not write.  `size` is what the writer's tokens come to; what a decoder must do with a member is the
+    yardstick's -- zlib's -- word, see check_crafted_set.
+      good  all_symbols (see _all_symbols), one_dist_code, empty_dist, only_eob (a literal/length set of the end-of-block code alone: no
+            output), rep16_crosses / rep17_crosses (one repeat code writes the last literal/length and the first distance lengths),
+            dist_10_of_10, many_blocks, stored_align{k}_{n} (a stored header at every bit position, n stored bytes), stored_in{n} (a
+            stored member of n input bytes, around the 1 KiB input chunks)
+      bad   the other code of a single-code set used (one_dist_code_unused_bit, only_eob_unused_bit), a match with no distance code
+            (empty_dist_used), code 16 first, a repeat running over HLIT + HDIST, no end-of-block code, an incomplete and an
+            over-subscribed literal/length set, symbol 286 and distance symbol 30 in a fixed block, a distance one beyond the bytes so
+            far, HDIST 31"""
+    from tests import deflate_writer as dw
+    good, bad = _crafted()
+    return tuple([(name, dw.write(blocks), len(dw.apply(blocks, part is good))) for name, blocks in part] for part in (good, bad))
+
+
+def check_crafted_set():
+    """zlib's verdict on every crafted member, and -- by the profiler's own decoder -- the decoder paths the good ones are there for.  A
+    member that is simplified until a path is lost fails here."""
+    from tests import deflate_writer as dw
+    good, bad = crafted_set()
+    assert len({n for n, _, _ in good + bad}) == len(good) + len(bad) == 8 + 8 * len(STORED_ALIGN_N) + len(STORED_IN_N) + 12
+    for n, m, s in good:
+        assert yardstick(m, s)[0], n
+    for n, m, s in bad:
+        assert not yardstick(m, s)[0], n
+    prof = {n: dw.profile(m) for n, m, s in good}
+    for n, m, s in good:
+        assert prof[n]["out"] == yardstick(m, s)[1], n  # the profiler reads the stream as zlib does
+    for n, m, s in bad:
+        try:
+            dw.profile(m)
+        except ValueError:
+            continue
+        raise AssertionError("the profiler accepts " + n)
+    every = list(prof.values())
+    assert set().union(*(p["len_symbols"] for p in every)) == set(range(257, 286))
+    assert set().union(*(p["dist_symbols"] for p in every)) == set(range(30))
+    assert max(p["ll_bits_in_match"] for p in every) == 15 and max(p["dd_bits_in_match"] for p in every) == 15
+    assert sum(p["repeats_crossing"] for p in every) >= 1
+    assert sum(p["single_dist_sets"] for p in every) >= 1 and sum(p["empty_dist_sets"] for p in every) >= 1
+    assert sum(p["single_ll_sets"] for p in every) >= 1
+    assert {b % 8 for p in every for b in p["stored_bits"]} == set(range(8))
+    for d in (63, 64, 65):
+        assert max(p["len_at_dist"][d] for p in every) >= 258, d
+    # member by member: what each one is there for
+    a = prof["all_symbols"]
+    assert a["blocks"] == ["stored", "dynamic"] and a["len_symbols"] == set(range(257, 286)) and a["dist_symbols"] == set(range(30))
+    assert (a["ll_bits_in_match"], a["dd_bits_in_match"]) == (15, 15) and a["len_at_dist"] == {63: 258, 64: 258, 65: 258}
+    assert 32768 + 256 < len(a["out"]) <= MAX_OUT and set(a["out"][32768:32768 + 256]) == set(range(256))
+    assert prof["one_dist_code"]["single_dist_sets"] == 1 and 285 in prof["one_dist_code"]["len_symbols"]
+    assert prof["empty_dist"]["empty_dist_sets"] == 1 and not prof["empty_dist"]["len_symbols"]
+    assert prof["only_eob"]["single_ll_sets"] == 1 and prof["only_eob"]["out"] == b""
+    assert prof["rep16_crosses"]["repeats_crossing"] == 1 and prof["rep17_crosses"]["repeats_crossing"] == 1
+    assert prof["dist_10_of_10"]["blocks"] == ["stored", "fixed"] and len(prof["dist_10_of_10"]["out"]) == 30
+    m = prof["many_blocks"]
+    assert m["blocks"] == ["dynamic"] * 200 and len(m["out"]) <= MAX_OUT
+    assert len({b // 8192 for b in m["block_bits"]}) >= 20  # block headers in (and across) many 1 KiB input chunks
+    d = {n: (m_, s) for n, m_, s in good}
+    for k in range(8):
+        for n in STORED_ALIGN_N:
+            p = prof["stored_align%d_%d" % (k, n)]
+            assert p["blocks"] == ["fixed", "stored"] and p["stored_bits"][0] % 8 == (2 + k) % 8 and len(p["out"]) == k + n
+    for n in STORED_IN_N:
+        assert len(d["stored_in%d" % n][0]) == n and prof["stored_in%d" % n]["blocks"] == ["stored"]
+
+
+CRAFTED_SWEEP_SEED = 1951
+
+
+@functools.lru_cache(maxsize=None)
+def crafted_sweep():
+    """the mutation sweep of the crafted members (all but stored_align* and stored_in*): of each, 150 single-bit flips -- seven in ten
+    of them in the first 96 bytes of its first block that is not stored, where the header checks are -- and 20 truncations.  List of
+    (data, size), shuffled; the GPU tests run the first 300.  By zlib (crafted_sweep_verdicts), with seed CRAFTED_SWEEP_SEED:
+    244 of the 3 400 cases are accepted and 3 156 rejected; of the first 300, 21 and 279."""
+    from tests import deflate_writer as dw
+    good, bad = _crafted()
+    r = random.Random(CRAFTED_SWEEP_SEED)
+    cases = []
+    for name, blocks in good + bad:
+        if name.startswith("stored_"):
+            continue
+        data, size, head = dw.write(blocks), len(dw.apply(blocks, False)), _first_coded_byte(dw, blocks)
+        for _ in range(150):
+            at = head * 8 + r.randrange(8 * min(96, len(data) - head)) if r.random() < 0.7 else r.randrange(8 * len(data))
+            m = bytearray(data)
+            m[at >> 3] ^= 1 << (at & 7)
+            cases.append((bytes(m), size))
+        for _ in range(20):
+            cases.append((data[:r.randrange(len(data))], size))
+    r.shuffle(cases)
+    return cases
+
+
+@functools.lru_cache(maxsize=None)
+def crafted_sweep_verdicts():
+    return [yardstick(m, s) for m, s in crafted_sweep()]
+
+
+def check_crafted_sweep():
+    """a condition, not a measurement: enough cases of either verdict in the whole sweep and in the GPU's share of it"""
+    v = [ok for ok, _ in crafted_sweep_verdicts()]
+    assert len(v) == 3400
+    assert min(sum(v), len(v) - sum(v)) >= 100, (sum(v), len(v))
+    assert min(sum(v[:300]), 300 - sum(v[:300])) >= 10, sum(v[:300])
+
+
+FOREIGN_NAMES = ("reads150b_level1", "reads150b_level12", "reads5kb_level1", "reads5kb_level12")
+
+
+def foreign_texts():
+    from tests import deflate_cases as dc
+    return {"reads150b": dc.fastq_150b(20000), "reads5kb": dc.fastq_5kb(20000)}
+
+
+@functools.lru_cache(maxsize=None)
+def foreign_set():
+    """list of (name, data, size, crc): raw deflate members written by libdeflate, not zlib -- tests/golden/foreign_members.bin, made by
+    tests/golden/make_foreign_members.py.  The file is a count, then for each member its input length, output length and CRC-32
+    (little-endian 32-bit words) and its bytes."""
+    import os
+    import struct
+    blob = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "foreign_members.bin"), "rb").read()
+    (n,), at, out = struct.unpack_from("<I", blob, 0), 4, []
+    assert n == len(FOREIGN_NAMES)
+    for name in FOREIGN_NAMES:
+        in_len, out_len, crc = struct.unpack_from("<III", blob, at)
+        out.append((name, blob[at + 12:at + 12 + in_len], out_len, crc))
+        at += 12 + in_len
+    assert at == len(blob)
+    return out
+
+
+def check_foreign_set():
+    """zlib inflates every foreign member to the seeded text, and the CRC-32 of the fixture is that text's; they hold what zlib's
+    members lack: length symbols with 2 and more extra bits out of dynamic tables, dynamic blocks with nothing between them"""
+    from tests import deflate_writer as dw
+    texts = foreign_texts()
+    for name, m, s, crc in foreign_set():
+        want = texts[name.split("_")[0]]
+        assert s == len(want) == 20000 and yardstick(m, s) == (True, want), name
+        assert crc == (zlib.crc32(want) & 0xFFFFFFFF), name
+        p = dw.profile(m)
+        assert p["out"] == want and set(p["blocks"]) == {"dynamic"}, name
+        if name.startswith("reads150b"):  # (the 5 kb reads are random letters: few matches, and short ones)
+            assert len(p["len_symbols"]) >= 24 and max(p["len_symbols"]) >= 281, (name, sorted(p["len_symbols"]))
+        if name == "reads5kb_level12":
+            assert p["blocks"] == ["dynamic"] * 3
 
 
 def bgzf(data, level=6, block=65280):

@@ -1,5 +1,6 @@
 """GPU tests (-m gpu) of k_inflate_members behind chn_inflate_run and of CHARON_GPU_INFLATE=1 in the front end.  The yardstick is
 Python's zlib (tests/inflate_cases.py); the host decoder (chn_inflate_run_host) is compared status by status on top."""
+import functools
 import gzip
 import os
 import subprocess
@@ -108,6 +109,101 @@ def test_rejected_members_and_mutations_between_good_ones(inflater, good_set):
     assert [(int(x) == 0) for x in st] == [e is not None for e in expect]
     assert res == expect
     assert (st == hst).all() and res == hres
+
+
+@functools.lru_cache(maxsize=None)
+def crafted_good():
+    """the crafted good set and the foreign set (streams zlib's deflate does not write): (members, sizes, names, zlib's bytes)"""
+    good, _ = ic.crafted_set()
+    every = good + [(n, m, s) for n, m, s, _ in ic.foreign_set()]
+    return [m for _, m, _ in every], [s for _, _, s in every], [n for n, _, _ in every], [ic.yardstick(m, s)[1] for _, m, s in every]
+
+
+@functools.lru_cache(maxsize=None)
+def crafted_bad_job():
+    """the crafted rejects and the first 300 cases of crafted_sweep() (every one of which the host decoder has been through in
+    tests/test_inflate_cpu.py), each behind a small good member: (members, sizes, zlib's bytes -- None where zlib rejects)"""
+    _, bad = ic.crafted_set()
+    good, _, trailing = ic.member_set()
+    small = [(m, s, ic.yardstick(m, s)[1]) for n, m, s in good if n in ("fixed_one_byte", "empty", "run_of_a", "dynamic", "stored")]
+    cases = [(m, s) for _, m, s in bad] + ic.crafted_sweep()[:300]
+    verdicts = [ic.yardstick(m, s) for _, m, s in bad] + ic.crafted_sweep_verdicts()[:300]
+    ms, sizes, expect = [], [], []
+    for k, ((m, s), (ok, out)) in enumerate(zip(cases, verdicts)):
+        g = small[k % len(small)]
+        ms += [g[0], m]; sizes += [g[1], s]; expect += [g[2], out if ok else None]
+    assert sum(e is None for e in expect) >= 12 + 10 and sum(e is not None for e in expect[1::2]) >= 10
+    return ms, sizes, expect
+
+
+@functools.lru_cache(maxsize=None)
+def repeated_job(copies=70):
+    """all_symbols and many_blocks `copies` times each, in turn.  In front of copy k stand filler members (stored blocks of 0 .. 15
+    bytes, empty members) that bring its input onto the offset k mod 16 of the caller's array and its output -- the members of a job
+    lie back to back in device memory, and the window is shifted by the output's misalignment -- onto 7 k + 3 mod 16: every class of
+    either occurs for both members.  (members, sizes, zlib's bytes, crcs)"""
+    import zlib
+    from tests import deflate_writer as dw
+    good, _ = ic.crafted_set()
+    big = [(m, s, ic.yardstick(m, s)[1]) for n, m, s in good if n in ("all_symbols", "many_blocks")]
+    assert len(big) == 2
+    r = util.rng(70)
+    empty = (b"\x03\x00", 0, b"")
+
+    def fillers(din, dout):
+        for n_stored in (0, 1, 2):
+            for n_empty in range(8):
+                if (5 * n_stored + (dout if n_stored else 0) + 2 * n_empty) % 16 == din and (dout if n_stored else 0) == dout:
+                    payload = [bytes(int(x) for x in r.integers(0, 256, dout if q == 0 else 0)) for q in range(n_stored)]
+                    return [(dw.write([dw.stored(p)]), len(p), p) for p in payload] + [empty] * n_empty
+        raise AssertionError((din, dout))
+
+    job, at_in, at_out, seen_in, seen_out = [], 0, 0, set(), set()
+    for k in range(copies):
+        for which, b in enumerate(big):
+            for f in fillers((k - at_in) % 16, (7 * k + 3 + which - at_out) % 16):
+                job.append(f)
+                at_in += len(f[0]); at_out += f[1]
+            seen_in.add((which, at_in % 16)); seen_out.add((which, at_out % 16))
+            job.append(b)
+            at_in += len(b[0]); at_out += b[1]
+    assert len(seen_in) == 32 and len(seen_out) == 32
+    assert all(ic.yardstick(m, s) == (True, w) for m, s, w in job if s < 16)
+    return [j[0] for j in job], [j[1] for j in job], [j[2] for j in job], [zlib.crc32(j[2]) & 0xFFFFFFFF for j in job]
+
+
+def test_crafted_and_foreign_members_in_one_job(inflater):
+    """the streams zlib's deflate never writes: every length and distance symbol out of tables of 14- and 15-bit codes, single-code
+    and empty sets, repeat codes across HLIT, 200 table builds in one member, stored headers at every bit position, libdeflate's
+    members -- status 0, zlib's bytes, and the host decoder's results status by status"""
+    import charon_amd.api as api
+    ms, sizes, names, want = crafted_good()
+    res, st = inflater.run(ms, sizes, guard=64)
+    assert [n for n, x in zip(names, st) if int(x) != 0] == []
+    for name, out, w in zip(names, res, want):
+        assert out == w, name
+    hres, hst = api.inflate_host(ms, sizes, guard=64)
+    assert (hst == st).all() and hres == res
+
+
+def test_crafted_rejects_and_mutations_between_good_ones(inflater):
+    """non-zero exactly where zlib rejects, the host decoder's status, the neighbours intact, no byte behind an out_length written"""
+    import charon_amd.api as api
+    ms, sizes, expect = crafted_bad_job()
+    hres, hst = api.inflate_host(ms, sizes, guard=64)
+    res, st = inflater.run(ms, sizes, guard=64)  # raises if a guard byte was touched
+    assert [(int(x) == 0) for x in st] == [e is not None for e in expect]
+    assert res == expect
+    assert (st == hst).all() and res == hres
+
+
+def test_all_symbols_and_many_blocks_seventy_times(inflater):
+    """more members than one pass of a small grid, so a workgroup builds these tables over what the previous member left; see
+    repeated_job for the offsets"""
+    ms, sizes, want, _ = repeated_job()
+    assert len(ms) > 140
+    res, st = inflater.run(ms, sizes)
+    assert not st.any() and res == want
 
 
 def test_descriptor_error_runs_nothing(inflater, good_set):

@@ -12,7 +12,7 @@ import pytest
 from tests import inflate_cases as ic
 from tests import util
 from tests.test_gpu_cli import assert_same_tsv
-from tests.test_gpu_inflate import run_cli
+from tests.test_gpu_inflate import crafted_bad_job, crafted_good, repeated_job, run_cli
 from tests.test_inflate_crc_cpu import CORRUPT, crc_set
 
 pytestmark = pytest.mark.gpu
@@ -164,6 +164,37 @@ def test_rejected_members_keep_their_status_with_expected_present(inflater):
     assert all(int(c) == e for c, e, d in zip(crc, exp, data) if d is not None)
     _, st7 = inflater.run(ms, sizes, guard=64, expected=[e ^ 1 for e in exp])
     assert [int(x) for x in st7] == [7 if int(p) == 0 else int(p) for p in plain]
+
+
+def test_crafted_and_foreign_members_through_the_crc_kernel(inflater):
+    """tests/test_gpu_inflate.py's crafted and foreign members again, with the CRC-32 taken and compared on the device"""
+    import charon_amd.api as api
+    ms, sizes, names, want = crafted_good()
+    crcs = [zlib.crc32(w) & 0xFFFFFFFF for w in want]
+    assert crcs[-4:] == [c for _, _, _, c in ic.foreign_set()]  # the fixture's own
+    res, st, crc = inflater.run(ms, sizes, guard=64, expected=crcs, want_crc=True)
+    assert [n for n, x in zip(names, st) if int(x) != 0] == []
+    for name, out, w, got, c in zip(names, res, want, crc, crcs):
+        assert out == w and int(got) == c, name
+    hres, hst, hcrc = api.inflate_host(ms, sizes, guard=64, expected=crcs, want_crc=True)
+    assert (hst == st).all() and (hcrc == crc).all() and hres == res
+
+
+def test_crafted_rejects_keep_their_status_with_expected_present(inflater):
+    import charon_amd.api as api
+    ms, sizes, expect = crafted_bad_job()
+    exp = [zlib.crc32(e) & 0xFFFFFFFF if e is not None else 0x12345678 for e in expect]
+    _, plain = api.inflate_host(ms, sizes, guard=64)
+    res, st, crc = inflater.run(ms, sizes, guard=64, expected=exp, want_crc=True)
+    assert (st == plain).all() and res == expect
+    assert [(int(x) == 0) for x in st] == [e is not None for e in expect]
+    assert all(int(c) == x for c, x, e in zip(crc, exp, expect) if e is not None)
+
+
+def test_all_symbols_and_many_blocks_seventy_times(inflater):
+    ms, sizes, want, crcs = repeated_job()
+    res, st, crc = inflater.run(ms, sizes, expected=crcs, want_crc=True)
+    assert not st.any() and res == want and [int(x) for x in crc] == crcs
 
 
 def test_plain_run_is_what_it_was(inflater):

@@ -107,6 +107,53 @@ def test_mutation_sweep_agrees_with_zlib_on_every_case():
     assert 0 < accepted < len(cases)
 
 
+def test_crafted_and_foreign_sets_are_what_they_claim():
+    """by zlib and by the profiler of tests/deflate_writer.py, neither of which is the code under test"""
+    ic.check_crafted_set()
+    ic.check_foreign_set()
+    ic.check_crafted_sweep()
+
+
+# statuses of the named rejects, as they follow from inflate_members.inc: 3 (INF_E_LENGTHS) where the header or a code set is at
+# fault, 4 (INF_E_SYMBOL) where a symbol or a distance is
+CRAFTED_STATUS = {"one_dist_code_unused_bit": 4, "empty_dist_used": 4, "only_eob_unused_bit": 4, "first_is_16": 3, "repeat_overruns": 3,
+                  "no_eob": 3, "incomplete_ll": 3, "oversub_ll": 3, "fixed_286": 4, "fixed_dist30": 4, "dist_11_of_10": 4, "hdist_31": 3}
+
+
+def test_crafted_and_foreign_members_on_the_host_decoder():
+    import zlib
+    import charon_amd.api as api
+    good, bad = ic.crafted_set()
+    every = good + bad + [(n, m, s) for n, m, s, _ in ic.foreign_set()]
+    ms, sizes = [m for _, m, _ in every], [s for _, _, s in every]
+    verdicts = [ic.yardstick(m, s) for m, s in zip(ms, sizes)]
+    res, st = api.inflate_host(ms, sizes, guard=64)
+    for (name, _, _), (ok, want), out, status in zip(every, verdicts, res, st):
+        assert (status == 0) == ok, (name, int(status))
+        assert out == want, name
+    assert [n for (n, _, _), (ok, _) in zip(every, verdicts) if not ok] == [n for n, _, _ in bad]
+    assert {n: int(x) for (n, _, _), x in zip(every, st) if x != 0} == CRAFTED_STATUS
+    cres, cst, crc = api.inflate_host(ms, sizes, guard=64, want_crc=True)
+    assert (cst == st).all() and cres == res
+    for (name, _, _), (ok, want), got in zip(every, verdicts, crc):
+        if ok:
+            assert int(got) == (zlib.crc32(want) & 0xFFFFFFFF), name
+    for (name, _, _, want), got in zip(ic.foreign_set(), crc[len(good) + len(bad):]):
+        assert int(got) == want, name  # the fixture's own CRC-32
+
+
+def test_crafted_sweep_agrees_with_zlib_on_every_case():
+    import charon_amd.api as api
+    cases, verdicts = ic.crafted_sweep(), ic.crafted_sweep_verdicts()
+    assert len(cases) == 3400
+    res, st = api.inflate_host([m for m, _ in cases], [s for _, s in cases], guard=64)  # raises if a guard byte was touched
+    wrong = [i for i, ((ok, _), status) in enumerate(zip(verdicts, st)) if (status == 0) != ok]
+    assert not wrong, (len(wrong), wrong[:10], [int(st[i]) for i in wrong[:10]])
+    assert all(out == want for out, (ok, want) in zip(res, verdicts) if ok)
+    accepted = sum(1 for ok, _ in verdicts if ok)
+    print("crafted sweep: %d of %d cases accepted by zlib" % (accepted, len(cases)))
+
+
 def _job(n=3):
     import charon_amd.api as api
     good, _, _ = ic.member_set()
