@@ -245,13 +245,18 @@ _L.chn_extract_records_host.argtypes = [C.POINTER(ExtractJob), C.c_void_p, C.c_u
 _L.chn_extract_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
 
 
+E_INVALID, E_HIP, E_NOMEM, E_STATE, E_CAPACITY = -1, -2, -3, -4, -5  # CHN_E_*
+
+
 class ChnError(RuntimeError):
-    pass
+    code = 0  # the CHN_E_* value
 
 
 def _chk(rc):
     if rc != 0:
-        raise ChnError("libcharon_hip error %d: %s" % (rc, _L.chn_last_error().decode()))
+        e = ChnError("libcharon_hip error %d: %s" % (rc, _L.chn_last_error().decode()))
+        e.code = rc
+        raise e
 
 
 def lib():
@@ -455,8 +460,8 @@ class Stream:
         return out[:e.value]
 
     # ---- row-sharded mode (see include/charon_hip.h) ----
-    def shard_minimise_host(self, packed):
-        b, keep, n = self._host_batch(packed, None, None)
+    def shard_minimise_host(self, packed, mean_quality=None, compression=None):
+        b, keep, n = self._host_batch(packed, mean_quality, compression)
         e = C.c_uint64()
         _chk(_L.chn_shard_minimise(self.h, C.byref(b), C.byref(e)))
         self._shard = (n, keep)
@@ -624,18 +629,21 @@ class Stream:
                    out["probs"].ctypes.data, out["call"].ctypes.data, out["conf"].ctypes.data, out["flags"].ctypes.data,
                    out["gzip_tallies"].ctypes.data if "gzip_tallies" in out else None,
                    out["gzip_sizes"].ctypes.data if "gzip_sizes" in out else None)
-        if text_result is not None:
-            _chk(_L.chn_text_wait(self.h, C.byref(r), C.byref(text_result)))
-        else:
-            _chk(_L.chn_batch_wait(self.h, C.byref(r)))
-        self._fifo.pop(0)
+        self._waited(_L.chn_text_wait(self.h, C.byref(r), C.byref(text_result)) if text_result is not None else
+                     _L.chn_batch_wait(self.h, C.byref(r)))
         return out
+
+    def _waited(self, rc):
+        """A wait that reports the batch's failure has still taken the batch off the stream (only a call-sequence error leaves it in
+        flight): the next wait must size its arrays for the next batch."""
+        if rc != E_STATE and self._fifo:
+            self._fifo.pop(0)
+        _chk(rc)
 
     def wait_device(self):
         r = Result()
         r.struct_size, r.on_device = C.sizeof(Result), 1
-        _chk(_L.chn_batch_wait(self.h, C.byref(r)))
-        self._fifo.pop(0)
+        self._waited(_L.chn_batch_wait(self.h, C.byref(r)))
         return r
 
     def sync(self):

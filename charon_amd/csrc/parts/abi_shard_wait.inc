@@ -26,7 +26,7 @@ static ShardArgs shard_args(chn_stream *s, const chn_index *shard, uint64_t *par
 
 extern "C" int chn_shard_minimise(chn_stream *s, const chn_batch *b, uint64_t *n_entries) {
     if (!s || !b || !n_entries) return fail(CHN_E_INVALID, "chn_shard_minimise: null argument");
-    if (s->shard_open) return fail(CHN_E_STATE, "chn_shard_minimise: previous sharded batch not finished");
+    if (s->shard_open || s->shx_stage != 0) return fail(CHN_E_STATE, "chn_shard_minimise: previous sharded batch not finished");  // (it would take the open batch's slot)
     HIPCHK(hipSetDevice(s->idx->d.device));
     int rc = ensure_shard_buffers(s);
     if (rc) return rc;
@@ -95,8 +95,9 @@ extern "C" int chn_index_emplace(chn_index *idx, const uint64_t *host_values, ui
 }
 
 extern "C" int chn_shard_probe(chn_stream *s, const chn_index *shard, uint64_t *dev_partial, uint64_t capacity_words) {
-    if (!s || !shard || !dev_partial) return fail(CHN_E_INVALID, "chn_shard_probe: null argument");
+    if (!s || !shard) return fail(CHN_E_INVALID, "chn_shard_probe: null argument");
     if (!s->shard_open) return fail(CHN_E_STATE, "chn_shard_probe: call chn_shard_minimise first");
+    if (!dev_partial && s->shard_entries) return fail(CHN_E_INVALID, "chn_shard_probe: null argument");  // (a batch without a minimiser has no partial words)
     const chn_index_desc &a = s->idx->d, &c = shard->d;
     if (a.bin_size != c.bin_size || a.bin_words != c.bin_words || a.hash_funs != c.hash_funs || a.device != c.device)
         return fail(CHN_E_INVALID, "chn_shard_probe: shard does not belong to the stream's index");
@@ -117,8 +118,9 @@ extern "C" int chn_shard_probe(chn_stream *s, const chn_index *shard, uint64_t *
 }
 
 extern "C" int chn_shard_finish(chn_stream *s, const uint64_t *dev_partial) {
-    if (!s || !dev_partial) return fail(CHN_E_INVALID, "chn_shard_finish: null argument");
+    if (!s) return fail(CHN_E_INVALID, "chn_shard_finish: null argument");
     if (!s->shard_open) return fail(CHN_E_STATE, "chn_shard_finish: no sharded batch open");
+    if (!dev_partial && s->shard_entries) return fail(CHN_E_INVALID, "chn_shard_finish: null argument");
     HIPCHK(hipSetDevice(s->idx->d.device));
     Slot &sl = s->slot[s->head];
     const uint32_t n_waves = (uint32_t)((sl.n_reads + WAVE - 1) / WAVE);

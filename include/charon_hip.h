@@ -544,7 +544,8 @@ int chn_classify_counts_raw(chn_stream *s, uint64_t n_reads, const uint32_t *num
  *   3. the caller sums `partial` (E*h*W uint64) over ranks with ONE all-reduce (RCCL; sum == select because exactly
  *      one rank owns each row) -- the library itself has no RCCL dependency
  *   4. chn_shard_finish     AND over the h hash functions, counts, model+call; then chn_batch_wait as usual.
- * `dev_partial` is a device buffer of the caller (e.g. a torch tensor). No reference counterpart (the reference is
+ * `dev_partial` is a device buffer of the caller (e.g. a torch tensor); it may be NULL when E = 0 (a batch without a
+ * minimiser has no partial words).  One sharded batch, dense or sparse, at a time per stream.  No reference counterpart (the reference is
  * single-process); replaces the same loop body as chn_batch_submit. */
 int chn_shard_minimise(chn_stream *s, const chn_batch *b, uint64_t *n_entries);
 int chn_shard_probe(chn_stream *s, const chn_index *shard, uint64_t *dev_partial, uint64_t capacity_words);

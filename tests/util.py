@@ -39,7 +39,7 @@ def sample_reads(r, genomes, n, length, sub_rate=0.05, random_fraction=0.1):
     return out
 
 
-def build_oracle_index(po, genomes_by_bin, bin_to_cat, categories, k=19, w=41, bin_size=None, fill_seed=None, fill=0.0):
+def build_oracle_index(po, genomes_by_bin, bin_to_cat, categories, k=19, w=41, bin_size=None, fill_seed=None, fill=0.0, hash_funs=3):
     """genomes_by_bin: list (one entry per bin) of lists of sequences.  Inserts the distinct minimisers of every
     sequence into its bin (what `charon index` does, src/index_main.cpp:118-160,238-263)."""
     mins = []
@@ -49,8 +49,8 @@ def build_oracle_index(po, genomes_by_bin, bin_to_cat, categories, k=19, w=41, b
             s.update(int(x) for x in po.minimisers(g.decode() if isinstance(g, bytes) else g, k, w))
         mins.append(np.array(sorted(s), dtype=np.uint64))
     if bin_size is None:
-        bin_size = int(po.lib().orc_bin_size_in_bits(max(1, max(len(m) for m in mins)), 3, 0.01))
-    idx = po.Index.new(len(genomes_by_bin), bin_size, bin_to_cat, categories, k=k, w=w)
+        bin_size = int(po.lib().orc_bin_size_in_bits(max(1, max(len(m) for m in mins)), hash_funs, 0.01))
+    idx = po.Index.new(len(genomes_by_bin), bin_size, bin_to_cat, categories, k=k, w=w, nhash=hash_funs)
     if fill_seed is not None and fill > 0:
         r = rng(fill_seed)
         words = idx.words()
