@@ -49,6 +49,7 @@
 #include "default_kde.inc"
 
 #include "parts/common.inc"
+#include "parts/lds_budget.hpp"
 #include "parts/k1_minimise_probe.inc"
 #include "parts/k2_count_wavelog.inc"
 #include "parts/shard_kernels.inc"

@@ -175,7 +175,7 @@ static int rerun_worst_case(chn_stream *s, Slot &sl) {
     K1Args a = sl.k1;
     a.gate_started = a.gate_signal = nullptr;  // no probe gate: the slot's counter has counted this grid once already, and nothing waits for it
     fill_k1_log(a, sl, s->big, true);
-    const size_t lds = k1_lds_bytes(a.wn, d.num_categories, MODE_ROWS, a.h, (uint32_t)d.bin_words, (uint32_t)d.bins);
+    const size_t lds = k1_lds_bytes(a.wn, d.num_categories, MODE_ROWS, a.h, (uint32_t)d.bin_words, (uint32_t)d.bins, a.pack != 0);
     hipError_t e = launch_k1_mode(MODE_ROWS, (uint32_t)d.bin_words, a, lds, s->stream);
     if (e == hipSuccess && sl.split_bound) e = launch_k1_split_mode(MODE_ROWS, (uint32_t)d.bin_words, a, lds, s->stream, split_grid(sl.split_bound));
     if (e != hipSuccess) return fail(CHN_E_HIP, std::string("k_minimise_probe re-run: ") + hipGetErrorString(e));

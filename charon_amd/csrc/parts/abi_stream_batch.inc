@@ -244,8 +244,7 @@ extern "C" int chn_model_set(chn_stream *s, const chn_model *m) {
     return CHN_OK;
 }
 
-// conditional probing (k1_minimise_probe.inc): MODE_FUSED indexes of few bins
-static bool k1_cond(int mode, uint32_t B) { return mode == MODE_FUSED && B <= K1_COND_MAX_BINS; }
+// (k1_cond, k1_lds_bytes, ring_pack_ok: lds_budget.hpp)
 // blocks = 0: the ordinary launch, one wavefront per 64 reads; else the SPLIT launch (one long read per wavefront), `blocks` looping workgroups
 template <int W, int MODE, bool SPLIT = false, bool COND = false>
 static hipError_t launch_k1(const K1Args &a, size_t lds, hipStream_t st, uint32_t blocks = 0) {
@@ -254,7 +253,9 @@ static hipError_t launch_k1(const K1Args &a, size_t lds, hipStream_t st, uint32_
         hipError_t e = hipFuncSetAttribute((const void *)k_minimise_probe<W, MODE, 0, SPLIT, COND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    if (a.wn == 23)  // w=41, k=19: the defaults every real Charon index uses (include/index_arguments.hpp:16-17)
+    // w=41, k=19: the defaults every real Charon index uses (include/index_arguments.hpp:16-17).  The fixed-window instance has a packed ring and
+    // nothing else: a window of 23 with k >= 26, where the ring words have no room for the offsets, goes to the general instance.
+    if (a.wn == 23 && a.pack)
         hipLaunchKernelGGL((k_minimise_probe<W, MODE, 23, SPLIT, COND>), dim3(blocks), dim3(WAVE), lds, st, a);
     else
         hipLaunchKernelGGL((k_minimise_probe<W, MODE, 0, SPLIT, COND>), dim3(blocks), dim3(WAVE), lds, st, a);
@@ -293,17 +294,6 @@ static hipError_t launch_k1_w(uint32_t W, const K1Args &a, size_t lds, hipStream
         case 3: return launch_k1<3, MODE>(a, lds, st);
         default: return launch_k1<4, MODE>(a, lds, st);
     }
-}
-static size_t k1_lds_bytes(uint32_t wn, uint32_t C, int mode, uint32_t h, uint32_t W, uint32_t B) {
-    const bool cond = k1_cond(mode, B);  // conditional probing: one row per round, a longer queue with the ANDs so far
-    const size_t qc = cond ? QCAP + WAVE : QCAP;
-    size_t b = (size_t)wn * WAVE * 8 + qc * 8 + qc * 4 + (cond ? qc * 8 : 0) + (mode == MODE_EMPLACE ? WAVE * 8 : 0) + (size_t)wn * WAVE;
-    if (mode == MODE_FUSED) b += (size_t)2 * C * WAVE * 4;
-    if (cond) b += (size_t)FUSED_ROUNDS * 1024;
-    else if (mode == MODE_FUSED || mode == MODE_ROWS) b += (size_t)2 * h * (W <= 2 ? 1 : 2) * 1024;  // probe buffer: two rounds of h x NBLK x 1 KiB
-    b = (b + 15) & ~(size_t)15;
-    if (mode == MODE_ROWS) b += (size_t)(CHN_LOG_BATCH + 1) * WAVE * 4;  // staged row-log entries (+ the at most 63 behind a full store)
-    return b;
 }
 
 // (reserve: the most this buffer will ever hold -- allocated at first use, so that a later, larger batch never re-allocates:
@@ -641,6 +631,7 @@ static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind, bool bo
     a.words = s->idx->words; a.S = d.bin_size; a.row_begin = d.row_begin; a.row_end = d.row_end; a.seed = d.minimiser_seed; a.powk1 = pow5(d.kmer_size - 1);
     a.shift = (uint32_t)d.hash_shift; a.h = d.hash_funs; a.k = d.kmer_size; a.wn = d.window_size - d.kmer_size + 1;
     a.n_reads = (uint32_t)n; a.nseg = paired ? 2 : 1; a.B = (uint32_t)d.bins; a.C = C;
+    a.pack = ring_pack_ok(a.k, a.wn, a.seed) ? 1u : 0u;  // decided once here; k1_lds_bytes below and the launch follow it
     for (uint32_t bb = 0; bb < 8 && bb < d.bins; ++bb) a.b2c_packed |= (uint64_t)d.bin_to_category[bb] << (8 * bb);
     a.bases = bases; a.nmask = nmask; a.off1 = off1; a.off2 = off2; a.len1 = sl.len1; a.len2 = sl.len2; a.n_bases = b->n_bases;
     a.order = sl.d_order.as<uint32_t>();
@@ -668,7 +659,7 @@ static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind, bool bo
         fill_k1_log(a, sl, sl.lb, true);
     }
     const int mode = list_mode ? MODE_LIST : fused ? MODE_FUSED : MODE_ROWS;
-    size_t lds = k1_lds_bytes(a.wn, C, mode, a.h, W, a.B);
+    size_t lds = k1_lds_bytes(a.wn, C, mode, a.h, W, a.B, a.pack != 0);
     if (const char *pad = diag_env("CHN_LDS_PAD")) lds += (size_t)std::atoi(pad);  // occupancy-sensitivity diagnostic
     if (lds > 160 * 1024) return fail(CHN_E_INVALID, "window too large for LDS");
     if (sl.split_bound) {
@@ -748,11 +739,12 @@ static int launch_tail(chn_stream *s, Slot &sl, LogBuf &lb, hipStream_t st) {
         k2.n_long_ptr = sl.split_bound && !sl.list_mode ? ctl + CTL_NLONG : nullptr; k2.wave_slot0 = n_waves;
         const dim3 grid(n_waves), block(K2_THREADS);
         // 16-bit totals when no read of this launch can have 2^16 minimisers (reads of 2^15 bases and more go to the SPLIT launch); as many
-        // owners per sweep as keep the tables within what seven probe wavefronts leave of a CU's LDS (K2_LDS_BUDGET), so that the kernel runs
-        // under the next batch's probe kernel
+        // owners per sweep as keep the tables within what the probe wavefronts of this stream's probe configuration leave of a CU's LDS
+        // (k2_lds_budget, lds_budget.hpp), so that the kernel runs under the next batch's probe kernel
         const bool t16 = !sl.list_mode && sl.len2 == nullptr && s->long_bucket <= LONG_BUCKET_DEFAULT;
-        uint32_t G = WAVE;
-        while (G > 8 && k2_lds_bytes((uint32_t)d.bins, C, W, G, t16) > K2_LDS_BUDGET) G >>= 1;
+        const uint32_t wn = d.window_size - d.kmer_size + 1;
+        const size_t probe_lds = k1_lds_bytes(wn, C, MODE_ROWS, d.hash_funs, W, (uint32_t)d.bins, ring_pack_ok(d.kmer_size, wn, d.minimiser_seed));
+        const uint32_t G = k2_group((uint32_t)d.bins, C, W, t16, k2_lds_budget(probe_lds));
         k2.group = G;
         const size_t lds2 = k2_lds_bytes((uint32_t)d.bins, C, W, G, t16);
         if (lds2 > 150 * 1024) return fail(CHN_E_INVALID, "bins x categories too large for the count kernel's LDS");

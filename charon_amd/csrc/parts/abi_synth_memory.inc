@@ -128,7 +128,8 @@ extern "C" int chn_synth_plant(chn_index *idx, const uint32_t *dev_bases2, uint6
     a.shift = (uint32_t)d.hash_shift; a.h = d.hash_funs; a.k = d.kmer_size; a.wn = d.window_size - d.kmer_size + 1;
     a.n_reads = (uint32_t)n; a.nseg = 1; a.B = (uint32_t)d.bins; a.C = d.num_categories;
     a.bases = dev_bases2; a.off1 = off; a.len1 = len; a.read_bin = bin; a.n_bases = n_genomes * genome_len;
-    const size_t lds = k1_lds_bytes(a.wn, d.num_categories, MODE_EMPLACE, a.h, (uint32_t)d.bin_words, (uint32_t)d.bins);
+    a.pack = ring_pack_ok(a.k, a.wn, a.seed) ? 1u : 0u;
+    const size_t lds = k1_lds_bytes(a.wn, d.num_categories, MODE_EMPLACE, a.h, (uint32_t)d.bin_words, (uint32_t)d.bins, a.pack != 0);
     hipError_t e = launch_k1_w<MODE_EMPLACE>((uint32_t)d.bin_words, a, lds, 0);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     (void)hipFree(off); (void)hipFree(len); (void)hipFree(bin);

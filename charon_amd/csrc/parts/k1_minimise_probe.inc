@@ -4,7 +4,7 @@
 // ------------------------------------------------------------------------------------------------
 // k_minimise_probe
 // ------------------------------------------------------------------------------------------------
-enum { MODE_FUSED = 0, MODE_ROWS = 1, MODE_EMPLACE = 2, MODE_LIST = 3 };
+// (MODE_FUSED, MODE_ROWS, MODE_EMPLACE, MODE_LIST and the defaults of the macros below: lds_budget.hpp, which sizes this kernel's LDS)
 #ifndef CHN_LOG_BATCH
 #define CHN_LOG_BATCH 4  // probe rounds per row-log store (1: a 256-byte dword store per round; 4: a 1 KiB dwordx4 store per four rounds)
 #endif
@@ -56,6 +56,8 @@ struct K1Args {
     uint32_t nt_probes;      // non-temporal row gathers (index much larger than the Infinity Cache)
     const uint8_t *read_bin; // MODE_EMPLACE: target bin of "read" (genome chunk) r
     uint32_t ablate;         // diagnostics only (CHN_ABLATE env): 1 = skip the gathers, 2 = skip hash+gathers
+    uint32_t pack;           // the ring words carry their own offsets (ring_pack_ok(k, wn, seed), lds_budget.hpp): no offset plane in LDS.
+                             // The WN_T > 0 instances are always packed: the host launches them only when the rule holds.
     // Long reads over the lanes of a wavefront (SPLIT launches, below).  n_long = *n_long_ptr reads -- the first n_long entries of
     // `order`, which lists the longest reads first -- are left out by the ordinary launch and taken one per wavefront by the SPLIT
     // launch, whose workgroup x loops over the reads x, x + gridDim.x, ...; its wavefront logs are numbered from wave_slot0.
@@ -178,6 +180,13 @@ __device__ __forceinline__ void wait_vmcnt(uint32_t n) {
 // rightmost minimum of the window ending at offset t is then combine(S[t+1], running prefix minimum), and the
 // suffix minima are produced in place by one backward pass at every block end (all lanes are at the same t).
 //
+// Packed ring (a.pack; always when WN_T > 0): there is no `spos` plane.  A slot holds (v << pb) | (wn - 1 - u), pb = bits(wn - 1), u the
+// offset of the value in its block -- a raw value stored during the block and a suffix minimum read the same.  The top pb bits of v
+// are constants of the launch (the seed's: the k-mer ranks are below 5^k and ring_pack_ok says they end below bit 64 - pb), so the shift
+// loses nothing and they are put back when a word is unpacked.  The offset is complemented so that of two equal values the RIGHTMOST
+// has the smaller word: the backward pass is a chain of unsigned 64-bit minima over the words and still yields the rightmost suffix
+// minimum (the tie rule of SURVEY A.2), with no position select and no byte stores.
+//
 // Probe rounds are software-pipelined, two in flight: a round's h gathers are LDS-DMA loads into the wavefront's probe buffer
 // and are only retired (AND + accumulate / row-log store) two rounds (~22 bases) later, behind a counted s_waitcnt vmcnt(N),
 // so the HBM latency of the random gathers overlaps the hash rolling of the same wavefront.  Bases are fetched
@@ -191,6 +200,11 @@ __device__ __forceinline__ void wait_vmcnt(uint32_t n) {
 // rule would be; the piece before it runs up to and including that window's last value.  A piece whose first window has a tie
 // is not started: the piece before it simply runs on through it (a homopolymer read ends up as one lane's work, as before).  All
 // lanes add to owner slot 0 (LDS counters or the owner field of the row-log entries); lane 0 writes the read's results.
+__host__ __device__ constexpr uint32_t ring_pbits(uint32_t wn) {  // bits(wn - 1): width of a packed ring word's offset field
+    uint32_t n = 0;
+    for (uint32_t x = wn - 1; x; x >>= 1) ++n;
+    return n;
+}
 template <int W, int MODE, int WN_T, bool SPLIT = false, bool COND_T = false>
 __global__ __launch_bounds__(WAVE) void k_minimise_probe(const K1Args a) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -230,9 +244,15 @@ __global__ __launch_bounds__(WAVE) void k_minimise_probe(const K1Args a) {
     uint64_t *rbase = reinterpret_cast<uint64_t *>(qm + QC);                  // [64] EMPLACE bin
     uint32_t *cnt = reinterpret_cast<uint32_t *>(rbase + (MODE == MODE_EMPLACE ? WAVE : 0));  // MODE_FUSED [C][64]
     uint32_t *unq = cnt + (MODE == MODE_FUSED ? a.C * WAVE : 0);              // MODE_FUSED [C][64]
-    uint8_t *spos = reinterpret_cast<uint8_t *>(unq + (MODE == MODE_FUSED ? a.C * WAVE : 0));  // [wn][64] offset of S[u]
+    // packed ring: the words carry their offsets (wave-uniform; a compile-time fact of the WN_T > 0 instances)
+    const bool PK = WN_T ? true : a.pack != 0;
+    constexpr uint32_t PB_T = ring_pbits(WN_T ? WN_T : 1);
+    const uint32_t pbits = WN_T ? PB_T : ring_pbits(wn);  // bits(wn - 1)
+    const uint32_t omask = (1u << pbits) - 1u;
+    const uint64_t seed_top = pbits ? (a.seed >> (64u - pbits)) << (64u - pbits) : 0ULL;  // the bits of every value that the shift drops
+    uint8_t *spos = reinterpret_cast<uint8_t *>(unq + (MODE == MODE_FUSED ? a.C * WAVE : 0));  // [wn][64] offset of S[u] (not packed)
     // MODE_ROWS: CHN_LOG_BATCH rounds of compact entries are staged here and leave as ONE store of 16 bytes per lane
-    uint32_t *sbuf = reinterpret_cast<uint32_t *>(smem + (((size_t)(spos + (size_t)wn * WAVE - smem) + 15) & ~(size_t)15));
+    uint32_t *sbuf = reinterpret_cast<uint32_t *>(smem + (((size_t)(spos + (PK ? (size_t)0 : (size_t)wn * WAVE) - smem) + 15) & ~(size_t)15));
 
     const uint32_t lane = lane_id();
     const uint32_t g = SPLIT ? item : item * WAVE + lane;
@@ -666,14 +686,16 @@ __global__ __launch_bounds__(WAVE) void k_minimise_probe(const K1Args a) {
                 } else if (q + wn == p) {  // tracked minimum left the window: rightmost minimum of the new one
                     mv = pv; q = pq;
                     if (t + 1 < wn) {
-                        const uint64_t sv = ring[(t + 1) * WAVE + lane];
-                        if (sv < pv) { mv = sv; q = blk - wn + spos[(t + 1) * WAVE + lane]; }
+                        const uint64_t sw = ring[(t + 1) * WAVE + lane];
+                        const uint64_t sv = PK ? (sw >> pbits) | seed_top : sw;
+                        // (packed: the word holds wn - 1 - offset, the block before this one starts at blk - wn)
+                        if (sv < pv) { mv = sv; q = PK ? blk - 1u - ((uint32_t)sw & omask) : blk - wn + spos[(t + 1) * WAVE + lane]; }
                     }
                     emit = true;
                 } else if (v < mv) {
                     mv = v; q = p; emit = true;
                 }
-                ring[t * WAVE + lane] = v;
+                ring[t * WAVE + lane] = PK ? (v << pbits) | (uint64_t)(wn - 1u - t) : v;
                 // sequence shorter than one window: a single minimiser over all its values
                 if (!kSteady && i + 1 == L && p + 1 < wn) emit = true;
             }
@@ -682,14 +704,22 @@ __global__ __launch_bounds__(WAVE) void k_minimise_probe(const K1Args a) {
             if (t + 1 == wn) {
                 // block end: turn the raw values of this block into rightmost suffix minima, in place
                 uint64_t sv = ring[(wn - 1) * WAVE + lane];
-                uint32_t sp = wn - 1;
-                spos[(wn - 1) * WAVE + lane] = (uint8_t)sp;
+                if (PK) {  // the words order by (value, rightmost first): a plain minimum chain
+                    for (int u = (int)wn - 2; u >= 1; --u) {
+                        const uint64_t x = ring[u * WAVE + lane];
+                        sv = x < sv ? x : sv;
+                        ring[u * WAVE + lane] = sv;
+                    }
+                } else {
+                    uint32_t sp = wn - 1;
+                    spos[(wn - 1) * WAVE + lane] = (uint8_t)sp;
 #pragma unroll
-                for (int u = (int)wn - 2; u >= 1; --u) {
-                    const uint64_t x = ring[u * WAVE + lane];
-                    if (x < sv) { sv = x; sp = (uint32_t)u; }
-                    ring[u * WAVE + lane] = sv;
-                    spos[u * WAVE + lane] = (uint8_t)sp;
+                    for (int u = (int)wn - 2; u >= 1; --u) {
+                        const uint64_t x = ring[u * WAVE + lane];
+                        if (x < sv) { sv = x; sp = (uint32_t)u; }
+                        ring[u * WAVE + lane] = sv;
+                        spos[u * WAVE + lane] = (uint8_t)sp;
+                    }
                 }
                 t = 0; blk += wn;
             } else {
@@ -736,8 +766,9 @@ __global__ __launch_bounds__(WAVE) void k_minimise_probe(const K1Args a) {
         uint64_t sv = ~0ULL;
         uint32_t sq = 0;
         if (t + 1 < wn) {  // wave-uniform
-            sv = ring[(t + 1) * WAVE + lane];
-            sq = blk - wn + spos[(t + 1) * WAVE + lane];
+            const uint64_t sw = ring[(t + 1) * WAVE + lane];
+            sv = PK ? (sw >> pbits) | seed_top : sw;
+            sq = PK ? blk - 1u - ((uint32_t)sw & omask) : blk - wn + spos[(t + 1) * WAVE + lane];
         }
         const uint32_t code = (cur >> (j * 2)) & 3u;
         const uint32_t oc = (uint32_t)(hist2 >> (2 * (k - 1))) & 3u;
@@ -761,10 +792,10 @@ __global__ __launch_bounds__(WAVE) void k_minimise_probe(const K1Args a) {
         const bool emit = expire || less;
         mv = expire ? ev : (less ? v : mv);
         q = expire ? eq : (less ? p : q);
-        ring[t * WAVE + lane] = v;
+        ring[t * WAVE + lane] = PK ? (v << pbits) | (uint64_t)(wn - 1u - t) : v;
         if (t + 1 == wn) {
             // block end: turn the raw values of this block into rightmost suffix minima, in place
-            if (WN_T > 1) {
+            if (WN_T > 1) {  // (always packed)
                 uint64_t x[WN_T > 1 ? WN_T : 2];
 #pragma unroll
                 for (int u = 1; u < WN_T; ++u) x[u] = ring[u * WAVE + lane];
@@ -772,14 +803,17 @@ __global__ __launch_bounds__(WAVE) void k_minimise_probe(const K1Args a) {
                 for (int u = 1; u < WN_T; ++u) asm volatile("" : "+v"(x[u]));  // all reads issued and landed before the first store
                 constexpr int LAST = WN_T > 1 ? WN_T - 1 : 1;
                 uint64_t bsv = x[LAST];
-                uint32_t bsp = LAST;
-                spos[LAST * WAVE + lane] = (uint8_t)bsp;
 #pragma unroll
                 for (int u = WN_T - 2; u >= 1; --u) {
-                    const bool lt = x[u] < bsv;
-                    bsv = lt ? x[u] : bsv; bsp = lt ? (uint32_t)u : bsp;
+                    bsv = x[u] < bsv ? x[u] : bsv;
                     ring[u * WAVE + lane] = bsv;
-                    spos[u * WAVE + lane] = (uint8_t)bsp;
+                }
+            } else if (PK) {
+                uint64_t bsv = ring[(wn - 1) * WAVE + lane];
+                for (int u = (int)wn - 2; u >= 1; --u) {
+                    const uint64_t xx = ring[u * WAVE + lane];
+                    bsv = xx < bsv ? xx : bsv;
+                    ring[u * WAVE + lane] = bsv;
                 }
             } else {
                 uint64_t bsv = ring[(wn - 1) * WAVE + lane];

@@ -22,14 +22,14 @@ struct K2Args {
 };
 
 #define K2_THREADS 512
-#ifndef K2_LDS_BUDGET
-#define K2_LDS_BUDGET 7680u  // what seven probe wavefronts (22 208 B each at the default k, w, W <= 2) leave of a CU's 160 KB, less a margin
-#endif
 #define K2_UNROLL 4
 // T16: totals are 16 bits wide, two to a word (a read of fewer than 2^16 minimisers: the ordinary launch when longer reads go to the SPLIT
-// launch).  a.group owners are counted per sweep over the log (64 / a.group sweeps; the log slice stays in L2 between them): with 32 owners of
-// 100 bins the tables take 7.2 KB, which fits beside seven probe wavefronts on a CU (8.2 KB left), so the kernel runs UNDER the next batch's
-// probe kernel instead of waiting for the boundary between two of them (the 27 KB of 64 owners x 32-bit totals never fitted).
+// launch).  a.group owners are counted per sweep over the log (64 / a.group sweeps of two passes each; under the probe kernel an XCD's L2 turns
+// over between them, so count every sweep as a read of the log from HBM).  The host gives the tables what the probe wavefronts leave of a CU's
+// LDS (k2_lds_budget, lds_budget.hpp): at the default k, w and W <= 2 a probe wavefront with a packed ring takes 20 736 B, seven leave 18 688 B,
+// and all 64 owners of 100 bins (14 480 B + 256 B static) fit -- one sweep, the log read twice; where the ring is not packed (22 208 B, 8 384 B
+// left) 32 owners (7.2 KB) do, as before.  Either way the kernel runs UNDER the next batch's probe kernel instead of waiting for the boundary
+// between two of them (the 27 KB of 64 owners x 32-bit totals never fitted).
 template <int W, bool T16>
 __global__ __launch_bounds__(K2_THREADS) void k_count_wavelog(const K2Args a) {
     extern __shared__ __align__(16) unsigned char smem2[];
@@ -217,11 +217,7 @@ __global__ __launch_bounds__(K2L_THREADS) void k_count_longlog(const K2Args a) {
         if (tid < C) a.unique[(size_t)r * C + tid] = unq[tid];
     }
 }
-// LDS of one workgroup counting `G` owners at a time
-static size_t k2_lds_bytes(uint32_t B, uint32_t C, uint32_t W, uint32_t G, bool t16) {
-    const size_t tb = t16 ? (B + 1) / 2 : B;
-    return (size_t)G * tb * 4 + ((size_t)G * C + ((G * C) & 1u)) * 4 + (size_t)G * W * 8 + (size_t)G * C + 16;
-}
+// (LDS of one workgroup counting `G` owners at a time: k2_lds_bytes, lds_budget.hpp)
 
 // Deterministic log layout (dense row-sharded mode, chn_minimisers): region sizes per wavefront, then an exclusive scan.
 // (The default path lets every k_minimise_probe wavefront claim its region from an atomic cursor instead.)
