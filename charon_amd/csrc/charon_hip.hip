@@ -50,6 +50,7 @@
 
 #include "parts/common.inc"
 #include "parts/lds_budget.hpp"
+#include "parts/rowlog_entry.hpp"
 #include "parts/k1_minimise_probe.inc"
 #include "parts/k2_count_wavelog.inc"
 #include "parts/shard_kernels.inc"

@@ -172,6 +172,7 @@ static int rerun_worst_case(chn_stream *s, Slot &sl) {
     HIPCHK(hipStreamSynchronize(s->stream));
     int rc = s->big.ensure(total, (n + WAVE - 1) / WAVE + std::min<uint64_t>(sl.split_bound, total / len_bucket_floor(std::min(s->long_bucket, 247u)) + 1), (uint32_t)d.bin_words, 65536, 0, nw);
     if (rc) return rc;
+    sl.k1.chain = 0;  // worst-case regions are one entry per base: no chained second entries (launch_tail reads the flag from the slot)
     K1Args a = sl.k1;
     a.gate_started = a.gate_signal = nullptr;  // no probe gate: the slot's counter has counted this grid once already, and nothing waits for it
     fill_k1_log(a, sl, s->big, true);

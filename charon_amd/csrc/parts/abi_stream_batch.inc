@@ -684,6 +684,9 @@ static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind, bool bo
         a.gate_started = ctl + CTL_GATE; a.gate_signal = s->gate_signal; a.gate_value = s->gate_seq + 1;
     }
     if (prof) { HIPCHK(hipEventRecord(sl.ev[0], ps)); }
+    // Chained row-log entries (rowlog_entry.hpp): the ordinary launch of a whole-index MODE_ROWS batch only.  The SPLIT launch above went
+    // out unchained (k_count_longlog reads its logs), the list modes never chain, and a re-run after an overflow clears the flag again.
+    a.chain = (mode == MODE_ROWS && rowlog_chain_ok(a.B)) ? 1u : 0u;
     hipError_t e = launch_k1_mode(mode, W, a, lds, ps);
     if (e != hipSuccess) return fail(CHN_E_HIP, std::string("k_minimise_probe launch: ") + hipGetErrorString(e));
     if (gated) s->gate_seq += 1;
@@ -737,6 +740,7 @@ static int launch_tail(chn_stream *s, Slot &sl, LogBuf &lb, hipStream_t st) {
         k2.n_reads = (uint32_t)n; k2.B = (uint32_t)d.bins; k2.C = C; k2.W = W;
         std::memcpy(k2.b2c, d.bin_to_category, 256);
         k2.n_long_ptr = sl.split_bound && !sl.list_mode ? ctl + CTL_NLONG : nullptr; k2.wave_slot0 = n_waves;
+        k2.chain = sl.list_mode ? 0u : sl.k1.chain;  // as the ordinary probe launch of this batch wrote its logs
         const dim3 grid(n_waves), block(K2_THREADS);
         // 16-bit totals when no read of this launch can have 2^16 minimisers (reads of 2^15 bases and more go to the SPLIT launch); as many
         // owners per sweep as keep the tables within what the probe wavefronts of this stream's probe configuration leave of a CU's LDS

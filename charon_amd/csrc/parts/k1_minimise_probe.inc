@@ -58,6 +58,8 @@ struct K1Args {
     uint32_t ablate;         // diagnostics only (CHN_ABLATE env): 1 = skip the gathers, 2 = skip hash+gathers
     uint32_t pack;           // the ring words carry their own offsets (ring_pack_ok(k, wn, seed), lds_budget.hpp): no offset plane in LDS.
                              // The WN_T > 0 instances are always packed: the host launches them only when the rule holds.
+    uint32_t chain;          // MODE_ROWS, B <= 128: a row with 4..6 set bins is logged as two chained entries instead of escaping (rowlog_entry.hpp).
+                             // Only the ordinary launch of a whole-index batch; its log then goes to k_count_wavelog with K2Args::chain set.
     // Long reads over the lanes of a wavefront (SPLIT launches, below).  n_long = *n_long_ptr reads -- the first n_long entries of
     // `order`, which lists the longest reads first -- are left out by the ordinary launch and taken one per wavefront by the SPLIT
     // launch, whose workgroup x loops over the reads x, x + gridDim.x, ...; its wavefront logs are numbered from wave_slot0.
@@ -107,39 +109,16 @@ __device__ bool first_window_tied(const K1Args &a, uint64_t o, uint32_t wn) {
     return tie;
 }
 
-// Compact row-log entry: bits 0-1 number of set bins (0..3), bits 2-9 / 10-17 / 18-25 their indices, bits 26-31 the owner
-// lane.  A row with more than three set bins is rare (true bins + ~1 % false positives per bin): it is flagged by
-// count = 0 with a non-zero 24-bit field (bits 2-25) = 1 + index of its W full words in the wavefront's escaped-row region.
-#define ROWLOG_ESC_MASK 0x03fffffcu
-#define ROWLOG_ESC_MAX 0x00fffffeu  // largest escaped-row index one entry can name
+// (the compact row-log entry, its escape and its chain mode: rowlog_entry.hpp)
 // regions are multiples of 64 entries: with 256-byte aligned buffers every probe round's store is two whole 128-byte lines
 __host__ __device__ __forceinline__ uint64_t wave_log_cap(uint64_t sum_len, uint32_t cap_num) { return (((sum_len * cap_num) >> 16) + 64 + 63) & ~63ULL; }
 __host__ __device__ __forceinline__ uint64_t wave_esc_cap(uint64_t cap, uint32_t esc_shift) { return (cap >> esc_shift) + 64; }
 // returns the entry without the escape index (the caller adds (index + 1) << 2 for an escaped row)
 template <int W>
 __device__ __forceinline__ uint32_t encode_row(const uint64_t *acc, uint32_t B, uint32_t owner, bool &escaped) {
-    uint64_t m[W];
-    uint32_t pc = 0;
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-        m[w] = acc[w];
-        if (w == W - 1 && (B & 63u)) m[w] &= (1ULL << (B & 63u)) - 1;  // technical bins >= B never count
-        pc += (uint32_t)__popcll(m[w]);
-    }
-    escaped = pc > 3;
-    if (escaped) return owner << 26;
-    uint32_t e = pc | (owner << 26), slot = 0;
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-        uint64_t x = m[w];
-        while (x) {
-            const uint32_t b = (uint32_t)w * 64 + (uint32_t)__ffsll((long long)x) - 1;
-            x &= x - 1;
-            e |= b << (2 + 8 * slot);
-            ++slot;
-        }
-    }
-    return e;
+    uint32_t e[2];  // (unchained: the row-sharded kernels' logs; a row without a set bin gives owner << 26, which names nothing)
+    rowlog_encode<W>(acc, B, owner, false, e, escaped);
+    return e[0];
 }
 
 // LDS-DMA gather: every active lane's 16 bytes at `src` land at LDS byte address lds_dst (wave-uniform) + 16 * lane; no VGPR
@@ -359,9 +338,10 @@ __global__ __launch_bounds__(WAVE) void k_minimise_probe(const K1Args a) {
         if (lane == 0) { a.wave_meta[wslot].cap = wcap; a.wave_meta[wslot].esc_cap = ecap; }
     }
     bool overflow = false;   // wave-uniform
+    const bool chain = MODE == MODE_ROWS && !SPLIT && a.chain != 0;  // rows with 4..6 set bins are chained, not escaped (wave-uniform)
     uint32_t staged = 0, flushed = 0;  // MODE_ROWS: kept entries waiting in sbuf / already stored (consumed = flushed + staged)
 
-    // write the staged compact entries [0, count) to the row log at entry `first` (a multiple of CHN_LOG_BATCH x 64): 16 bytes per lane
+    // write the staged compact entries [0, count) to the row log at entry `first` (a multiple of 64; of CHN_LOG_BATCH x 64 unless a chained round forced an early flush): 16 bytes per lane
     auto log_flush = [&](uint32_t first, uint32_t count) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
@@ -424,14 +404,18 @@ __global__ __launch_bounds__(WAVE) void k_minimise_probe(const K1Args a) {
             }
         } else if (MODE == MODE_ROWS) {
             bool esc = false;
-            uint32_t entry = 0;
-            if (has) entry = encode_row<W>(acc, a.B, owner, esc);
+            uint32_t ent[2] = {0u, 0u}, ne = 0;
+            if (has) ne = rowlog_encode<W>(acc, a.B, owner, chain, ent, esc);
+            uint32_t entry = ent[0];
             // A row without a set bin says nothing to the count kernel (it only counts in num_hashes, which this kernel keeps itself):
             // it gets no entry.  In a read set that mostly misses the index -- what dehosting sees -- that is most of the log.
-            const bool keep = has && (esc || (entry & 0x03ffffffu) != 0);
-            const uint64_t km = __ballot(keep);
-            const uint32_t nk = (uint32_t)__popcll(km);
-            const uint32_t krank = __builtin_amdgcn_mbcnt_hi((uint32_t)(km >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)km, 0u));
+            // Chain mode: a row with 4..6 set bins gets two entries, back to back: a lane's rank counts the lanes before it once more
+            // for each of them that has two.
+            const bool keep = ne != 0, two = ne == 2;
+            const uint64_t km = __ballot(keep), tm = __ballot(two);
+            const uint32_t nk = (uint32_t)__popcll(km) + (uint32_t)__popcll(tm);
+            const uint32_t krank = __builtin_amdgcn_mbcnt_hi((uint32_t)(km >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)km, 0u)) +
+                                   __builtin_amdgcn_mbcnt_hi((uint32_t)(tm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tm, 0u));
             const bool fits = consumed + nk <= wcap;  // wave-uniform
             const uint64_t em = __ballot(esc);
             if (em) {  // escaped rows take the next free slots of the wavefront's escaped-row region
@@ -451,10 +435,25 @@ __global__ __launch_bounds__(WAVE) void k_minimise_probe(const K1Args a) {
 #ifndef CHN_DIAG_NO_STORE  // DIAGNOSTICS BUILD ONLY: what do the row-log stores cost the probe pipeline?
             if (CHN_LOG_BATCH == 1) {
                 if (keep && fits) a.rowlog[wbase + consumed + krank] = entry;
+                if (two && fits) a.rowlog[wbase + consumed + krank + 1] = ent[1];
             } else {
                 // kept entries are staged back to back; whenever CHN_LOG_BATCH x 64 of them are there they leave as one 1 KiB store
-                // and the (at most 63) entries behind them move to the front
+                // and the (at most 64) entries behind them move to the front
+                if (staged + nk > (CHN_LOG_BATCH + 1) * WAVE) {
+                    // (chain mode only, and rare: a round of up to 128 entries that the staging buffer cannot take beside what waits there --
+                    //  the whole 256-byte pieces of that leave first)
+                    const uint32_t whole = staged & ~(WAVE - 1u);
+                    if (fits) log_flush(flushed, whole);
+                    flushed += whole;
+                    const uint32_t rem = staged - whole;
+                    uint32_t t = 0;
+                    if (lane < rem) t = sbuf[whole + lane];
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    if (lane < rem) sbuf[lane] = t;
+                    staged = rem;
+                }
                 if (keep) sbuf[staged + krank] = entry;
+                if (two) sbuf[staged + krank + 1] = ent[1];
                 staged += nk;
                 if (staged >= CHN_LOG_BATCH * WAVE) {
                     if (fits) log_flush(flushed, CHN_LOG_BATCH * WAVE);

@@ -19,6 +19,7 @@ struct K2Args {
     const unsigned long long *n_long_ptr;
     uint32_t wave_slot0;
     uint32_t group;            // k_count_wavelog: owners counted per sweep over the log (64, 32, 16 or 8)
+    uint32_t chain;            // k_count_wavelog: the logs were written in chain mode (K1Args::chain, rowlog_entry.hpp); k_count_longlog's never are
 };
 
 #define K2_THREADS 512
@@ -35,6 +36,7 @@ __global__ __launch_bounds__(K2_THREADS) void k_count_wavelog(const K2Args a) {
     extern __shared__ __align__(16) unsigned char smem2[];
     __builtin_amdgcn_s_setprio(3);  // (runs under the next batch's probe kernel: see k_model_call)
     const uint32_t B = a.B, C = a.C, G = a.group;
+    const bool chain = a.chain != 0;
     const uint32_t TB = T16 ? (B + 1) / 2 : B;                            // words of totals per owner
     uint32_t *tot = reinterpret_cast<uint32_t *>(smem2);                 // [G][TB] total_bits_per_bin (:96-99)
     uint32_t *unq = tot + (size_t)G * TB;                                // [G][C]
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(K2_THREADS) void k_count_wavelog(const K2Args a) {
                 const uint32_t xs[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
-                    if ((i4 + u * K2_THREADS) * 4 + q < count) f(xs[q]);
+                    if ((i4 + u * K2_THREADS) * 4 + q < count) f(xs[q], (i4 + u * K2_THREADS) * 4 + q);
             }
         }
     };
@@ -81,14 +83,14 @@ __global__ __launch_bounds__(K2_THREADS) void k_count_wavelog(const K2Args a) {
         for (uint32_t i = tid; i < G * W; i += K2_THREADS) cmask[i] = 0;
         __syncthreads();
         // pass A: per-bin totals of each read
-        sweep([&](uint32_t x) {
-            const uint32_t o = (x >> 26) - o0, pc = x & 3u;
+        sweep([&](uint32_t x, uint32_t) {
+            const uint32_t o = (x >> 26) - o0, pc = rowlog_count(x);
             if (o >= G) return;
-            if (pc) {
-                bump(o, (x >> 2) & 0xffu);
-                if (pc > 1) bump(o, (x >> 10) & 0xffu);
-                if (pc > 2) bump(o, (x >> 18) & 0xffu);
-            } else if (x & ROWLOG_ESC_MASK) {  // escaped: more than three set bins, full row in the wavefront's escaped-row region
+            if (pc) {  // (both entries of a chained row come by here, each with its own bins)
+                bump(o, rowlog_bin(x, 0, chain));
+                if (pc > 1) bump(o, rowlog_bin(x, 1, chain));
+                if (pc > 2) bump(o, rowlog_bin(x, 2, chain));
+            } else if (x & ROWLOG_ESC_MASK) {  // escaped: more set bins than entries can name, full row in the wavefront's escaped-row region
                 const size_t j = ((x & ROWLOG_ESC_MASK) >> 2) - 1;
 #pragma unroll
                 for (int w = 0; w < W; ++w) {
@@ -119,15 +121,16 @@ __global__ __launch_bounds__(K2_THREADS) void k_count_wavelog(const K2Args a) {
         }
         __syncthreads();
         // pass B: a minimiser is a unique hit if exactly one category's chosen bin contains it (:121-136)
-        sweep([&](uint32_t x) {
-            const uint32_t o = (x >> 26) - o0, pc = x & 3u;
+        sweep([&](uint32_t x, uint32_t e) {
+            const uint32_t o = (x >> 26) - o0, pc = rowlog_count(x);
             if (o >= G) return;
             uint32_t found = 0, fbin = 0;
             if (pc) {
-                for (uint32_t j = 0; j < pc; ++j) {
-                    const uint32_t b = (x >> (2 + 8 * j)) & 0xffu;
-                    if ((cmask[o * W + (b >> 6)] >> (b & 63u)) & 1ULL) { ++found; fbin = b; }
-                }
+                if (rowlog_is_tail(x, chain)) return;  // judged with the entry before it
+                auto is_chosen = [&](uint32_t b) -> bool { return (cmask[o * W + (b >> 6)] >> (b & 63u)) & 1ULL; };
+                found = rowlog_match(x, chain, is_chosen, fbin);
+                // a chained row: its other bins are in the next entry (never read at or beyond `count`: rowlog_tail)
+                if (rowlog_has_tail(x, chain)) found += rowlog_match(rowlog_tail(log, e, count, chain), chain, is_chosen, fbin);
             } else if (x & ROWLOG_ESC_MASK) {
                 const size_t j = ((x & ROWLOG_ESC_MASK) >> 2) - 1;
 #pragma unroll

@@ -53,7 +53,7 @@ static inline size_t k1_lds_bytes(uint32_t wn, uint32_t C, int mode, uint32_t h,
     if (cond) b += (size_t)FUSED_ROUNDS * 1024;
     else if (mode == MODE_FUSED || mode == MODE_ROWS) b += (size_t)2 * h * (W <= 2 ? 1 : 2) * 1024;  // probe buffer: two rounds of h x NBLK x 1 KiB
     b = (b + 15) & ~(size_t)15;
-    if (mode == MODE_ROWS) b += (size_t)(CHN_LOG_BATCH + 1) * WAVE * 4;  // staged row-log entries (+ the at most 63 behind a full store)
+    if (mode == MODE_ROWS) b += (size_t)(CHN_LOG_BATCH + 1) * WAVE * 4;  // staged row-log entries (+ the at most 64 behind a full store)
     return b;
 }
 
