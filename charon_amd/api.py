@@ -129,6 +129,19 @@ class InflateCrc(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("expected", C.c_void_p), ("crc32", C.c_void_p)]
 
 
+INFLATE_STREAM_MAX_CHUNKS = 4096    # CHN_INFLATE_STREAM_MAX_CHUNKS
+INFLATE_STREAM_MIN_SYMS = 131072    # CHN_INFLATE_STREAM_MIN_SYMS
+INFLATE_E_ROOM = 8                  # CHN_INFLATE_E_ROOM
+
+
+class InflateStreamJob(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_chunks", C.c_uint64), ("in_", C.c_void_p), ("in_bytes", C.c_uint64),
+                ("begin_bit", C.c_void_p), ("target_bit", C.c_void_p), ("window", C.c_void_p), ("window_bytes", C.c_uint64),
+                ("sym_capacity", C.c_uint64), ("out", C.c_void_p), ("out_bytes", C.c_uint64), ("end_bit", C.c_void_p),
+                ("out_length", C.c_void_p), ("status", C.c_void_p), ("final", C.c_void_p), ("crc32", C.c_void_p),
+                ("n_counted", C.c_void_p), ("out_used", C.c_void_p)]
+
+
 DEFLATE_MAX_IN = 65280       # CHN_DEFLATE_MAX_IN
 DEFLATE_BGZF = 1             # CHN_DEFLATE_BGZF
 
@@ -158,7 +171,7 @@ EXPORTS = ["chn_index_create", "chn_index_upload_rows", "chn_index_device_words"
            "chn_stream_last_batch_bytes", "chn_synth_genomes", "chn_synth_fill_index", "chn_synth_plant", "chn_synth_reads",
            "chn_device_free", "chn_device_download", "chn_device_malloc", "chn_device_upload", "chn_host_alloc", "chn_host_free", "chn_shard_minimise",
            "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_text_submit", "chn_text_wait", "chn_text_pack", "chn_text_split", "chn_text_split_host", "chn_fasta_split", "chn_fasta_split_host", "chn_text_fetch", "chn_text_fetch_host", "chn_text_pair_ids", "chn_text_pair_ids_host", "chn_device_copy", "chn_inflate_create", "chn_inflate_run",
-           "chn_inflate_run_host", "chn_inflate_destroy", "chn_inflate_kernel_ms", "chn_inflate_run_crc", "chn_inflate_run_host_crc", "chn_deflate_create", "chn_deflate_run", "chn_deflate_run_host",
+           "chn_inflate_run_host", "chn_inflate_destroy", "chn_inflate_kernel_ms", "chn_inflate_run_crc", "chn_inflate_run_host_crc", "chn_inflate_stream_run", "chn_inflate_stream_run_host", "chn_deflate_create", "chn_deflate_run", "chn_deflate_run_host",
            "chn_deflate_destroy", "chn_deflate_bound", "chn_deflate_kernel_ms", "chn_deflate_group_members", "chn_extract_create", "chn_extract_destroy",
            "chn_extract_bound", "chn_extract_append_records", "chn_extract_append_bytes", "chn_extract_finish", "chn_extract_records_host",
            "chn_extract_kernel_ms", "chn_last_error", "chn_version"]
@@ -228,6 +241,8 @@ _L.chn_inflate_destroy.argtypes = [C.c_void_p]
 _L.chn_inflate_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
 _L.chn_inflate_run_crc.argtypes = [C.c_void_p, C.POINTER(InflateJob), C.POINTER(InflateCrc)]
 _L.chn_inflate_run_host_crc.argtypes = [C.POINTER(InflateJob), C.POINTER(InflateCrc)]
+_L.chn_inflate_stream_run.argtypes = [C.c_void_p, C.POINTER(InflateStreamJob)]
+_L.chn_inflate_stream_run_host.argtypes = [C.POINTER(InflateStreamJob)]
 _L.chn_deflate_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
 _L.chn_deflate_run.argtypes = [C.c_void_p, C.POINTER(DeflateJob)]
 _L.chn_deflate_run_host.argtypes = [C.POINTER(DeflateJob)]
@@ -920,8 +935,79 @@ def inflate_host(members, sizes, guard=0, expected=None, want_crc=False):
     return _inflate_crc_results(a, ca, want_crc)
 
 
+# ---- chunks of one deflate stream (see include/charon_hip.h) ----
+def inflate_stream_job(data, begin_bit, target_bit, window=b"", sym_capacity=INFLATE_STREAM_MIN_SYMS, out_bytes=0, guard=0, out=None,
+                       out_device=None, want_crc=True):
+    """the chn_inflate_stream_job of raw deflate `data` with chunks at begin_bit / target_bit and `window` in front of chunk 0.
+    out_bytes is what the job may write, `guard` bytes (0xA5) lie behind it in the array; `out`: a uint8 array to use (e.g. a
+    pinned_array); out_device: (device pointer, bytes) -- CHN_INFLATE_OUT_DEVICE, arrays["out"] is None.  Every output array starts
+    as all ones.  Returns (job, arrays) -- `arrays` keeps the memory alive and names it."""
+    n = len(begin_bit)
+    assert len(target_bit) == n
+    inp = np.frombuffer(bytes(data), np.uint8) if len(data) else np.zeros(0, np.uint8)
+    win = np.frombuffer(bytes(window), np.uint8) if len(window) else np.zeros(0, np.uint8)
+    begin = np.array([int(x) for x in begin_bit] + [0], np.uint64)
+    target = np.array([int(x) for x in target_bit] + [0], np.uint64)
+    if out_device is not None:
+        out = None
+        assert out_device[1] >= out_bytes
+    else:
+        if out is None:
+            out = np.empty(max(out_bytes + guard, 1), np.uint8)
+        assert out.dtype == np.uint8 and out.size >= out_bytes + guard
+        out[:] = 0xA5
+    a = dict(data=inp, window=win, begin_bit=begin, target_bit=target, out=out, out_bytes=out_bytes, guard=guard, n=n,
+             end_bit=np.full(n + 1, 2 ** 64 - 1, np.uint64), out_length=np.full(n + 1, 2 ** 64 - 1, np.uint64),
+             status=np.full(n + 1, 0xFFFFFFFF, np.uint32), final=np.full(n + 1, 0xFF, np.uint8),
+             crc32=np.full(n + 1, 0xFFFFFFFF, np.uint32) if want_crc else None, counts=np.full(2, 2 ** 64 - 1, np.uint64))
+    j = InflateStreamJob()
+    j.struct_size, j.flags, j.n_chunks = C.sizeof(InflateStreamJob), INFLATE_OUT_DEVICE if out_device is not None else 0, n
+    j.in_, j.in_bytes = (inp.ctypes.data if inp.size else None), inp.size
+    j.begin_bit, j.target_bit = begin.ctypes.data, target.ctypes.data
+    j.window, j.window_bytes = (win.ctypes.data if win.size else None), win.size
+    j.sym_capacity = sym_capacity
+    j.out, j.out_bytes = (out_device[0] if out_device is not None else out.ctypes.data), out_bytes
+    j.end_bit, j.out_length, j.status, j.final = a["end_bit"].ctypes.data, a["out_length"].ctypes.data, a["status"].ctypes.data, a["final"].ctypes.data
+    j.crc32 = a["crc32"].ctypes.data if want_crc else None
+    j.n_counted, j.out_used = a["counts"].ctypes.data, a["counts"].ctypes.data + 8
+    return j, a
+
+
+def _inflate_stream_results(a):
+    """dict of a finished stream job: n_counted, out_used, the per-chunk arrays cut to the COUNTED chunks, and `bytes` =
+    out[:out_used] (None for device output); the guard bytes behind out_bytes must be untouched"""
+    nc, used = int(a["counts"][0]), int(a["counts"][1])
+    res = dict(n_counted=nc, out_used=used, end_bit=[int(x) for x in a["end_bit"][:nc]], out_length=[int(x) for x in a["out_length"][:nc]],
+               status=[int(x) for x in a["status"][:nc]], final=[int(x) for x in a["final"][:nc]],
+               crc32=[int(x) for x in a["crc32"][:nc]] if a["crc32"] is not None else None, bytes=None)
+    if a["out"] is not None:
+        ob = a["out_bytes"]
+        if not (a["out"][ob:] == 0xA5).all():
+            raise ChnError("inflate stream: a byte behind out_bytes was written")
+        res["bytes"] = a["out"][:used].tobytes()
+    return res
+
+
+def inflate_stream_host(data, begin_bit, target_bit, **kw):
+    """chn_inflate_stream_run_host: the chunk decoder, the window hand-down and the byte rules the GPU runs, on the CPU.
+    Keywords as in inflate_stream_job.  Returns the dict of _inflate_stream_results."""
+    j, a = inflate_stream_job(data, begin_bit, target_bit, **kw)
+    _chk(_L.chn_inflate_stream_run_host(C.byref(j)))
+    return _inflate_stream_results(a)
+
+
 class Inflater:
     """chn_inflate: raw deflate members decoded on the device, one wavefront a member.  One thread at a time per object."""
+
+    def run_stream(self, data, begin_bit, target_bit, **kw):
+        """chn_inflate_stream_run: chunks of one deflate stream decoded side by side on the device (see inflate_stream_host)"""
+        j, a = inflate_stream_job(data, begin_bit, target_bit, **kw)
+        _chk(_L.chn_inflate_stream_run(self.h, C.byref(j)))
+        return _inflate_stream_results(a)
+
+    def run_stream_job(self, job):
+        """chn_inflate_stream_run on a prepared InflateStreamJob: no copies on the Python side, for measurements"""
+        _chk(_L.chn_inflate_stream_run(self.h, C.byref(job)))
 
     def __init__(self, device=0):
         self.h = C.c_void_p()

@@ -69,6 +69,7 @@
 #include "parts/text_pair.inc"
 #include "parts/extract_records.inc"
 #include "parts/inflate_members.inc"
+#include "parts/inflate_stream.inc"
 #include "parts/deflate_members.inc"
 #include "parts/ef_decode.inc"
 #include "parts/synth_kernels.inc"
@@ -81,6 +82,7 @@
 #include "parts/abi_text_pair.inc"
 #include "parts/abi_text_batch.inc"
 #include "parts/abi_inflate.inc"
+#include "parts/abi_inflate_stream.inc"
 #include "parts/abi_deflate.inc"
 #include "parts/abi_extract.inc"
 #include "parts/abi_shardx.inc"

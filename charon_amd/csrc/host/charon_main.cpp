@@ -100,6 +100,18 @@ static bool parse_gpu_inflate_env(const DehostArguments *opt) {
     else if (const char *d = std::getenv("CHARON_DEVICE")) g_gpu_inflate_device = std::atoi(d);
     return true;
 }
+// CHARON_GPU_INFLATE_STREAM: 1 (only together with CHARON_GPU_INFLATE=1) = the chunks of a one-stream .gz are inflated on the device
+// (chn_inflate_stream_run), 0 or unset = on the reader's threads; anything else is an error.  Read behind CHARON_GPU_INFLATE: same device.
+static bool parse_gpu_inflate_stream_env() {
+    const char *e = std::getenv("CHARON_GPU_INFLATE_STREAM");
+    if (!e) return true;
+    const std::string v(e);
+    if (v != "0" && v != "1") { std::cerr << "charon: CHARON_GPU_INFLATE_STREAM: '" << v << "' is neither 0 nor 1" << std::endl; return false; }
+    if (v == "1" && !g_gpu_inflate) { std::cerr << "charon: CHARON_GPU_INFLATE_STREAM: takes effect only together with CHARON_GPU_INFLATE=1, which is not set" << std::endl; return false; }
+    g_gpu_inflate_stream = v == "1";
+    g_gpu_inflate_stream_device = g_gpu_inflate_device;
+    return true;
+}
 // CHARON_GPU_DEFLATE: 1 = the extract files are compressed on the device as BGZF, 0 or unset = by zlib on the -t threads; anything else
 // is an error.  The device is CHARON_DEVICE, or the first entry of CHARON_DEVICES.
 static bool parse_gpu_deflate_env(const DehostArguments &opt) {
@@ -355,7 +367,7 @@ int main(int argc, char **argv) {
     if (sub == "_records") {  // hidden diagnostic: dump what the block reader sees (no GPU involved unless CHARON_GPU_INFLATE=1)
         try {
             if (argc < 3) return 2;
-            if (!parse_gpu_inflate_env(nullptr)) return 1;
+            if (!parse_gpu_inflate_env(nullptr) || !parse_gpu_inflate_stream_env()) return 1;
             if (const char *t = std::getenv("CHARON_READER_THREADS")) g_reader_threads = std::max(1, std::atoi(t));
             BlockReader in(argv[2]);
             RawBlock blk;
@@ -414,6 +426,7 @@ int main(int argc, char **argv) {
         opt.text_batches = v == "1";
     }
     if (!parse_gpu_inflate_env(&opt)) return 1;  // checked before the index file is opened and before any HIP call
+    if (!parse_gpu_inflate_stream_env()) return 1;  // likewise
     if (!parse_gpu_deflate_env(opt)) return 1;   // likewise
     if (const char *e = std::getenv("CHARON_GPU_TEXT")) {
         // CHARON_GPU_TEXT: 1 = single-end BGZF FASTQ is inflated into device memory and stays there (split, packed and classified on the device of

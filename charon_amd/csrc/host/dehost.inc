@@ -101,6 +101,15 @@ int dehost_main(DehostArguments &opt) {
     struct SlabPoolDrain { ~SlabPoolDrain() { std::lock_guard<std::mutex> lk(g_slab_pool.m); g_slab_pool.v.clear(); } } slab_pool_drain;
     struct DevTextPoolDrain { ~DevTextPoolDrain() { g_dev_text_pool.drain(); } } dev_text_pool_drain;  // (CHARON_GPU_TEXT=1) likewise
     if (g_gpu_inflate) g_log.info("CHARON_GPU_INFLATE=1: BGZF members are inflated on device " + std::to_string(g_gpu_inflate_device) + " (size and CRC-32 are checked on the device)");
+    if (g_gpu_inflate_stream) {  // one line per input file: on (and where), or why not; the kind of input is what a reader makes of the file
+        for (const std::string &f : {opt.read_file, opt.read_file2}) {
+            if (f.empty()) continue;
+            std::string why;
+            try { why = BlockReader(f).gpu_inflate_stream_note(); } catch (std::exception &) { continue; }  // (the reader thread reports what is wrong with it)
+            if (why.empty()) g_log.info("CHARON_GPU_INFLATE_STREAM=1: the chunks of the one-stream .gz are inflated on device " + std::to_string(g_gpu_inflate_stream_device) + " (chn_inflate_stream_run; block starts are searched on the reader's threads)");
+            else g_log.info("CHARON_GPU_INFLATE_STREAM=1 does not apply: " + why);
+        }
+    }
     if (g_gpu_deflate) g_log.info("CHARON_GPU_DEFLATE=1: extract files are compressed on device " + std::to_string(g_gpu_deflate_device) + " (BGZF members of 65280 bytes)");
     if (opt.text_batches) g_log.info("CHARON_TEXT_BATCHES=1: reads go to the device as text (letters -> codes and mean quality on the GPU)");
     // reader thread: parses whole-record blocks while the previous batch is packed / compressed / classified / printed.  It starts

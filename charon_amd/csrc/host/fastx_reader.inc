@@ -599,6 +599,15 @@ public:
     BlockReader(const BlockReader &) = delete;
     BlockReader &operator=(const BlockReader &) = delete;
 
+    // CHARON_GPU_INFLATE_STREAM=1 applies to a one-stream .gz that this build's decoder reads in parallel rounds; empty if it does,
+    // else why it does not
+    std::string gpu_inflate_stream_note() const {
+        if (bgzf_) return "the input is BGZF (its members are inflated on the device under CHARON_GPU_INFLATE=1)";
+        if (bz_) return "the input is bzip2";
+        if (gz_) return std::getenv("CHARON_SERIAL_INFLATE") ? "CHARON_SERIAL_INFLATE is set (one sequential inflate, no chunks)" : "";
+        if (ends_with(path_, ".gz")) return std::getenv("CHARON_ZLIB_INFLATE") ? "CHARON_ZLIB_INFLATE is set (zlib reads the file)" : "zlib reads the file (it is not a mappable gzip file)";
+        return "the input is not compressed";
+    }
     // CHARON_GPU_TEXT=1 applies to BGZF input in FASTQ form only
     bool is_bgzf_fastq() const { return bgzf_ && fastq_; }
     // the next block of the file as text in device memory (null at the end of the file)

@@ -530,14 +530,20 @@ const char *huffman(BitIn &in_, const uint32_t *lt, const uint32_t *dt, Out *bas
 }
 }  // namespace inflate_core
 
+// CHARON_GPU_INFLATE_STREAM=1 (with CHARON_GPU_INFLATE=1): phases B-D of a parallel round -- decode, windows, bytes and CRC -- are one
+// chn_inflate_stream_run on this device; the block-start search stays on the reader's threads
+bool g_gpu_inflate_stream = false;
+int g_gpu_inflate_stream_device = 0;
+
 class FastInflate {
     typedef inflate_core::BitIn BitIn;
     enum { WSIZE = inflate_core::WSIZE };
 public:
     explicit FastInflate(const std::string &path) : path_(path) {}
     ~FastInflate() {
-        if (std::getenv("CHARON_DIAG_INFLATE"))
+        if (std::getenv("CHARON_DIAG_INFLATE") && t_fill_ > 0)  // (a reader that was opened only to be asked what it is says nothing)
             std::fprintf(stderr, "inflate totals: fill %.3f s; rounds: search %.3f  decode %.3f  windows %.3f  bytes+crc %.3f  (round calls %.3f)\n", t_fill_, t_ph_[0], t_ph_[1], t_ph_[2], t_ph_[3], t_round_);
+        if (gpu_) (void)chn_inflate_destroy(gpu_);
         if (map_) ::munmap(const_cast<uint8_t *>(map_), map_size_);
     }
     FastInflate(const FastInflate &) = delete;
@@ -561,6 +567,13 @@ public:
         work_.assign(WSIZE + 8, 0);
         if (const char *c = std::getenv("CHARON_INFLATE_CHUNK")) chunk_bytes_ = std::max<size_t>(1024, (size_t)std::atol(c));  // tests
         serial_only_ = std::getenv("CHARON_SERIAL_INFLATE") != nullptr;
+        gpu_stream_ = g_gpu_inflate_stream && !serial_only_;
+        if (gpu_stream_) {
+            // more and smaller chunks than the host path's -t chunks of 1 MiB: a chunk is one wavefront's work, and a device has LDS for
+            // two workgroups a CU.  Both defaults are guesses that no measurement stands behind.
+            if (!std::getenv("CHARON_INFLATE_CHUNK")) chunk_bytes_ = (size_t)256 << 10;
+            if (const char *c = std::getenv("CHARON_GPU_INFLATE_ROUND")) gpu_round_ = std::min<size_t>(CHN_INFLATE_STREAM_MAX_CHUNKS, std::max<size_t>(2, (size_t)std::atol(c)));  // tests
+        }
         return true;
     }
     bool at_end() const { return state_ == DONE && pend_pos_ >= pend_len_; }
@@ -586,10 +599,10 @@ public:
             }
             if (state_ == DONE) break;
             if (state_ == MEMBER_HEADER) member_header();
-            const bool want_parallel = !serial_only_ && g_reader_threads > 1 && !parallel_failed;
+            const bool want_parallel = !serial_only_ && (g_reader_threads > 1 || gpu_stream_) && !parallel_failed;
             if (want_parallel && state_ == BLOCK_HEADER) {
                 const double tr0 = omp_get_wtime();
-                const bool did = parallel_round(out, max_out - produced, produced);
+                const bool did = gpu_stream_ ? gpu_round(out, max_out - produced, produced) : parallel_round(out, max_out - produced, produced);
                 t_round_ += omp_get_wtime() - tr0;
                 if (did) continue;
                 parallel_failed = true;  // too close to the end, or no block starts found: the rest of this call sequentially
@@ -623,6 +636,10 @@ private:
     uint64_t rounds_ = 0, chunks_ok_ = 0, chunks_lost_ = 0;
     unsigned poor_rounds_ = 0;
     double t_fill_ = 0, t_round_ = 0, t_ph_[4] = {0, 0, 0, 0};
+    // CHARON_GPU_INFLATE_STREAM=1
+    bool gpu_stream_ = false;
+    size_t gpu_round_ = 256;  // chunks per round
+    chn_inflate *gpu_ = nullptr;
 
     [[noreturn]] void fail(const char *what) const { throw std::runtime_error("gzip read error in " + path_ + ": " + what); }
 
@@ -998,6 +1015,102 @@ private:
         in_.start(map_, map_ + map_size_, lastc.end_pos);
         final_block_ = lastc.final_seen;
         state_ = lastc.final_seen ? MEMBER_TRAILER : BLOCK_HEADER;
+        return true;
+    }
+
+    // One round with phases B-D on the device (CHARON_GPU_INFLATE_STREAM=1): the search as in parallel_round, then ONE
+    // chn_inflate_stream_run over the round's stretch of the mapped file -- its counting rule is the induction of phase C, its window the
+    // reader's kept window, its per-chunk CRCs are joined as phase D's.  The round's bytes arrive in pending_; the first `budget` of them
+    // are copied to the end of `out`.  False: no progress possible this way (fewer than two starts; chunk 0 stopped for want of input,
+    // symbol capacity or room, or on corrupt data, without a complete block) -- the caller decodes on sequentially, and it is the
+    // sequential decoder that names what is wrong with a corrupt stream, in the words and with the exit status of the host path.
+    bool gpu_round(Slab &out, size_t budget, size_t &produced) {
+        const uint64_t pos0 = in_.bitpos(map_);
+        const size_t byte0 = (size_t)(pos0 >> 3);
+        if (map_size_ < byte0 + 8 + 2 * chunk_bytes_) return false;
+        const size_t room = map_size_ - 8 - byte0;
+        const int nchunks = (int)std::min<size_t>(gpu_round_, room / chunk_bytes_);
+        if (nchunks < 2) return false;
+        const double tA = omp_get_wtime();
+        std::vector<uint64_t> found((size_t)nchunks, NONE);
+        found[0] = pos0;
+#pragma omp parallel num_threads(std::max(1, std::min(g_reader_threads, nchunks - 1)))
+        {
+            std::vector<uint16_t> scratch;
+#pragma omp for schedule(dynamic, 1)
+            for (int i = 1; i < nchunks; ++i)
+                found[(size_t)i] = find_block((uint64_t)(byte0 + (size_t)i * chunk_bytes_) * 8, (uint64_t)(byte0 + (size_t)(i + 1) * chunk_bytes_) * 8, scratch);
+        }
+        std::vector<uint64_t> begin, target;  // bit positions from byte0
+        for (int i = 0; i < nchunks; ++i) if (found[(size_t)i] != NONE) begin.push_back(found[(size_t)i] - (uint64_t)byte0 * 8);
+        if (begin.size() < 2) {
+            if (++poor_rounds_ >= 3) serial_only_ = true;
+            return false;
+        }
+        const size_t n = begin.size();
+        const uint64_t round_end = (uint64_t)nchunks * chunk_bytes_ * 8;
+        for (size_t k = 0; k < n; ++k) target.push_back(k + 1 < n ? begin[k + 1] : round_end);
+        const double tB = omp_get_wtime();
+        if (!gpu_ && chn_inflate_create(g_gpu_inflate_stream_device, &gpu_) != CHN_OK)
+            throw std::runtime_error(std::string("CHARON_GPU_INFLATE_STREAM: ") + chn_last_error());
+        // the last chunk decodes on to a block boundary behind the round's end: a block more of input.  What a chunk may produce and what
+        // the round may produce are bounds: a chunk or a round beyond them ends the chain there (status 5 / CHN_INFLATE_E_ROOM)
+        const size_t stretch = std::min(map_size_ - byte0, (size_t)nchunks * chunk_bytes_ + std::max<size_t>(chunk_bytes_, (size_t)256 << 10));
+        const size_t out_room = (size_t)nchunks * chunk_bytes_ * 6 + 65536;
+        if (pending_.size() < out_room) pending_.resize(out_room);
+        std::vector<uint64_t> end_bit(n), out_length(n);
+        std::vector<uint32_t> status(n), crc(n);
+        std::vector<uint8_t> fin(n);
+        uint64_t counted = 0, used = 0;
+        const uint64_t reach = std::min<uint64_t>(member_out_, WSIZE);
+        chn_inflate_stream_job job;
+        std::memset(&job, 0, sizeof job);
+        job.struct_size = sizeof job; job.n_chunks = n;
+        job.in = map_ + byte0; job.in_bytes = stretch;
+        job.begin_bit = begin.data(); job.target_bit = target.data();
+        job.window = work_.data() + WSIZE - reach; job.window_bytes = reach;
+        job.sym_capacity = std::max<uint64_t>(CHN_INFLATE_STREAM_MIN_SYMS, (uint64_t)chunk_bytes_ * 12);
+        job.out = pending_.data(); job.out_bytes = out_room;
+        job.end_bit = end_bit.data(); job.out_length = out_length.data(); job.status = status.data(); job.final = fin.data(); job.crc32 = crc.data();
+        job.n_counted = &counted; job.out_used = &used;
+        if (chn_inflate_stream_run(gpu_, &job) != CHN_OK) throw std::runtime_error(std::string("CHARON_GPU_INFLATE_STREAM: ") + chn_last_error());
+        const double tC = omp_get_wtime();
+        // the stream stands where the last counted chunk that came forward at all stopped
+        size_t last = 0;
+        bool any = false;
+        for (size_t k = 0; k < counted; ++k) if (end_bit[k] > begin[k]) { last = k; any = true; }
+        const uint32_t why = status[counted ? counted - 1 : 0];
+        if (why == 2 || why == 3 || why == 4) serial_only_ = true;  // corrupt where its start is proven: the sequential decoder says what it is
+        if (!any) {
+            if (++poor_rounds_ >= 3) serial_only_ = true;
+            return false;
+        }
+        chunks_ok_ += last + 1; chunks_lost_ += n - (last + 1); rounds_ += 1;
+        if (last == 0 && ++poor_rounds_ >= 3) serial_only_ = true;
+        static const bool skip_crc = std::getenv("CHARON_DIAG_NO_CRC") != nullptr;
+        size_t total = 0;
+        for (size_t k = 0; k <= last; ++k) {
+            if (!skip_crc && out_length[k]) crc_ = (uint32_t)crc32_combine(crc_, crc[k], (z_off_t)out_length[k]);
+            total += (size_t)out_length[k];
+        }
+        const size_t direct = std::min(total, budget);
+        out.insert(out.end(), reinterpret_cast<char *>(pending_.data()), reinterpret_cast<char *>(pending_.data()) + direct);
+        pend_pos_ = direct; pend_len_ = total;
+        if (pend_pos_ >= pend_len_) { pend_pos_ = 0; pend_len_ = 0; }
+        produced += direct;
+        member_out_ += total;
+        keep_window(pending_.data(), total);
+        in_.start(map_, map_ + map_size_, (uint64_t)byte0 * 8 + end_bit[last]);
+        final_block_ = fin[last] != 0;
+        state_ = final_block_ ? MEMBER_TRAILER : BLOCK_HEADER;
+        t_ph_[0] += tB - tA; t_ph_[1] += tC - tB; t_ph_[3] += omp_get_wtime() - tC;
+        static const bool diag = std::getenv("CHARON_DIAG_INFLATE") != nullptr;
+        if (diag && std::getenv("CHARON_DIAG_INFLATE_ROUNDS")) {
+            double ms = 0;
+            (void)chn_inflate_kernel_ms(gpu_, &ms);
+            std::fprintf(stderr, "inflate round (device): %d chunks, %zu with a start, %zu counted; search %.1f ms, chn_inflate_stream_run %.1f ms (kernels %.1f ms); %zu bytes out\n",
+                         nchunks, n, last + 1, (tB - tA) * 1e3, (tC - tB) * 1e3, ms, total);
+        }
         return true;
     }
 };

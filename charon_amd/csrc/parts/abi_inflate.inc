@@ -22,12 +22,15 @@ struct InflateSet {
     uint64_t first = 0, n = 0, out_bytes = 0;  // the group in this set
     bool direct = false, busy = false, crc = false, dev_out = false;
 };
+struct InflateStreamState;  // chn_inflate_stream_run's buffers (abi_inflate_stream.inc), made by its first call
+static void inflate_stream_release(InflateStreamState *s);
 struct chn_inflate {
     int device = 0;
     hipStream_t s_up = nullptr, s_run = nullptr, s_down = nullptr;
     InflateSet set[2];
     double kernel_ms = 0;  // device time of the last run's kernels
     int cus = 0;
+    InflateStreamState *ss = nullptr;
 };
 
 static int inflate_check_job(const chn_inflate_job *j, const char *who, bool host_call) {
@@ -125,6 +128,7 @@ extern "C" int chn_inflate_destroy(chn_inflate *h) {
         st.h_in.release(); st.h_out.release(); st.h_desc.release(); st.h_status.release();
         for (hipEvent_t ev : {st.up, st.done, st.down, st.k0, st.k1}) if (ev) (void)hipEventDestroy(ev);
     }
+    inflate_stream_release(h->ss);
     if (h->s_up) (void)hipStreamDestroy(h->s_up);
     if (h->s_run) (void)hipStreamDestroy(h->s_run);
     if (h->s_down) (void)hipStreamDestroy(h->s_down);

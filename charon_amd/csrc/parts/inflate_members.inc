@@ -173,17 +173,50 @@ struct InfWavePolicy {
 };
 #endif
 
+// ---- output sides ----------------------------------------------------------------------------------------------------------------
+// What the decoder does with a literal, a stored byte and a match is its output side O: room(n) -- may n more come?  reach(dist) -- is
+// that far back still the stream's?  lit / put / match -- the writes (the decoder's p.sync() stand around match);  block_end(bit, final)
+// -- a block is complete at that bit position: stop here?  finish() -- the status of a decode that stopped there.
+// InfMemberOut: a member of known size, whole in `win` (sh.win + the destination's misalignment); a back-reference is an LDS read.
+// (inflate_stream.inc has the other one: an unbounded stream of 16-bit symbols behind a ring.)
+struct InfMemberOut {
+    uint8_t *win;  // output byte k lives at win[k]
+    uint32_t out_len, opos;
+    __host__ __device__ bool room(uint32_t n) const { return opos + n <= out_len; }
+    __host__ __device__ bool reach(uint32_t dist) const { return dist <= opos; }  // not before the member's first byte
+    template <class P> __host__ __device__ void lit(P &p, uint32_t b) {
+        if (p.lane() == 0) win[opos] = (uint8_t)b;
+        ++opos;
+    }
+    template <class P> __host__ __device__ void put(P &p, uint32_t v, uint32_t n) {  // the low n <= 4 bytes of v
+        for (uint32_t i = p.lane(); i < n; i += P::LANES) win[opos + i] = (uint8_t)(v >> (8 * i));
+        opos += n;
+    }
+    // lane j copies byte j; an overlapping copy (dist < len) repeats the dist bytes in front of it
+    template <class P> __host__ __device__ void match(P &p, uint32_t dist, uint32_t len) {
+        const uint32_t lane = p.lane();
+        uint8_t *to = win + opos;
+        const uint8_t *from = to - dist;
+        if (dist >= len) for (uint32_t k = lane; k < len; k += P::LANES) to[k] = from[k];
+        else if (dist == 1) { const uint8_t b = from[0]; for (uint32_t k = lane; k < len; k += P::LANES) to[k] = b; }
+        else for (uint32_t k = lane; k < len; k += P::LANES) to[k] = from[k % dist];
+        opos += len;
+    }
+    __host__ __device__ bool block_end(uint64_t, bool final) { return final; }
+    __host__ __device__ int finish() const { return opos == out_len ? INF_OK : INF_E_SHORT; }
+};
+
 // ---- the decoder -----------------------------------------------------------------------------------------------------------------
-template <class P> struct InfDecoder {
+template <class P, class O = InfMemberOut> struct InfDecoder {
     P &p;
     InfShared &sh;
+    O &o;
     uint64_t bb = 0;      // bit buffer
     uint32_t bc = 0;      // bits in it
     uint32_t wpos = 0;    // next input word
     uint64_t bit_end;     // the member's last bit, counted like wpos * 32 - bc
-    uint32_t opos = 0, out_len, wmis;
 
-    __host__ __device__ InfDecoder(P &p_, InfShared &sh_, uint32_t out_len_, uint32_t wmis_) : p(p_), sh(sh_), bit_end(p_.bit_end()), out_len(out_len_), wmis(wmis_) {
+    __host__ __device__ InfDecoder(P &p_, InfShared &sh_, O &o_) : p(p_), sh(sh_), o(o_), bit_end(p_.bit_end()) {
         wpos = p.first_word();
         refill(); refill();
         const uint32_t skip = (uint32_t)(p.bit_begin() - (uint64_t)p.first_word() * 32);  // 0, 8, 16 or 24 bits in front of the member
@@ -298,21 +331,18 @@ template <class P> struct InfDecoder {
         const uint32_t len = bits(16), nlen = bits(16);
         if (over()) return INF_E_INPUT;
         if ((len ^ nlen) != 0xFFFFu) return INF_E_HEADER;
-        if (opos + len > out_len) return INF_E_OVER;
+        if (!o.room(len)) return INF_E_OVER;
         if ((bit_end - ((uint64_t)wpos * 32 - bc)) / 8 < len) return INF_E_INPUT;
         uint32_t left = len;
-        const uint32_t lane = p.lane();
         while (left >= 4) {
             refill();
-            const uint32_t v = bits(32);
-            for (uint32_t i = lane; i < 4; i += P::LANES) sh.win[wmis + opos + i] = (uint8_t)(v >> (8 * i));
-            opos += 4; left -= 4;
+            o.put(p, bits(32), 4);
+            left -= 4;
         }
         while (left) {
             refill();
-            const uint32_t v = bits(8);
-            if (lane == 0) sh.win[wmis + opos] = (uint8_t)v;
-            ++opos; --left;
+            o.lit(p, bits(8));
+            --left;
         }
         p.sync();
         return INF_OK;
@@ -370,16 +400,14 @@ template <class P> struct InfDecoder {
     }
 
     __host__ __device__ int symbols() {
-        const uint32_t lane = p.lane();
         for (;;) {
             refill();
             const uint32_t e = symbol(sh.ll, INF_LL_ROOT);
             const uint32_t kind = (e >> 4) & 15;
             if (over()) return INF_E_INPUT;
             if (kind == INF_K_LIT) {
-                if (opos >= out_len) return INF_E_OVER;
-                if (lane == 0) sh.win[wmis + opos] = (uint8_t)(e >> 16);
-                ++opos;
+                if (!o.room(1)) return INF_E_OVER;
+                o.lit(p, e >> 16);
                 continue;
             }
             if (kind == INF_K_EOB) return INF_OK;
@@ -390,16 +418,10 @@ template <class P> struct InfDecoder {
             if (((d >> 4) & 15) != INF_K_LEN) return over() ? INF_E_INPUT : INF_E_SYMBOL;
             const uint32_t dist = (d >> 16) + bits((d >> 8) & 31);
             if (over()) return INF_E_INPUT;
-            if (dist > opos) return INF_E_SYMBOL;  // reaches before the member's first byte
-            if (opos + len > out_len) return INF_E_OVER;
+            if (!o.reach(dist)) return INF_E_SYMBOL;  // reaches before the member's first byte
+            if (!o.room(len)) return INF_E_OVER;
             p.sync();  // the literals written so far are visible to every lane
-            // lane j copies byte j; an overlapping copy (dist < len) repeats the dist bytes in front of it
-            uint8_t *to = sh.win + wmis + opos;
-            const uint8_t *from = to - dist;
-            if (dist >= len) for (uint32_t k = lane; k < len; k += P::LANES) to[k] = from[k];
-            else if (dist == 1) { const uint8_t b = from[0]; for (uint32_t k = lane; k < len; k += P::LANES) to[k] = b; }
-            else for (uint32_t k = lane; k < len; k += P::LANES) to[k] = from[k % dist];
-            opos += len;
+            o.match(p, dist, len);
             p.sync();
         }
     }
@@ -418,9 +440,9 @@ template <class P> struct InfDecoder {
                 if (rc == INF_OK) rc = symbols();
             }
             if (rc) return rc;
-            if (hdr & 1) break;
+            if (o.block_end((uint64_t)wpos * 32 - bc, (hdr & 1) != 0)) break;
         }
-        return opos == out_len ? INF_OK : INF_E_SHORT;
+        return o.finish();
     }
 };
 
@@ -494,9 +516,10 @@ template <class P> __host__ __device__ static uint32_t inf_crc32(P &p, InfShared
 // host entry: one member, `sh` is the caller's scratch; writes min(produced, out_len) bytes; *crc (if asked for) is set where the status is 0
 static int inf_member_host(InfShared &sh, const uint8_t *in, uint64_t in_len, uint8_t *out, uint32_t out_len, uint32_t *crc = nullptr) {
     InfHostPolicy pol{in, in_len};
-    InfDecoder<InfHostPolicy> d(pol, sh, out_len, 0);
+    InfMemberOut o{sh.win, out_len, 0};
+    InfDecoder<InfHostPolicy> d(pol, sh, o);
     const int st = d.run();
-    if (d.opos) std::memcpy(out, sh.win, std::min(d.opos, out_len));
+    if (o.opos) std::memcpy(out, sh.win, std::min(o.opos, out_len));
     if (crc && st == INF_OK) *crc = inf_crc32(pol, sh, 0, out_len);
     return st;
 }
@@ -537,9 +560,10 @@ template <bool CRC> __global__ void __launch_bounds__(WAVE) k_inflate_members(In
         int st;
         uint32_t produced;
         {
-            InfDecoder<InfWavePolicy> d(pol, sh, out_len, wmis);
+            InfMemberOut o{sh.win + wmis, out_len, 0};
+            InfDecoder<InfWavePolicy> d(pol, sh, o);
             st = d.run();
-            produced = min(d.opos, out_len);
+            produced = min(o.opos, out_len);
         }
         pol.sync();
         if (CRC && st == INF_OK) {  // (wave-uniform) only a member that decoded completely has a CRC

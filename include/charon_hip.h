@@ -673,6 +673,59 @@ typedef struct chn_inflate_crc {
 int chn_inflate_run_crc(chn_inflate *h, const chn_inflate_job *job, const chn_inflate_crc *crc);   /* synchronous */
 int chn_inflate_run_host_crc(const chn_inflate_job *job, const chn_inflate_crc *crc);
 
+/* ---- chunks of ONE deflate stream on the device (the ordinary one-stream .gz of the front end; no reference counterpart: the
+ * reference reads through seqan3's gz input stream on CPU threads, src/dehost_main.cpp:324) ---------------------------------------
+ * A job names n_chunks bit positions inside raw deflate data `in` (RFC 1951, no gzip header; it need not reach the end of the stream):
+ * begin_bit[i] is the position of the block header chunk i starts at, strictly increasing; chunk 0's is a true block start BY CONTRACT,
+ * the others may be guesses.  k_inflate_chunks decodes all chunks side by side, one wavefront each, without the 32 KiB of output in
+ * front of them (16-bit symbols; a match reaching in front of its chunk leaves markers that name window positions): chunk i decodes
+ * whole blocks until it stands at a block boundary at or behind target_bit[i] (>= begin_bit[i]) or has decoded a final block.  Then the
+ * windows are handed down the chunks in stream order (window[k + 1] = the last 32 768 bytes of window[k] followed by chunk k's bytes;
+ * `window`, at most 32 768 bytes, is what lies in front of chunk 0, window_bytes == 0: a member starts here) and every chunk's symbols
+ * become bytes and a CRC-32 (zlib's crc32(0, bytes of chunk i, out_length[i])).
+ * Per chunk: end_bit[i] / out_length[i] = the last complete block boundary it reached and the bytes it produced up to there;
+ * final[i] = 1 if that block had BFINAL; status[i] says why it stopped: 0 at its target or behind a final block | 1 input exhausted
+ * | 2, 3, 4 as in chn_inflate_job | 5 sym_capacity exhausted inside a block | CHN_INFLATE_E_ROOM out_bytes exhausted.
+ * THE COUNTING RULE (the front end's induction): chunk k is PROVEN if k == 0, or if chunk k - 1 is proven, status[k - 1] == 0,
+ * final[k - 1] == 0 and end_bit[k - 1] == begin_bit[k] -- its predecessor came to stand exactly on its start.  *n_counted is the
+ * number of proven chunks.  The bytes of proven chunk k -- through its last complete block, whatever its status -- lie in `out` back
+ * to back at the running sum of out_length; *out_used is their total.  The outputs of unproven chunks and the bytes of `out` behind
+ * *out_used are unspecified; nothing is ever written behind out_bytes.  A proven chunk whose bytes do not fit gets
+ * CHN_INFLATE_E_ROOM and out_length 0 and ends the chain.
+ * THE DISTANCE RULE: a match that reaches in front of the member's first byte is status 4 (zlib's "invalid distance too far back").
+ * Chunk 0 notices it while decoding (the distance exceeds window_bytes + its bytes so far), a later chunk when a marker resolves to a
+ * window position below 32 768 - (window_bytes + the bytes of the chunks before it); such a chunk reports out_length 0 and
+ * end_bit == begin_bit and ends the chain.
+ * A corrupt or falsely started chunk is never an error of the call.  CHN_E_INVALID, with chn_last_error() naming the chunk and nothing
+ * having run or been written: a wrong struct_size, an unknown flag (CHN_INFLATE_OUT_DEVICE is the only one; the _host form refuses
+ * it), n_chunks > CHN_INFLATE_STREAM_MAX_CHUNKS, begin_bit not increasing or at or beyond 8 * in_bytes, target_bit[i] < begin_bit[i],
+ * window_bytes > 32768, sym_capacity < CHN_INFLATE_STREAM_MIN_SYMS, a NULL array but crc32.  n_chunks == 0 is a no-op.
+ * sym_capacity is the number of symbols ONE chunk may produce (the device keeps n_chunks stretches of that many 16-bit symbols;
+ * values above 2^30 are taken as 2^30).  `in` is host memory, pageable or page-locked; `out` is host memory, or with
+ * CHN_INFLATE_OUT_DEVICE device memory of the handle's device (checked before anything is launched, as in chn_inflate_run).
+ * chn_inflate_stream_run is synchronous and shares the handle (ONE thread at a time) with chn_inflate_run; chn_inflate_kernel_ms
+ * afterwards reports the device time of this run's kernels.  chn_inflate_stream_run_host runs the same decoder source and the same
+ * hand-down and byte rules on one CPU thread. */
+#define CHN_INFLATE_STREAM_MAX_CHUNKS 4096u
+#define CHN_INFLATE_STREAM_MIN_SYMS 131072u
+#define CHN_INFLATE_E_ROOM 8u   /* status: a proven chunk whose bytes do not fit into out_bytes */
+typedef struct chn_inflate_stream_job {
+    uint32_t struct_size, flags;              /* flags: 0 or CHN_INFLATE_OUT_DEVICE */
+    uint64_t n_chunks;
+    const uint8_t *in;  uint64_t in_bytes;    /* HOST */
+    const uint64_t *begin_bit; const uint64_t *target_bit;   /* [n] */
+    const uint8_t *window;  uint64_t window_bytes;           /* HOST: the output in front of chunk 0, at most 32 768 bytes */
+    uint64_t sym_capacity;
+    uint8_t *out;  uint64_t out_bytes;        /* HOST (CHN_INFLATE_OUT_DEVICE: DEVICE) */
+    uint64_t *end_bit; uint64_t *out_length;  /* [n] out */
+    uint32_t *status;                         /* [n] out */
+    uint8_t *final;                           /* [n] out */
+    uint32_t *crc32;                          /* [n] out, or NULL */
+    uint64_t *n_counted; uint64_t *out_used;  /* out */
+} chn_inflate_stream_job;
+int chn_inflate_stream_run(chn_inflate *h, const chn_inflate_stream_job *job);   /* synchronous */
+int chn_inflate_stream_run_host(const chn_inflate_stream_job *job);              /* same decoder source on the CPU, one thread; no GPU needed */
+
 /* ---- deflate on the device (the extract files of the front end; no reference counterpart: the reference writes through zlib's
  * gzFile on one CPU thread) -------------------------------------------------------------------------------------------------------
  * A job names n_members independent pieces of at most CHN_DEFLATE_MAX_IN bytes (bgzip's block size) inside `in`.  Every piece becomes
