@@ -142,6 +142,14 @@ class InflateStreamJob(C.Structure):
                 ("n_counted", C.c_void_p), ("out_used", C.c_void_p)]
 
 
+INFLATE_SEARCH_NONE = 2 ** 64 - 1    # CHN_INFLATE_SEARCH_NONE
+
+
+class InflateSearchJob(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_ranges", C.c_uint64), ("in_", C.c_void_p), ("in_bytes", C.c_uint64),
+                ("from_bit", C.c_void_p), ("to_bit", C.c_void_p), ("found_bit", C.c_void_p)]
+
+
 DEFLATE_MAX_IN = 65280       # CHN_DEFLATE_MAX_IN
 DEFLATE_BGZF = 1             # CHN_DEFLATE_BGZF
 
@@ -171,7 +179,7 @@ EXPORTS = ["chn_index_create", "chn_index_upload_rows", "chn_index_device_words"
            "chn_stream_last_batch_bytes", "chn_synth_genomes", "chn_synth_fill_index", "chn_synth_plant", "chn_synth_reads",
            "chn_device_free", "chn_device_download", "chn_device_malloc", "chn_device_upload", "chn_host_alloc", "chn_host_free", "chn_shard_minimise",
            "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_text_submit", "chn_text_wait", "chn_text_pack", "chn_text_split", "chn_text_split_host", "chn_fasta_split", "chn_fasta_split_host", "chn_text_fetch", "chn_text_fetch_host", "chn_text_pair_ids", "chn_text_pair_ids_host", "chn_device_copy", "chn_inflate_create", "chn_inflate_run",
-           "chn_inflate_run_host", "chn_inflate_destroy", "chn_inflate_kernel_ms", "chn_inflate_run_crc", "chn_inflate_run_host_crc", "chn_inflate_stream_run", "chn_inflate_stream_run_host", "chn_deflate_create", "chn_deflate_run", "chn_deflate_run_host",
+           "chn_inflate_run_host", "chn_inflate_destroy", "chn_inflate_kernel_ms", "chn_inflate_run_crc", "chn_inflate_run_host_crc", "chn_inflate_stream_run", "chn_inflate_stream_run_host", "chn_inflate_stream_search_host", "chn_deflate_create", "chn_deflate_run", "chn_deflate_run_host",
            "chn_deflate_destroy", "chn_deflate_bound", "chn_deflate_kernel_ms", "chn_deflate_group_members", "chn_extract_create", "chn_extract_destroy",
            "chn_extract_bound", "chn_extract_append_records", "chn_extract_append_bytes", "chn_extract_finish", "chn_extract_records_host",
            "chn_extract_kernel_ms", "chn_last_error", "chn_version"]
@@ -243,6 +251,7 @@ _L.chn_inflate_run_crc.argtypes = [C.c_void_p, C.POINTER(InflateJob), C.POINTER(
 _L.chn_inflate_run_host_crc.argtypes = [C.POINTER(InflateJob), C.POINTER(InflateCrc)]
 _L.chn_inflate_stream_run.argtypes = [C.c_void_p, C.POINTER(InflateStreamJob)]
 _L.chn_inflate_stream_run_host.argtypes = [C.POINTER(InflateStreamJob)]
+_L.chn_inflate_stream_search_host.argtypes = [C.POINTER(InflateSearchJob)]
 _L.chn_deflate_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
 _L.chn_deflate_run.argtypes = [C.c_void_p, C.POINTER(DeflateJob)]
 _L.chn_deflate_run_host.argtypes = [C.POINTER(DeflateJob)]
@@ -994,6 +1003,37 @@ def inflate_stream_host(data, begin_bit, target_bit, **kw):
     j, a = inflate_stream_job(data, begin_bit, target_bit, **kw)
     _chk(_L.chn_inflate_stream_run_host(C.byref(j)))
     return _inflate_stream_results(a)
+
+
+# ---- block starts of one deflate stream (see include/charon_hip.h) ----
+def inflate_search_job(data, from_bit, to_bit):
+    """the chn_inflate_search_job of the ranges [from_bit[i], to_bit[i]) of `data`.  found_bit starts as 0xA5 bytes.
+    Returns (job, arrays) -- `arrays` keeps the memory alive and names it."""
+    n = len(from_bit)
+    assert len(to_bit) == n
+    inp = np.frombuffer(bytes(data), np.uint8) if len(data) else np.zeros(0, np.uint8)
+    a = dict(data=inp, n=n, from_bit=np.array([int(x) for x in from_bit] + [0], np.uint64),
+             to_bit=np.array([int(x) for x in to_bit] + [0], np.uint64), found_bit=np.full(n + 1, 0xA5A5A5A5A5A5A5A5, np.uint64))
+    j = InflateSearchJob()
+    j.struct_size, j.flags, j.n_ranges = C.sizeof(InflateSearchJob), 0, n
+    j.in_, j.in_bytes = (inp.ctypes.data if inp.size else None), inp.size
+    j.from_bit, j.to_bit, j.found_bit = a["from_bit"].ctypes.data, a["to_bit"].ctypes.data, a["found_bit"].ctypes.data
+    return j, a
+
+
+def _inflate_search_results(a):
+    """the found positions of a finished search job, None where there is none; the element behind the last must be untouched"""
+    if int(a["found_bit"][a["n"]]) != 0xA5A5A5A5A5A5A5A5:
+        raise ChnError("inflate search: an element behind found_bit[n_ranges - 1] was written")
+    return [None if int(x) == INFLATE_SEARCH_NONE else int(x) for x in a["found_bit"][:a["n"]]]
+
+
+def inflate_search_host(data, from_bit, to_bit):
+    """chn_inflate_stream_search_host: the first position of every range [from_bit[i], to_bit[i]) where a dynamic block seems to
+    start (rules R0 - R6 of the header), on the CPU.  Returns a list of positions, None for none."""
+    j, a = inflate_search_job(data, from_bit, to_bit)
+    _chk(_L.chn_inflate_stream_search_host(C.byref(j)))
+    return _inflate_search_results(a)
 
 
 class Inflater:

@@ -70,6 +70,7 @@
 #include "parts/extract_records.inc"
 #include "parts/inflate_members.inc"
 #include "parts/inflate_stream.inc"
+#include "parts/inflate_search.inc"
 #include "parts/deflate_members.inc"
 #include "parts/ef_decode.inc"
 #include "parts/synth_kernels.inc"
@@ -83,6 +84,7 @@
 #include "parts/abi_text_batch.inc"
 #include "parts/abi_inflate.inc"
 #include "parts/abi_inflate_stream.inc"
+#include "parts/abi_inflate_search.inc"
 #include "parts/abi_deflate.inc"
 #include "parts/abi_extract.inc"
 #include "parts/abi_shardx.inc"

@@ -223,6 +223,17 @@ int main(int argc, char **argv) {
             return total == ztotal || std::getenv("CHARON_SKIP_ZLIB") ? 0 : 3;
         } catch (std::exception &e) { std::cerr << "charon: " << e.what() << std::endl; return 1; }
     }
+    if (sub == "_find_blocks") {  // hidden diagnostic: _find_blocks <file> <chunk bytes> [first byte]: the reader's own block-start search
+        try {                     // (FastInflate::find_block) over the raw file in ranges of that size; "from to found" in bits, "-" for none
+            if (argc < 4) return 2;
+            const long chunk = std::atol(argv[3]), first = argc > 4 ? std::atol(argv[4]) : 0;
+            if (chunk < 1 || first < 0) return 2;
+            FastInflate fi(argv[2]);
+            if (!fi.open()) { std::cerr << "charon: not a mappable gzip file\n"; return 1; }
+            fi.find_blocks_dump((size_t)chunk, (size_t)first, std::cout);
+            return 0;
+        } catch (std::exception &e) { std::cerr << "charon: " << e.what() << std::endl; return 1; }
+    }
     if (sub == "_bgzf_crc") {  // hidden diagnostic: the CRC-32 pass of the reader's threads over the first members of a BGZF file (no GPU involved)
         try {                  // _bgzf_crc <file> <members> <-t value> [repetitions]: what CHARON_GPU_INFLATE=1 no longer does on the host
             if (argc < 5) return 2;

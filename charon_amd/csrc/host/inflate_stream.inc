@@ -576,6 +576,16 @@ public:
         }
         return true;
     }
+    // hidden diagnostic (charon _find_blocks): find_block over the mapped file from byte `first` on in ranges of `chunk` bytes, one line
+    // a range: from to found, in bits of the file, "-" for none
+    void find_blocks_dump(size_t chunk, size_t first, std::ostream &os) const {
+        std::vector<uint16_t> scratch;
+        for (uint64_t from = (uint64_t)first * 8, end = (uint64_t)map_size_ * 8; from < end; from += (uint64_t)chunk * 8) {
+            const uint64_t to = std::min(end, from + (uint64_t)chunk * 8), at = find_block(from, to, scratch);
+            os << from << " " << to << " ";
+            if (at == NONE) os << "-\n"; else os << at << "\n";
+        }
+    }
     bool at_end() const { return state_ == DONE && pend_pos_ >= pend_len_; }
     uint64_t parallel_rounds() const { return rounds_; }
     uint64_t chunks_accepted() const { return chunks_ok_; }

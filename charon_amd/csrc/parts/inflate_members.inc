@@ -180,6 +180,7 @@ struct InfWavePolicy {
 // InfMemberOut: a member of known size, whole in `win` (sh.win + the destination's misalignment); a back-reference is an LDS read.
 // (inflate_stream.inc has the other one: an unbounded stream of 16-bit symbols behind a ring.)
 struct InfMemberOut {
+    static const bool ASKS_FIRST = false;  // room() is asked for what a code produced, behind the code (true: also in front of every literal/length code)
     uint8_t *win;  // output byte k lives at win[k]
     uint32_t out_len, opos;
     __host__ __device__ bool room(uint32_t n) const { return opos + n <= out_len; }
@@ -401,6 +402,7 @@ template <class P, class O = InfMemberOut> struct InfDecoder {
 
     __host__ __device__ int symbols() {
         for (;;) {
+            if (O::ASKS_FIRST && !o.room(1)) return INF_E_OVER;  // (a compile-time constant: only the search's side stops in front of a code)
             refill();
             const uint32_t e = symbol(sh.ll, INF_LL_ROOT);
             const uint32_t kind = (e >> 4) & 15;
@@ -424,6 +426,23 @@ template <class P, class O = InfMemberOut> struct InfDecoder {
             o.match(p, dist, len);
             p.sync();
         }
+    }
+
+    // the header of the block that starts here and nothing of its data: the three bits, a stored block's LEN / NLEN behind the byte
+    // boundary, a dynamic block's code sets (inflate_search.inc: what follows an end-of-block must be a block again)
+    __host__ __device__ int header_only() {
+        refill();
+        const uint32_t hdr = bits(3);
+        if (over()) return INF_E_INPUT;
+        const uint32_t type = hdr >> 1;
+        if (type == 1) return INF_OK;
+        if (type == 2) return dynamic_tables();
+        if (type == 3) return INF_E_HEADER;
+        drop(bc & 7);
+        refill();
+        const uint32_t len = bits(16), nlen = bits(16);
+        if (over()) return INF_E_INPUT;
+        return (len ^ nlen) != 0xFFFFu ? INF_E_HEADER : INF_OK;
     }
 
     __host__ __device__ int run() {

@@ -34,6 +34,7 @@ struct alignas(16) Inf16 { uint32_t w[4]; };  // one 16-byte load / store on eit
 __host__ __device__ static inline uint64_t infs_stride(uint32_t cap) { return ((uint64_t)cap + INFS_GROUP - 1) / INFS_GROUP * INFS_GROUP; }
 
 struct InfRingOut {
+    static const bool ASKS_FIRST = false;
     uint16_t *ring;     // INFS_WIN symbols: symbol p lives at ring[p % INFS_WIN] until it is stored
     uint16_t *sym;      // the chunk's stretch of the scratch, 16-byte aligned, infs_stride(cap) symbols
     uint32_t cap;       // symbols the chunk may produce

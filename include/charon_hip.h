@@ -726,6 +726,41 @@ typedef struct chn_inflate_stream_job {
 int chn_inflate_stream_run(chn_inflate *h, const chn_inflate_stream_job *job);   /* synchronous */
 int chn_inflate_stream_run_host(const chn_inflate_stream_job *job);              /* same decoder source on the CPU, one thread; no GPU needed */
 
+/* ---- block starts of ONE deflate stream (the search in front of chn_inflate_stream_run; CPU form only; no reference counterpart: the
+ * reference reads through seqan3's gz input stream on CPU threads, src/dehost_main.cpp:324) ---------------------------------------
+ * A job names n_ranges ranges [from_bit[i], to_bit[i]) of bit positions inside `in` (positions count from bit 0 of `in`, LSB first);
+ * the ranges need not be ordered or disjoint.  found_bit[i] is the FIRST position p of range i that passes all of R0 - R6, or
+ * CHN_INFLATE_SEARCH_NONE:
+ *   R0  (p >> 3) + 8 <= in_bytes, and with at = p + 17 also (at >> 3) + 9 <= in_bytes;
+ *   R1  the 3 bits at p are BFINAL = 0, BTYPE = 2 (value 4), the HLIT field is <= 29 and the HDIST field is <= 29;
+ *   R2  of the HCLEN + 4 three-bit code-length-code lengths at p + 17, 128 >> l summed over the non-zero lengths l is exactly 128;
+ *   R3  the dynamic header parses by the rules of the library's decoder (zlib's: a complete code-length code, repeats in range, an
+ *       end-of-block code present, literal/length and distance sets complete or a single 1-bit code, an empty distance set);
+ *   R4  the block decodes symbol by symbol until end-of-block or until at least 32 768 output symbols have been produced: the count is
+ *       checked before each literal/length code is read, a match counts as its length and may pass the limit, nothing read after the
+ *       limit is reached can refute; every literal is text (9, 10, 13 or 32 .. 126), every code is valid, no more bits are consumed
+ *       than `in` holds.  There is NO distance check: the window is unknown, any distance up to 32 768 is acceptable anywhere;
+ *   R5  at least 32 symbols were produced;
+ *   R6  if the block ended at end-of-block, the next three bits start a block header that parses, with any BFINAL: type 0 with
+ *       LEN == ~NLEN behind the byte boundary, type 1 always, type 2 a dynamic header as under R3; type 3 refutes.
+ * A found position is only a CANDIDATE: noise passes these tests now and then, and it is the counting rule of chn_inflate_stream_run
+ * (a chunk in front of it comes to stand exactly on it) that proves or refutes it.
+ * CHN_E_INVALID, with chn_last_error() naming the range and nothing having run or been written: a wrong struct_size, a non-zero flag,
+ * n_ranges > CHN_INFLATE_STREAM_MAX_CHUNKS, a NULL array, from_bit[i] > to_bit[i], to_bit[i] > 8 * in_bytes.  n_ranges == 0 is a
+ * no-op; an empty range reports CHN_INFLATE_SEARCH_NONE.
+ * chn_inflate_stream_search_host runs on the calling thread, with the decoder source of chn_inflate_stream_run_host and an output side
+ * that stores nothing.  There is no device form of the call yet: the job struct is laid out for one (a handle as first argument, as
+ * chn_inflate_stream_run has it). */
+#define CHN_INFLATE_SEARCH_NONE (~(uint64_t)0)
+typedef struct chn_inflate_search_job {
+    uint32_t struct_size, flags;              /* flags: 0 */
+    uint64_t n_ranges;                        /* <= CHN_INFLATE_STREAM_MAX_CHUNKS */
+    const uint8_t *in;  uint64_t in_bytes;    /* HOST */
+    const uint64_t *from_bit; const uint64_t *to_bit;   /* [n] from <= to <= 8 * in_bytes */
+    uint64_t *found_bit;                      /* [n] out: the position, or CHN_INFLATE_SEARCH_NONE */
+} chn_inflate_search_job;
+int chn_inflate_stream_search_host(const chn_inflate_search_job *job);              /* one CPU thread; no GPU needed */
+
 /* ---- deflate on the device (the extract files of the front end; no reference counterpart: the reference writes through zlib's
  * gzFile on one CPU thread) -------------------------------------------------------------------------------------------------------
  * A job names n_members independent pieces of at most CHN_DEFLATE_MAX_IN bytes (bgzip's block size) inside `in`.  Every piece becomes
