@@ -74,6 +74,7 @@
 #include "parts/deflate_members.inc"
 #include "parts/ef_decode.inc"
 #include "parts/synth_kernels.inc"
+#include "parts/abi_device_call.inc"
 #include "parts/abi_index_model.inc"
 #include "parts/abi_stream_batch.inc"
 #include "parts/abi_shard_wait.inc"

@@ -3,7 +3,8 @@
 //
 // chn_deflate_run works through a job in groups of members (at most 1 024, about 64 MiB of input) on three streams of the handle's own,
 // as chn_inflate_run does: while group g is compressed, the pieces of group g + 1 are packed into page-locked staging (each on a 16-byte
-// boundary) and uploaded, and the members of group g - 1 are downloaded.  Two sets of grow-only buffers take turns.
+// boundary) and uploaded, and the members of group g - 1 are downloaded.  Two sets of grow-only buffers take turns.  The handle is a
+// CodecPipe and the loop is run_groups (abi_device_call.inc); deflate_launch, deflate_ensure and deflate_collect also serve chn_extract.
 // k_deflate_members leaves member i in its own stretch of DFL_SLOT bytes; k_deflate_scan turns the sizes into offsets and
 // k_deflate_gather moves the members back to back, so one copy of exactly the group's bytes brings them to the host -- straight into
 // `out` where that is page-locked, through staging otherwise.  The sizes travel first (a few bytes a member): the host needs their sum
@@ -17,14 +18,17 @@ struct DeflateSet {
     hipEvent_t up = nullptr, done = nullptr, sized = nullptr, down = nullptr, k0 = nullptr, k1 = nullptr;
     uint64_t first = 0, n = 0;  // the group in this set
     bool busy = false;
+    int make_events(const char *who) { return events_create(who, {&up, &done, &sized, &down}, {&k0, &k1}); }
+    void release() {
+        for (DevBuf *b : {&d_in, &d_desc, &d_slots, &d_res, &d_packed, &d_cursor}) b->release();
+        for (PinBuf *b : {&h_in, &h_desc, &h_res, &h_out}) b->release();
+        events_destroy({&up, &done, &sized, &down, &k0, &k1});
+    }
 };
-struct chn_deflate {
-    int device = 0;
-    hipStream_t s_up = nullptr, s_run = nullptr, s_down = nullptr;
+struct chn_deflate : CodecPipe {
     DeflateSet set[2];
     DevBuf d_tokens;       // the workgroups' token scratch (one kernel runs at a time)
     double kernel_ms = 0;  // device time of the last run's kernels
-    int cus = 0;
     uint32_t group_members = DFL_GROUP_MEMBERS;
 };
 
@@ -87,55 +91,15 @@ extern "C" int chn_deflate_run_host(const chn_deflate_job *j) {
     return CHN_OK;
 }
 
-extern "C" int chn_deflate_create(int32_t device, chn_deflate **out) {
-    if (!out) return fail(CHN_E_INVALID, "chn_deflate_create: null argument");
-    *out = nullptr;
-    int count = 0;
-    HIPCHK(hipGetDeviceCount(&count));
-    if (device < 0 || device >= count) return fail(CHN_E_INVALID, "chn_deflate_create: device " + std::to_string(device) + " is not below the device count " + std::to_string(count));
-    HIPCHK(hipSetDevice(device));
-    chn_deflate *h = new (std::nothrow) chn_deflate;
-    if (!h) return fail(CHN_E_NOMEM, "chn_deflate_create: no memory");
-    h->device = device;
-    hipDeviceProp_t prop;
-    hipError_t e = hipGetDeviceProperties(&prop, device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->s_up, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->s_run, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->s_down, hipStreamNonBlocking);
-    for (int s = 0; s < 2 && e == hipSuccess; ++s) {
-        DeflateSet &st = h->set[s];
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&st.up, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&st.done, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&st.sized, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&st.down, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreate(&st.k0);
-        if (e == hipSuccess) e = hipEventCreate(&st.k1);
-    }
-    if (e != hipSuccess) {
-        const std::string msg = std::string("chn_deflate_create: ") + hipGetErrorString(e);
-        chn_deflate_destroy(h);
-        return fail(CHN_E_HIP, msg);
-    }
-    h->cus = prop.multiProcessorCount;
-    *out = h;
-    return CHN_OK;
-}
+extern "C" int chn_deflate_create(int32_t device, chn_deflate **out) { return codec_create(device, out, "chn_deflate_create", chn_deflate_destroy); }
 
 extern "C" int chn_deflate_destroy(chn_deflate *h) {
     if (!h) return CHN_OK;
     (void)hipSetDevice(h->device);
-    if (h->s_up) (void)hipStreamSynchronize(h->s_up);
-    if (h->s_run) (void)hipStreamSynchronize(h->s_run);
-    if (h->s_down) (void)hipStreamSynchronize(h->s_down);
-    for (DeflateSet &st : h->set) {
-        st.d_in.release(); st.d_desc.release(); st.d_slots.release(); st.d_res.release(); st.d_packed.release(); st.d_cursor.release();
-        st.h_in.release(); st.h_desc.release(); st.h_res.release(); st.h_out.release();
-        for (hipEvent_t ev : {st.up, st.done, st.sized, st.down, st.k0, st.k1}) if (ev) (void)hipEventDestroy(ev);
-    }
+    h->drain();
+    for (DeflateSet &st : h->set) st.release();
     h->d_tokens.release();
-    if (h->s_up) (void)hipStreamDestroy(h->s_up);
-    if (h->s_run) (void)hipStreamDestroy(h->s_run);
-    if (h->s_down) (void)hipStreamDestroy(h->s_down);
+    h->destroy();
     delete h;
     return CHN_OK;
 }
@@ -190,7 +154,7 @@ static int deflate_ensure(chn_deflate *h, DeflateSet &st, uint64_t n, uint64_t i
     int rc;
     if ((rc = st.h_desc.ensure(desc_bytes)) || (rc = st.d_desc.ensure(st.h_desc.cap)) ||
         (rc = st.d_slots.ensure((size_t)n * DFL_SLOT + 16)) || (rc = st.h_res.ensure(res_bytes)) || (rc = st.d_res.ensure(st.h_res.cap)) ||
-        (rc = st.d_packed.ensure(packed_bytes + (st.d_packed.cap < packed_bytes ? packed_bytes / 4 : 0))) || (rc = st.d_cursor.ensure(16)) ||
+        (rc = st.d_packed.ensure_grow(packed_bytes, packed_bytes / 4)) || (rc = st.d_cursor.ensure(16)) ||
         (rc = h->d_tokens.ensure((size_t)std::max(1, h->cus) * 2 * DFL_MAX_IN * 4)))  // (for the widest grid at once: a kernel may be running on it)
         return rc;
     return CHN_OK;
@@ -204,7 +168,7 @@ static int deflate_issue(chn_deflate *h, DeflateSet &st, const chn_deflate_job *
     const size_t desc_bytes = (size_t)n * 12;
     int rc;
     if ((rc = deflate_ensure(h, st, n, in_total, j->flags)) ||
-        (rc = st.h_in.ensure((size_t)in_bytes + 16 + (st.h_in.cap < in_bytes + 16 ? in_bytes / 4 : 0))) || (rc = st.d_in.ensure(st.h_in.cap)))
+        (rc = st.h_in.ensure_grow((size_t)in_bytes + 16, (size_t)(in_bytes / 4))) || (rc = st.d_in.ensure(st.h_in.cap)))
         return rc;
     uint64_t *in_off = st.h_desc.as<uint64_t>();
     uint32_t *in_len = reinterpret_cast<uint32_t *>(in_off + n);
@@ -223,34 +187,29 @@ static int deflate_issue(chn_deflate *h, DeflateSet &st, const chn_deflate_job *
     return deflate_launch(h, st, st.d_in.as<uint8_t>(), n, in_total, j->flags);
 }
 
-// wait for the group in set `st`, download its members behind `*used` and hand offsets, sizes and CRCs to the caller
-static int deflate_collect(chn_deflate *h, DeflateSet &st, const chn_deflate_job *j, bool out_pinned, uint64_t *used) {
+// Wait for the sizes of the group in set `st`, check them against DFL_SLOT and the bound of `in_total` bytes of input, and download the
+// group's members to out + *used: straight there where `out` is page-locked, through staging otherwise.  `*kernel_ms` takes the group's
+// device time; `who`, `member` and `of_what` word the two refusals.  The offsets, sizes and CRCs stay in st.h_res for the caller.
+static int deflate_collect(chn_deflate *h, DeflateSet &st, uint64_t in_total, uint32_t flags, uint8_t *out, bool out_pinned, uint64_t *used, double *kernel_ms,
+                           const char *who, const char *member, const char *of_what) {
     if (!st.busy) return CHN_OK;
     st.busy = false;
     HIPCHK(hipEventSynchronize(st.sized));
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, st.k0, st.k1));
-    h->kernel_ms += ms;
+    *kernel_ms += ms;
     const uint64_t n = st.n, *off = st.h_res.as<uint64_t>();
-    const uint32_t *len = reinterpret_cast<const uint32_t *>(off + n + 1), *crc = len + n;
-    uint64_t in_total = 0;
-    for (uint64_t k = 0; k < n; ++k) {
-        if (len[k] > DFL_SLOT) return fail(CHN_E_HIP, "chn_deflate_run: member " + std::to_string(st.first + k) + " did not come out at its planned size");
-        in_total += j->in_length[st.first + k];
-    }
+    const uint32_t *len = reinterpret_cast<const uint32_t *>(off + n + 1);
+    for (uint64_t k = 0; k < n; ++k)
+        if (len[k] > DFL_SLOT) return fail(CHN_E_HIP, std::string(who) + ": " + member + " " + std::to_string(st.first + k) + of_what + " did not come out at its planned size");
     const uint64_t bytes = off[n];
-    if (bytes > deflate_bound(n, in_total, j->flags)) return fail(CHN_E_HIP, "chn_deflate_run: a group came out above its bound");
+    if (bytes > deflate_bound(n, in_total, flags)) return fail(CHN_E_HIP, std::string(who) + ": a group came out above its bound");
     if (bytes) {
-        if (!out_pinned) { const int rc = st.h_out.ensure((size_t)bytes + (st.h_out.cap < bytes ? bytes / 4 : 0)); if (rc) return rc; }
-        HIPCHK(hipMemcpyAsync(out_pinned ? static_cast<void *>(j->out + *used) : st.h_out.p, st.d_packed.p, bytes, hipMemcpyDeviceToHost, h->s_down));
+        if (!out_pinned) { const int rc = st.h_out.ensure_grow((size_t)bytes, (size_t)(bytes / 4)); if (rc) return rc; }
+        HIPCHK(hipMemcpyAsync(out_pinned ? static_cast<void *>(out + *used) : st.h_out.p, st.d_packed.p, bytes, hipMemcpyDeviceToHost, h->s_down));
         HIPCHK(hipEventRecord(st.down, h->s_down));
         HIPCHK(hipEventSynchronize(st.down));
-        if (!out_pinned) std::memcpy(j->out + *used, st.h_out.p, bytes);
-    }
-    for (uint64_t k = 0; k < n; ++k) {
-        j->out_offset[st.first + k] = *used + off[k];
-        j->out_length[st.first + k] = len[k];
-        if (j->crc32) j->crc32[st.first + k] = crc[k];
+        if (!out_pinned) std::memcpy(out + *used, st.h_out.p, bytes);
     }
     *used += bytes;
     return CHN_OK;
@@ -264,22 +223,30 @@ extern "C" int chn_deflate_run(chn_deflate *h, const chn_deflate_job *j) {
     *j->out_used = 0;
     if (j->n_members == 0) return CHN_OK;
     HIPCHK(hipSetDevice(h->device));
-    const bool out_pinned = inflate_is_pinned(j->out, j->out_bytes);
-    uint64_t first = 0, g = 0, used = 0;
-    while (first < j->n_members) {
-        const uint64_t n = std::min<uint64_t>(h->group_members, j->n_members - first);
-        // the set's staging and device buffers are free: its last group was collected when the one after it was issued
-        rc = deflate_issue(h, h->set[g & 1], j, first, n);
-        if (rc == CHN_OK && g > 0) rc = deflate_collect(h, h->set[(g - 1) & 1], j, out_pinned, &used);
-        if (rc) break;
-        first += n; ++g;
-    }
-    if (rc == CHN_OK) rc = deflate_collect(h, h->set[(g - 1) & 1], j, out_pinned, &used);
-    if (rc) {  // nothing of this call may still be on its way into the caller's memory
-        (void)hipStreamSynchronize(h->s_up); (void)hipStreamSynchronize(h->s_run); (void)hipStreamSynchronize(h->s_down);
-        h->set[0].busy = h->set[1].busy = false;
-        return rc;
-    }
+    const bool out_pinned = page_locked_host(j->out, j->out_bytes);
+    uint64_t used = 0;
+    rc = run_groups(*h, h->set, j->n_members,
+        [&](DeflateSet &st, uint64_t first, uint64_t &n) {
+            n = std::min<uint64_t>(h->group_members, j->n_members - first);
+            return deflate_issue(h, st, j, first, n);
+        },
+        [&](DeflateSet &st) {  // the group's members behind `used`; offsets, sizes and CRCs to the caller
+            if (!st.busy) return CHN_OK;
+            uint64_t in_total = 0;
+            for (uint64_t k = 0; k < st.n; ++k) in_total += j->in_length[st.first + k];
+            const uint64_t base = used;
+            const int r = deflate_collect(h, st, in_total, j->flags, j->out, out_pinned, &used, &h->kernel_ms, "chn_deflate_run", "member", "");
+            if (r) return r;
+            const uint64_t *off = st.h_res.as<uint64_t>();
+            const uint32_t *len = reinterpret_cast<const uint32_t *>(off + st.n + 1), *crc = len + st.n;
+            for (uint64_t k = 0; k < st.n; ++k) {
+                j->out_offset[st.first + k] = base + off[k];
+                j->out_length[st.first + k] = len[k];
+                if (j->crc32) j->crc32[st.first + k] = crc[k];
+            }
+            return CHN_OK;
+        });
+    if (rc) return rc;
     *j->out_used = used;
     return CHN_OK;
 }

@@ -7,7 +7,7 @@
 //      descriptors a record go up first), or one copy of the caller's host bytes;
 //   2. hands every whole piece to deflate_launch in groups, as chn_deflate_run does -- the group's descriptors (piece k at
 //      k * 65 280) follow the bytes on the upload stream, the compressor reads `pend` in place, group g is collected when group g + 1
-//      has been issued -- and downloads the members behind one another into `out`;
+//      has been issued (deflate_collect) -- and downloads the members behind one another into `out`;
 //   3. moves the tail to the front on the run stream, behind the last group's kernels, and waits for everything.
 // `pend` always has 16 readable bytes behind the text (DeflateArgs::in); k_deflate_members ignores what they hold.
 
@@ -80,41 +80,19 @@ static int extract_reserve(chn_extract *h, uint64_t have) {
     return CHN_OK;
 }
 
-// wait for the group in set `st` and download its members to out + *used
-static int extract_collect(chn_extract *h, DeflateSet &st, uint8_t *out, bool out_pinned, uint64_t *used) {
-    chn_deflate *d = h->dfl;
-    if (!st.busy) return CHN_OK;
-    st.busy = false;
-    HIPCHK(hipEventSynchronize(st.sized));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, st.k0, st.k1));
-    h->kernel_ms += ms;
-    const uint64_t n = st.n, *off = st.h_res.as<uint64_t>();
-    const uint32_t *len = reinterpret_cast<const uint32_t *>(off + n + 1);
-    for (uint64_t k = 0; k < n; ++k)
-        if (len[k] > DFL_SLOT) return fail(CHN_E_HIP, "chn_extract: piece " + std::to_string(st.first + k) + " of the call did not come out at its planned size");
-    const uint64_t bytes = off[n];
-    if (bytes > deflate_bound(n, n * XR_PIECE, CHN_DEFLATE_BGZF)) return fail(CHN_E_HIP, "chn_extract: a group came out above its bound");
-    if (bytes) {
-        if (!out_pinned) { const int rc = st.h_out.ensure((size_t)bytes + (st.h_out.cap < bytes ? bytes / 4 : 0)); if (rc) return rc; }
-        HIPCHK(hipMemcpyAsync(out_pinned ? static_cast<void *>(out + *used) : st.h_out.p, st.d_packed.p, bytes, hipMemcpyDeviceToHost, d->s_down));
-        HIPCHK(hipEventRecord(st.down, d->s_down));
-        HIPCHK(hipEventSynchronize(st.down));
-        if (!out_pinned) std::memcpy(out + *used, st.h_out.p, bytes);
-    }
-    *used += bytes;
-    return CHN_OK;
-}
-
 // Steps 2 and 3 of an append, and chn_extract_finish: `have` bytes of text lie at the front of `pend`, the last of them written by work
 // queued on the upload stream.  Compress `pieces` whole pieces -- or, `last` set, the `have` < XR_PIECE bytes as one shorter member --
 // into out, and keep the `tail` bytes behind the pieces.  Returns with nothing queued.
 static int extract_compress(chn_extract *h, uint64_t have, uint64_t pieces, uint64_t tail, bool last, uint8_t *out, uint64_t out_capacity, uint64_t *out_used) {
     chn_deflate *d = h->dfl;
-    const bool out_pinned = out && inflate_is_pinned(out, out_capacity);
+    const bool out_pinned = out && out_capacity && page_locked_host(out, out_capacity);
     const uint64_t members = last ? 1 : pieces;
     uint64_t first = 0, g = 0, used = 0;
     int rc = CHN_OK;
+    // (not run_groups: the tail moves between the last issue and the last collect, and the streams are waited for whatever happened)
+    const auto collect = [&](DeflateSet &st) {
+        return deflate_collect(d, st, st.n * XR_PIECE, CHN_DEFLATE_BGZF, out, out_pinned, &used, &h->kernel_ms, "chn_extract", "piece", " of the call");
+    };
     while (first < members) {
         const uint64_t n = std::min<uint64_t>(d->group_members, members - first);
         const uint64_t in_total = last ? have : n * XR_PIECE;
@@ -129,7 +107,7 @@ static int extract_compress(chn_extract *h, uint64_t have, uint64_t pieces, uint
         if (e == hipSuccess) e = hipEventRecord(st.up, d->s_up);
         if (e != hipSuccess) { rc = fail(CHN_E_HIP, std::string("chn_extract: ") + hipGetErrorString(e)); break; }
         rc = deflate_launch(d, st, h->pend.as<uint8_t>(), n, in_total, CHN_DEFLATE_BGZF);
-        if (rc == CHN_OK && g > 0) rc = extract_collect(h, d->set[(g - 1) & 1], out, out_pinned, &used);
+        if (rc == CHN_OK && g > 0) rc = collect(d->set[(g - 1) & 1]);
         if (rc) break;
         first += n; ++g;
     }
@@ -137,7 +115,7 @@ static int extract_compress(chn_extract *h, uint64_t have, uint64_t pieces, uint
         const hipError_t e = hipMemcpyAsync(h->pend.p, h->pend.as<uint8_t>() + pieces * XR_PIECE, tail, hipMemcpyDeviceToDevice, d->s_run);
         if (e != hipSuccess) rc = fail(CHN_E_HIP, std::string("chn_extract: ") + hipGetErrorString(e));
     }
-    if (rc == CHN_OK && g > 0) rc = extract_collect(h, d->set[(g - 1) & 1], out, out_pinned, &used);
+    if (rc == CHN_OK && g > 0) rc = collect(d->set[(g - 1) & 1]);
     // nothing of this call stays queued, whatever happened
     const hipError_t w0 = hipStreamSynchronize(d->s_up), w1 = hipStreamSynchronize(d->s_run), w2 = hipStreamSynchronize(d->s_down);
     d->set[0].busy = d->set[1].busy = false;
@@ -233,8 +211,8 @@ extern "C" int chn_extract_append_bytes(chn_extract *h, const uint8_t *bytes, ui
     const XrPlan plan = xr_plan_append(h->pending, n);
     if ((rc = extract_reserve(h, h->pending + n))) return rc;
     const uint8_t *src = bytes;
-    if (!inflate_is_pinned(bytes, n)) {  // through page-locked staging, so that the copy is a stream's like everything behind it
-        if ((rc = h->h_bytes.ensure((size_t)n + (h->h_bytes.cap < n ? n / 4 : 0)))) return rc;
+    if (!page_locked_host(bytes, n)) {  // through page-locked staging, so that the copy is a stream's like everything behind it
+        if ((rc = h->h_bytes.ensure_grow((size_t)n, (size_t)(n / 4)))) return rc;
         std::memcpy(h->h_bytes.p, bytes, n);
         src = h->h_bytes.as<uint8_t>();
     }

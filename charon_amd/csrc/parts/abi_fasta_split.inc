@@ -19,10 +19,8 @@ extern "C" int chn_fasta_split(chn_stream *s, chn_fasta_split_job *j) {
     std::string why;
     int rc = fsp_check_job(j, who, why);
     if (rc) return fail(rc, why);
-    if (s->inflight >= chn_stream::N_SLOTS) return fail(CHN_E_INVALID, "chn_fasta_split: three batches in flight on the stream: call chn_batch_wait first");
-    const int device = s->idx->d.device;
-    HIPCHK(hipSetDevice(device));
-    if ((rc = device_text_check(j->text, j->text_bytes, device, who))) return rc;
+    int device = 0;
+    if ((rc = stream_text_call(s, who, &device)) || (rc = device_text_check(j->text, j->text_bytes, device, who))) return rc;
     if (j->seq_capacity) {
         if ((reinterpret_cast<uintptr_t>(j->seq_text) & 15) || (j->seq_capacity & 15)) return fail(CHN_E_INVALID, "chn_fasta_split: seq_text must be 16-byte aligned and seq_capacity a multiple of 16");
         if (!device_memory_of(j->seq_text, j->seq_capacity, device, why)) return fail(CHN_E_INVALID, "chn_fasta_split: seq_text " + why);
@@ -56,10 +54,7 @@ extern "C" int chn_fasta_split(chn_stream *s, chn_fasta_split_job *j) {
     const uint32_t cus = std::max<uint32_t>(1, s->n_cus);
     const uint32_t tile_blocks = std::min<uint32_t>((n_tiles + 3) / 4, cus * 8), rec_blocks = std::min<uint32_t>((bound + 255) / 256, cus * 8);
     const bool prof = (s->cfg.flags & CHN_STREAM_PROFILE) != 0;
-    if (prof) {
-        for (hipEvent_t &e : x.ev) if (!e) HIPCHK(hipEventCreate(&e));
-        HIPCHK(hipEventRecord(x.ev[0], cs));
-    }
+    HIPCHK(x.timer.begin(prof, cs));
     HIPCHK(hipMemsetAsync(ctl, 0, FSP_CTL_WORDS * 4, cs));
     HIPCHK(hipMemsetAsync(ctl + FSP_FIRST_BAD, 0xFF, 4, cs));
     hipLaunchKernelGGL(k_fasta_tiles, dim3(tile_blocks), dim3(256), 0, cs, j->text, start, end, tile0, n_tiles, tiles);
@@ -83,33 +78,13 @@ extern "C" int chn_fasta_split(chn_stream *s, chn_fasta_split_job *j) {
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, cs, a.id_len, x.d_idpos.as<uint32_t>(), ctl + FSP_N, bound, ctl + FSP_IDS_BYTES);
     HIPCHK(hipGetLastError());
-    if (prof) HIPCHK(hipEventRecord(x.ev[1], cs));
+    HIPCHK(x.timer.end(prof, cs));
     HIPCHK(hipMemcpyAsync(x.h_ctl.p, ctl, FSP_CTL_WORDS * 4, hipMemcpyDeviceToHost, cs));
     HIPCHK(hipStreamSynchronize(cs));
-    if (prof) {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, x.ev[0], x.ev[1]));
-        x.ms += ms; x.calls += 1;
-    }
+    HIPCHK(x.timer.collect(prof));
     const uint32_t *h = x.h_ctl.as<uint32_t>();
     const uint64_t n = h[FSP_N], ids_bytes = h[FSP_IDS_BYTES];
-    if (j->ids && ids_bytes > j->ids_capacity) return fail(fsp_ids_too_small(j, ids_bytes, who, why), why);
-    if (n) {
-        if (j->ids && ids_bytes) {
-            if ((rc = x.d_ids.ensure((size_t)ids_bytes + (x.d_ids.cap < ids_bytes ? ids_bytes / 4 : 0)))) return rc;
-            hipLaunchKernelGGL(k_split_ids, dim3(std::min<uint32_t>((uint32_t)((n + 15) / 16), cus * 8)), dim3(256), 0, cs, j->text, a.id_off, a.id_len,
-                               x.d_idpos.as<uint32_t>(), (uint32_t)n, x.d_ids.as<uint8_t>());
-            HIPCHK(hipGetLastError());
-        }
-        hipError_t e = hipMemcpyAsync(j->id_offset, a.id_off, n * 8, hipMemcpyDeviceToHost, cs);
-        if (e == hipSuccess) e = hipMemcpyAsync(j->seq_offset, a.seq_off, n * 8, hipMemcpyDeviceToHost, cs);
-        if (e == hipSuccess) e = hipMemcpyAsync(j->id_length, a.id_len, n * 4, hipMemcpyDeviceToHost, cs);
-        if (e == hipSuccess) e = hipMemcpyAsync(j->seq_length, a.seq_len, n * 4, hipMemcpyDeviceToHost, cs);
-        if (e == hipSuccess && j->ids && ids_bytes) e = hipMemcpyAsync(j->ids, x.d_ids.p, ids_bytes, hipMemcpyDeviceToHost, cs);
-        const hipError_t w = hipStreamSynchronize(cs);  // nothing stays queued into the caller's arrays, whatever happened
-        if (e == hipSuccess) e = w;
-        if (e != hipSuccess) return fail(CHN_E_HIP, std::string("chn_fasta_split: ") + hipGetErrorString(e));
-    }
+    if ((rc = split_download(s, x, j, n, ids_bytes, a.id_off, a.seq_off, nullptr, nullptr, a.id_len, a.seq_len, who, fsp_ids_too_small))) return rc;
     j->n_records = n; j->consumed = h[FSP_CONSUMED]; j->ids_bytes = ids_bytes; j->seq_bytes = h[FSP_SEQ_BYTES];
     return CHN_OK;
 }

@@ -1,4 +1,4 @@
-// abi_index_model.inc -- host objects; chn_index_* entry points; chn_model_default
+// abi_index_model.inc -- host objects (index, batch slot, the text calls' scratch, stream); chn_index_* entry points; chn_model_default
 // Part of the single translation unit charon_hip.hip (included in order); not a stand-alone source.
 
 // ------------------------------------------------------------------------------------------------
@@ -29,37 +29,6 @@ struct chn_index {
         if (ef_stream) (void)hipStreamDestroy(ef_stream);
         ef_stream = nullptr;
     }
-};
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return CHN_OK;
-        if (p) { HIPCHK(hipFree(p)); p = nullptr; cap = 0; }
-        HIPCHK(hipMalloc(&p, bytes));
-        cap = bytes;
-        return CHN_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <class T> T *as() { return reinterpret_cast<T *>(p); }
-};
-
-struct PinBuf {  // page-locked host memory (targets of in-stream result downloads)
-    void *p = nullptr;
-    size_t cap = 0;
-    bool borrowed = false;  // a piece of the stream's one block (hipHostMalloc costs ~20 ms a call whatever the size)
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return CHN_OK;
-        if (p && !borrowed) HIPCHK(hipHostFree(p));
-        p = nullptr; cap = 0; borrowed = false;
-        HIPCHK(hipHostMalloc(&p, bytes, hipHostMallocDefault));
-        cap = bytes;
-        return CHN_OK;
-    }
-    void lend(void *piece, size_t bytes) { release(); p = piece; cap = bytes; borrowed = true; }
-    void release() { if (p && !borrowed) (void)hipHostFree(p); p = nullptr; cap = 0; borrowed = false; }
-    template <class T> T *as() { return reinterpret_cast<T *>(p); }
 };
 
 struct HostModel {  // deep copy of chn_model
@@ -147,13 +116,8 @@ struct Slot {
 struct TextSplitScratch {
     DevBuf d_tile, d_line, d_desc, d_idpos, d_ids, d_ctl;
     PinBuf h_ctl;
-    hipEvent_t ev[2] = {nullptr, nullptr};  // profiling streams: around the kernels in front of the first wait
-    double ms = 0;
-    uint64_t calls = 0;
-    void release() {
-        d_tile.release(); d_line.release(); d_desc.release(); d_idpos.release(); d_ids.release(); d_ctl.release(); h_ctl.release();
-        for (hipEvent_t &e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    }
+    CallTimer timer;  // profiling streams: around the kernels in front of the first wait
+    void release() { d_tile.release(); d_line.release(); d_desc.release(); d_idpos.release(); d_ids.release(); d_ctl.release(); h_ctl.release(); timer.release(); }
 };
 
 // chn_text_fetch's staging (abi_text_fetch.inc; allocated with the first call): the range descriptors page-locked and on the device,
@@ -161,13 +125,8 @@ struct TextSplitScratch {
 struct TextFetchScratch {
     DevBuf d_desc, d_out;
     PinBuf h_desc, h_out;
-    hipEvent_t ev[2] = {nullptr, nullptr};  // profiling streams: around the kernel
-    double ms = 0;
-    uint64_t calls = 0;
-    void release() {
-        d_desc.release(); d_out.release(); h_desc.release(); h_out.release();
-        for (hipEvent_t &e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    }
+    CallTimer timer;  // profiling streams: around the kernel
+    void release() { d_desc.release(); d_out.release(); h_desc.release(); h_out.release(); timer.release(); }
 };
 
 // chn_text_pair_ids' staging (abi_text_pair.inc; allocated with the first call): the id descriptors of both files page-locked and on
@@ -175,13 +134,8 @@ struct TextFetchScratch {
 struct TextPairScratch {
     DevBuf d_desc, d_first;
     PinBuf h_desc, h_first;
-    hipEvent_t ev[2] = {nullptr, nullptr};  // profiling streams: around the kernel
-    double ms = 0;
-    uint64_t calls = 0;
-    void release() {
-        d_desc.release(); d_first.release(); h_desc.release(); h_first.release();
-        for (hipEvent_t &e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    }
+    CallTimer timer;  // profiling streams: around the kernel
+    void release() { d_desc.release(); d_first.release(); h_desc.release(); h_first.release(); timer.release(); }
 };
 
 struct chn_stream {
@@ -251,6 +205,16 @@ struct chn_stream {
     TextFetchScratch txg;
     TextPairScratch tpi;
 };
+
+// What chn_text_split, chn_fasta_split, chn_text_fetch and chn_text_pair_ids do between their job check and their text check: a stream
+// with three batches in flight has no idle copy stream to offer; the stream's device is selected and handed back.
+static int stream_text_call(chn_stream *s, const char *who, int *device_out) {
+    if (s->inflight >= chn_stream::N_SLOTS) return fail(CHN_E_INVALID, std::string(who) + ": three batches in flight on the stream: call chn_batch_wait first");
+    const int device = s->idx->d.device;
+    HIPCHK(hipSetDevice(device));
+    *device_out = device;
+    return CHN_OK;
+}
 
 static uint64_t pow5(unsigned e) { uint64_t p = 1; while (e--) p *= 5; return p; }
 

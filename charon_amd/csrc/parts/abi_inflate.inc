@@ -5,7 +5,7 @@
 // while group g is decoded, the compressed bytes of group g + 1 are packed into page-locked staging (member by member, each on a
 // 16-byte boundary, so nothing of `in` between or around the members is uploaded) and uploaded, and the output of group g - 1 is
 // downloaded -- straight into `out` where that is page-locked and the group's members lie back to back there, through staging otherwise.
-// Two sets of grow-only buffers take turns.
+// Two sets of grow-only buffers take turns.  The handle is a CodecPipe and the loop is run_groups (abi_device_call.inc).
 // With a chn_inflate_crc that names an array, the CRC form of the kernel runs: `expected` travels behind the descriptors in their
 // upload, the CRCs behind the statuses in their download -- no further copy, launch or wait.
 // With CHN_INFLATE_OUT_DEVICE `out` is the caller's device memory: the kernel writes every member to out + out_offset[i] itself (its
@@ -21,15 +21,18 @@ struct InflateSet {
     hipEvent_t up = nullptr, done = nullptr, down = nullptr, k0 = nullptr, k1 = nullptr;
     uint64_t first = 0, n = 0, out_bytes = 0;  // the group in this set
     bool direct = false, busy = false, crc = false, dev_out = false;
+    int make_events(const char *who) { return events_create(who, {&up, &done, &down}, {&k0, &k1}); }
+    void release() {
+        for (DevBuf *b : {&d_in, &d_out, &d_desc, &d_status, &d_cursor}) b->release();
+        for (PinBuf *b : {&h_in, &h_out, &h_desc, &h_status}) b->release();
+        events_destroy({&up, &done, &down, &k0, &k1});
+    }
 };
 struct InflateStreamState;  // chn_inflate_stream_run's buffers (abi_inflate_stream.inc), made by its first call
 static void inflate_stream_release(InflateStreamState *s);
-struct chn_inflate {
-    int device = 0;
-    hipStream_t s_up = nullptr, s_run = nullptr, s_down = nullptr;
+struct chn_inflate : CodecPipe {
     InflateSet set[2];
     double kernel_ms = 0;  // device time of the last run's kernels
-    int cus = 0;
     InflateStreamState *ss = nullptr;
 };
 
@@ -84,69 +87,17 @@ static int inflate_run_host(const chn_inflate_job *j, const chn_inflate_crc *c, 
 extern "C" int chn_inflate_run_host(const chn_inflate_job *j) { return inflate_run_host(j, nullptr, "chn_inflate_run_host"); }
 extern "C" int chn_inflate_run_host_crc(const chn_inflate_job *j, const chn_inflate_crc *c) { return inflate_run_host(j, c, "chn_inflate_run_host_crc"); }
 
-extern "C" int chn_inflate_create(int32_t device, chn_inflate **out) {
-    if (!out) return fail(CHN_E_INVALID, "chn_inflate_create: null argument");
-    *out = nullptr;
-    int count = 0;
-    HIPCHK(hipGetDeviceCount(&count));
-    if (device < 0 || device >= count) return fail(CHN_E_INVALID, "chn_inflate_create: device " + std::to_string(device) + " is not below the device count " + std::to_string(count));
-    HIPCHK(hipSetDevice(device));
-    chn_inflate *h = new (std::nothrow) chn_inflate;
-    if (!h) return fail(CHN_E_NOMEM, "chn_inflate_create: no memory");
-    h->device = device;
-    hipDeviceProp_t prop;
-    hipError_t e = hipGetDeviceProperties(&prop, device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->s_up, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->s_run, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->s_down, hipStreamNonBlocking);
-    for (int s = 0; s < 2 && e == hipSuccess; ++s) {
-        InflateSet &st = h->set[s];
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&st.up, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&st.done, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&st.down, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreate(&st.k0);
-        if (e == hipSuccess) e = hipEventCreate(&st.k1);
-    }
-    if (e != hipSuccess) {
-        const std::string msg = std::string("chn_inflate_create: ") + hipGetErrorString(e);
-        chn_inflate_destroy(h);
-        return fail(CHN_E_HIP, msg);
-    }
-    h->cus = prop.multiProcessorCount;
-    *out = h;
-    return CHN_OK;
-}
+extern "C" int chn_inflate_create(int32_t device, chn_inflate **out) { return codec_create(device, out, "chn_inflate_create", chn_inflate_destroy); }
 
 extern "C" int chn_inflate_destroy(chn_inflate *h) {
     if (!h) return CHN_OK;
     (void)hipSetDevice(h->device);
-    if (h->s_up) (void)hipStreamSynchronize(h->s_up);
-    if (h->s_run) (void)hipStreamSynchronize(h->s_run);
-    if (h->s_down) (void)hipStreamSynchronize(h->s_down);
-    for (InflateSet &st : h->set) {
-        st.d_in.release(); st.d_out.release(); st.d_desc.release(); st.d_status.release(); st.d_cursor.release();
-        st.h_in.release(); st.h_out.release(); st.h_desc.release(); st.h_status.release();
-        for (hipEvent_t ev : {st.up, st.done, st.down, st.k0, st.k1}) if (ev) (void)hipEventDestroy(ev);
-    }
+    h->drain();
+    for (InflateSet &st : h->set) st.release();
     inflate_stream_release(h->ss);
-    if (h->s_up) (void)hipStreamDestroy(h->s_up);
-    if (h->s_run) (void)hipStreamDestroy(h->s_run);
-    if (h->s_down) (void)hipStreamDestroy(h->s_down);
+    h->destroy();
     delete h;
     return CHN_OK;
-}
-
-// is [p, p + bytes) page-locked memory the runtime knows?
-static bool inflate_is_pinned(const void *p, uint64_t bytes) {
-    if (!p || !bytes) return false;
-    hipPointerAttribute_t a;
-    std::memset(&a, 0, sizeof a);
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (a.type != hipMemoryTypeHost) return false;
-    hipPointerAttribute_t b;
-    std::memset(&b, 0, sizeof b);
-    if (hipPointerGetAttributes(&b, static_cast<const char *>(p) + bytes - 1) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return b.type == hipMemoryTypeHost;
 }
 
 // pack, upload, decode and start the download of members [first, first + n) in set `st`
@@ -167,9 +118,9 @@ static int inflate_issue(chn_inflate *h, InflateSet &st, const chn_inflate_job *
     // statuses in one block: status[n], and crc[n] behind them where CRCs are taken
     const size_t desc_bytes = (size_t)n * (expect ? 28 : 24), status_bytes = (size_t)n * (st.crc ? 8 : 4);
     if ((rc = st.h_desc.ensure(desc_bytes + desc_bytes / 4)) || (rc = st.d_desc.ensure(st.h_desc.cap)) ||
-        (rc = st.h_in.ensure((size_t)in_bytes + 2 * INF_PAD + (st.h_in.cap < in_bytes + 2 * INF_PAD ? in_bytes / 4 : 0))) || (rc = st.d_in.ensure(st.h_in.cap)) ||
-        (!st.dev_out && (rc = st.d_out.ensure((size_t)out_bytes + 64 + (st.d_out.cap < out_bytes + 64 ? out_bytes / 4 : 0)))) ||
-        (rc = st.h_status.ensure(status_bytes + (st.h_status.cap < status_bytes ? status_bytes / 4 : 0))) || (rc = st.d_status.ensure(st.h_status.cap)) || (rc = st.d_cursor.ensure(16)))
+        (rc = st.h_in.ensure_grow((size_t)in_bytes + 2 * INF_PAD, (size_t)(in_bytes / 4))) || (rc = st.d_in.ensure(st.h_in.cap)) ||
+        (!st.dev_out && (rc = st.d_out.ensure_grow((size_t)out_bytes + 64, (size_t)(out_bytes / 4)))) ||
+        (rc = st.h_status.ensure_grow(status_bytes, status_bytes / 4)) || (rc = st.d_status.ensure(st.h_status.cap)) || (rc = st.d_cursor.ensure(16)))
         return rc;
     if (!st.direct && (rc = st.h_out.ensure(st.d_out.cap))) return rc;
     uint64_t *in_off = st.h_desc.as<uint64_t>(), *out_off = in_off + n;
@@ -253,27 +204,16 @@ static int inflate_run(chn_inflate *h, const chn_inflate_job *j, const chn_infla
         if (!device_memory_of(j->out, j->out_bytes, h->device, why)) return fail(CHN_E_INVALID, std::string(who) + ": CHN_INFLATE_OUT_DEVICE: out " + why);
     }
     h->kernel_ms = 0;
-    const bool out_pinned = !dev_out && inflate_is_pinned(j->out, j->out_bytes);
-    uint64_t first = 0, g = 0;
-    while (first < j->n_members) {
-        uint64_t n = 0, ob = 0, ib = 0;
-        while (first + n < j->n_members && n < INF_GROUP_MEMBERS && (n == 0 || (ob + j->out_length[first + n] <= INF_GROUP_OUT && ib + j->in_length[first + n] <= INF_GROUP_IN))) {
-            ob += j->out_length[first + n]; ib += j->in_length[first + n]; ++n;
-        }
-        InflateSet &st = h->set[g & 1];
-        // the set's staging and device buffers are free: its last group was collected when the one after it was issued
-        rc = inflate_issue(h, st, j, c, first, n, out_pinned);
-        if (rc == CHN_OK && g > 0) rc = inflate_collect(h, h->set[(g - 1) & 1], j, c);
-        if (rc) {  // nothing of this call may still be on its way into the caller's memory
-            (void)hipStreamSynchronize(h->s_up); (void)hipStreamSynchronize(h->s_run); (void)hipStreamSynchronize(h->s_down);
-            h->set[0].busy = h->set[1].busy = false;
-            return rc;
-        }
-        first += n; ++g;
-    }
-    rc = inflate_collect(h, h->set[(g - 1) & 1], j, c);
-    if (rc) { (void)hipStreamSynchronize(h->s_down); h->set[0].busy = h->set[1].busy = false; }
-    return rc;
+    const bool out_pinned = !dev_out && j->out_bytes && page_locked_host(j->out, j->out_bytes);  // (no bytes: the staged path, which then moves none)
+    return run_groups(*h, h->set, j->n_members,
+        [&](InflateSet &st, uint64_t first, uint64_t &n) {
+            uint64_t ob = 0, ib = 0;
+            while (first + n < j->n_members && n < INF_GROUP_MEMBERS && (n == 0 || (ob + j->out_length[first + n] <= INF_GROUP_OUT && ib + j->in_length[first + n] <= INF_GROUP_IN))) {
+                ob += j->out_length[first + n]; ib += j->in_length[first + n]; ++n;
+            }
+            return inflate_issue(h, st, j, c, first, n, out_pinned);
+        },
+        [&](InflateSet &st) { return inflate_collect(h, st, j, c); });
 }
 extern "C" int chn_inflate_run(chn_inflate *h, const chn_inflate_job *j) { return inflate_run(h, j, nullptr, "chn_inflate_run"); }
 extern "C" int chn_inflate_run_crc(chn_inflate *h, const chn_inflate_job *j, const chn_inflate_crc *c) { return inflate_run(h, j, c, "chn_inflate_run_crc"); }

@@ -132,7 +132,7 @@ extern "C" int chn_inflate_stream_run(chn_inflate *h, const chn_inflate_stream_j
     const uint64_t stride = infs_stride(cap);
     const uint64_t first = (j->begin_bit[0] >> 3) & ~15ull, up = j->in_bytes - first;
     const size_t desc_bytes = (size_t)n * 16 + INFS_WIN, res_bytes = (size_t)n * 20;
-    if ((rc = s.d_in.ensure((size_t)up + INF_PAD + (s.d_in.cap < up + INF_PAD ? up / 4 : 0))) || (rc = s.h_desc.ensure(desc_bytes)) || (rc = s.d_desc.ensure(desc_bytes)) ||
+    if ((rc = s.d_in.ensure_grow((size_t)up + INF_PAD, (size_t)(up / 4))) || (rc = s.h_desc.ensure(desc_bytes)) || (rc = s.d_desc.ensure(desc_bytes)) ||
         (rc = s.h_res.ensure(res_bytes)) || (rc = s.d_res.ensure(res_bytes)) || (rc = s.d_sym.ensure((size_t)(n * stride * 2))) ||
         (rc = s.d_win.ensure((size_t)(n + 1) * INFS_WIN)) || (rc = s.d_cursor.ensure(16)))
         return rc;
@@ -180,7 +180,7 @@ extern "C" int chn_inflate_stream_run(chn_inflate *h, const chn_inflate_stream_j
     const uint32_t *p_crc = nullptr, *p_low = nullptr;
     if (pieces) {
         if ((rc = s.h_plan.ensure(plan_bytes + plan_bytes / 4)) || (rc = s.d_plan.ensure(s.h_plan.cap)) || (rc = s.h_pres.ensure(pres_bytes + pres_bytes / 4)) ||
-            (rc = s.d_pres.ensure(s.h_pres.cap)) || (!dev_out && (rc = s.d_out.ensure((size_t)used + (s.d_out.cap < used ? used / 4 : 0)))))
+            (rc = s.d_pres.ensure(s.h_pres.cap)) || (!dev_out && (rc = s.d_out.ensure_grow((size_t)used, (size_t)(used / 4)))))
             return rc;
         uint64_t *plan = s.h_plan.as<uint64_t>(), *pc = plan + made;
         for (uint64_t k = 0; k < made; ++k) {

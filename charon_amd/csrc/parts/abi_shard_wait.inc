@@ -358,34 +358,14 @@ extern "C" int chn_classify_counts(chn_stream *s, uint64_t n, const uint32_t *nu
 
 extern "C" int chn_stream_profile(chn_stream *s, int which, double *total_ms, uint64_t *launches, int reset) {
     if (!s || which < 0 || which > 14 || which == 10 || which == 12) return fail(CHN_E_INVALID, "chn_stream_profile: bad argument");
-    if (which == 14) {  // chn_fasta_split: its kernels in front of the first wait
-        if (total_ms) *total_ms = s->fsp.ms;
-        if (launches) *launches = s->fsp.calls;
-        if (reset) { s->fsp.ms = 0; s->fsp.calls = 0; }
-        return CHN_OK;
-    }
+    if (which == 14) { s->fsp.timer.report(total_ms, launches, reset); return CHN_OK; }  // chn_fasta_split: its kernels in front of the first wait
+    if (which == 11) { s->tpi.timer.report(total_ms, launches, reset); return CHN_OK; }  // chn_text_pair_ids: k_pair_ids
+    if (which == 9) { s->txg.timer.report(total_ms, launches, reset); return CHN_OK; }   // chn_text_fetch: k_text_gather
+    if (which == 8) { s->tsp.timer.report(total_ms, launches, reset); return CHN_OK; }   // chn_text_split: its kernels in front of the first wait
     if (which == 13) {  // batches whose ordinary probe launch was queued behind a probe-gate wait
         if (total_ms) *total_ms = s->gate_signal ? 1.0 : 0.0;  // (no time: whether this stream gates at all)
         if (launches) *launches = s->gated_batches;
         if (reset) s->gated_batches = 0;
-        return CHN_OK;
-    }
-    if (which == 11) {  // chn_text_pair_ids: k_pair_ids
-        if (total_ms) *total_ms = s->tpi.ms;
-        if (launches) *launches = s->tpi.calls;
-        if (reset) { s->tpi.ms = 0; s->tpi.calls = 0; }
-        return CHN_OK;
-    }
-    if (which == 9) {  // chn_text_fetch: k_text_gather
-        if (total_ms) *total_ms = s->txg.ms;
-        if (launches) *launches = s->txg.calls;
-        if (reset) { s->txg.ms = 0; s->txg.calls = 0; }
-        return CHN_OK;
-    }
-    if (which == 8) {  // chn_text_split: its kernels in front of the first wait
-        if (total_ms) *total_ms = s->tsp.ms;
-        if (launches) *launches = s->tsp.calls;
-        if (reset) { s->tsp.ms = 0; s->tsp.calls = 0; }
         return CHN_OK;
     }
     if (which >= 6) {  // text batches: upload of the text, k_text_pack + k_text_mq

@@ -6,18 +6,6 @@
 // that is page-locked, else into page-locked staging from which they are copied out.  One wait.  The staging is the stream's
 // (chn_stream::txg, grow-only): 20 bytes per range and the gathered bytes, on the device and page-locked.
 
-// Is [p, p + bytes) page-locked host memory the runtime knows?
-static bool page_locked_host(const void *p, uint64_t bytes) {
-    for (int k = 0; k < 2; ++k) {
-        const void *q = k == 0 ? p : static_cast<const char *>(p) + (bytes ? bytes - 1 : 0);
-        hipPointerAttribute_t a;
-        std::memset(&a, 0, sizeof a);
-        if (hipPointerGetAttributes(&a, q) != hipSuccess) { (void)hipGetLastError(); return false; }
-        if (a.type != hipMemoryTypeHost) return false;
-    }
-    return true;
-}
-
 extern "C" int chn_text_fetch_host(chn_text_fetch_job *job) {
     std::string why;
     const int rc = txg_host_job(job, why);
@@ -31,14 +19,12 @@ extern "C" int chn_text_fetch(chn_stream *s, chn_text_fetch_job *j) {
     uint64_t total = 0;
     int rc = txg_check_job(j, who, why, total);
     if (rc) return fail(rc, why);
-    if (s->inflight >= chn_stream::N_SLOTS) return fail(CHN_E_INVALID, "chn_text_fetch: three batches in flight on the stream: call chn_batch_wait first");
-    const int device = s->idx->d.device;
-    HIPCHK(hipSetDevice(device));
-    if ((rc = device_text_check(j->text, j->text_bytes, device, who))) return rc;
+    int device = 0;
+    if ((rc = stream_text_call(s, who, &device)) || (rc = device_text_check(j->text, j->text_bytes, device, who))) return rc;
     TextFetchScratch &x = s->txg;
     const bool prof = (s->cfg.flags & CHN_STREAM_PROFILE) != 0;
     if (total == 0) {  // nothing to move
-        if (prof) x.calls += 1;
+        if (prof) x.timer.count_only();
         j->out_bytes = 0;
         return CHN_OK;
     }
@@ -55,25 +41,20 @@ extern "C" int chn_text_fetch(chn_stream *s, chn_text_fetch_job *j) {
     const uint64_t *d_src = x.d_desc.as<uint64_t>(), *d_dst = d_src + n;
     const uint32_t *d_len = reinterpret_cast<const uint32_t *>(d_dst + n);
     hipStream_t cs = s->stream0;
-    if (prof) for (hipEvent_t &e : x.ev) if (!e) HIPCHK(hipEventCreate(&e));
     uint8_t *host_dst = direct ? j->out : x.h_out.as<uint8_t>();
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(n, (uint64_t)std::max<uint32_t>(1, s->n_cus) * 16);
     hipError_t e = hipMemcpyAsync(x.d_desc.p, x.h_desc.p, n * 20, hipMemcpyHostToDevice, cs);
-    if (e == hipSuccess && prof) e = hipEventRecord(x.ev[0], cs);
+    if (e == hipSuccess) e = x.timer.begin(prof, cs);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_text_gather, dim3(blocks), dim3(WAVE), 0, cs, j->text, d_src, d_dst, d_len, n, x.d_out.as<uint8_t>());
         e = hipGetLastError();
     }
-    if (e == hipSuccess && prof) e = hipEventRecord(x.ev[1], cs);
+    if (e == hipSuccess) e = x.timer.end(prof, cs);
     if (e == hipSuccess) e = hipMemcpyAsync(host_dst, x.d_out.p, total, hipMemcpyDeviceToHost, cs);
     const hipError_t w = hipStreamSynchronize(cs);  // nothing stays queued into the caller's memory, whatever happened
     if (e == hipSuccess) e = w;
     if (e != hipSuccess) return fail(CHN_E_HIP, std::string("chn_text_fetch: ") + hipGetErrorString(e));
-    if (prof) {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, x.ev[0], x.ev[1]));
-        x.ms += ms; x.calls += 1;
-    }
+    HIPCHK(x.timer.collect(prof));
     if (!direct) std::memcpy(j->out, x.h_out.p, total);
     j->out_bytes = total;
     return CHN_OK;

@@ -17,10 +17,8 @@ extern "C" int chn_text_pair_ids(chn_stream *s, chn_text_pair_job *j) {
     std::string why;
     int rc = tpi_check_head(j, who, why);
     if (rc) return fail(rc, why);
-    if (s->inflight >= chn_stream::N_SLOTS) return fail(CHN_E_INVALID, "chn_text_pair_ids: three batches in flight on the stream: call chn_batch_wait first");
-    const int device = s->idx->d.device;
-    HIPCHK(hipSetDevice(device));
-    if ((rc = device_text_check(j->text1, j->text1_bytes, device, std::string(who) + ": text1")) ||
+    int device = 0;
+    if ((rc = stream_text_call(s, who, &device)) || (rc = device_text_check(j->text1, j->text1_bytes, device, std::string(who) + ": text1")) ||
         (rc = device_text_check(j->text2, j->text2_bytes, device, std::string(who) + ": text2")))
         return rc;
     if ((rc = tpi_check_ranges(j, who, why))) return fail(rc, why);
@@ -43,25 +41,20 @@ extern "C" int chn_text_pair_ids(chn_stream *s, chn_text_pair_job *j) {
     a.len1 = reinterpret_cast<const uint32_t *>(a.off2 + n); a.len2 = a.len1 + n;
     a.n = n; a.first = x.d_first.as<unsigned long long>();
     hipStream_t cs = s->stream0;
-    if (prof) for (hipEvent_t &e : x.ev) if (!e) HIPCHK(hipEventCreate(&e));
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)std::max<uint32_t>(1, s->n_cus) * 8);
     hipError_t e = hipMemcpyAsync(x.d_desc.p, x.h_desc.p, n * 24, hipMemcpyHostToDevice, cs);
     if (e == hipSuccess) e = hipMemsetAsync(x.d_first.p, 0xFF, 8, cs);
-    if (e == hipSuccess && prof) e = hipEventRecord(x.ev[0], cs);
+    if (e == hipSuccess) e = x.timer.begin(prof, cs);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_pair_ids, dim3(blocks), dim3(256), 0, cs, a);
         e = hipGetLastError();
     }
-    if (e == hipSuccess && prof) e = hipEventRecord(x.ev[1], cs);
+    if (e == hipSuccess) e = x.timer.end(prof, cs);
     if (e == hipSuccess) e = hipMemcpyAsync(x.h_first.p, x.d_first.p, 8, hipMemcpyDeviceToHost, cs);
     const hipError_t w = hipStreamSynchronize(cs);  // nothing stays queued, whatever happened
     if (e == hipSuccess) e = w;
     if (e != hipSuccess) return fail(CHN_E_HIP, std::string("chn_text_pair_ids: ") + hipGetErrorString(e));
-    if (prof) {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, x.ev[0], x.ev[1]));
-        x.ms += ms; x.calls += 1;
-    }
+    HIPCHK(x.timer.collect(prof));
     j->first_mismatch = std::min<uint64_t>(*x.h_first.as<uint64_t>(), n);
     return CHN_OK;
 }

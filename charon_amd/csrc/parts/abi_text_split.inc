@@ -1,4 +1,4 @@
-// abi_text_split.inc -- chn_text_split / chn_text_split_host, and the check that a caller's pointer is device memory
+// abi_text_split.inc -- chn_text_split / chn_text_split_host, and split_download: the tail it shares with chn_fasta_split
 // Part of the single translation unit charon_hip.hip (included in order); not a stand-alone source.
 //
 // chn_text_split queues text_split.inc's kernels on the stream's copy stream and waits twice: once for the three output words (how
@@ -6,27 +6,32 @@
 // which come down in one batch of copies.  The scratch is the stream's (chn_stream::tsp, grow-only): a word per 4 KiB tile of the
 // text, and line starts, descriptors and id positions by the record bound min(max_records, bytes / 8).
 
-// Is [p, p + bytes) device memory of `device`?  `why` says what it is instead.  (The runtime answers a pageable pointer with an
-// error, which is cleared: it is "not device memory".)
-static bool device_memory_of(const void *p, uint64_t bytes, int device, std::string &why) {
-    for (int k = 0; k < 2; ++k) {
-        const void *q = k == 0 ? p : static_cast<const char *>(p) + (bytes ? bytes - 1 : 0);
-        hipPointerAttribute_t a;
-        std::memset(&a, 0, sizeof a);
-        if (hipPointerGetAttributes(&a, q) != hipSuccess) { (void)hipGetLastError(); why = "is not device memory (pageable host memory, or a pointer the runtime does not know)"; return false; }
-        if (a.type == hipMemoryTypeHost) { why = "is page-locked host memory, not device memory"; return false; }
-        if (a.type != hipMemoryTypeDevice) { why = "is not device memory"; return false; }
-        if (a.device != device) { why = "is memory of device " + std::to_string(a.device) + ", not of device " + std::to_string(device); return false; }
-    }
-    return true;
-}
-
-// the device text contract of chn_text_split and CHN_TEXT_ON_DEVICE
-static int device_text_check(const uint8_t *text, uint64_t text_bytes, int device, const std::string &who) {
-    if (!text_bytes) return CHN_OK;  // nothing is read
-    if (reinterpret_cast<uintptr_t>(text) & 15) return fail(CHN_E_INVALID, who + ": device text must be 16-byte aligned");
+// The tail the two split calls share, behind their first wait (n records, ids_bytes of ids): refuse ids that do not fit, put the ids
+// back to back (k_split_ids), download the descriptor columns -- the quality offsets where the job has them -- and the ids, and wait
+// once.  The job's out fields are the caller's to fill.
+template <class J>
+static int split_download(chn_stream *s, TextSplitScratch &x, J *j, uint64_t n, uint64_t ids_bytes, const uint64_t *id_off, const uint64_t *seq_off, const uint64_t *qual_off,
+                          uint64_t *qual_offset, const uint32_t *id_len, const uint32_t *seq_len, const char *who, int (*ids_too_small)(const J *, uint64_t, const char *, std::string &)) {
     std::string why;
-    if (!device_memory_of(text, (text_bytes + 15) & ~(uint64_t)15, device, why)) return fail(CHN_E_INVALID, who + ": text " + why);
+    if (j->ids && ids_bytes > j->ids_capacity) return fail(ids_too_small(j, ids_bytes, who, why), why);
+    if (!n) return CHN_OK;
+    hipStream_t cs = s->stream0;
+    if (j->ids && ids_bytes) {
+        const int rc = x.d_ids.ensure_grow((size_t)ids_bytes, (size_t)(ids_bytes / 4));
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_split_ids, dim3(std::min<uint32_t>((uint32_t)((n + 15) / 16), std::max<uint32_t>(1, s->n_cus) * 8)), dim3(256), 0, cs, j->text, id_off, id_len,
+                           x.d_idpos.as<uint32_t>(), (uint32_t)n, x.d_ids.as<uint8_t>());
+        HIPCHK(hipGetLastError());
+    }
+    hipError_t e = hipMemcpyAsync(j->id_offset, id_off, n * 8, hipMemcpyDeviceToHost, cs);
+    if (e == hipSuccess) e = hipMemcpyAsync(j->seq_offset, seq_off, n * 8, hipMemcpyDeviceToHost, cs);
+    if (e == hipSuccess && qual_off) e = hipMemcpyAsync(qual_offset, qual_off, n * 8, hipMemcpyDeviceToHost, cs);
+    if (e == hipSuccess) e = hipMemcpyAsync(j->id_length, id_len, n * 4, hipMemcpyDeviceToHost, cs);
+    if (e == hipSuccess) e = hipMemcpyAsync(j->seq_length, seq_len, n * 4, hipMemcpyDeviceToHost, cs);
+    if (e == hipSuccess && j->ids && ids_bytes) e = hipMemcpyAsync(j->ids, x.d_ids.p, ids_bytes, hipMemcpyDeviceToHost, cs);
+    const hipError_t w = hipStreamSynchronize(cs);  // nothing stays queued into the caller's arrays, whatever happened
+    if (e == hipSuccess) e = w;
+    if (e != hipSuccess) return fail(CHN_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
     return CHN_OK;
 }
 
@@ -42,10 +47,8 @@ extern "C" int chn_text_split(chn_stream *s, chn_text_split_job *j) {
     std::string why;
     int rc = tsp_check_job(j, who, why);
     if (rc) return fail(rc, why);
-    if (s->inflight >= chn_stream::N_SLOTS) return fail(CHN_E_INVALID, "chn_text_split: three batches in flight on the stream: call chn_batch_wait first");
-    const int device = s->idx->d.device;
-    HIPCHK(hipSetDevice(device));
-    if ((rc = device_text_check(j->text, j->text_bytes, device, who))) return rc;
+    int device = 0;
+    if ((rc = stream_text_call(s, who, &device)) || (rc = device_text_check(j->text, j->text_bytes, device, who))) return rc;
     const uint64_t start = j->start, end = j->text_bytes, bound64 = tsp_record_bound(j);
     if (bound64 == 0) {  // nothing to look at, or no room for a record
         j->n_records = 0; j->consumed = start; j->ids_bytes = 0;
@@ -69,10 +72,7 @@ extern "C" int chn_text_split(chn_stream *s, chn_text_split_job *j) {
     const uint32_t cus = std::max<uint32_t>(1, s->n_cus);
     const uint32_t tile_blocks = std::min<uint32_t>((n_tiles + 3) / 4, cus * 8), rec_blocks = std::min<uint32_t>((bound + 255) / 256, cus * 8);
     const bool prof = (s->cfg.flags & CHN_STREAM_PROFILE) != 0;
-    if (prof) {
-        for (hipEvent_t &e : x.ev) if (!e) HIPCHK(hipEventCreate(&e));
-        HIPCHK(hipEventRecord(x.ev[0], cs));
-    }
+    HIPCHK(x.timer.begin(prof, cs));
     HIPCHK(hipMemsetAsync(ctl, 0, TSP_CTL_WORDS * 4, cs));
     HIPCHK(hipMemsetAsync(ctl + TSP_FIRST_BAD, 0xFF, 4, cs));
     hipLaunchKernelGGL(k_split_count, dim3(tile_blocks), dim3(256), 0, cs, j->text, start, end, tile0, n_tiles, tile_count);
@@ -87,34 +87,13 @@ extern "C" int chn_text_split(chn_stream *s, chn_text_split_job *j) {
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, cs, a.id_len, x.d_idpos.as<uint32_t>(), ctl + TSP_N, bound, ctl + TSP_IDS_BYTES);
     HIPCHK(hipGetLastError());
-    if (prof) HIPCHK(hipEventRecord(x.ev[1], cs));
+    HIPCHK(x.timer.end(prof, cs));
     HIPCHK(hipMemcpyAsync(x.h_ctl.p, ctl, TSP_CTL_WORDS * 4, hipMemcpyDeviceToHost, cs));
     HIPCHK(hipStreamSynchronize(cs));
-    if (prof) {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, x.ev[0], x.ev[1]));
-        x.ms += ms; x.calls += 1;
-    }
+    HIPCHK(x.timer.collect(prof));
     const uint32_t *h = x.h_ctl.as<uint32_t>();
     const uint64_t n = h[TSP_N], ids_bytes = h[TSP_IDS_BYTES];
-    if (j->ids && ids_bytes > j->ids_capacity) return fail(tsp_ids_too_small(j, ids_bytes, who, why), why);
-    if (n) {
-        if (j->ids && ids_bytes) {
-            if ((rc = x.d_ids.ensure((size_t)ids_bytes + (x.d_ids.cap < ids_bytes ? ids_bytes / 4 : 0)))) return rc;
-            hipLaunchKernelGGL(k_split_ids, dim3(std::min<uint32_t>((uint32_t)((n + 15) / 16), cus * 8)), dim3(256), 0, cs, j->text, a.id_off, a.id_len,
-                               x.d_idpos.as<uint32_t>(), (uint32_t)n, x.d_ids.as<uint8_t>());
-            HIPCHK(hipGetLastError());
-        }
-        hipError_t e = hipMemcpyAsync(j->id_offset, a.id_off, n * 8, hipMemcpyDeviceToHost, cs);
-        if (e == hipSuccess) e = hipMemcpyAsync(j->seq_offset, a.seq_off, n * 8, hipMemcpyDeviceToHost, cs);
-        if (e == hipSuccess) e = hipMemcpyAsync(j->qual_offset, a.qual_off, n * 8, hipMemcpyDeviceToHost, cs);
-        if (e == hipSuccess) e = hipMemcpyAsync(j->id_length, a.id_len, n * 4, hipMemcpyDeviceToHost, cs);
-        if (e == hipSuccess) e = hipMemcpyAsync(j->seq_length, a.seq_len, n * 4, hipMemcpyDeviceToHost, cs);
-        if (e == hipSuccess && j->ids && ids_bytes) e = hipMemcpyAsync(j->ids, x.d_ids.p, ids_bytes, hipMemcpyDeviceToHost, cs);
-        const hipError_t w = hipStreamSynchronize(cs);  // nothing stays queued into the caller's arrays, whatever happened
-        if (e == hipSuccess) e = w;
-        if (e != hipSuccess) return fail(CHN_E_HIP, std::string("chn_text_split: ") + hipGetErrorString(e));
-    }
+    if ((rc = split_download(s, x, j, n, ids_bytes, a.id_off, a.seq_off, a.qual_off, j->qual_offset, a.id_len, a.seq_len, who, tsp_ids_too_small))) return rc;
     j->n_records = n; j->consumed = h[TSP_CONSUMED]; j->ids_bytes = ids_bytes;
     return CHN_OK;
 }
