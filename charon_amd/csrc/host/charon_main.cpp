@@ -80,8 +80,19 @@ bool g_gzip_emulator = true;
 #include "bz2_stream.inc"
 #include "fastx_reader.inc"
 #include "result.inc"
+#include "run_util.inc"
 #include "ordered_merge.inc"
+#include "flight_pool.inc"
+#include "row_writer.inc"
+#include "replica_set.inc"
 #include "host_batch.inc"
+#include "dehost_modes.inc"
+#include "dehost_readers.inc"
+#include "dehost_setup.inc"
+#include "dehost_flight.inc"
+#include "dehost_rows.inc"
+#include "dehost_loop.inc"
+#include "dehost_resident.inc"
 #include "dehost.inc"
 #include "index_builder.inc"
 

@@ -341,9 +341,6 @@ struct HostBatch {
     }
 };
 
-// a fault of the input (as opposed to one of the device or the program): reported without naming the replica that met it
-struct InputError : std::runtime_error { using std::runtime_error::runtime_error; };
-
 // bounded hand-over of parsed blocks from the reader thread
 struct BlockQueue {
     std::mutex m;

@@ -535,3 +535,37 @@ def test_cli_gzip_column_from_device_tallies(tmp_path, oracle_lib):
     b = run_cli(pargs, str(tmp_path), {"CHARON_ZLIB_ONLY": "1"}, sub="classify")
     assert a[0] == 0 and b[0] == 0 and a[1] == b[1] and a[1].count("\n") == len(m1) - 1
     assert any(ln.startswith("U") for ln in a[1].split("\n")) and any(ln.startswith("C") for ln in a[1].split("\n"))
+
+
+def _summary(log_path):
+    """the results summary at the end of a run's log, without the time stamps"""
+    lines = [ln.split(" ", 3)[3].lstrip() for ln in open(log_path).read().splitlines() if ln[:2] == "20"]
+    at = max(i for i, ln in enumerate(lines) if ln.startswith("Results summary"))
+    return lines[at:]
+
+
+@pytest.mark.parametrize("devices", [None, "0,0"], ids=["one-replica", "two-replicas-on-one-device"])
+def test_cli_row_writer_switch(tmp_path, devices):
+    """CHARON_ROW_WRITER=0 writes every batch's rows on the main thread (the inline branch of RowWriter::hand_on, otherwise reached
+    through --extract or training alone), =1 hands them to the writer's thread, unset decides by -t and the CPUs: the TSV and the
+    results summary are the same bytes, with many small batches queueing, on one replica and on two replicas of one device"""
+    fq = os.path.join(G, "cfg1_reads.fastq.gz")
+    runs = {}
+    for setting in ("0", "1", None):
+        cwd = tmp_path / ("w" + str(setting))
+        cwd.mkdir()
+        env = {k: v for k, v in os.environ.items() if k not in ("CHARON_ROW_WRITER", "CHARON_DEVICES")}
+        env["CHARON_BATCH_READS"] = "37"
+        if setting is not None:
+            env["CHARON_ROW_WRITER"] = setting
+        if devices is not None:
+            env["CHARON_DEVICES"] = devices
+        p = subprocess.run([EXE, "dehost", "--db", os.path.join(G, "cfg1.idx"), "-t", "4", fq, "--log", str(cwd / "charon.log")], cwd=str(cwd), env=env,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+        assert p.returncode == 0, p.stderr.decode()
+        log = open(cwd / "charon.log").read()
+        assert ("replicas: 2 (devices 0,0)" if devices else "replicas: 1 (devices ") in log
+        runs[setting] = (p.stdout, _summary(cwd / "charon.log"))
+    assert_same_tsv(runs["0"][0].decode(), open(os.path.join(G, "cfg1_expected.tsv")).read())
+    assert len(runs["0"][1]) == 4  # the heading, two categories, unclassified
+    assert runs["0"] == runs["1"] == runs[None]
