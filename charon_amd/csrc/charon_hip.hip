@@ -30,8 +30,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
-#include <functional>
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -74,6 +74,7 @@
 #include "parts/deflate_members.inc"
 #include "parts/ef_decode.inc"
 #include "parts/synth_kernels.inc"
+#include "parts/batch_plan.inc"
 #include "parts/abi_device_call.inc"
 #include "parts/abi_index_model.inc"
 #include "parts/abi_stream_batch.inc"

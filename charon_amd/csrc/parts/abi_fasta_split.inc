@@ -35,7 +35,6 @@ extern "C" int chn_fasta_split(chn_stream *s, chn_fasta_split_job *j) {
     const uint64_t tile0 = start / TSP_TILE;
     const uint32_t n_tiles = (uint32_t)((end + TSP_TILE - 1) / TSP_TILE - tile0);  // >= 1, <= 2^19
     TextSplitScratch &x = s->fsp;
-    hipStream_t cs = s->stream0;
     // per tile: the summary (FspTile), then seven words: state, headers, header feeds, kept bytes, and the exclusive sums of the last three
     // per record of the bound: hdr_pos, feed_pos, kept_before [cap]; id_off seq_off (64-bit), id_len seq_len (32-bit)
     if ((rc = x.d_tile.ensure((size_t)n_tiles * (sizeof(FspTile) + 28))) || (rc = x.d_line.ensure((size_t)cap * 12)) || (rc = x.d_desc.ensure((size_t)bound * 24)) ||
@@ -54,33 +53,33 @@ extern "C" int chn_fasta_split(chn_stream *s, chn_fasta_split_job *j) {
     const uint32_t cus = std::max<uint32_t>(1, s->n_cus);
     const uint32_t tile_blocks = std::min<uint32_t>((n_tiles + 3) / 4, cus * 8), rec_blocks = std::min<uint32_t>((bound + 255) / 256, cus * 8);
     const bool prof = (s->cfg.flags & CHN_STREAM_PROFILE) != 0;
-    HIPCHK(x.timer.begin(prof, cs));
-    HIPCHK(hipMemsetAsync(ctl, 0, FSP_CTL_WORDS * 4, cs));
-    HIPCHK(hipMemsetAsync(ctl + FSP_FIRST_BAD, 0xFF, 4, cs));
-    hipLaunchKernelGGL(k_fasta_tiles, dim3(tile_blocks), dim3(256), 0, cs, j->text, start, end, tile0, n_tiles, tiles);
+    HIPCHK(x.timer.begin(prof, s->q_copy));
+    HIPCHK(hipMemsetAsync(ctl, 0, FSP_CTL_WORDS * 4, s->q_copy));
+    HIPCHK(hipMemsetAsync(ctl + FSP_FIRST_BAD, 0xFF, 4, s->q_copy));
+    hipLaunchKernelGGL(k_fasta_tiles, dim3(tile_blocks), dim3(256), 0, s->q_copy, j->text, start, end, tile0, n_tiles, tiles);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_fasta_resolve, dim3(1), dim3(256), 0, cs, tiles, n_tiles, tile_state, tile_hdr, tile_feed, tile_kept);
+    hipLaunchKernelGGL(k_fasta_resolve, dim3(1), dim3(256), 0, s->q_copy, tiles, n_tiles, tile_state, tile_hdr, tile_feed, tile_kept);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, cs, tile_hdr, hdr_off, (const uint32_t *)nullptr, n_tiles, ctl + FSP_HDRS);
+    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, s->q_copy, tile_hdr, hdr_off, (const uint32_t *)nullptr, n_tiles, ctl + FSP_HDRS);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, cs, tile_feed, feed_off, (const uint32_t *)nullptr, n_tiles, ctl + FSP_FEEDS);
+    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, s->q_copy, tile_feed, feed_off, (const uint32_t *)nullptr, n_tiles, ctl + FSP_FEEDS);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, cs, tile_kept, kept_off, (const uint32_t *)nullptr, n_tiles, ctl + FSP_KEPT);
+    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, s->q_copy, tile_kept, kept_off, (const uint32_t *)nullptr, n_tiles, ctl + FSP_KEPT);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_fasta_headers, dim3(tile_blocks), dim3(256), 0, cs, j->text, start, end, tile0, n_tiles, tile_state, hdr_off, feed_off, kept_off, ctl, hdr_pos,
+    hipLaunchKernelGGL(k_fasta_headers, dim3(tile_blocks), dim3(256), 0, s->q_copy, j->text, start, end, tile0, n_tiles, tile_state, hdr_off, feed_off, kept_off, ctl, hdr_pos,
                        feed_pos, kept_before, cap);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_fasta_records, dim3(rec_blocks), dim3(256), 0, cs, a);
+    hipLaunchKernelGGL(k_fasta_records, dim3(rec_blocks), dim3(256), 0, s->q_copy, a);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_fasta_close, dim3(1), dim3(64), 0, cs, a);
+    hipLaunchKernelGGL(k_fasta_close, dim3(1), dim3(64), 0, s->q_copy, a);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_fasta_compact, dim3(tile_blocks), dim3(256), 0, cs, j->text, start, end, tile0, n_tiles, tile_state, kept_off, ctl, j->seq_text);
+    hipLaunchKernelGGL(k_fasta_compact, dim3(tile_blocks), dim3(256), 0, s->q_copy, j->text, start, end, tile0, n_tiles, tile_state, kept_off, ctl, j->seq_text);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, cs, a.id_len, x.d_idpos.as<uint32_t>(), ctl + FSP_N, bound, ctl + FSP_IDS_BYTES);
+    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, s->q_copy, a.id_len, x.d_idpos.as<uint32_t>(), ctl + FSP_N, bound, ctl + FSP_IDS_BYTES);
     HIPCHK(hipGetLastError());
-    HIPCHK(x.timer.end(prof, cs));
-    HIPCHK(hipMemcpyAsync(x.h_ctl.p, ctl, FSP_CTL_WORDS * 4, hipMemcpyDeviceToHost, cs));
-    HIPCHK(hipStreamSynchronize(cs));
+    HIPCHK(x.timer.end(prof, s->q_copy));
+    HIPCHK(hipMemcpyAsync(x.h_ctl.p, ctl, FSP_CTL_WORDS * 4, hipMemcpyDeviceToHost, s->q_copy));
+    HIPCHK(hipStreamSynchronize(s->q_copy));
     HIPCHK(x.timer.collect(prof));
     const uint32_t *h = x.h_ctl.as<uint32_t>();
     const uint64_t n = h[FSP_N], ids_bytes = h[FSP_IDS_BYTES];

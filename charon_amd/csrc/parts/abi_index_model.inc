@@ -66,6 +66,12 @@ struct LogBuf {
     void release() { log.release(); rows.release(); meta.release(); wcount.release(); log_cap = esc_cap = 0; }
 };
 
+// A profiling bracket: two timed events around a piece of a batch's work, and whether this batch recorded them.
+struct EvBracket {
+    hipEvent_t begin = nullptr, end = nullptr;
+    bool used = false;
+};
+
 // Per-batch state.  Two slots let batch i+1 be submitted while batch i's count and model+call kernels (side stream) are still
 // running: they then overlap the HBM-bound minimise+probe kernel of the next batch.
 struct Slot {
@@ -81,7 +87,7 @@ struct Slot {
     uint32_t gz_output = 0;
     hipEvent_t bases_up = nullptr, gz_done = nullptr;
     DevBuf d_gzlong;                      // CHN_GZIP_SIZES_ALL: k_gzip_long's sizes [max_reads], then its launches' read counters [64]
-    hipEvent_t gzt_done = nullptr;        // ... the tally launches (stream3) are done: stream5 forms the sizes behind them and its long-read launch
+    hipEvent_t gzt_done = nullptr;        // ... the tally launches (tally stream) are done: the long-gzip stream forms the sizes behind them and its long-read launch
     DevBuf d_order;                       // length-class order of this batch (read by the count kernel on the side stream)
     LogBuf lb;                            // this batch's row log
     DevBuf d_len1, d_len2, d_mq, d_comp;  // staging of the small per-read arrays of host batches (read by k_model_call)
@@ -93,7 +99,7 @@ struct Slot {
     PinBuf h_text;
     std::vector<uint64_t> h_toff1, h_toff2;  // the segment layout chn_text_submit computed
     bool is_text = false;
-    hipEvent_t tev[4] = {nullptr, nullptr, nullptr, nullptr};  // profiling streams: text upload 0-1, k_text_pack + k_text_mq 2-3
+    EvBracket t_text_upload, t_text_pack;  // profiling streams: the text's upload; k_text_pack + k_text_mq (made by the first text batch)
     uint32_t text_has_n = 0;
     uint64_t text_n_bases = 0;
     hipEvent_t uploaded = nullptr;
@@ -104,11 +110,12 @@ struct Slot {
     K1Args k1;                            // the launch arguments of this batch's minimise+probe kernel (re-run after a log overflow)
     std::vector<uint32_t> h_len1, h_len2;
     std::vector<float> h_mq, h_comp;
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // K1 0-1, K2 2-3, K3 4-5, chain 6-7
+    // profiling streams: the probe kernel (both its launches), the count kernels, model + call, the whole chain from the probe
+    // stream's first call of the batch to the last kernel on the side stream
+    EvBracket t_probe, t_count, t_model, t_chain;
     hipEvent_t k1_done = nullptr, done = nullptr, split_done = nullptr;
     bool new_anchor = false;              // profiling streams: the stream's next time anchor was recorded behind this batch's probe kernel
     uint32_t split_bound = 0;            // most reads this batch's SPLIT launch (long reads over the lanes of a wavefront) can meet; 0: no such launch
-    bool ev_used[4] = {false, false, false, false};
 };
 
 // chn_text_split's scratch (abi_text_split.inc; allocated with the first call): tile counts and offsets, line starts, the descriptor
@@ -141,13 +148,14 @@ struct TextPairScratch {
 struct chn_stream {
     chn_index *idx = nullptr;
     chn_stream_cfg cfg;
-    hipStream_t stream = nullptr;   // minimise+probe of the even batches; the list-mode chains, chn_classify_counts, re-runs after a log overflow
-    hipStream_t stream1 = nullptr;  // minimise+probe of the odd batches: the next batch's wavefronts take the slots a draining grid frees
-    hipStream_t stream2 = nullptr;  // count + model+call (overlap the next batch's minimise+probe)
-    hipStream_t stream0 = nullptr;  // host -> device uploads of host batches (truly asynchronous when the caller's memory is pinned)
-    hipStream_t stream3 = nullptr;  // deflate tallies (latency-bound LDS work beside the HBM-bound probe kernel)
-    hipStream_t stream4 = nullptr;  // the SPLIT launch of k_minimise_probe (long reads), beside the ordinary launch
-    hipStream_t stream5 = nullptr;  // k_gzip_long on the reads beyond CHN_GZIP_MAX_LEN (CHN_GZIP_SIZES_ALL), beside the tally launches (created with the first such batch)
+    // The seven streams of a batch's chain (stream_roles, abi_stream_batch.inc, lists them with their priorities):
+    hipStream_t q_probe[2] = {nullptr, nullptr};  // minimise+probe: [0] the even batches, the list-mode chains, chn_classify_counts, re-runs after a log overflow;
+                                                  // [1] the odd batches: the next batch's wavefronts take the slots a draining grid frees
+    hipStream_t q_side = nullptr;    // count + model+call (overlap the next batch's minimise+probe)
+    hipStream_t q_copy = nullptr;    // host -> device uploads of host batches (truly asynchronous when the caller's memory is pinned), the ordering kernels, the text calls
+    hipStream_t q_tally = nullptr;   // deflate tallies (latency-bound LDS work beside the HBM-bound probe kernel)
+    hipStream_t q_split = nullptr;   // the SPLIT launch of k_minimise_probe (long reads), beside the ordinary launch
+    hipStream_t q_gzlong = nullptr;  // k_gzip_long on the reads beyond CHN_GZIP_MAX_LEN (CHN_GZIP_SIZES_ALL), beside the tally launches (created with the first such batch)
     uint32_t long_bucket = 104;     // reads from this length class on are split over the lanes of a wavefront (256: never)
     DevBuf d_hist, d_model;
     DevBuf d_memo;                    // k_model_call memo table (cleared whenever the model changes)
@@ -163,7 +171,7 @@ struct chn_stream {
     uint64_t overflow_reruns = 0;
     bool gzt_big_lds = false;         // k_gzip_tally's dynamic-LDS limit has been raised
     DevBuf d_gzscratch;               // k_gzip_tally's per-wavefront class arrays (shared by the launches of the stream, which run one after the other)
-    DevBuf d_gzlscratch[2];           // k_gzip_long's per-wavefront epoch arrays: [0] its launches on stream5, [1] the re-runs on stream3
+    DevBuf d_gzlscratch[2];           // k_gzip_long's per-wavefront epoch arrays: [0] its launches on the long-gzip stream, [1] the re-runs on the tally stream
     bool gzl_big_lds = false;         // k_gzip_long's dynamic-LDS limit has been raised
     uint32_t n_cus = 256;             // compute units of the device
     static const int N_SLOTS = 3;  // batches that may be in flight at once
@@ -215,6 +223,9 @@ static int stream_text_call(chn_stream *s, const char *who, int *device_out) {
     *device_out = device;
     return CHN_OK;
 }
+
+// seconds on the steady clock: every host time point of the submit / wait diagnostics (CHN_DIAG_SUBMIT, CHN_DIAG_WAIT)
+static double wall_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 static uint64_t pow5(unsigned e) { uint64_t p = 1; while (e--) p *= 5; return p; }
 

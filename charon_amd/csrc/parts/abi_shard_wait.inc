@@ -2,10 +2,21 @@
 // Part of the single translation unit charon_hip.hip (included in order); not a stand-alone source.
 
 // ---- row-sharded mode -----------------------------------------------------------------------------
+// A slot's status word (CTL_STATUS) as an error.  What an overflow of the row log (bit 1) means is the caller's to say; null: the
+// caller deals with it (chn_batch_wait re-runs the batch).  chn_shard_minimise hands in bits 1 and 2 only, the two it has always tested.
+static int status_error(unsigned long long status, const char *overflow) {
+    if (status & 2) return fail(CHN_E_INVALID, "a segment of the batch is misaligned or lies outside the base buffer");
+    if (status & 4)  // k_shx_serve answered such a query with row 0: the counts of whoever asked are wrong
+        return fail(CHN_E_INVALID, "chn_shardx_serve was asked for rows this shard does not hold: the queries were built from other row_splits than the shards' "
+                                   "(or went to the wrong owner)");
+    if ((status & 1) && overflow) return fail(CHN_E_CAPACITY, overflow);
+    return CHN_OK;
+}
+
 static int ensure_shard_buffers(chn_stream *s) {
     // the dense row-sharded chain cannot be re-run behind the caller's collective, so it is laid out for the worst case
     // (one minimiser per base, every row escaped), deterministically
-    const uint64_t nw = (s->cfg.max_reads + WAVE - 1) / WAVE;
+    const uint64_t nw = waves_of(s->cfg.max_reads);
     int rc;
     if ((rc = s->big.ensure(s->cfg.max_bases, nw, (uint32_t)s->idx->d.bin_words, 65536, 0))) return rc;
     if ((rc = s->d_list.ensure(s->big.log_cap * 8)) || (rc = s->d_cbase.ensure((nw + 1) * 8))) return rc;
@@ -19,7 +30,7 @@ static ShardArgs shard_args(chn_stream *s, const chn_index *shard, uint64_t *par
     a.wave_count = s->big.wcount.as<uint32_t>(); a.words = shard->words; a.S = d.bin_size; a.row_begin = d.row_begin; a.row_end = d.row_end;
     a.shift = (uint32_t)d.hash_shift; a.h = d.hash_funs; a.W = (uint32_t)d.bin_words; a.partial = partial; a.rows = s->big.rows.as<uint64_t>();
     a.rowlog = s->big.log.as<uint32_t>(); a.B = (uint32_t)d.bins;
-    a.n_waves = (uint32_t)((sl.n_reads + WAVE - 1) / WAVE); a.esc_capacity = s->big.esc_cap;
+    a.n_waves = (uint32_t)waves_of(sl.n_reads); a.esc_capacity = s->big.esc_cap;
     a.status = reinterpret_cast<uint32_t *>(const_cast<Slot &>(sl).d_ctl.as<unsigned long long>() + CTL_STATUS);
     return a;
 }
@@ -31,17 +42,16 @@ extern "C" int chn_shard_minimise(chn_stream *s, const chn_batch *b, uint64_t *n
     int rc = ensure_shard_buffers(s);
     if (rc) return rc;
     if ((rc = submit_impl(s, b, LIST_DENSE))) return rc;
-    const uint32_t n_waves = (uint32_t)((b->n_reads + WAVE - 1) / WAVE);
-    hipLaunchKernelGGL(k_counts_to_u64, dim3((n_waves + 1 + 255) / 256), dim3(256), 0, s->stream, s->big.wcount.as<uint32_t>(), n_waves, s->d_cbase.as<uint64_t>());
-    hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, s->stream, s->d_cbase.as<uint64_t>(), n_waves + 1);
+    const uint32_t n_waves = (uint32_t)waves_of(b->n_reads);
+    hipLaunchKernelGGL(k_counts_to_u64, dim3((n_waves + 1 + 255) / 256), dim3(256), 0, s->q_probe[0], s->big.wcount.as<uint32_t>(), n_waves, s->d_cbase.as<uint64_t>());
+    hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, s->q_probe[0], s->d_cbase.as<uint64_t>(), n_waves + 1);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipStreamSynchronize(s->q_probe[0]));
     uint64_t total = 0;
     HIPCHK(hipMemcpy(&total, s->d_cbase.as<uint64_t>() + n_waves, 8, hipMemcpyDeviceToHost));
     unsigned long long st = 0;
     HIPCHK(hipMemcpy(&st, s->slot[s->head].d_ctl.as<unsigned long long>() + CTL_STATUS, 8, hipMemcpyDeviceToHost));
-    if (st & 2) return fail(CHN_E_INVALID, "a segment of the batch is misaligned or lies outside the base buffer");
-    if (st & 1) return fail(CHN_E_CAPACITY, "minimiser log overflow (batch larger than the stream's max_bases?)");
+    if ((rc = status_error(st & 3, "minimiser log overflow (batch larger than the stream's max_bases?)"))) return rc;
     s->shard_entries = total;
     s->shard_open = true;
     *n_entries = total;
@@ -60,12 +70,12 @@ extern "C" int chn_minimisers(chn_stream *s, const chn_batch *b, uint64_t *host_
     // compact the per-wavefront logs into the (unused here) escaped-row buffer, then copy out
     if ((rc = s->big.rows.ensure(total * 8))) return rc;
     const Slot &sl = s->slot[s->head];
-    const uint32_t n_waves = (uint32_t)((sl.n_reads + WAVE - 1) / WAVE);
+    const uint32_t n_waves = (uint32_t)waves_of(sl.n_reads);
     const ShardArgs sa = shard_args(s, s->idx, nullptr, sl);
-    hipLaunchKernelGGL(k_compact_list, dim3(n_waves), dim3(256), 0, s->stream, sa, s->big.rows.as<uint64_t>());
+    hipLaunchKernelGGL(k_compact_list, dim3(n_waves), dim3(256), 0, s->q_probe[0], sa, s->big.rows.as<uint64_t>());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(host_values, s->big.rows.p, total * 8, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipMemcpyAsync(host_values, s->big.rows.p, total * 8, hipMemcpyDeviceToHost, s->q_probe[0]));
+    HIPCHK(hipStreamSynchronize(s->q_probe[0]));
     return CHN_OK;
 }
 
@@ -104,16 +114,11 @@ extern "C" int chn_shard_probe(chn_stream *s, const chn_index *shard, uint64_t *
     if (capacity_words < s->shard_entries * c.hash_funs * c.bin_words) return fail(CHN_E_CAPACITY, "chn_shard_probe: partial buffer too small");
     HIPCHK(hipSetDevice(a.device));
     const Slot &sl = s->slot[s->head];
-    const uint32_t n_waves = (uint32_t)((sl.n_reads + WAVE - 1) / WAVE);
+    const uint32_t n_waves = (uint32_t)waves_of(sl.n_reads);
     const ShardArgs sa = shard_args(s, shard, dev_partial, sl);
-    switch (c.bin_words) {
-        case 1: hipLaunchKernelGGL(k_probe_partial<1>, dim3(n_waves), dim3(256), 0, s->stream, sa); break;
-        case 2: hipLaunchKernelGGL(k_probe_partial<2>, dim3(n_waves), dim3(256), 0, s->stream, sa); break;
-        case 3: hipLaunchKernelGGL(k_probe_partial<3>, dim3(n_waves), dim3(256), 0, s->stream, sa); break;
-        default: hipLaunchKernelGGL(k_probe_partial<4>, dim3(n_waves), dim3(256), 0, s->stream, sa); break;
-    }
+    by_words(c.bin_words, [&](auto w) { hipLaunchKernelGGL(k_probe_partial<decltype(w)::value>, dim3(n_waves), dim3(256), 0, s->q_probe[0], sa); });
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s->stream));  // the caller's collective runs on its own stream
+    HIPCHK(hipStreamSynchronize(s->q_probe[0]));  // the caller's collective runs on its own stream
     return CHN_OK;
 }
 
@@ -123,19 +128,14 @@ extern "C" int chn_shard_finish(chn_stream *s, const uint64_t *dev_partial) {
     if (!dev_partial && s->shard_entries) return fail(CHN_E_INVALID, "chn_shard_finish: null argument");
     HIPCHK(hipSetDevice(s->idx->d.device));
     Slot &sl = s->slot[s->head];
-    const uint32_t n_waves = (uint32_t)((sl.n_reads + WAVE - 1) / WAVE);
+    const uint32_t n_waves = (uint32_t)waves_of(sl.n_reads);
     const ShardArgs sa = shard_args(s, s->idx, const_cast<uint64_t *>(dev_partial), sl);
-    switch (s->idx->d.bin_words) {
-        case 1: hipLaunchKernelGGL(k_and_partial<1>, dim3(n_waves), dim3(256), 0, s->stream, sa); break;
-        case 2: hipLaunchKernelGGL(k_and_partial<2>, dim3(n_waves), dim3(256), 0, s->stream, sa); break;
-        case 3: hipLaunchKernelGGL(k_and_partial<3>, dim3(n_waves), dim3(256), 0, s->stream, sa); break;
-        default: hipLaunchKernelGGL(k_and_partial<4>, dim3(n_waves), dim3(256), 0, s->stream, sa); break;
-    }
+    by_words(s->idx->d.bin_words, [&](auto w) { hipLaunchKernelGGL(k_and_partial<decltype(w)::value>, dim3(n_waves), dim3(256), 0, s->q_probe[0], sa); });
     HIPCHK(hipGetLastError());
     s->shard_open = false;
-    HIPCHK(hipEventRecord(sl.k1_done, s->stream));
-    HIPCHK(hipStreamWaitEvent(s->stream2, sl.k1_done, 0));
-    int rc = launch_tail(s, sl, s->big, s->stream2);
+    HIPCHK(hipEventRecord(sl.k1_done, s->q_probe[0]));
+    HIPCHK(hipStreamWaitEvent(s->q_side, sl.k1_done, 0));
+    int rc = launch_tail(s, sl, s->big, TAIL_BATCH);
     if (rc) return rc;
     s->head = (s->head + 1) % chn_stream::N_SLOTS;
     s->inflight += 1;
@@ -145,11 +145,7 @@ extern "C" int chn_shard_finish(chn_stream *s, const uint64_t *dev_partial) {
 extern "C" int chn_stream_sync(chn_stream *s) {
     if (!s) return fail(CHN_E_INVALID, "null stream");
     HIPCHK(hipSetDevice(s->idx->d.device));
-    HIPCHK(hipStreamSynchronize(s->stream0));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream1));
-    HIPCHK(hipStreamSynchronize(s->stream4));
-    HIPCHK(hipStreamSynchronize(s->stream2));
+    for (const StreamRole &r : stream_roles(s)) if (r.synced) HIPCHK(hipStreamSynchronize(*r.q));
     return CHN_OK;
 }
 
@@ -162,29 +158,74 @@ extern "C" int chn_stream_sync(chn_stream *s) {
 static int rerun_worst_case(chn_stream *s, Slot &sl) {
     const chn_index_desc &d = s->idx->d;
     unsigned long long *ctl = sl.d_ctl.as<unsigned long long>();
-    const uint64_t n = sl.n_reads, nw = (n + WAVE - 1) / WAVE + sl.split_bound;
-    HIPCHK(hipMemsetAsync(ctl, 0, CTL_NLONG * 8, s->stream));  // (the number of split reads stays)
-    HIPCHK(hipMemsetAsync(ctl + CTL_FETCHES, 0, (CTL_WORDS - CTL_FETCHES) * 8, s->stream));
-    hipLaunchKernelGGL(k_sum_len, dim3((uint32_t)std::min<uint64_t>(1024, (n + 255) / 256)), dim3(256), 0, s->stream, sl.len1, sl.len2, (uint32_t)n, ctl + CTL_WORDS - 1);
+    const uint64_t n = sl.n_reads, nw = waves_of(n) + sl.split_bound;
+    HIPCHK(hipMemsetAsync(ctl, 0, CTL_NLONG * 8, s->q_probe[0]));  // (the number of split reads stays)
+    HIPCHK(hipMemsetAsync(ctl + CTL_FETCHES, 0, (CTL_WORDS - CTL_FETCHES) * 8, s->q_probe[0]));
+    hipLaunchKernelGGL(k_sum_len, dim3((uint32_t)std::min<uint64_t>(1024, (n + 255) / 256)), dim3(256), 0, s->q_probe[0], sl.len1, sl.len2, (uint32_t)n, ctl + CTL_SUM_LEN);
     HIPCHK(hipGetLastError());
     unsigned long long total = 0;
-    HIPCHK(hipMemcpyAsync(&total, ctl + CTL_WORDS - 1, 8, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    int rc = s->big.ensure(total, (n + WAVE - 1) / WAVE + std::min<uint64_t>(sl.split_bound, total / len_bucket_floor(std::min(s->long_bucket, 247u)) + 1), (uint32_t)d.bin_words, 65536, 0, nw);
+    HIPCHK(hipMemcpyAsync(&total, ctl + CTL_SUM_LEN, 8, hipMemcpyDeviceToHost, s->q_probe[0]));
+    HIPCHK(hipStreamSynchronize(s->q_probe[0]));
+    int rc = s->big.ensure(total, waves_of(n) + std::min<uint64_t>(sl.split_bound, total / len_bucket_floor(std::min(s->long_bucket, 247u)) + 1), (uint32_t)d.bin_words, 65536, 0, nw);
     if (rc) return rc;
     sl.k1.chain = 0;  // worst-case regions are one entry per base: no chained second entries (launch_tail reads the flag from the slot)
     K1Args a = sl.k1;
     a.gate_started = a.gate_signal = nullptr;  // no probe gate: the slot's counter has counted this grid once already, and nothing waits for it
     fill_k1_log(a, sl, s->big, true);
-    const size_t lds = k1_lds_bytes(a.wn, d.num_categories, MODE_ROWS, a.h, (uint32_t)d.bin_words, (uint32_t)d.bins, a.pack != 0);
-    hipError_t e = launch_k1_mode(MODE_ROWS, (uint32_t)d.bin_words, a, lds, s->stream);
-    if (e == hipSuccess && sl.split_bound) e = launch_k1_split_mode(MODE_ROWS, (uint32_t)d.bin_words, a, lds, s->stream, split_grid(sl.split_bound));
+    const size_t lds = k1_rows_lds(d);
+    hipError_t e = launch_k1(MODE_ROWS, (uint32_t)d.bin_words, a, lds, s->q_probe[0]);
+    if (e == hipSuccess && sl.split_bound) e = launch_k1(MODE_ROWS, (uint32_t)d.bin_words, a, lds, s->q_probe[0], split_grid(sl.split_bound));
     if (e != hipSuccess) return fail(CHN_E_HIP, std::string("k_minimise_probe re-run: ") + hipGetErrorString(e));
-    if ((rc = launch_tail(s, sl, s->big, s->stream))) return rc;
-    HIPCHK(hipStreamSynchronize(s->stream));
+    if ((rc = launch_tail(s, sl, s->big, TAIL_RERUN))) return rc;
+    HIPCHK(hipStreamSynchronize(s->q_probe[0]));
     s->overflow_reruns += 1;
     return CHN_OK;
 }
+
+// Profiling streams, at a batch's wait: its brackets' times into the stream's sums.
+// The probe kernel counts only with what lies behind the end of the probe kernels before it (they overlap, on two streams) -- the sum
+// over batches is the time some probe kernel was running, and one batch at a time gives the bracket time.  That end is kept as
+// milliseconds behind the stream's time anchor (chn_stream::prof_anchor); a batch behind whose probe kernel the next anchor was
+// recorded moves the stream on to it.
+static int prof_collect(chn_stream *s, Slot &sl) {
+    const EvBracket *const brackets[4] = {&sl.t_probe, &sl.t_count, &sl.t_model, &sl.t_chain};  // PROF_PROBE .. PROF_CHAIN
+    for (int i = 0; i < 4; ++i) {
+        const EvBracket &t = *brackets[i];
+        if (!t.used) continue;
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, t.begin, t.end));
+        if (i == PROF_PROBE) {
+            float t0 = 0, t1 = 0;
+            HIPCHK(hipEventElapsedTime(&t0, s->prof_anchor[s->prof_cur], t.begin));
+            HIPCHK(hipEventElapsedTime(&t1, s->prof_anchor[s->prof_cur], t.end));
+            if (s->prof_have_end && s->prof_prev_end > (double)t0) ms = (float)std::max(0.0, (double)t1 - s->prof_prev_end);
+            if (!s->prof_have_end || (double)t1 > s->prof_prev_end) s->prof_prev_end = t1;
+            s->prof_have_end = true;
+            if (sl.new_anchor) {
+                float off = 0;
+                HIPCHK(hipEventElapsedTime(&off, s->prof_anchor[s->prof_cur], s->prof_anchor[s->prof_cur ^ 1]));
+                s->prof_prev_end -= off; s->prof_cur ^= 1;
+                sl.new_anchor = s->prof_anchor_pending = false;
+            }
+        }
+        s->prof_ms[i] += ms; s->prof_n[i] += 1;
+    }
+    return CHN_OK;
+}
+
+// one result column into the caller's memory: from the slot's page-locked copy, filled in stream, or (null) from the device
+static int copy_out(void *dst, const void *staged, const void *dev, size_t bytes) {
+    if (staged) std::memcpy(dst, staged, bytes);
+    else HIPCHK(hipMemcpy(dst, dev, bytes, hipMemcpyDeviceToHost));
+    return CHN_OK;
+}
+
+// CHN_DIAG_WAIT: one line per chn_batch_wait, printed as the call returns
+struct WaitDiag {
+    bool on;
+    double at, done, gz;
+    ~WaitDiag() { if (on) std::fprintf(stderr, "chn_batch_wait: at %.4f  done-event %.2f ms  gz-event %.2f ms  rest %.2f ms\n", at, (done - at) * 1e3, (gz - done) * 1e3, (wall_now() - gz) * 1e3); }
+};
 
 extern "C" int chn_batch_wait(chn_stream *s, chn_result *r) {
     if (!s || !r || r->struct_size != sizeof(chn_result)) return fail(CHN_E_INVALID, "chn_batch_wait: bad argument");
@@ -192,57 +233,28 @@ extern "C" int chn_batch_wait(chn_stream *s, chn_result *r) {
     HIPCHK(hipSetDevice(s->idx->d.device));
     Slot &sl = s->slot[(s->head + chn_stream::N_SLOTS - s->inflight) % chn_stream::N_SLOTS];  // oldest batch in flight
     static const bool diag_wait = diag_env("CHN_DIAG_WAIT") != nullptr;
-    auto dnow = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double dw0 = diag_wait ? dnow() : 0;
+    const double at = diag_wait ? wall_now() : 0;
     HIPCHK(hipEventSynchronize(sl.done));
-    const double dw1 = diag_wait ? dnow() : 0;
+    const double done = diag_wait ? wall_now() : 0;
     if (sl.want_gzt) HIPCHK(hipEventSynchronize(sl.gz_done));
-    const double dw2 = diag_wait ? dnow() : 0;
-    struct DiagPrint { bool on; double a, b, c; std::function<double()> now; ~DiagPrint() { if (on) std::fprintf(stderr, "chn_batch_wait: at %.4f  done-event %.2f ms  gz-event %.2f ms  rest %.2f ms\n", a, (b - a) * 1e3, (c - b) * 1e3, (now() - c) * 1e3); } } diag_print{diag_wait, dw0, dw1, dw2, dnow};
+    const WaitDiag diag{diag_wait, at, done, diag_wait ? wall_now() : 0};
     s->inflight -= 1;
-    static const int evpair[4][2] = {{0, 1}, {2, 3}, {4, 5}, {6, 7}};
-    for (int i = 0; i < 4; ++i)
-        if (sl.ev_used[i]) {
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, sl.ev[evpair[i][0]], sl.ev[evpair[i][1]]));
-            if (i == 0) {
-                // the probe kernel: only what lies behind the end of the probe kernels before it (they overlap, on two streams) -- the
-                // sum over batches is the time some probe kernel was running, and one batch at a time gives the bracket time
-                float t0 = 0, t1 = 0;
-                HIPCHK(hipEventElapsedTime(&t0, s->prof_anchor[s->prof_cur], sl.ev[0]));
-                HIPCHK(hipEventElapsedTime(&t1, s->prof_anchor[s->prof_cur], sl.ev[1]));
-                if (s->prof_have_end && s->prof_prev_end > (double)t0) ms = (float)std::max(0.0, (double)t1 - s->prof_prev_end);
-                if (!s->prof_have_end || (double)t1 > s->prof_prev_end) s->prof_prev_end = t1;
-                s->prof_have_end = true;
-                if (sl.new_anchor) {
-                    float off = 0;
-                    HIPCHK(hipEventElapsedTime(&off, s->prof_anchor[s->prof_cur], s->prof_anchor[s->prof_cur ^ 1]));
-                    s->prof_prev_end -= off; s->prof_cur ^= 1;
-                    sl.new_anchor = s->prof_anchor_pending = false;
-                }
-            }
-            s->prof_ms[i] += ms; s->prof_n[i] += 1;
-        }
+    int rc = prof_collect(s, sl);
+    if (rc) return rc;
     unsigned long long ctl[CTL_WORDS];
     const uint64_t n = sl.n_reads, C = s->idx->d.num_categories;
     const ResLayout L(n, C);
     const char *staged = sl.staged ? sl.h_res.as<char>() : nullptr;  // the slot's page-locked copy, filled in stream
-    if (staged) std::memcpy(ctl, staged + L.ctl, sizeof ctl);
-    else HIPCHK(hipMemcpy(ctl, sl.d_ctl.p, sizeof ctl, hipMemcpyDeviceToHost));
-    if (ctl[CTL_STATUS] & 2) return fail(CHN_E_INVALID, "a segment of the batch is misaligned or lies outside the base buffer");
-    if (ctl[CTL_STATUS] & 4)  // k_shx_serve answered such a query with row 0: the counts of whoever asked are wrong
-        return fail(CHN_E_INVALID, "chn_shardx_serve was asked for rows this shard does not hold: the queries were built from other row_splits than the shards' "
-                                   "(or went to the wrong owner)");
+    if ((rc = copy_out(ctl, staged ? staged + L.ctl : nullptr, sl.d_ctl.p, sizeof ctl))) return rc;
+    if ((rc = status_error(ctl[CTL_STATUS], sl.list_mode ? "row log overflow in the row-sharded chain" : nullptr))) return rc;
     if (ctl[CTL_STATUS] & 1) {
-        if (sl.list_mode) return fail(CHN_E_CAPACITY, "row log overflow in the row-sharded chain");
-        int rc = rerun_worst_case(s, sl);
-        if (rc) return rc;
+        if ((rc = rerun_worst_case(s, sl))) return rc;
         staged = nullptr;  // the re-run's results are in the device arrays only
-        HIPCHK(hipMemcpy(ctl, sl.d_ctl.p, sizeof ctl, hipMemcpyDeviceToHost));
+        if ((rc = copy_out(ctl, nullptr, sl.d_ctl.p, sizeof ctl))) return rc;
         if (ctl[CTL_STATUS] & 1) return fail(CHN_E_CAPACITY, "row log overflow at worst-case capacity (a wavefront of 64 reads with more than 2^24 escaped rows)");
     }
     s->last_bytes = ctl[CTL_BYTES]; s->last_min = ctl[CTL_MINIMISERS]; s->last_fetches = ctl[CTL_FETCHES];
-    if (!sl.list_mode) s->last_had_long = ctl[CTL_NLONG] != 0;  // (decides the next batches' probe stream: chn_batch_submit)
+    if (!sl.list_mode) s->last_had_long = ctl[CTL_NLONG] != 0;  // (decides the next batches' probe stream: pick_probe_stream)
     if (r->on_device) {  // valid until the third-next chn_batch_submit
         r->num_hashes = sl.d_num_hashes.as<uint32_t>(); r->counts = sl.d_counts.as<uint32_t>(); r->unique_counts = sl.d_unique.as<uint32_t>();
         r->probabilities = sl.d_prob.as<double>(); r->call = sl.d_call.as<uint8_t>(); r->confidence = sl.d_conf.as<uint8_t>();
@@ -251,21 +263,15 @@ extern "C" int chn_batch_wait(chn_stream *s, chn_result *r) {
         r->gzip_sizes = sl.want_gzt && sl.gz_output != CHN_GZIP_TALLIES ? sl.d_gzsize.as<uint32_t>() : nullptr;
         return CHN_OK;
     }
-    auto fetch = [&](void *dst, const void *dev, size_t off, size_t bytes) -> int {
-        if (staged) std::memcpy(dst, staged + off, bytes);
-        else HIPCHK(hipMemcpy(dst, dev, bytes, hipMemcpyDeviceToHost));
-        return CHN_OK;
-    };
+    auto fetch = [&](void *dst, const void *dev, size_t off, size_t bytes) { return copy_out(dst, staged ? staged + off : nullptr, dev, bytes); };
     int frc = CHN_OK;
     if (sl.want_gzt && r->gzip_tallies) {
         if (sl.gz_output == CHN_GZIP_SIZES || sl.gz_output == CHN_GZIP_SIZES_ALL) return fail(CHN_E_INVALID, "chn_result.gzip_tallies: the batch asked for sizes only");
-        if (sl.gz_staged) std::memcpy(r->gzip_tallies, sl.h_gzt.p, n * GZT_WORDS * 2);
-        else HIPCHK(hipMemcpy(r->gzip_tallies, sl.d_gzt.p, n * GZT_WORDS * 2, hipMemcpyDeviceToHost));
+        if ((frc = copy_out(r->gzip_tallies, sl.gz_staged ? sl.h_gzt.p : nullptr, sl.d_gzt.p, n * GZT_WORDS * 2))) return frc;
     }
     if (sl.want_gzt && r->gzip_sizes) {
         if (sl.gz_output == CHN_GZIP_TALLIES) return fail(CHN_E_INVALID, "chn_result.gzip_sizes: the batch asked for tallies only");
-        if (sl.gz_staged) std::memcpy(r->gzip_sizes, sl.h_gzsize.p, n * 4);
-        else HIPCHK(hipMemcpy(r->gzip_sizes, sl.d_gzsize.p, n * 4, hipMemcpyDeviceToHost));
+        if ((frc = copy_out(r->gzip_sizes, sl.gz_staged ? sl.h_gzsize.p : nullptr, sl.d_gzsize.p, n * 4))) return frc;
     }
     if (r->num_hashes && (frc = fetch(r->num_hashes, sl.d_num_hashes.p, L.nh, n * 4))) return frc;
     if (r->counts && (frc = fetch(r->counts, sl.d_counts.p, L.counts, n * C * 4))) return frc;
@@ -315,21 +321,21 @@ extern "C" int chn_classify_counts_raw(chn_stream *s, uint64_t n, const uint32_t
     if ((rc = b.num_hashes.ensure(m * 4)) || (rc = b.counts.ensure(m * C * 4)) || (rc = b.unique.ensure(m * C * 4)) ||
         (rc = b.prob.ensure(m * C * 8)) || (rc = b.call.ensure(m)) || (rc = b.conf.ensure(m)) || (rc = b.flags.ensure(m)))
         return rc;
-    if ((rc = upload(b.len1, lengths, n * 4, s->stream, m * 4))) return rc;
-    if (mean_quality && (rc = upload(b.mq, mean_quality, n * 4, s->stream, m * 4))) return rc;
-    if (compression && (rc = upload(b.comp, compression, n * 4, s->stream, m * 4))) return rc;
-    HIPCHK(hipMemcpyAsync(b.num_hashes.p, num_hashes, n * 4, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipMemcpyAsync(b.counts.p, counts, n * C * 4, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipMemcpyAsync(b.unique.p, unique_counts, n * C * 4, hipMemcpyHostToDevice, s->stream));
+    if ((rc = upload(b.len1, lengths, n * 4, s->q_probe[0], m * 4))) return rc;
+    if (mean_quality && (rc = upload(b.mq, mean_quality, n * 4, s->q_probe[0], m * 4))) return rc;
+    if (compression && (rc = upload(b.comp, compression, n * 4, s->q_probe[0], m * 4))) return rc;
+    HIPCHK(hipMemcpyAsync(b.num_hashes.p, num_hashes, n * 4, hipMemcpyHostToDevice, s->q_probe[0]));
+    HIPCHK(hipMemcpyAsync(b.counts.p, counts, n * C * 4, hipMemcpyHostToDevice, s->q_probe[0]));
+    HIPCHK(hipMemcpyAsync(b.unique.p, unique_counts, n * C * 4, hipMemcpyHostToDevice, s->q_probe[0]));
     K3Args k3 = s->k3;
     k3.num_hashes = b.num_hashes.as<uint32_t>(); k3.counts = b.counts.as<uint32_t>(); k3.unique = b.unique.as<uint32_t>();
     k3.len1 = b.len1.as<uint32_t>(); k3.len2 = nullptr;
     k3.mean_quality = mean_quality ? b.mq.as<float>() : nullptr; k3.compression = compression ? b.comp.as<float>() : nullptr;
     k3.prob = b.prob.as<double>(); k3.call = b.call.as<uint8_t>(); k3.conf = b.conf.as<uint8_t>(); k3.flags = b.flags.as<uint8_t>();
     k3.n_reads = (uint32_t)n;
-    hipLaunchKernelGGL(k_model_call, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s->stream, k3);
+    hipLaunchKernelGGL(k_model_call, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s->q_probe[0], k3);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipStreamSynchronize(s->q_probe[0]));
     HIPCHK(hipMemcpy(probabilities, b.prob.p, n * C * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(call, b.call.p, n, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(confidence, b.conf.p, n, hipMemcpyDeviceToHost));
@@ -357,38 +363,37 @@ extern "C" int chn_classify_counts(chn_stream *s, uint64_t n, const uint32_t *nu
 }
 
 extern "C" int chn_stream_profile(chn_stream *s, int which, double *total_ms, uint64_t *launches, int reset) {
-    if (!s || which < 0 || which > 14 || which == 10 || which == 12) return fail(CHN_E_INVALID, "chn_stream_profile: bad argument");
-    if (which == 14) { s->fsp.timer.report(total_ms, launches, reset); return CHN_OK; }  // chn_fasta_split: its kernels in front of the first wait
-    if (which == 11) { s->tpi.timer.report(total_ms, launches, reset); return CHN_OK; }  // chn_text_pair_ids: k_pair_ids
-    if (which == 9) { s->txg.timer.report(total_ms, launches, reset); return CHN_OK; }   // chn_text_fetch: k_text_gather
-    if (which == 8) { s->tsp.timer.report(total_ms, launches, reset); return CHN_OK; }   // chn_text_split: its kernels in front of the first wait
-    if (which == 13) {  // batches whose ordinary probe launch was queued behind a probe-gate wait
-        if (total_ms) *total_ms = s->gate_signal ? 1.0 : 0.0;  // (no time: whether this stream gates at all)
-        if (launches) *launches = s->gated_batches;
-        if (reset) s->gated_batches = 0;
+    if (!s || !profile_which_ok(which)) return fail(CHN_E_INVALID, "chn_stream_profile: bad argument");
+    // a counter without a time
+    auto count_of = [&](uint64_t &counter, double ms, bool resets) {
+        if (total_ms) *total_ms = ms;
+        if (launches) *launches = counter;
+        if (reset && resets) counter = 0;
         return CHN_OK;
-    }
-    if (which >= 6) {  // text batches: upload of the text, k_text_pack + k_text_mq
-        if (total_ms) *total_ms = s->text_ms[which - 6];
-        if (launches) *launches = s->text_n;
-        if (reset) { s->text_ms[which - 6] = 0; if (which == 7) s->text_n = 0; }
-        return CHN_OK;
-    }
-    if (which == 5) {  // row fetches the last batch's probe kernel issued
-        if (total_ms) *total_ms = 0;
-        if (launches) *launches = s->last_fetches;
-        return CHN_OK;
-    }
-    if (which == 4) {  // batches re-run on worst-case buffers after a row-log overflow
-        if (total_ms) *total_ms = 0;
-        if (launches) *launches = s->overflow_reruns;
-        if (reset) s->overflow_reruns = 0;
-        return CHN_OK;
+    };
+    switch ((ProfileWhich)which) {
+        case PROF_FASTA_SPLIT: s->fsp.timer.report(total_ms, launches, reset); return CHN_OK;  // chn_fasta_split: its kernels in front of the first wait
+        case PROF_PAIR_IDS: s->tpi.timer.report(total_ms, launches, reset); return CHN_OK;     // chn_text_pair_ids: k_pair_ids
+        case PROF_TEXT_FETCH: s->txg.timer.report(total_ms, launches, reset); return CHN_OK;   // chn_text_fetch: k_text_gather
+        case PROF_TEXT_SPLIT: s->tsp.timer.report(total_ms, launches, reset); return CHN_OK;   // chn_text_split: its kernels in front of the first wait
+        case PROF_GATED:  // batches whose ordinary probe launch was queued behind a probe-gate wait (no time: whether this stream gates at all)
+            return count_of(s->gated_batches, s->gate_signal ? 1.0 : 0.0, true);
+        case PROF_TEXT_UPLOAD:
+        case PROF_TEXT_PACK: {  // text batches: upload of the text, k_text_pack + k_text_mq
+            double &ms = s->text_ms[which - PROF_TEXT_UPLOAD];
+            if (total_ms) *total_ms = ms;
+            if (launches) *launches = s->text_n;
+            if (reset) { ms = 0; if (which == PROF_TEXT_PACK) s->text_n = 0; }
+            return CHN_OK;
+        }
+        case PROF_FETCHES: return count_of(s->last_fetches, 0, false);    // row fetches the last batch's probe kernel issued
+        case PROF_RERUNS: return count_of(s->overflow_reruns, 0, true);   // batches re-run on worst-case buffers after a row-log overflow
+        case PROF_PROBE: case PROF_COUNT: case PROF_MODEL: case PROF_CHAIN: break;  // a slot's brackets, summed by prof_collect
     }
     if (total_ms) *total_ms = s->prof_ms[which];
     if (launches) *launches = s->prof_n[which];
     if (reset) { s->prof_ms[which] = 0; s->prof_n[which] = 0; }
-    if (reset && which == 0 && s->prof_anchor[0]) {  // no earlier probe kernel to count behind; idle streams: a fresh anchor as well
+    if (reset && which == PROF_PROBE && s->prof_anchor[0]) {  // no earlier probe kernel to count behind; idle streams: a fresh anchor as well
         s->prof_have_end = false;
         if (s->inflight == 0) {
             HIPCHK(hipSetDevice(s->idx->d.device));

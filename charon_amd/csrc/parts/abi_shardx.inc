@@ -5,7 +5,7 @@ extern "C" int chn_shardx_minimise(chn_stream *s, const chn_batch *b) {
     if (!s || !b) return fail(CHN_E_INVALID, "chn_shardx_minimise: null argument");
     if (s->shx_stage != 0 || s->shard_open) return fail(CHN_E_STATE, "chn_shardx_minimise: previous sharded batch not finished");
     HIPCHK(hipSetDevice(s->idx->d.device));
-    const uint64_t nw = (s->cfg.max_reads + WAVE - 1) / WAVE;
+    const uint64_t nw = waves_of(s->cfg.max_reads);
     int rc;
     // density-sized regions (as the per-slot logs of the replica path); an overrun is reported by chn_shardx_counts, not re-run
     if ((rc = s->shx.ensure(s->cfg.max_bases, nw, (uint32_t)s->idx->d.bin_words, s->cap_num, s->esc_shift))) return rc;
@@ -26,7 +26,7 @@ extern "C" int chn_shardx_counts(chn_stream *s, uint32_t n_ranks, const uint64_t
             return fail(CHN_E_INVALID, "chn_shardx_counts: row_splits must ascend and a shard may hold at most 2^32 - 1 rows");
     HIPCHK(hipSetDevice(d.device));
     Slot &sl = s->slot[s->head];
-    const uint32_t n_waves = (uint32_t)((sl.n_reads + WAVE - 1) / WAVE);
+    const uint32_t n_waves = (uint32_t)waves_of(sl.n_reads);
     int rc;
     if ((rc = s->d_shx_cnt.ensure((size_t)n_ranks * (n_waves + 1) * 8))) return rc;
     ShxArgs &a = s->shx_args;
@@ -37,15 +37,15 @@ extern "C" int chn_shardx_counts(chn_stream *s, uint32_t n_ranks, const uint64_t
     a.cnt = s->d_shx_cnt.as<uint64_t>();
     a.rowlog = s->shx.log.as<uint32_t>(); a.rows = s->shx.rows.as<uint64_t>(); a.esc_capacity = s->shx.esc_cap;
     a.status = reinterpret_cast<uint32_t *>(sl.d_ctl.as<unsigned long long>() + CTL_STATUS); a.B = (uint32_t)d.bins;
-    hipLaunchKernelGGL(k_shx_count, dim3(n_waves), dim3(SHX_THREADS), 0, s->stream, a);
-    hipLaunchKernelGGL(k_shx_scan, dim3(n_ranks), dim3(1024), 0, s->stream, a.cnt, n_waves);
+    hipLaunchKernelGGL(k_shx_count, dim3(n_waves), dim3(SHX_THREADS), 0, s->q_probe[0], a);
+    hipLaunchKernelGGL(k_shx_scan, dim3(n_ranks), dim3(1024), 0, s->q_probe[0], a.cnt, n_waves);
     HIPCHK(hipGetLastError());
     std::vector<uint64_t> tot(n_ranks);
     for (uint32_t r = 0; r < n_ranks; ++r)
-        HIPCHK(hipMemcpyAsync(&tot[r], a.cnt + (size_t)r * (n_waves + 1) + n_waves, 8, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipMemcpyAsync(&tot[r], a.cnt + (size_t)r * (n_waves + 1) + n_waves, 8, hipMemcpyDeviceToHost, s->q_probe[0]));
     unsigned long long st = 0;
-    HIPCHK(hipMemcpyAsync(&st, sl.d_ctl.as<unsigned long long>() + CTL_STATUS, 8, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipMemcpyAsync(&st, sl.d_ctl.as<unsigned long long>() + CTL_STATUS, 8, hipMemcpyDeviceToHost, s->q_probe[0]));
+    HIPCHK(hipStreamSynchronize(s->q_probe[0]));
     if (st & 2) { s->shx_stage = 0; return fail(CHN_E_INVALID, "a segment of the batch is misaligned or lies outside the base buffer"); }
     if (st & 1) { s->shx_stage = 0; return fail(CHN_E_CAPACITY, "minimiser log overflow in the sparse row-sharded chain: submit the reads in smaller batches or create the stream with a larger max_bases"); }
     uint64_t run = 0;
@@ -64,7 +64,7 @@ extern "C" int chn_shardx_queries(chn_stream *s, uint32_t *dev_queries, uint64_t
     HIPCHK(hipSetDevice(s->idx->d.device));
     ShxArgs a = s->shx_args;
     a.queries = dev_queries;
-    hipLaunchKernelGGL(k_shx_scatter, dim3(a.n_waves), dim3(SHX_THREADS), 0, s->stream, a);
+    hipLaunchKernelGGL(k_shx_scatter, dim3(a.n_waves), dim3(SHX_THREADS), 0, s->q_probe[0], a);
     HIPCHK(hipGetLastError());
     s->shx_stage = 3;
     return CHN_OK;
@@ -86,12 +86,7 @@ extern "C" int chn_shardx_serve(chn_stream *s, const chn_index *shard, const uin
     static const long serve_blocks_env = []() { const char *e = diag_env("CHN_SERVE_BLOCKS"); return e ? std::atol(e) : 0L; }();
     const uint64_t serve_blocks = serve_blocks_env > 0 ? (uint64_t)serve_blocks_env : (uint64_t)std::max(1, cus) * 2;
     const dim3 grid((uint32_t)std::min<uint64_t>((n_in + 255) / 256, serve_blocks)), block(256);
-    switch (shard->d.bin_words) {
-        case 1: hipLaunchKernelGGL(k_shx_serve<1>, grid, block, 0, s->stream, shard->words, dev_queries_in, n_in, shard->rows_local, dev_rows_out, status); break;
-        case 2: hipLaunchKernelGGL(k_shx_serve<2>, grid, block, 0, s->stream, shard->words, dev_queries_in, n_in, shard->rows_local, dev_rows_out, status); break;
-        case 3: hipLaunchKernelGGL(k_shx_serve<3>, grid, block, 0, s->stream, shard->words, dev_queries_in, n_in, shard->rows_local, dev_rows_out, status); break;
-        default: hipLaunchKernelGGL(k_shx_serve<4>, grid, block, 0, s->stream, shard->words, dev_queries_in, n_in, shard->rows_local, dev_rows_out, status); break;
-    }
+    by_words(shard->d.bin_words, [&](auto w) { hipLaunchKernelGGL(k_shx_serve<decltype(w)::value>, grid, block, 0, s->q_probe[0], shard->words, dev_queries_in, n_in, shard->rows_local, dev_rows_out, status); });
     HIPCHK(hipGetLastError());
     return CHN_OK;
 }
@@ -103,17 +98,12 @@ extern "C" int chn_shardx_finish(chn_stream *s, const uint64_t *dev_rows_back) {
     Slot &sl = s->slot[s->head];
     ShxArgs a = s->shx_args;
     a.resp = dev_rows_back;
-    switch (s->idx->d.bin_words) {
-        case 1: hipLaunchKernelGGL(k_shx_and<1>, dim3(a.n_waves), dim3(SHX_THREADS), 0, s->stream, a); break;
-        case 2: hipLaunchKernelGGL(k_shx_and<2>, dim3(a.n_waves), dim3(SHX_THREADS), 0, s->stream, a); break;
-        case 3: hipLaunchKernelGGL(k_shx_and<3>, dim3(a.n_waves), dim3(SHX_THREADS), 0, s->stream, a); break;
-        default: hipLaunchKernelGGL(k_shx_and<4>, dim3(a.n_waves), dim3(SHX_THREADS), 0, s->stream, a); break;
-    }
+    by_words(s->idx->d.bin_words, [&](auto w) { hipLaunchKernelGGL(k_shx_and<decltype(w)::value>, dim3(a.n_waves), dim3(SHX_THREADS), 0, s->q_probe[0], a); });
     HIPCHK(hipGetLastError());
     s->shx_stage = 0;
-    HIPCHK(hipEventRecord(sl.k1_done, s->stream));
-    HIPCHK(hipStreamWaitEvent(s->stream2, sl.k1_done, 0));
-    int rc = launch_tail(s, sl, s->shx, s->stream2);
+    HIPCHK(hipEventRecord(sl.k1_done, s->q_probe[0]));
+    HIPCHK(hipStreamWaitEvent(s->q_side, sl.k1_done, 0));
+    int rc = launch_tail(s, sl, s->shx, TAIL_BATCH);
     if (rc) return rc;
     s->head = (s->head + 1) % chn_stream::N_SLOTS;
     s->inflight += 1;

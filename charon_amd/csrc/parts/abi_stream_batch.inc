@@ -2,14 +2,53 @@
 // Part of the single translation unit charon_hip.hip (included in order); not a stand-alone source.
 
 // ---- stream -------------------------------------------------------------------------------------
-// layout of a slot's page-locked result block
-struct ResLayout {
-    size_t ctl, prob, nh, counts, unique, call, conf, flags, total;
-    ResLayout(uint64_t n, uint64_t C) {
-        ctl = 0; prob = CTL_WORDS * 8; nh = prob + n * C * 8; counts = nh + n * 4; unique = counts + n * C * 4; call = unique + n * C * 4;
-        conf = call + n; flags = conf + n; total = flags + n;
-    }
-};
+// (ResLayout, the layout of a slot's page-locked result block: batch_plan.inc)
+
+// The streams of a chn_stream, in the order they are made.
+// Two probe streams, used alternately: batch i + 1's probe kernel does not wait for the last wavefront of batch i's, its workgroups
+// take the slots that batch i's retiring wavefronts free once batch i has none left to dispatch (equal-length reads leave a last
+// generation of one wavefront per CU; a front end's 65 536-read batches never fill the device at all).  Batch i + 2 queues behind
+// batch i, so at most two probe grids are on the device.
+// Priorities: the probe kernels' streams are the ordinary ones.  The side stream (count, model + call, result download of batch i)
+// and the copy stream (uploads and the two tiny ordering kernels of batch i+1) run ABOVE it: their short kernels must get
+// workgroup slots as the probe kernel of the neighbouring batch retires waves, or batch i only completes when batch i+1's probe
+// kernel does and a caller with host buffers cannot start the next upload in time.  The tally stream runs BELOW it: the
+// latency-bound deflate pass fills in beside the probe kernel, and so does the long-gzip stream, which the first CHN_GZIP_SIZES_ALL
+// batch makes.  (The runtime also keeps a separate set of hardware queues per priority level, so a long tally kernel never sits in
+// front of a copy or a probe launch in the same queue.)
+// synced: chn_stream_sync waits for it (the two gzip streams are waited for through a batch's gz_done event only).
+enum StreamPrio { PRIO_ORDINARY, PRIO_ABOVE, PRIO_BELOW };
+struct StreamRole { hipStream_t *q; StreamPrio prio; bool at_create, synced; };
+enum { N_STREAM_ROLES = 7 };
+static std::array<StreamRole, N_STREAM_ROLES> stream_roles(chn_stream *s) {
+    return {{{&s->q_probe[0], PRIO_ORDINARY, true, true}, {&s->q_probe[1], PRIO_ORDINARY, true, true}, {&s->q_side, PRIO_ABOVE, true, true},
+             {&s->q_copy, PRIO_ABOVE, true, true}, {&s->q_tally, PRIO_BELOW, true, false}, {&s->q_split, PRIO_ORDINARY, true, true},
+             {&s->q_gzlong, PRIO_BELOW, false, false}}};
+}
+// the list's entry for one of the streams (the long-gzip stream is opened late, by its first batch)
+static StreamRole stream_role(chn_stream *s, const hipStream_t *q) {
+    const auto roles = stream_roles(s);
+    for (const StreamRole &r : roles) if (r.q == q) return r;
+    return roles[0];  // (not reached: every stream of a chn_stream is in the list)
+}
+static hipError_t stream_open(const StreamRole &r) {
+    if (r.prio == PRIO_ORDINARY) return hipStreamCreateWithFlags(r.q, hipStreamNonBlocking);
+    int prio_least = 0, prio_greatest = 0;
+    const hipError_t e = hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
+    return e != hipSuccess ? e : hipStreamCreateWithPriority(r.q, hipStreamNonBlocking, r.prio == PRIO_ABOVE ? prio_greatest : prio_least);
+}
+
+// A slot's events: the ones that order the streams, and the profiling brackets of the chain (a text batch's brackets are made by the
+// first profiled text batch, abi_text_batch.inc; they are destroyed here with the others)
+static int slot_events_create(Slot &sl) {
+    return events_create("hipEventCreate", {&sl.k1_done, &sl.split_done, &sl.done, &sl.uploaded, &sl.bases_up, &sl.gz_done, &sl.gzt_done},
+                         {&sl.t_probe.begin, &sl.t_probe.end, &sl.t_count.begin, &sl.t_count.end, &sl.t_model.begin, &sl.t_model.end, &sl.t_chain.begin, &sl.t_chain.end});
+}
+static void slot_events_destroy(Slot &sl) {
+    events_destroy({&sl.k1_done, &sl.split_done, &sl.done, &sl.uploaded, &sl.bases_up, &sl.gz_done, &sl.gzt_done,
+                    &sl.t_probe.begin, &sl.t_probe.end, &sl.t_count.begin, &sl.t_count.end, &sl.t_model.begin, &sl.t_model.end, &sl.t_chain.begin, &sl.t_chain.end,
+                    &sl.t_text_upload.begin, &sl.t_text_upload.end, &sl.t_text_pack.begin, &sl.t_text_pack.end});
+}
 
 // Profiling streams: the age from which the time anchor is replaced at the next submit (at 10 s a float of milliseconds still resolves 0.001 ms)
 static const int PROF_ANCHOR_SECONDS = 8;
@@ -17,7 +56,7 @@ static const int PROF_ANCHOR_SECONDS = 8;
 static hipError_t prof_anchor_now(chn_stream *s) {
     for (Slot &sl : s->slot) sl.new_anchor = false;
     s->prof_cur = 0; s->prof_anchor_pending = false; s->prof_have_end = false; s->prof_prev_end = 0;
-    hipError_t e = hipEventRecord(s->prof_anchor[0], s->stream);
+    hipError_t e = hipEventRecord(s->prof_anchor[0], s->q_probe[0]);
     if (e == hipSuccess) e = hipEventSynchronize(s->prof_anchor[0]);
     s->prof_anchor_at = std::chrono::steady_clock::now();
     return e;
@@ -31,24 +70,8 @@ extern "C" int chn_stream_create(chn_index *idx, const chn_stream_cfg *cfg, chn_
     chn_stream *s = new (std::nothrow) chn_stream();
     if (!s) return fail(CHN_E_NOMEM, "host allocation failed");
     s->idx = idx; s->cfg = *cfg;
-    // Two probe streams, used alternately: batch i + 1's probe kernel does not wait for the last wavefront of batch i's, its workgroups
-    // take the slots that batch i's retiring wavefronts free once batch i has none left to dispatch (equal-length reads leave a last
-    // generation of one wavefront per CU; a front end's 65 536-read batches never fill the device at all).  Batch i + 2 queues behind
-    // batch i, so at most two probe grids are on the device.
-    // Priorities: the probe kernels' streams are the ordinary ones.  The side stream (count, model + call, result download of batch i)
-    // and the copy stream (uploads and the two tiny ordering kernels of batch i+1) run ABOVE it: their short kernels must get
-    // workgroup slots as the probe kernel of the neighbouring batch retires waves, or batch i only completes when batch i+1's probe
-    // kernel does and a caller with host buffers cannot start the next upload in time.  The tally stream runs BELOW it: the
-    // latency-bound deflate pass fills in beside the probe kernel.  (The runtime also keeps a separate set of hardware queues per
-    // priority level, so a long tally kernel never sits in front of a copy or a probe launch in the same queue.)
-    int prio_least = 0, prio_greatest = 0;
-    hipError_t e = hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->stream1, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithPriority(&s->stream2, hipStreamNonBlocking, prio_greatest);
-    if (e == hipSuccess) e = hipStreamCreateWithPriority(&s->stream0, hipStreamNonBlocking, prio_greatest);
-    if (e == hipSuccess) e = hipStreamCreateWithPriority(&s->stream3, hipStreamNonBlocking, prio_least);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->stream4, hipStreamNonBlocking);
+    hipError_t e = hipSuccess;
+    for (const StreamRole &r : stream_roles(s)) if (r.at_create && e == hipSuccess) e = stream_open(r);
     {   // long reads are cut over the lanes of a wavefront from this length class on (testing: CHN_STREAM_SPLIT_BUCKET)
         const uint32_t ob = (cfg->flags >> 8) & 0xffu;
         s->long_bucket = ob == 0 ? LONG_BUCKET_DEFAULT : ob == 255 ? 256u : std::max(64u, ob);
@@ -77,24 +100,16 @@ extern "C" int chn_stream_create(chn_index *idx, const chn_stream_cfg *cfg, chn_
     s->esc_shift = idx->d.bins <= 128 ? 3u : 1u;
     if (cfg->flags & CHN_STREAM_TINY_LOG) { s->cap_num = 64; s->esc_shift = 6; }  // testing: force the overflow -> re-run path
     // wavefront logs: one per 64 reads + one per read the SPLIT launch may take
-    const uint64_t nw = (n + WAVE - 1) / WAVE + (s->long_bucket < 256 ? std::min<uint64_t>(n, cfg->max_bases / len_bucket_floor(s->long_bucket)) : 0);
+    const uint64_t nw = waves_of(n) + (s->long_bucket < 256 ? std::min<uint64_t>(n, cfg->max_bases / len_bucket_floor(s->long_bucket)) : 0);
     for (Slot &sl : s->slot) {
-        for (int i = 0; i < 8 && e == hipSuccess; ++i) e = hipEventCreate(&sl.ev[i]);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.k1_done, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.split_done, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.uploaded, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.bases_up, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.gz_done, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.gzt_done, hipEventDisableTiming);
-        if (e != hipSuccess) { chn_stream_destroy(s); return fail(CHN_E_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e)); }
+        if ((rc = slot_events_create(sl))) { chn_stream_destroy(s); return rc; }
         if ((rc = sl.d_num_hashes.ensure(n * 4)) || (rc = sl.d_counts.ensure(n * C * 4)) || (rc = sl.d_unique.ensure(n * C * 4)) ||
             (rc = sl.d_prob.ensure(n * C * 8)) || (rc = sl.d_call.ensure(n)) || (rc = sl.d_conf.ensure(n)) || (rc = sl.d_flags.ensure(n)) ||
             (rc = sl.d_ctl.ensure(CTL_WORDS * 8)) || (rc = sl.d_order.ensure(n * 4))) {
             chn_stream_destroy(s);
             return rc;
         }
-        if (!fused && !sharded && (rc = sl.lb.ensure(cfg->max_bases, nw, (uint32_t)idx->d.bin_words, s->cap_num, s->esc_shift, (n + WAVE - 1) / WAVE + n))) { chn_stream_destroy(s); return rc; }
+        if (!fused && !sharded && (rc = sl.lb.ensure(cfg->max_bases, nw, (uint32_t)idx->d.bin_words, s->cap_num, s->esc_shift, waves_of(n) + n))) { chn_stream_destroy(s); return rc; }
     }
     if ((rc = s->d_hist.ensure(LEN_BLOCKS * 256 * 4))) { chn_stream_destroy(s); return rc; }
     if (cfg->flags & CHN_STREAM_PROFILE) {  // the anchor the probe kernels' times are taken against (chn_stream_profile, which = 0)
@@ -123,29 +138,14 @@ extern "C" int chn_stream_create(chn_index *idx, const chn_stream_cfg *cfg, chn_
 extern "C" int chn_stream_destroy(chn_stream *s) {
     if (!s) return CHN_OK;
     (void)hipSetDevice(s->idx->d.device);
-    if (s->stream) { (void)hipStreamSynchronize(s->stream); }
-    if (s->stream1) { (void)hipStreamSynchronize(s->stream1); (void)hipStreamDestroy(s->stream1); }
-    if (s->stream2) { (void)hipStreamSynchronize(s->stream2); (void)hipStreamDestroy(s->stream2); }
-    if (s->stream0) { (void)hipStreamSynchronize(s->stream0); (void)hipStreamDestroy(s->stream0); }
-    if (s->stream3) { (void)hipStreamSynchronize(s->stream3); (void)hipStreamDestroy(s->stream3); }
-    if (s->stream4) { (void)hipStreamSynchronize(s->stream4); (void)hipStreamDestroy(s->stream4); }
-    if (s->stream5) { (void)hipStreamSynchronize(s->stream5); (void)hipStreamDestroy(s->stream5); }
-    if (s->stream) (void)hipStreamDestroy(s->stream);
+    for (const StreamRole &r : stream_roles(s)) if (*r.q) (void)hipStreamSynchronize(*r.q);
+    for (const StreamRole &r : stream_roles(s)) if (*r.q) (void)hipStreamDestroy(*r.q);
     if (s->gate_signal) (void)hipFree(s->gate_signal);
     for (hipEvent_t a : s->prof_anchor) if (a) (void)hipEventDestroy(a);
     for (Slot &sl : s->slot) {
-        for (int i = 0; i < 8; ++i) if (sl.ev[i]) (void)hipEventDestroy(sl.ev[i]);
-        if (sl.k1_done) (void)hipEventDestroy(sl.k1_done);
-        if (sl.split_done) (void)hipEventDestroy(sl.split_done);
-        if (sl.done) (void)hipEventDestroy(sl.done);
-        if (sl.uploaded) (void)hipEventDestroy(sl.uploaded);
-        if (sl.bases_up) (void)hipEventDestroy(sl.bases_up);
-        if (sl.gz_done) (void)hipEventDestroy(sl.gz_done);
-        if (sl.gzt_done) (void)hipEventDestroy(sl.gzt_done);
+        slot_events_destroy(sl);
         sl.h_res.release(); sl.h_gzt.release(); sl.h_gzsize.release(); sl.d_gzsize.release();
         sl.h_text.release(); sl.d_text.release(); sl.d_tdesc.release(); sl.d_tctl.release();
-        for (int i = 0; i < 4; ++i) if (sl.tev[i]) (void)hipEventDestroy(sl.tev[i]);
-        s->h_block.release();
         DevBuf *bufs[] = {&sl.d_num_hashes, &sl.d_counts, &sl.d_unique, &sl.d_prob, &sl.d_call, &sl.d_conf, &sl.d_flags, &sl.d_ctl, &sl.d_order, &sl.d_gzt, &sl.d_gzidx, &sl.d_gzctr, &sl.d_gzlong,
                           &sl.d_len1, &sl.d_len2, &sl.d_mq, &sl.d_comp, &sl.d_bases, &sl.d_nmask, &sl.d_off1, &sl.d_off2};
         for (DevBuf *b : bufs) b->release();
@@ -155,6 +155,7 @@ extern "C" int chn_stream_destroy(chn_stream *s) {
                       &s->cc.num_hashes, &s->cc.counts, &s->cc.unique, &s->cc.len1, &s->cc.mq, &s->cc.comp, &s->cc.prob, &s->cc.call,
                       &s->cc.conf, &s->cc.flags};
     for (DevBuf *b : bufs) b->release();
+    s->h_block.release();  // (behind the slots: they may have borrowed pieces of it)
     s->big.release();
     s->shx.release();
     s->tsp.release();
@@ -213,9 +214,9 @@ extern "C" int chn_model_set(chn_stream *s, const chn_model *m) {
         tab[2 * C + c] = (uint32_t)flat.size(); tab[3 * C + c] = (uint32_t)M.neg[c].size();
         flat.insert(flat.end(), M.neg[c].begin(), M.neg[c].end());
     }
-    HIPCHK(hipStreamSynchronize(s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream1));
-    HIPCHK(hipStreamSynchronize(s->stream2));
+    HIPCHK(hipStreamSynchronize(s->q_probe[0]));
+    HIPCHK(hipStreamSynchronize(s->q_probe[1]));
+    HIPCHK(hipStreamSynchronize(s->q_side));
     // From here on the device tables are being replaced: a failure leaves the stream WITHOUT a model (never with a torn one).
     s->model.set = false;
     const size_t tab_bytes = tab.size() * 4, flat_bytes = std::max<size_t>(flat.size() * 4, 4), par_bytes = M.dparams.size() * 4;
@@ -245,10 +246,11 @@ extern "C" int chn_model_set(chn_stream *s, const chn_model *m) {
 }
 
 // (k1_cond, k1_lds_bytes, ring_pack_ok: lds_budget.hpp)
-// blocks = 0: the ordinary launch, one wavefront per 64 reads; else the SPLIT launch (one long read per wavefront), `blocks` looping workgroups
-template <int W, int MODE, bool SPLIT = false, bool COND = false>
-static hipError_t launch_k1(const K1Args &a, size_t lds, hipStream_t st, uint32_t blocks = 0) {
-    if (!SPLIT) blocks = (a.n_reads + WAVE - 1) / WAVE;
+// One instance of the probe kernel.  blocks = 0: the ordinary launch, one wavefront per 64 reads; else the SPLIT launch (one long read per
+// wavefront), `blocks` looping workgroups
+template <int W, int MODE, bool SPLIT, bool COND>
+static hipError_t launch_k1_as(const K1Args &a, size_t lds, hipStream_t st, uint32_t blocks) {
+    if (!SPLIT) blocks = (uint32_t)waves_of(a.n_reads);
     if (lds > 48 * 1024) {  // long windows: opt in to large dynamic LDS
         hipError_t e = hipFuncSetAttribute((const void *)k_minimise_probe<W, MODE, 0, SPLIT, COND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -261,40 +263,29 @@ static hipError_t launch_k1(const K1Args &a, size_t lds, hipStream_t st, uint32_
         hipLaunchKernelGGL((k_minimise_probe<W, MODE, 0, SPLIT, COND>), dim3(blocks), dim3(WAVE), lds, st, a);
     return hipGetLastError();
 }
-static hipError_t launch_k1_split_mode(int mode, uint32_t W, const K1Args &a, size_t lds, hipStream_t st, uint32_t blocks) {
-    if (mode == MODE_FUSED) return k1_cond(mode, a.B) ? launch_k1<1, MODE_FUSED, true, true>(a, lds, st, blocks) : launch_k1<1, MODE_FUSED, true, false>(a, lds, st, blocks);
-    switch (W) {
-        case 1: return launch_k1<1, MODE_ROWS, true>(a, lds, st, blocks);
-        case 2: return launch_k1<2, MODE_ROWS, true>(a, lds, st, blocks);
-        case 3: return launch_k1<3, MODE_ROWS, true>(a, lds, st, blocks);
-        default: return launch_k1<4, MODE_ROWS, true>(a, lds, st, blocks);
+// The probe kernel's launch: the instance for `mode` and W = bin_words, on `st`.  split_blocks = 0: the ordinary launch; else the SPLIT
+// launch with that many workgroups.  MODE_FUSED and MODE_LIST are W = 1 by definition; the list modes never split a read.
+// (MODE_EMPLACE is no batch's: chn_synth_plant takes its instance itself.)
+static hipError_t launch_k1(int mode, uint32_t W, const K1Args &a, size_t lds, hipStream_t st, uint32_t split_blocks = 0) {
+    const bool cond = k1_cond(mode, a.B);
+    if (split_blocks) {
+        if (mode == MODE_FUSED) return cond ? launch_k1_as<1, MODE_FUSED, true, true>(a, lds, st, split_blocks) : launch_k1_as<1, MODE_FUSED, true, false>(a, lds, st, split_blocks);
+        return by_words(W, [&](auto w) { return launch_k1_as<decltype(w)::value, MODE_ROWS, true, false>(a, lds, st, split_blocks); });
     }
+    if (mode == MODE_LIST) return launch_k1_as<1, MODE_LIST, false, false>(a, lds, st, 0);
+    if (mode == MODE_FUSED) return cond ? launch_k1_as<1, MODE_FUSED, false, true>(a, lds, st, 0) : launch_k1_as<1, MODE_FUSED, false, false>(a, lds, st, 0);
+    return by_words(W, [&](auto w) { return launch_k1_as<decltype(w)::value, MODE_ROWS, false, false>(a, lds, st, 0); });
 }
-// Most reads the SPLIT launch can meet in a batch, as far as the host can tell: exact for a host batch, all of them for a device batch.
-// 0: no launch.
-static uint32_t split_bound(const chn_stream *s, const Slot &sl, uint64_t n, uint64_t n_bases, bool paired) {
-    if (paired || s->long_bucket >= 256) return 0;
-    const uint32_t floor_len = len_bucket_floor(s->long_bucket);
-    (void)n_bases;
-    if (!sl.host_batch) return (uint32_t)n;  // (segments of a device batch may overlap: any number of its reads can be long)
-    uint64_t c = 0;
-    for (uint32_t L : sl.h_len1) c += L >= floor_len;
-    return (uint32_t)c;
+// the probe kernel's LDS for this index in MODE_ROWS: what the count kernel's budget is taken from, and what a re-run launches with
+static size_t k1_rows_lds(const chn_index_desc &d) {
+    const uint32_t wn = d.window_size - d.kmer_size + 1;
+    return k1_lds_bytes(wn, d.num_categories, MODE_ROWS, d.hash_funs, (uint32_t)d.bin_words, (uint32_t)d.bins, ring_pack_ok(d.kmer_size, wn, d.minimiser_seed));
 }
 // Workgroups of a SPLIT launch: they loop over the long reads in strides of the grid.  More than the device holds at once (1 792 at seven
 // per CU) on purpose: the reads a workgroup meets differ in length, and with four times as many workgroups as slots the dispatcher evens
 // that out as slots fall free.  A grid of exactly what is resident was measured on 500 b - 50 kb reads: the step 3 ms (4 %) longer
 // (profiles/r06/probe_overlap_ab.txt).  A device batch's bound is all its reads; its workgroups beyond the long reads return at once.
 static uint32_t split_grid(uint32_t bound) { return std::min<uint32_t>(bound, 8192u); }
-template <int MODE>
-static hipError_t launch_k1_w(uint32_t W, const K1Args &a, size_t lds, hipStream_t st) {
-    switch (W) {
-        case 1: return launch_k1<1, MODE>(a, lds, st);
-        case 2: return launch_k1<2, MODE>(a, lds, st);
-        case 3: return launch_k1<3, MODE>(a, lds, st);
-        default: return launch_k1<4, MODE>(a, lds, st);
-    }
-}
 
 // (reserve: the most this buffer will ever hold -- allocated at first use, so that a later, larger batch never re-allocates:
 //  hipFree waits for the device, i.e. for whatever kernels of the batches in flight are running)
@@ -305,18 +296,14 @@ static int upload(DevBuf &buf, const void *src, size_t bytes, hipStream_t st, si
     return CHN_OK;
 }
 
-// count (general layouts) + model/call + byte counter on the side stream; closes the batch in slot `sl`
-static int launch_tail(chn_stream *s, Slot &sl, LogBuf &lb, hipStream_t st);
-static void fill_k1_log(K1Args &a, Slot &sl, LogBuf &lb, bool dynamic) {
-    a.rowlog = lb.log.as<uint32_t>(); a.rows = lb.rows.as<uint64_t>(); a.wave_meta = lb.meta.as<WaveMeta>(); a.wave_count = lb.wcount.as<uint32_t>();
-    a.log_capacity = lb.log_cap; a.esc_capacity = lb.esc_cap; a.cap_num = lb.cap_num; a.esc_shift = lb.esc_shift;
-    a.cursor = dynamic ? sl.d_ctl.as<unsigned long long>() + CTL_LOG_CURSOR : nullptr;
-}
-static hipError_t launch_k1_mode(int mode, uint32_t W, const K1Args &a, size_t lds, hipStream_t st) {
-    // (MODE_FUSED is W = 1 by definition)
-    return mode == MODE_LIST ? launch_k1<1, MODE_LIST>(a, lds, st) : mode == MODE_FUSED ? (k1_cond(mode, a.B) ? launch_k1<1, MODE_FUSED, false, true>(a, lds, st) : launch_k1<1, MODE_FUSED>(a, lds, st))
-                                                                   : launch_k1_w<MODE_ROWS>(W, a, lds, st);
-}
+// What the stages of a submit know of the batch on the device: a host batch in the slot's staging, a device batch where the caller has
+// it.  (The lengths, mean quality and compression are the slot's: sl.len1, sl.len2, sl.mq, sl.comp -- the tail reads them too.)
+struct DevBatch {
+    const uint32_t *bases, *nmask;  // nmask null: no N in the batch
+    const uint64_t *off1, *off2;    // off2 null: single reads
+    uint64_t n, n_bases;
+    bool paired, on_device;
+};
 
 // ---- the gzip column: deflate tallies / gzip member sizes of a batch's reads (k_gzip_tally, k_gzip_long, k_gzip_size) ----
 // What a launch of either deflate kernel needs beside its arguments.  A launch is as many wavefronts as the device holds at once (a CU's
@@ -340,43 +327,33 @@ static int gz_launch_room(const chn_stream *s, size_t lds, uint32_t max_wpc, uin
     }
     return CHN_OK;
 }
-// f(integral_constant<int, BITS>): the kernels' form for a batch with N (4-bit codes) or without (2-bit codes: half the LDS, twice the
-// wavefronts for long reads)
-template <class F>
-static void gz_by_bits(int bits, F f) {
-    if (bits == 4) f(std::integral_constant<int, 4>());
-    else f(std::integral_constant<int, 2>());
-}
 
 // The kernel's LDS (and with it the number of reads a CU works on at once) goes with the longest read of a launch, so a host batch is
-// cut into occupancy classes (below), one launch per class in use; a device batch is one launch sized by the caller's bound.
-static int submit_gzip_column(chn_stream *s, Slot &sl, const chn_batch *b, const uint32_t *bases, const uint32_t *nmask, const uint64_t *off1, const uint64_t *off2,
-                              uint64_t n, bool paired) {
-    sl.want_gzt = b->gzip_tallies != 0 && !sl.list_mode;
-    if (sl.want_gzt && b->gzip_output > CHN_GZIP_SIZES_ALL) return fail(CHN_E_INVALID, "chn_batch.gzip_output: unknown value");
-    if (sl.want_gzt && b->gzip_output == CHN_GZIP_SIZES_ALL && b->on_device)
+// cut into occupancy classes (gz_plan, batch_plan.inc), one launch per class in use; a device batch is one launch sized by the caller's
+// bound.  Reads: plan, upload, launches longest class first, sizes, downloads.
+static int submit_gzip_column(chn_stream *s, Slot &sl, const DevBatch &db, uint32_t gzip_tallies, uint32_t gzip_output) {
+    sl.want_gzt = gzip_tallies != 0 && !sl.list_mode;
+    if (sl.want_gzt && gzip_output > CHN_GZIP_SIZES_ALL) return fail(CHN_E_INVALID, "chn_batch.gzip_output: unknown value");
+    if (sl.want_gzt && gzip_output == CHN_GZIP_SIZES_ALL && db.on_device)
         return fail(CHN_E_INVALID, "chn_batch.gzip_output = CHN_GZIP_SIZES_ALL: host batches only");
-    sl.gz_output = b->gzip_output;
+    sl.gz_output = gzip_output;
     if (!sl.want_gzt) return CHN_OK;
+    const uint64_t n = db.n;
     int rc = sl.d_gzt.ensure((size_t)s->cfg.max_reads * GZT_WORDS * 2);
     if (rc) return rc;
-    const int bits = nmask ? 4 : 2;
-    const uint32_t bound = std::min<uint32_t>(b->gzip_tallies, GZT_MAX_LEN);
+    const int bits = db.nmask ? 4 : 2;
+    const uint32_t bound = std::min<uint32_t>(gzip_tallies, GZT_MAX_LEN);
     // CHN_GZIP_SIZES_ALL: k_gzip_long sizes the reads beyond the tally kernel's reach -- longer than GZT_MAX_LEN (on its own stream,
     // beside the tally launches) and those the tallies hand back for a second deflate block (behind the tally launches)
     const bool all_sizes = sl.gz_output == CHN_GZIP_SIZES_ALL;
-    const uint32_t long_bound = b->gzip_tallies;
+    const uint32_t long_bound = gzip_tallies;
     const size_t cap_n = (size_t)s->cfg.max_reads;
-    bool long_launch = false;  // a k_gzip_long launch on stream5: the sizes are formed there, behind it and behind the tallies
+    bool long_launch = false;  // a k_gzip_long launch on the long-gzip stream: the sizes are formed there, behind it and behind the tallies
     if (all_sizes) {
-        if (!s->stream5) {
-            int prio_least = 0, prio_greatest = 0;
-            HIPCHK(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-            HIPCHK(hipStreamCreateWithPriority(&s->stream5, hipStreamNonBlocking, prio_least));
-        }
+        if (!s->q_gzlong) HIPCHK(stream_open(stream_role(s, &s->q_gzlong)));
         if ((rc = sl.d_gzlong.ensure((cap_n + 64) * 4))) return rc;
-        HIPCHK(hipMemsetAsync(sl.d_gzlong.p, 0, n * 4, s->stream0));  // 0: not sized (yet)
-        HIPCHK(hipMemsetAsync(sl.d_gzlong.as<uint32_t>() + cap_n, 0, 64 * 4, s->stream0));
+        HIPCHK(hipMemsetAsync(sl.d_gzlong.p, 0, n * 4, s->q_copy));  // 0: not sized (yet)
+        HIPCHK(hipMemsetAsync(sl.d_gzlong.as<uint32_t>() + cap_n, 0, 64 * 4, s->q_copy));
     }
     // one k_gzip_long launch
     auto launch_long = [&](hipStream_t st, DevBuf &scratch, uint32_t ctr, uint32_t filter, const uint32_t *index, uint32_t count) -> int {
@@ -388,7 +365,7 @@ static int submit_gzip_column(chn_stream *s, Slot &sl, const chn_batch *b, const
             return rc2;
         GzlArgs gl;
         std::memset(&gl, 0, sizeof gl);
-        gl.bases = bases; gl.nmask = nmask; gl.off1 = off1; gl.off2 = off2; gl.len1 = sl.len1; gl.len2 = sl.len2; gl.n_bases = b->n_bases;
+        gl.bases = db.bases; gl.nmask = db.nmask; gl.off1 = db.off1; gl.off2 = db.off2; gl.len1 = sl.len1; gl.len2 = sl.len2; gl.n_bases = db.n_bases;
         gl.bound = long_bound; gl.short_max = bound; gl.filter = filter; gl.tallies = sl.d_gzt.as<uint16_t>();
         gl.index = index; gl.count = count; gl.sizes = sl.d_gzlong.as<uint32_t>();
         gl.scratch = scratch.as<uint32_t>(); gl.counter = sl.d_gzlong.as<uint32_t>() + cap_n + ctr;
@@ -396,14 +373,14 @@ static int submit_gzip_column(chn_stream *s, Slot &sl, const chn_batch *b, const
         HIPCHK(hipGetLastError());
         return CHN_OK;
     };
-    HIPCHK(hipMemsetAsync(sl.d_gzt.p, 1, n * GZT_WORDS * 2, s->stream3));  // status word != 0: "not tallied" unless a launch says otherwise
+    HIPCHK(hipMemsetAsync(sl.d_gzt.p, 1, n * GZT_WORDS * 2, s->q_tally));  // status word != 0: "not tallied" unless a launch says otherwise
     GztArgs g;
     std::memset(&g, 0, sizeof g);
-    g.bases = bases; g.nmask = nmask; g.off1 = off1; g.off2 = off2; g.len1 = sl.len1; g.len2 = sl.len2;
-    g.n_reads = (uint32_t)n; g.out = sl.d_gzt.as<uint16_t>(); g.n_bases = b->n_bases;
+    g.bases = db.bases; g.nmask = db.nmask; g.off1 = db.off1; g.off2 = db.off2; g.len1 = sl.len1; g.len2 = sl.len2;
+    g.n_reads = (uint32_t)n; g.out = sl.d_gzt.as<uint16_t>(); g.n_bases = db.n_bases;
     // every launch of the batch takes its reads from a counter of its own
     if ((rc = sl.d_gzctr.ensure(32 * 4))) return rc;
-    HIPCHK(hipMemsetAsync(sl.d_gzctr.p, 0, 32 * 4, s->stream3));
+    HIPCHK(hipMemsetAsync(sl.d_gzctr.p, 0, 32 * 4, s->q_tally));
     uint32_t n_launch = 0;
     // one k_gzip_tally launch (LDS: half a byte per letter; scratch: 6 bytes per letter)
     auto launch = [&](const uint32_t *index, uint32_t count, uint32_t max_len) -> int {
@@ -421,91 +398,51 @@ static int submit_gzip_column(chn_stream *s, Slot &sl, const chn_batch *b, const
             return rc2;
         g.scratch = s->d_gzscratch.as<uint32_t>();
         g.counter = sl.d_gzctr.as<uint32_t>() + (n_launch++ & 31u);
-        gz_by_bits(bits, [&](auto B) { hipLaunchKernelGGL(k_gzip_tally<decltype(B)::value>, dim3(grid), dim3(WAVE), glds, s->stream3, g); });
+        gz_by_bits(bits, [&](auto B) { hipLaunchKernelGGL(k_gzip_tally<decltype(B)::value>, dim3(grid), dim3(WAVE), glds, s->q_tally, g); });
         HIPCHK(hipGetLastError());
         return CHN_OK;
     };
-    if (!b->on_device) {
-        // Counting sort of the read numbers by OCCUPANCY class: class w holds the reads of which w wavefronts fit a CU's LDS
-        // (2.5 bytes per letter); reads short enough for 16 and more share class 16.  One launch per class in use, its LDS sized
-        // for the longest read of the class in this batch -- few launches with many reads each (512-letter classes left a
-        // long-read batch with some 90 launches of 30 reads on a 256-CU device).
-        const uint32_t NCLS = 17;  // classes 1 .. 16 (0 unused)
-        const size_t lds_cu = (size_t)160 * 1024;
-        uint32_t start[NCLS + 1], cmax[NCLS];
-        std::memset(start, 0, sizeof start);
-        std::memset(cmax, 0, sizeof cmax);
-        auto cls_of = [&](uint64_t i, uint32_t &L32) -> uint32_t {
-            const uint64_t L = (uint64_t)b->seg1_length[i] + (paired ? b->seg2_length[i] : 0);
-            if (L == 0 || L > bound) return NCLS;
-            L32 = (uint32_t)L;
-            return (uint32_t)std::min<size_t>(16, std::max<size_t>(1, lds_cu / gzt_lds_bytes(L32, bits)));
-        };
-        for (uint64_t i = 0; i < n; ++i) { uint32_t L = 0; const uint32_t c = cls_of(i, L); if (c < NCLS) { ++start[c + 1]; cmax[c] = std::max(cmax[c], L); } }
-        for (uint32_t c = 0; c < NCLS; ++c) start[c + 1] += start[c];
-        sl.h_gzidx.resize(start[NCLS]);
-        {
-            uint32_t fill[NCLS];
-            std::memcpy(fill, start, sizeof fill);
-            for (uint64_t i = 0; i < n; ++i) { uint32_t L = 0; const uint32_t c = cls_of(i, L); if (c < NCLS) sl.h_gzidx[fill[c]++] = (uint32_t)i; }
-        }
-        // CHN_GZIP_SIZES_ALL: behind the class lists, the reads beyond GZT_MAX_LEN (longest first), then the tallied reads long
-        // enough to reach a second deflate block (at least GZT_SYMBOL_LIMIT letters)
-        const size_t long_at = sl.h_gzidx.size();
-        size_t rerun_at = long_at;
-        if (all_sizes) {
-            for (uint64_t i = 0; i < n; ++i) {
-                const uint64_t L = (uint64_t)b->seg1_length[i] + (paired ? b->seg2_length[i] : 0);
-                if (L > GZT_MAX_LEN && L <= long_bound && L <= GZL_MAX_READ) sl.h_gzidx.push_back((uint32_t)i);
-            }
-            std::sort(sl.h_gzidx.begin() + long_at, sl.h_gzidx.end(), [&](uint32_t x, uint32_t y) {
-                const uint64_t lx = (uint64_t)b->seg1_length[x] + (paired ? b->seg2_length[x] : 0), ly = (uint64_t)b->seg1_length[y] + (paired ? b->seg2_length[y] : 0);
-                return lx != ly ? lx > ly : x < y;
-            });
-            rerun_at = sl.h_gzidx.size();
-            for (size_t j = 0; j < long_at; ++j) {
-                const uint32_t i = sl.h_gzidx[j];
-                if ((uint64_t)b->seg1_length[i] + (paired ? b->seg2_length[i] : 0) >= GZT_SYMBOL_LIMIT) sl.h_gzidx.push_back(i);
-            }
-        }
+    if (!db.on_device) {
+        const GzPlan p = gz_plan(sl.h_len1.data(), db.paired ? sl.h_len2.data() : nullptr, n, bits, bound, long_bound, all_sizes, sl.h_gzidx);
         // (on the copy stream: a pageable upload on the tally stream would wait for the previous batch's tally kernels)
-        if ((rc = upload(sl.d_gzidx, sl.h_gzidx.data(), sl.h_gzidx.size() * 4, s->stream0, (size_t)s->cfg.max_reads * 4 * (all_sizes ? 2 : 1)))) return rc;
-        HIPCHK(hipEventRecord(sl.bases_up, s->stream0));
-        HIPCHK(hipStreamWaitEvent(s->stream3, sl.bases_up, 0));
-        if (all_sizes && rerun_at > long_at) {
-            HIPCHK(hipStreamWaitEvent(s->stream5, sl.bases_up, 0));
-            if ((rc = launch_long(s->stream5, s->d_gzlscratch[0], 0, GZL_ALL, sl.d_gzidx.as<uint32_t>() + long_at, (uint32_t)(rerun_at - long_at)))) return rc;
+        if ((rc = upload(sl.d_gzidx, sl.h_gzidx.data(), sl.h_gzidx.size() * 4, s->q_copy, (size_t)s->cfg.max_reads * 4 * (all_sizes ? 2 : 1)))) return rc;
+        HIPCHK(hipEventRecord(sl.bases_up, s->q_copy));
+        HIPCHK(hipStreamWaitEvent(s->q_tally, sl.bases_up, 0));
+        const uint32_t *d_index = sl.d_gzidx.as<uint32_t>();
+        if (all_sizes && p.rerun_at > p.long_at) {
+            HIPCHK(hipStreamWaitEvent(s->q_gzlong, sl.bases_up, 0));
+            if ((rc = launch_long(s->q_gzlong, s->d_gzlscratch[0], 0, GZL_ALL, d_index + p.long_at, (uint32_t)(p.rerun_at - p.long_at)))) return rc;
             long_launch = true;
         }
-        for (uint32_t c = 1; c < NCLS; ++c)  // longest first: the slow, low-occupancy launches start early
-            if ((rc = launch(sl.d_gzidx.as<uint32_t>() + start[c], start[c + 1] - start[c], cmax[c]))) return rc;
-        if (all_sizes && (rc = launch_long(s->stream3, s->d_gzlscratch[1], 1, GZL_HANDED_BACK, sl.d_gzidx.as<uint32_t>() + rerun_at, (uint32_t)(sl.h_gzidx.size() - rerun_at)))) return rc;
+        for (uint32_t c = 1; c < GZ_NCLS; ++c)  // longest first: the slow, low-occupancy launches start early
+            if ((rc = launch(d_index + p.start[c], p.start[c + 1] - p.start[c], p.cmax[c]))) return rc;
+        if (all_sizes && (rc = launch_long(s->q_tally, s->d_gzlscratch[1], 1, GZL_HANDED_BACK, d_index + p.rerun_at, (uint32_t)(sl.h_gzidx.size() - p.rerun_at)))) return rc;
     } else {
-        HIPCHK(hipEventRecord(sl.bases_up, s->stream0));
-        HIPCHK(hipStreamWaitEvent(s->stream3, sl.bases_up, 0));
+        HIPCHK(hipEventRecord(sl.bases_up, s->q_copy));
+        HIPCHK(hipStreamWaitEvent(s->q_tally, sl.bases_up, 0));
         if ((rc = launch(nullptr, (uint32_t)n, bound))) return rc;
     }
-    // where the sizes are formed and downloaded: behind the tallies on stream3, or -- with a long-read launch -- on stream5 behind both,
-    // so that the next batch's tally launches on stream3 do not queue behind this batch's longest read
-    hipStream_t zs = s->stream3;
+    // where the sizes are formed and downloaded: behind the tallies on the tally stream, or -- with a long-read launch -- on the long-gzip
+    // stream behind both, so that the next batch's tally launches do not queue behind this batch's longest read
+    hipStream_t zs = s->q_tally;
     if (long_launch) {
-        HIPCHK(hipEventRecord(sl.gzt_done, s->stream3));
-        HIPCHK(hipStreamWaitEvent(s->stream5, sl.gzt_done, 0));
-        zs = s->stream5;
+        HIPCHK(hipEventRecord(sl.gzt_done, s->q_tally));
+        HIPCHK(hipStreamWaitEvent(s->q_gzlong, sl.gzt_done, 0));
+        zs = s->q_gzlong;
     }
     if (sl.gz_output != CHN_GZIP_TALLIES) {  // the sizes from the tallies, one lane per read
         if ((rc = sl.d_gzsize.ensure((size_t)s->cfg.max_reads * 4))) return rc;
         GzSizeArgs gs;
         gs.tallies = sl.d_gzt.as<uint16_t>(); gs.len1 = sl.len1; gs.len2 = sl.len2; gs.n_reads = (uint32_t)n; gs.sizes = sl.d_gzsize.as<uint32_t>();
         gs.long_sizes = all_sizes ? sl.d_gzlong.as<uint32_t>() : nullptr;  // k_gzip_long's sizes fill in where the tallies hand a read back
-        hipLaunchKernelGGL(k_gzip_size, dim3((uint32_t)((n + WAVE - 1) / WAVE)), dim3(WAVE), 0, zs, gs);
+        hipLaunchKernelGGL(k_gzip_size, dim3((uint32_t)waves_of(n)), dim3(WAVE), 0, zs, gs);
         HIPCHK(hipGetLastError());
     }
     sl.gz_staged = false;
-    if (!b->on_device) {
+    if (!db.on_device) {
         if (sl.gz_output == CHN_GZIP_TALLIES || sl.gz_output == CHN_GZIP_BOTH) {
             if ((rc = sl.h_gzt.ensure(n * GZT_WORDS * 2))) return rc;
-            HIPCHK(hipMemcpyAsync(sl.h_gzt.p, sl.d_gzt.p, n * GZT_WORDS * 2, hipMemcpyDeviceToHost, s->stream3));
+            HIPCHK(hipMemcpyAsync(sl.h_gzt.p, sl.d_gzt.p, n * GZT_WORDS * 2, hipMemcpyDeviceToHost, s->q_tally));
         }
         if (sl.gz_output != CHN_GZIP_TALLIES) {
             if ((rc = sl.h_gzsize.ensure(n * 4))) return rc;
@@ -517,14 +454,19 @@ static int submit_gzip_column(chn_stream *s, Slot &sl, const chn_batch *b, const
     return CHN_OK;
 }
 
+// ---- a batch's submit, stage by stage (submit_impl below is the driver) ----
 // list_kind != 0: stop after logging the minimiser VALUES -- LIST_DENSE (dense row-sharded mode, chn_minimisers: deterministic
 // worst-case layout on s->big) or LIST_SPARSE (sparse row-sharded mode: density-sized regions claimed from the cursor on s->shx);
 // 0: the whole chain
 enum { LIST_NONE = 0, LIST_DENSE = 1, LIST_SPARSE = 2 };
-// born_on_device: a text batch (abi_text_batch.inc) -- a host batch whose bases, N mask, layout and mean quality k_text_pack has
-// already written into the slot's buffers (b->bases2 / nmask only say which of them exist, b->mean_quality is the host copy)
-static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind, bool born_on_device = false) {
-    const bool list_mode = list_kind != LIST_NONE;
+// which caller launch_tail serves: a batch's own tail on the side stream, or the synchronous re-run after a row-log overflow on the
+// first probe stream (no profiling, no result download, no `done` event: chn_batch_wait is already past them)
+enum TailFor { TAIL_BATCH, TAIL_RERUN };
+// count (general layouts) + model/call + byte counter; closes the batch in slot `sl`
+static int launch_tail(chn_stream *s, Slot &sl, LogBuf &lb, TailFor who);
+
+// Stage 1: is this a batch the stream can take now?  Nothing is queued before it has passed (the stream's device is selected).
+static int check_batch(const chn_stream *s, const chn_batch *b, bool list_mode) {
     if (!s || !b || b->struct_size != sizeof(chn_batch)) return fail(CHN_E_INVALID, "chn_batch_submit: bad argument");
     if (!list_mode && (s->idx->d.row_begin != 0 || s->idx->d.row_end != s->idx->d.bin_size))
         return fail(CHN_E_INVALID, "chn_batch_submit needs an index object holding all rows; use the chn_shard_* calls with a row shard");
@@ -535,139 +477,166 @@ static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind, bool bo
     if (!b->bases2 || !b->seg1_offset || !b->seg1_length) return fail(CHN_E_INVALID, "missing batch arrays");
     if ((b->seg2_offset == nullptr) != (b->seg2_length == nullptr)) return fail(CHN_E_INVALID, "seg2_offset/seg2_length must both be set or both NULL");
     if (b->n_bases % 64) return fail(CHN_E_INVALID, "n_bases must be a multiple of 64");
-    const chn_index_desc &d = s->idx->d;
-    HIPCHK(hipSetDevice(d.device));
-    const uint64_t n = b->n_reads;
+    HIPCHK(hipSetDevice(s->idx->d.device));
+    return CHN_OK;
+}
+// ... and, for a host batch, the shapes of its operands before anything is launched (device batches are validated by the kernel itself)
+static int check_segments(const chn_batch *b) {
+    if (b->on_device) return CHN_OK;
     const bool paired = b->seg2_offset != nullptr;
-    const uint32_t W = (uint32_t)d.bin_words, C = d.num_categories;
-    const bool fused = !list_mode && s->idx->single_bin_categories && C <= 8 && W == 1;
-    Slot &sl = s->slot[s->head];
-    static const bool diag_sub = diag_env("CHN_DIAG_SUBMIT") != nullptr;
-    auto dnow = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double dt[6] = {dnow(), 0, 0, 0, 0, 0};
+    for (uint64_t i = 0; i < b->n_reads; ++i) {
+        const uint64_t o1 = b->seg1_offset[i], l1 = b->seg1_length[i];
+        if ((o1 & 63) || o1 + l1 > b->n_bases) return fail(CHN_E_INVALID, "segment 1 of read " + std::to_string(i) + " is misaligned or out of range");
+        if (paired) {
+            const uint64_t o2 = b->seg2_offset[i], l2 = b->seg2_length[i];
+            if ((o2 & 63) || o2 + l2 > b->n_bases) return fail(CHN_E_INVALID, "segment 2 of read " + std::to_string(i) + " is misaligned or out of range");
+        }
+    }
+    return CHN_OK;
+}
+
+// Stage 2: the batch's inputs where the kernels read them.  A host batch is uploaded into the slot's staging on the COPY stream (the
+// probe stream waits on the slot's `uploaded` event, stage 5) and its small columns are kept on the host for chn_batch_wait; the slot's
+// previous batch was waited for before this submit could happen (at most N_SLOTS batches in flight), so its staging is free.
+// born_on_device: a text batch (abi_text_batch.inc) -- a host batch whose bases, N mask, layout and mean quality k_text_pack has
+// already written into the slot's buffers (b->bases2 / nmask only say which of them exist, b->mean_quality is the host copy).
+// A device batch stays where the caller has it.
+static int stage_inputs(chn_stream *s, Slot &sl, const chn_batch *b, bool born_on_device, DevBatch &db) {
+    const uint64_t n = b->n_reads;
+    db.n = n; db.n_bases = b->n_bases; db.paired = b->seg2_offset != nullptr; db.on_device = b->on_device != 0;
     sl.host_batch = !b->on_device;
     sl.is_text = born_on_device;
-    sl.fused = fused; sl.list_mode = list_mode;
-    const uint32_t *bases, *nmask;
-    const uint64_t *off1, *off2;
-    if (!b->on_device) {
-        // host-side validation of operand shapes before anything is launched (device batches are validated by the kernel itself)
-        for (uint64_t i = 0; i < n; ++i) {
-            const uint64_t o1 = b->seg1_offset[i], l1 = b->seg1_length[i];
-            if ((o1 & 63) || o1 + l1 > b->n_bases) return fail(CHN_E_INVALID, "segment 1 of read " + std::to_string(i) + " is misaligned or out of range");
-            if (paired) {
-                const uint64_t o2 = b->seg2_offset[i], l2 = b->seg2_length[i];
-                if ((o2 & 63) || o2 + l2 > b->n_bases) return fail(CHN_E_INVALID, "segment 2 of read " + std::to_string(i) + " is misaligned or out of range");
-            }
-        }
-        int rc;
-        // uploads go through the copy stream; the compute stream waits on the slot's event.  The slot's previous batch was
-        // waited for before this submit could happen (at most N_SLOTS batches in flight), so its staging is free.
-        hipStream_t cs = s->stream0;
-        const size_t cap_b = (size_t)s->cfg.max_bases, cap_n = (size_t)s->cfg.max_reads;
-        if (!born_on_device) {
-            if ((rc = upload(sl.d_bases, b->bases2, b->n_bases / 4, cs, cap_b / 4))) return rc;
-            if (b->nmask && (rc = upload(sl.d_nmask, b->nmask, b->n_bases / 8, cs, cap_b / 8))) return rc;
-            if ((rc = upload(sl.d_off1, b->seg1_offset, n * 8, cs, cap_n * 8)) || (rc = upload(sl.d_len1, b->seg1_length, n * 4, cs, cap_n * 4))) return rc;
-            if (paired && ((rc = upload(sl.d_off2, b->seg2_offset, n * 8, cs, cap_n * 8)) || (rc = upload(sl.d_len2, b->seg2_length, n * 4, cs, cap_n * 4)))) return rc;
-            if (b->mean_quality && (rc = upload(sl.d_mq, b->mean_quality, n * 4, cs, cap_n * 4))) return rc;
-        }
-        if (b->compression && (rc = upload(sl.d_comp, b->compression, n * 4, cs, cap_n * 4))) return rc;
-        bases = sl.d_bases.as<uint32_t>();
-        nmask = b->nmask ? sl.d_nmask.as<uint32_t>() : nullptr;
-        off1 = sl.d_off1.as<uint64_t>(); sl.len1 = sl.d_len1.as<uint32_t>();
-        off2 = paired ? sl.d_off2.as<uint64_t>() : nullptr; sl.len2 = paired ? sl.d_len2.as<uint32_t>() : nullptr;
-        sl.mq = b->mean_quality ? sl.d_mq.as<float>() : nullptr;
-        sl.comp = b->compression ? sl.d_comp.as<float>() : nullptr;
-        sl.h_len1.assign(b->seg1_length, b->seg1_length + n);
-        if (paired) sl.h_len2.assign(b->seg2_length, b->seg2_length + n); else sl.h_len2.clear();
-        if (b->mean_quality) sl.h_mq.assign(b->mean_quality, b->mean_quality + n); else sl.h_mq.clear();
-        if (b->compression) sl.h_comp.assign(b->compression, b->compression + n); else sl.h_comp.clear();
-    } else {
-        bases = b->bases2; nmask = b->nmask; off1 = b->seg1_offset; sl.len1 = b->seg1_length;
-        off2 = b->seg2_offset; sl.len2 = b->seg2_length; sl.mq = b->mean_quality; sl.comp = b->compression;
-    }
     sl.n_reads = n;
-    dt[1] = dnow();
-    const bool prof = (s->cfg.flags & CHN_STREAM_PROFILE) != 0;
-    for (int i = 0; i < 4; ++i) sl.ev_used[i] = false;
-    // This batch's probe stream: the ordinary launch and everything that brackets it.  The list modes run with nothing in flight and keep
-    // to the first.  So do the batches of a caller whose reads are long enough for the SPLIT launch (judged by the batch waited for last:
-    // a front end's length distribution does not change from batch to batch): there the SPLIT launches carry most of the bases, the
-    // length order already fills the ordinary grid's tail with its shortest reads, and a second ordinary grid beside them measured
-    // 1 - 2 % SLOWER (DESIGN section 5).  Diagnostics builds: CHN_PROBE_STREAMS=1 puts every batch on the first stream (the schedule
-    // before there were two), CHN_PROBE_STREAMS=2 alternates whatever the reads.
+    if (b->on_device) {
+        db.bases = b->bases2; db.nmask = b->nmask; db.off1 = b->seg1_offset; sl.len1 = b->seg1_length;
+        db.off2 = b->seg2_offset; sl.len2 = b->seg2_length; sl.mq = b->mean_quality; sl.comp = b->compression;
+        return CHN_OK;
+    }
+    int rc;
+    const bool paired = db.paired;
+    const size_t cap_b = (size_t)s->cfg.max_bases, cap_n = (size_t)s->cfg.max_reads;
+    if (!born_on_device) {
+        if ((rc = upload(sl.d_bases, b->bases2, b->n_bases / 4, s->q_copy, cap_b / 4))) return rc;
+        if (b->nmask && (rc = upload(sl.d_nmask, b->nmask, b->n_bases / 8, s->q_copy, cap_b / 8))) return rc;
+        if ((rc = upload(sl.d_off1, b->seg1_offset, n * 8, s->q_copy, cap_n * 8)) || (rc = upload(sl.d_len1, b->seg1_length, n * 4, s->q_copy, cap_n * 4))) return rc;
+        if (paired && ((rc = upload(sl.d_off2, b->seg2_offset, n * 8, s->q_copy, cap_n * 8)) || (rc = upload(sl.d_len2, b->seg2_length, n * 4, s->q_copy, cap_n * 4)))) return rc;
+        if (b->mean_quality && (rc = upload(sl.d_mq, b->mean_quality, n * 4, s->q_copy, cap_n * 4))) return rc;
+    }
+    if (b->compression && (rc = upload(sl.d_comp, b->compression, n * 4, s->q_copy, cap_n * 4))) return rc;
+    db.bases = sl.d_bases.as<uint32_t>();
+    db.nmask = b->nmask ? sl.d_nmask.as<uint32_t>() : nullptr;
+    db.off1 = sl.d_off1.as<uint64_t>(); sl.len1 = sl.d_len1.as<uint32_t>();
+    db.off2 = paired ? sl.d_off2.as<uint64_t>() : nullptr; sl.len2 = paired ? sl.d_len2.as<uint32_t>() : nullptr;
+    sl.mq = b->mean_quality ? sl.d_mq.as<float>() : nullptr;
+    sl.comp = b->compression ? sl.d_comp.as<float>() : nullptr;
+    sl.h_len1.assign(b->seg1_length, b->seg1_length + n);
+    if (paired) sl.h_len2.assign(b->seg2_length, b->seg2_length + n); else sl.h_len2.clear();
+    if (b->mean_quality) sl.h_mq.assign(b->mean_quality, b->mean_quality + n); else sl.h_mq.clear();
+    if (b->compression) sl.h_comp.assign(b->compression, b->compression + n); else sl.h_comp.clear();
+    return CHN_OK;
+}
+
+// Stage 3: this batch's PROBE stream -- the ordinary launch and everything that brackets it.  The list modes run with nothing in flight
+// and keep to the first.  So do the batches of a caller whose reads are long enough for the SPLIT launch (judged by the batch waited for
+// last: a front end's length distribution does not change from batch to batch): there the SPLIT launches carry most of the bases, the
+// length order already fills the ordinary grid's tail with its shortest reads, and a second ordinary grid beside them measured
+// 1 - 2 % SLOWER (DESIGN section 5).  Diagnostics builds: CHN_PROBE_STREAMS=1 puts every batch on the first stream (the schedule
+// before there were two), CHN_PROBE_STREAMS=2 alternates whatever the reads.
+// Profiling streams: the chain's bracket opens on it, behind a fresh time anchor where the old one has aged.
+struct ProbeStream { hipStream_t q; bool alternate; };
+static int pick_probe_stream(chn_stream *s, Slot &sl, bool prof, ProbeStream &ps) {
     static const int probe_streams = [] { const char *v = diag_env("CHN_PROBE_STREAMS"); return v ? std::atoi(v) : 0; }();
-    const bool alternate = probe_streams == 2 || (probe_streams != 1 && !s->last_had_long);
-    const hipStream_t ps = list_mode || !alternate || !(s->batch_seq & 1) ? s->stream : s->stream1;
+    ps.alternate = probe_streams == 2 || (probe_streams != 1 && !s->last_had_long);
+    ps.q = s->q_probe[sl.list_mode || !ps.alternate ? 0 : s->batch_seq & 1];
+    for (EvBracket *t : {&sl.t_probe, &sl.t_count, &sl.t_model, &sl.t_chain}) t->used = false;
     if (sl.new_anchor) { sl.new_anchor = false; s->prof_anchor_pending = false; }  // (left by a submit that failed half-way)
     if (prof) {
         // nothing in flight and the time anchor is old (the caller paused): a fresh one, or this batch's times would be floats of the
-        // milliseconds since before the pause (the anchor otherwise only moves on behind a running batch, below)
+        // milliseconds since before the pause (the anchor otherwise only moves on behind a running batch, launch_probe)
         if (s->inflight == 0 && std::chrono::steady_clock::now() - s->prof_anchor_at > std::chrono::seconds(PROF_ANCHOR_SECONDS)) HIPCHK(prof_anchor_now(s));
-        HIPCHK(hipEventRecord(sl.ev[6], ps));
+        HIPCHK(hipEventRecord(sl.t_chain.begin, ps.q));
     }
+    return CHN_OK;
+}
 
-    // 0. deflate tallies for the gzip column, if asked for: their own stream, as soon as the bases are on the device
-    if (int rc = submit_gzip_column(s, sl, b, bases, nmask, off1, off2, n, paired)) return rc;
+// (stage 4, the gzip column, is submit_gzip_column above: the TALLY stream, and the LONG-GZIP stream, behind the uploads on the copy stream)
 
-    dt[2] = dnow();
-    // 1. length-class ordering: two launches (the first also clears the slot's control words).  They run on the copy stream, behind
-    // this batch's uploads and beside the previous batch's minimise+probe kernel (they depend on neither), so that a small batch's
-    // critical path is just that kernel; the compute stream picks up at the event.
+// Stage 5: length-class ordering, two launches (the first also clears the slot's control words).  They run on the COPY stream, behind
+// this batch's uploads and beside the previous batch's minimise+probe kernel (they depend on neither), so that a small batch's
+// critical path is just that kernel; the probe stream picks up at the slot's `uploaded` event.
+static int order_reads(chn_stream *s, Slot &sl, const DevBatch &db, hipStream_t probe_q) {
     unsigned long long *ctl = sl.d_ctl.as<unsigned long long>();
-    hipLaunchKernelGGL(k_len_hist, dim3(LEN_BLOCKS), dim3(256), 0, s->stream0, sl.len1, sl.len2, (uint32_t)n, s->d_hist.as<uint32_t>(), ctl);
+    hipLaunchKernelGGL(k_len_hist, dim3(LEN_BLOCKS), dim3(256), 0, s->q_copy, sl.len1, sl.len2, (uint32_t)db.n, s->d_hist.as<uint32_t>(), ctl);
     // (list modes -- row-sharded chains, chn_minimisers -- never split a read: every rank must log the same entries in the same order)
-    sl.split_bound = list_mode ? 0u : split_bound(s, sl, n, b->n_bases, paired);
-    hipLaunchKernelGGL(k_len_scatter, dim3(LEN_BLOCKS), dim3(256), 0, s->stream0, sl.len1, sl.len2, (uint32_t)n, s->d_hist.as<uint32_t>(), sl.d_order.as<uint32_t>(),
+    sl.split_bound = sl.list_mode ? 0u : split_bound(s->long_bucket, db.paired, sl.host_batch ? &sl.h_len1 : nullptr, db.n);
+    hipLaunchKernelGGL(k_len_scatter, dim3(LEN_BLOCKS), dim3(256), 0, s->q_copy, sl.len1, sl.len2, (uint32_t)db.n, s->d_hist.as<uint32_t>(), sl.d_order.as<uint32_t>(),
                        ctl, sl.split_bound ? s->long_bucket : 256u, sl.split_bound);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(sl.uploaded, s->stream0));
-    HIPCHK(hipStreamWaitEvent(ps, sl.uploaded, 0));
+    HIPCHK(hipEventRecord(sl.uploaded, s->q_copy));
+    HIPCHK(hipStreamWaitEvent(probe_q, sl.uploaded, 0));
+    return CHN_OK;
+}
 
-    // 2. minimise + probe
-    K1Args &a = sl.k1;
+// Stage 6: the probe kernel's arguments from the index and the slot (kept in the slot: a re-run after a log overflow starts from them).
+// The row log, the probe gate and the chain flag are not set here: fill_k1_log, launch_probe.
+static void fill_k1(K1Args &a, const chn_index *idx, Slot &sl, const DevBatch &db) {
+    const chn_index_desc &d = idx->d;
+    unsigned long long *ctl = sl.d_ctl.as<unsigned long long>();
     std::memset(&a, 0, sizeof(a));
-    a.words = s->idx->words; a.S = d.bin_size; a.row_begin = d.row_begin; a.row_end = d.row_end; a.seed = d.minimiser_seed; a.powk1 = pow5(d.kmer_size - 1);
+    a.words = idx->words; a.S = d.bin_size; a.row_begin = d.row_begin; a.row_end = d.row_end; a.seed = d.minimiser_seed; a.powk1 = pow5(d.kmer_size - 1);
     a.shift = (uint32_t)d.hash_shift; a.h = d.hash_funs; a.k = d.kmer_size; a.wn = d.window_size - d.kmer_size + 1;
-    a.n_reads = (uint32_t)n; a.nseg = paired ? 2 : 1; a.B = (uint32_t)d.bins; a.C = C;
-    a.pack = ring_pack_ok(a.k, a.wn, a.seed) ? 1u : 0u;  // decided once here; k1_lds_bytes below and the launch follow it
+    a.n_reads = (uint32_t)db.n; a.nseg = db.paired ? 2 : 1; a.B = (uint32_t)d.bins; a.C = d.num_categories;
+    a.pack = ring_pack_ok(a.k, a.wn, a.seed) ? 1u : 0u;  // decided once here; k1_lds_bytes and the launch follow it
     for (uint32_t bb = 0; bb < 8 && bb < d.bins; ++bb) a.b2c_packed |= (uint64_t)d.bin_to_category[bb] << (8 * bb);
-    a.bases = bases; a.nmask = nmask; a.off1 = off1; a.off2 = off2; a.len1 = sl.len1; a.len2 = sl.len2; a.n_bases = b->n_bases;
+    a.bases = db.bases; a.nmask = db.nmask; a.off1 = db.off1; a.off2 = db.off2; a.len1 = sl.len1; a.len2 = sl.len2; a.n_bases = db.n_bases;
     a.order = sl.d_order.as<uint32_t>();
     a.status = reinterpret_cast<uint32_t *>(ctl + CTL_STATUS);
     if (const char *ab = diag_env("CHN_ABLATE")) a.ablate = (uint32_t)std::atoi(ab);  // (diagnostics builds: skipping the row fetches gives wrong results by design)
-    a.nt_probes = s->idx->rows_local * d.bin_words * 8 > (4ULL << 30) ? 1u : 0u;
+    a.nt_probes = idx->rows_local * d.bin_words * 8 > (4ULL << 30) ? 1u : 0u;
     if (const char *nt = diag_env("CHN_NT_PROBES")) a.nt_probes = (uint32_t)std::atoi(nt);  // A/B diagnostic
     a.num_hashes = sl.d_num_hashes.as<uint32_t>(); a.counts = sl.d_counts.as<uint32_t>(); a.unique = sl.d_unique.as<uint32_t>();
-    const uint32_t n_waves = (uint32_t)((n + WAVE - 1) / WAVE);
-    a.n_long_ptr = sl.split_bound ? ctl + CTL_NLONG : nullptr; a.wave_slot0 = n_waves;
+    a.n_long_ptr = sl.split_bound ? ctl + CTL_NLONG : nullptr; a.wave_slot0 = (uint32_t)waves_of(db.n);
     a.fetches = ctl + CTL_FETCHES;
+}
+static void fill_k1_log(K1Args &a, Slot &sl, LogBuf &lb, bool dynamic) {
+    a.rowlog = lb.log.as<uint32_t>(); a.rows = lb.rows.as<uint64_t>(); a.wave_meta = lb.meta.as<WaveMeta>(); a.wave_count = lb.wcount.as<uint32_t>();
+    a.log_capacity = lb.log_cap; a.esc_capacity = lb.esc_cap; a.cap_num = lb.cap_num; a.esc_shift = lb.esc_shift;
+    a.cursor = dynamic ? sl.d_ctl.as<unsigned long long>() + CTL_LOG_CURSOR : nullptr;
+}
+// ... and where the kernel logs: the slot's own row log (general layouts), or for the list modes the minimiser values on the stream's
+// buffers -- LIST_DENSE with its region table laid out on the probe stream first
+static int choose_log(chn_stream *s, Slot &sl, int list_kind, hipStream_t probe_q) {
+    K1Args &a = sl.k1;
     if (list_kind == LIST_SPARSE) {
         fill_k1_log(a, sl, s->shx, true);
         a.rows = s->d_list.as<uint64_t>();
-    } else if (list_mode) {
+    } else if (list_kind == LIST_DENSE) {
         // deterministic worst-case layout on the stream's big buffers (every rank of the dense row-sharded mode must log its
         // minimisers at the same positions)
         fill_k1_log(a, sl, s->big, false);
         a.rows = s->d_list.as<uint64_t>();
-        hipLaunchKernelGGL(k_wave_caps, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ps, sl.d_order.as<uint32_t>(), sl.len1, sl.len2,
-                           (uint32_t)n, s->big.cap_num, s->big.esc_shift, s->big.meta.as<WaveMeta>());
-        hipLaunchKernelGGL(k_scan_meta, dim3(1), dim3(1024), 0, ps, s->big.meta.as<WaveMeta>(), n_waves);
+        hipLaunchKernelGGL(k_wave_caps, dim3((uint32_t)((sl.n_reads + 255) / 256)), dim3(256), 0, probe_q, sl.d_order.as<uint32_t>(), sl.len1, sl.len2,
+                           (uint32_t)sl.n_reads, s->big.cap_num, s->big.esc_shift, s->big.meta.as<WaveMeta>());
+        hipLaunchKernelGGL(k_scan_meta, dim3(1), dim3(1024), 0, probe_q, s->big.meta.as<WaveMeta>(), (uint32_t)waves_of(sl.n_reads));
         HIPCHK(hipGetLastError());
-    } else if (!fused) {
+    } else if (!sl.fused) {
         fill_k1_log(a, sl, sl.lb, true);
     }
-    const int mode = list_mode ? MODE_LIST : fused ? MODE_FUSED : MODE_ROWS;
-    size_t lds = k1_lds_bytes(a.wn, C, mode, a.h, W, a.B, a.pack != 0);
-    if (const char *pad = diag_env("CHN_LDS_PAD")) lds += (size_t)std::atoi(pad);  // occupancy-sensitivity diagnostic
-    if (lds > 160 * 1024) return fail(CHN_E_INVALID, "window too large for LDS");
+    return CHN_OK;
+}
+
+// Stage 7: the probe kernel.  The long reads first, on the SPLIT stream; then, on the batch's PROBE stream, the gate wait, the ordinary
+// launch and (profiling streams) the end of its bracket and the stream's next time anchor.  gated: the launch takes part in the probe gate.
+static int launch_probe(chn_stream *s, Slot &sl, int mode, size_t lds, const ProbeStream &ps, bool prof, bool &gated) {
+    K1Args &a = sl.k1;
+    const uint32_t W = (uint32_t)s->idx->d.bin_words;
+    unsigned long long *ctl = sl.d_ctl.as<unsigned long long>();
     if (sl.split_bound) {
         // the long reads first, on a stream of their own: a few wavefronts that run beside the ordinary launch instead of holding it up
-        HIPCHK(hipStreamWaitEvent(s->stream4, sl.uploaded, 0));
-        hipError_t e4 = launch_k1_split_mode(mode, W, a, lds, s->stream4, split_grid(sl.split_bound));
+        HIPCHK(hipStreamWaitEvent(s->q_split, sl.uploaded, 0));
+        hipError_t e4 = launch_k1(mode, W, a, lds, s->q_split, split_grid(sl.split_bound));
         if (e4 != hipSuccess) return fail(CHN_E_HIP, std::string("k_minimise_probe (split) launch: ") + hipGetErrorString(e4));
-        HIPCHK(hipEventRecord(sl.split_done, s->stream4));
+        HIPCHK(hipEventRecord(sl.split_done, s->q_split));
     }
     // The probe gate.  A batch that alternates no longer starts beside its predecessor's grid for that grid's whole life (both then run at
     // half speed for twice as long, and the predecessor's side kernels starve under two grids): its launch waits, in its queue and not on a
@@ -675,61 +644,100 @@ static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind, bool bo
     // queues behind batch i - 2 by stream order.  The value waited for is the last one whose writers (the grid, and k_gate_release behind
     // it) are already enqueued: batches that launch no gated grid -- list modes, long-read batches on the first stream, re-runs --
     // write nothing and use up no value, and this batch's own value counts only once its launch has succeeded.
-    const bool gated = !list_mode && alternate && s->gate_signal != nullptr;
+    gated = !sl.list_mode && ps.alternate && s->gate_signal != nullptr;
     if (gated) {
         if (s->gate_seq) {
-            HIPCHK(hipStreamWaitValue64(ps, s->gate_signal, s->gate_seq, hipStreamWaitValueGte, ~0ull));
+            HIPCHK(hipStreamWaitValue64(ps.q, s->gate_signal, s->gate_seq, hipStreamWaitValueGte, ~0ull));
             s->gated_batches += 1;
         }
         a.gate_started = ctl + CTL_GATE; a.gate_signal = s->gate_signal; a.gate_value = s->gate_seq + 1;
     }
-    if (prof) { HIPCHK(hipEventRecord(sl.ev[0], ps)); }
+    if (prof) { HIPCHK(hipEventRecord(sl.t_probe.begin, ps.q)); }
     // Chained row-log entries (rowlog_entry.hpp): the ordinary launch of a whole-index MODE_ROWS batch only.  The SPLIT launch above went
     // out unchained (k_count_longlog reads its logs), the list modes never chain, and a re-run after an overflow clears the flag again.
     a.chain = (mode == MODE_ROWS && rowlog_chain_ok(a.B)) ? 1u : 0u;
-    hipError_t e = launch_k1_mode(mode, W, a, lds, ps);
+    hipError_t e = launch_k1(mode, W, a, lds, ps.q);
     if (e != hipSuccess) return fail(CHN_E_HIP, std::string("k_minimise_probe launch: ") + hipGetErrorString(e));
     if (gated) s->gate_seq += 1;
     if (prof) {
         // (profiling streams: the probe kernel's time is the time until BOTH its launches are done -- with long reads in the batch the SPLIT launch may
         //  carry most of the bases)
-        if (sl.split_bound) HIPCHK(hipStreamWaitEvent(ps, sl.split_done, 0));
-        HIPCHK(hipEventRecord(sl.ev[1], ps)); sl.ev_used[0] = true;
+        if (sl.split_bound) HIPCHK(hipStreamWaitEvent(ps.q, sl.split_done, 0));
+        HIPCHK(hipEventRecord(sl.t_probe.end, ps.q)); sl.t_probe.used = true;
         // the stream's time anchor moves on every few seconds: the next one behind this kernel, in use from this batch's wait on
         if (!s->prof_anchor_pending && std::chrono::steady_clock::now() - s->prof_anchor_at > std::chrono::seconds(PROF_ANCHOR_SECONDS)) {
-            HIPCHK(hipEventRecord(s->prof_anchor[s->prof_cur ^ 1], ps));
+            HIPCHK(hipEventRecord(s->prof_anchor[s->prof_cur ^ 1], ps.q));
             s->prof_anchor_at = std::chrono::steady_clock::now();
             sl.new_anchor = s->prof_anchor_pending = true;
         }
     }
+    return CHN_OK;
+}
 
-    if (list_mode) return CHN_OK;  // the caller continues with chn_shard_probe / chn_shard_finish
-    dt[3] = dnow();
-    HIPCHK(hipEventRecord(sl.k1_done, ps));
-    HIPCHK(hipStreamWaitEvent(s->stream2, sl.k1_done, 0));
-    if (sl.split_bound) HIPCHK(hipStreamWaitEvent(s->stream2, sl.split_done, 0));
+// Stage 8: hand over to the tail.  The SIDE stream waits for both probe launches; behind the ordinary one, on the probe stream, the
+// gate's backstop; then count, model + call and the result download on the side stream (launch_tail).
+static int hand_over(chn_stream *s, Slot &sl, hipStream_t probe_q, bool gated) {
+    HIPCHK(hipEventRecord(sl.k1_done, probe_q));
+    HIPCHK(hipStreamWaitEvent(s->q_side, sl.k1_done, 0));
+    if (sl.split_bound) HIPCHK(hipStreamWaitEvent(s->q_side, sl.split_done, 0));
     if (gated) {  // the backstop: a grid that died still releases its successor (a max: the successor's grid may have written already)
-        hipLaunchKernelGGL(k_gate_release, dim3(1), dim3(1), 0, ps, s->gate_signal, (unsigned long long)s->gate_seq);
+        hipLaunchKernelGGL(k_gate_release, dim3(1), dim3(1), 0, probe_q, s->gate_signal, (unsigned long long)s->gate_seq);
         HIPCHK(hipGetLastError());
     }
-    int rc = launch_tail(s, sl, sl.lb, s->stream2);
-    if (rc) return rc;
+    return launch_tail(s, sl, sl.lb, TAIL_BATCH);
+}
+
+// The driver.  A stage that refuses leaves the slot not in flight: the next submit takes it again, and whatever was queued for it drains.
+static int submit_impl(chn_stream *s, const chn_batch *b, int list_kind, bool born_on_device = false) {
+    static const bool diag_sub = diag_env("CHN_DIAG_SUBMIT") != nullptr;
+    const bool list_mode = list_kind != LIST_NONE;
+    int rc;
+    if ((rc = check_batch(s, b, list_mode))) return rc;
+    const double t_start = wall_now();
+    if ((rc = check_segments(b))) return rc;
+    const chn_index_desc &d = s->idx->d;
+    const uint32_t W = (uint32_t)d.bin_words, C = d.num_categories;
+    const bool prof = (s->cfg.flags & CHN_STREAM_PROFILE) != 0;
+    Slot &sl = s->slot[s->head];
+    sl.list_mode = list_mode;
+    sl.fused = !list_mode && s->idx->single_bin_categories && C <= 8 && W == 1;
+    DevBatch db;
+    if ((rc = stage_inputs(s, sl, b, born_on_device, db))) return rc;
+    const double t_staged = wall_now();
+    ProbeStream ps;
+    if ((rc = pick_probe_stream(s, sl, prof, ps))) return rc;
+    if ((rc = submit_gzip_column(s, sl, db, b->gzip_tallies, b->gzip_output))) return rc;
+    const double t_gzip = wall_now();
+    if ((rc = order_reads(s, sl, db, ps.q))) return rc;
+    fill_k1(sl.k1, s->idx, sl, db);
+    if ((rc = choose_log(s, sl, list_kind, ps.q))) return rc;
+    const int mode = list_mode ? MODE_LIST : sl.fused ? MODE_FUSED : MODE_ROWS;
+    size_t lds = k1_lds_bytes(sl.k1.wn, C, mode, sl.k1.h, W, sl.k1.B, sl.k1.pack != 0);
+    if (const char *pad = diag_env("CHN_LDS_PAD")) lds += (size_t)std::atoi(pad);  // occupancy-sensitivity diagnostic
+    if (lds > 160 * 1024) return fail(CHN_E_INVALID, "window too large for LDS");
+    bool gated = false;
+    if ((rc = launch_probe(s, sl, mode, lds, ps, prof, gated))) return rc;
+    if (list_mode) return CHN_OK;  // the caller continues with chn_shard_probe / chn_shard_finish
+    const double t_probe = wall_now();
+    if ((rc = hand_over(s, sl, ps.q, gated))) return rc;
     if (diag_sub) std::fprintf(stderr, "submit: validate + uploads %.2f ms, deflate tallies %.2f, ordering + probe launch %.2f, tail %.2f\n",
-                               (dt[1] - dt[0]) * 1e3, (dt[2] - dt[1]) * 1e3, (dt[3] - dt[2]) * 1e3, (dnow() - dt[3]) * 1e3);
+                               (t_staged - t_start) * 1e3, (t_gzip - t_staged) * 1e3, (t_probe - t_gzip) * 1e3, (wall_now() - t_probe) * 1e3);
     s->head = (s->head + 1) % chn_stream::N_SLOTS;
     s->inflight += 1;
     s->batch_seq += 1;
     return CHN_OK;
 }
 
-
-// 3. counts from the row log (general bin layouts), 4. model + call (+ the algorithmic byte counter) -- on `st`
-static int launch_tail(chn_stream *s, Slot &sl, LogBuf &lb, hipStream_t st) {
+// 3. counts from the row log (general bin layouts), 4. model + call (+ the algorithmic byte counter): a batch's own tail on the side
+// stream, with its profiling brackets, the in-stream result download of a host batch and the slot's `done` event; a re-run's on the
+// first probe stream, with none of them
+static int launch_tail(chn_stream *s, Slot &sl, LogBuf &lb, TailFor who) {
     const chn_index_desc &d = s->idx->d;
+    const hipStream_t st = who == TAIL_BATCH ? s->q_side : s->q_probe[0];
     const uint64_t n = sl.n_reads;
     const uint32_t W = (uint32_t)d.bin_words, C = d.num_categories;
-    const uint32_t n_waves = (uint32_t)((n + WAVE - 1) / WAVE);
-    const bool prof = (s->cfg.flags & CHN_STREAM_PROFILE) != 0 && st == s->stream2;
+    const uint32_t n_waves = (uint32_t)waves_of(n);
+    const bool prof = (s->cfg.flags & CHN_STREAM_PROFILE) != 0 && who == TAIL_BATCH;
     unsigned long long *ctl = sl.d_ctl.as<unsigned long long>();
     if (!sl.fused) {
         K2Args k2;
@@ -746,31 +754,24 @@ static int launch_tail(chn_stream *s, Slot &sl, LogBuf &lb, hipStream_t st) {
         // owners per sweep as keep the tables within what the probe wavefronts of this stream's probe configuration leave of a CU's LDS
         // (k2_lds_budget, lds_budget.hpp), so that the kernel runs under the next batch's probe kernel
         const bool t16 = !sl.list_mode && sl.len2 == nullptr && s->long_bucket <= LONG_BUCKET_DEFAULT;
-        const uint32_t wn = d.window_size - d.kmer_size + 1;
-        const size_t probe_lds = k1_lds_bytes(wn, C, MODE_ROWS, d.hash_funs, W, (uint32_t)d.bins, ring_pack_ok(d.kmer_size, wn, d.minimiser_seed));
-        const uint32_t G = k2_group((uint32_t)d.bins, C, W, t16, k2_lds_budget(probe_lds));
+        const uint32_t G = k2_group((uint32_t)d.bins, C, W, t16, k2_lds_budget(k1_rows_lds(d)));
         k2.group = G;
         const size_t lds2 = k2_lds_bytes((uint32_t)d.bins, C, W, G, t16);
         if (lds2 > 150 * 1024) return fail(CHN_E_INVALID, "bins x categories too large for the count kernel's LDS");
-        const void *fn = t16 ? (W == 1 ? (const void *)k_count_wavelog<1, true> : W == 2 ? (const void *)k_count_wavelog<2, true> : W == 3 ? (const void *)k_count_wavelog<3, true> : (const void *)k_count_wavelog<4, true>)
-                             : (W == 1 ? (const void *)k_count_wavelog<1, false> : W == 2 ? (const void *)k_count_wavelog<2, false> : W == 3 ? (const void *)k_count_wavelog<3, false> : (const void *)k_count_wavelog<4, false>);
+        const void *fn = t16 ? by_words(W, [](auto w) { return (const void *)k_count_wavelog<decltype(w)::value, true>; })
+                             : by_words(W, [](auto w) { return (const void *)k_count_wavelog<decltype(w)::value, false>; });
         if (lds2 > 48 * 1024) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));  // opt in to large dynamic LDS
-        if (prof) HIPCHK(hipEventRecord(sl.ev[2], st));
+        if (prof) HIPCHK(hipEventRecord(sl.t_count.begin, st));
         {
             void *args[] = {(void *)&k2};
             HIPCHK(hipLaunchKernel(fn, grid, block, args, lds2, st));
         }
         if (k2.n_long_ptr) {  // the logs of the reads that were split over a wavefront: one read per log
             const dim3 lgrid(std::min<uint32_t>(sl.split_bound, 4096u)), lblock(K2L_THREADS);
-            switch (W) {
-                case 1: hipLaunchKernelGGL(k_count_longlog<1>, lgrid, lblock, 0, st, k2); break;
-                case 2: hipLaunchKernelGGL(k_count_longlog<2>, lgrid, lblock, 0, st, k2); break;
-                case 3: hipLaunchKernelGGL(k_count_longlog<3>, lgrid, lblock, 0, st, k2); break;
-                default: hipLaunchKernelGGL(k_count_longlog<4>, lgrid, lblock, 0, st, k2); break;
-            }
+            by_words(W, [&](auto w) { hipLaunchKernelGGL(k_count_longlog<decltype(w)::value>, lgrid, lblock, 0, st, k2); });
         }
         HIPCHK(hipGetLastError());
-        if (prof) { HIPCHK(hipEventRecord(sl.ev[3], st)); sl.ev_used[1] = true; }
+        if (prof) { HIPCHK(hipEventRecord(sl.t_count.end, st)); sl.t_count.used = true; }
     }
     sl.model_ran = s->model.set;
     const uint32_t hW8 = (uint32_t)(d.hash_funs * W * 8), outb = (uint32_t)(8 + 8 * C);
@@ -782,18 +783,19 @@ static int launch_tail(chn_stream *s, Slot &sl, LogBuf &lb, hipStream_t st) {
         k3.n_reads = (uint32_t)n;
         k3.acc = ctl + CTL_BYTES; k3.hW8 = hW8; k3.outb = outb;
         k3.open_compression_gate = sl.want_gzt ? 1u : 0u;
-        if (prof) HIPCHK(hipEventRecord(sl.ev[4], st));
+        if (prof) HIPCHK(hipEventRecord(sl.t_model.begin, st));
         hipLaunchKernelGGL(k_model_call, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, k3);
         HIPCHK(hipGetLastError());
-        if (prof) { HIPCHK(hipEventRecord(sl.ev[5], st)); sl.ev_used[2] = true; }
+        if (prof) { HIPCHK(hipEventRecord(sl.t_model.end, st)); sl.t_model.used = true; }
     } else {
         hipLaunchKernelGGL(k_batch_bytes, dim3((uint32_t)std::min<uint64_t>(1024, (n + 255) / 256)), dim3(256), 0, st, sl.len1, sl.len2,
                            sl.d_num_hashes.as<uint32_t>(), (uint32_t)n, hW8, outb, ctl + CTL_BYTES);
         HIPCHK(hipGetLastError());
     }
-    if (prof) { HIPCHK(hipEventRecord(sl.ev[7], st)); sl.ev_used[3] = true; }
+    if (prof) { HIPCHK(hipEventRecord(sl.t_chain.end, st)); sl.t_chain.used = true; }
     sl.staged = false;
-    if (st == s->stream2 && sl.host_batch) {
+    if (who == TAIL_RERUN) return CHN_OK;  // chn_batch_wait fetches the re-run's results from the device arrays
+    if (sl.host_batch) {
         const ResLayout L(n, C);
         int rc = sl.h_res.ensure(L.total);
         if (rc) return rc;
@@ -810,16 +812,16 @@ static int launch_tail(chn_stream *s, Slot &sl, LogBuf &lb, hipStream_t st) {
         }
         sl.staged = true;
     }
-    if (st == s->stream2) HIPCHK(hipEventRecord(sl.done, st));
+    HIPCHK(hipEventRecord(sl.done, st));
     return CHN_OK;
 }
 
 extern "C" int chn_batch_submit(chn_stream *s, const chn_batch *b) {
     static const bool diag = diag_env("CHN_DIAG_WAIT") != nullptr;
     if (!diag) return submit_impl(s, b, LIST_NONE);
-    const double t0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+    const double t0 = wall_now();
     const int rc = submit_impl(s, b, LIST_NONE);
-    const double t1 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+    const double t1 = wall_now();
     std::fprintf(stderr, "chn_batch_submit: at %.4f  %.2f ms\n", t0, (t1 - t0) * 1e3);
     return rc;
 }

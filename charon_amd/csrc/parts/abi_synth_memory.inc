@@ -74,12 +74,7 @@ extern "C" int chn_index_gather_roof(chn_index *idx, int nt, double *fetches_per
     iters = iters / 12 * 12;
     if (const char *e = diag_env("CHN_ROOF_MEMSET")) HIPCHK(hipMemset(idx->words, std::atoi(e), idx->rows_local * W * 8));  // diagnostic: DESTROYS the index content
     auto go = [&](uint32_t it) {
-        switch (W) {
-            case 1: launch_gather_roof<1>(nt, unroll, blocks, lds, idx->words, idx->rows_local, it, sink); break;
-            case 2: launch_gather_roof<2>(nt, unroll, blocks, lds, idx->words, idx->rows_local, it, sink); break;
-            case 3: launch_gather_roof<3>(nt, unroll, blocks, lds, idx->words, idx->rows_local, it, sink); break;
-            default: launch_gather_roof<4>(nt, unroll, blocks, lds, idx->words, idx->rows_local, it, sink); break;
-        }
+        by_words(W, [&](auto w) { launch_gather_roof<decltype(w)::value>(nt, unroll, blocks, lds, idx->words, idx->rows_local, it, sink); });
     };
     go(iters / 12 / 8 * 12 + 12);  // warm-up
     HIPCHK(hipEventRecord(a, 0));
@@ -130,7 +125,7 @@ extern "C" int chn_synth_plant(chn_index *idx, const uint32_t *dev_bases2, uint6
     a.bases = dev_bases2; a.off1 = off; a.len1 = len; a.read_bin = bin; a.n_bases = n_genomes * genome_len;
     a.pack = ring_pack_ok(a.k, a.wn, a.seed) ? 1u : 0u;
     const size_t lds = k1_lds_bytes(a.wn, d.num_categories, MODE_EMPLACE, a.h, (uint32_t)d.bin_words, (uint32_t)d.bins, a.pack != 0);
-    hipError_t e = launch_k1_w<MODE_EMPLACE>((uint32_t)d.bin_words, a, lds, 0);
+    hipError_t e = by_words(d.bin_words, [&](auto w) { return launch_k1_as<decltype(w)::value, MODE_EMPLACE, false, false>(a, lds, 0, 0); });
     if (e == hipSuccess) e = hipDeviceSynchronize();
     (void)hipFree(off); (void)hipFree(len); (void)hipFree(bin);
     if (e != hipSuccess) return fail(CHN_E_HIP, std::string("plant: ") + hipGetErrorString(e));

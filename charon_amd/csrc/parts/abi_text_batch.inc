@@ -59,9 +59,8 @@ static int text_pack_run(chn_stream *s, Slot &sl, const chn_text_batch *t, const
     int rc;
     if (on_device && (rc = device_text_check(t->text, tb, s->idx->d.device, W + ": CHN_TEXT_ON_DEVICE"))) return rc;  // before any launch
     if (text2 && (rc = device_text_check(text2, tb2, s->idx->d.device, W + ": CHN_TEXT_ON_DEVICE: text2"))) return rc;
-    hipStream_t cs = s->stream0;
     const size_t cap_b = (size_t)s->cfg.max_bases, cap_n = (size_t)s->cfg.max_reads;
-    // the slot's batch buffers at the sizes submit_impl reserves for them (they never re-allocate afterwards)
+    // the slot's batch buffers at the sizes stage_inputs (abi_stream_batch.inc) reserves for them (they never re-allocate afterwards)
     if ((rc = sl.d_bases.ensure(std::max<size_t>(cap_b / 4, 16))) || (rc = sl.d_nmask.ensure(std::max<size_t>(cap_b / 8, 16))) ||
         (rc = sl.d_mq.ensure(std::max<size_t>(cap_n * 4, 16))) || (rc = sl.d_tctl.ensure(TXT_CTL_WORDS * 4)) ||
         (rc = sl.h_text.ensure(TEXT_MQ_AT + cap_n * 4)))
@@ -73,30 +72,30 @@ static int text_pack_run(chn_stream *s, Slot &sl, const chn_text_batch *t, const
     }
     const bool prof = (s->cfg.flags & CHN_STREAM_PROFILE) != 0;
     if (prof)
-        for (int i = 0; i < 4; ++i) if (!sl.tev[i]) HIPCHK(hipEventCreate(&sl.tev[i]));
+        for (hipEvent_t *e : {&sl.t_text_upload.begin, &sl.t_text_upload.end, &sl.t_text_pack.begin, &sl.t_text_pack.end}) if (!*e) HIPCHK(hipEventCreate(e));
     const uint8_t *d_text = on_device ? t->text : sl.d_text.as<uint8_t>() + TEXT_PAD;
-    if (prof) HIPCHK(hipEventRecord(sl.tev[0], cs));
-    if (tb && !on_device) HIPCHK(hipMemcpyAsync(sl.d_text.as<uint8_t>() + TEXT_PAD, t->text, tb, hipMemcpyHostToDevice, cs));
-    if (prof) HIPCHK(hipEventRecord(sl.tev[1], cs));
-    if ((rc = upload(sl.d_off1, sl.h_toff1.data(), n * 8, cs, cap_n * 8)) || (rc = upload(sl.d_len1, t->seq1_length, n * 4, cs, cap_n * 4))) return rc;
-    if (paired && ((rc = upload(sl.d_off2, sl.h_toff2.data(), n * 8, cs, cap_n * 8)) || (rc = upload(sl.d_len2, t->seq2_length, n * 4, cs, cap_n * 4)))) return rc;
+    if (prof) HIPCHK(hipEventRecord(sl.t_text_upload.begin, s->q_copy));
+    if (tb && !on_device) HIPCHK(hipMemcpyAsync(sl.d_text.as<uint8_t>() + TEXT_PAD, t->text, tb, hipMemcpyHostToDevice, s->q_copy));
+    if (prof) HIPCHK(hipEventRecord(sl.t_text_upload.end, s->q_copy));
+    if ((rc = upload(sl.d_off1, sl.h_toff1.data(), n * 8, s->q_copy, cap_n * 8)) || (rc = upload(sl.d_len1, t->seq1_length, n * 4, s->q_copy, cap_n * 4))) return rc;
+    if (paired && ((rc = upload(sl.d_off2, sl.h_toff2.data(), n * 8, s->q_copy, cap_n * 8)) || (rc = upload(sl.d_len2, t->seq2_length, n * 4, s->q_copy, cap_n * 4)))) return rc;
     // descriptors: four columns of byte offsets, then two of quality lengths
     if ((rc = sl.d_tdesc.ensure(cap_n * 40))) return rc;
     uint64_t *d_o = sl.d_tdesc.as<uint64_t>();
     uint32_t *d_q = reinterpret_cast<uint32_t *>(d_o + 4 * cap_n);
-    HIPCHK(hipMemcpyAsync(d_o, t->seq1_offset, n * 8, hipMemcpyHostToDevice, cs));
+    HIPCHK(hipMemcpyAsync(d_o, t->seq1_offset, n * 8, hipMemcpyHostToDevice, s->q_copy));
     if (q1) {
-        HIPCHK(hipMemcpyAsync(d_o + cap_n, t->qual1_offset, n * 8, hipMemcpyHostToDevice, cs));
-        HIPCHK(hipMemcpyAsync(d_q, t->qual1_length, n * 4, hipMemcpyHostToDevice, cs));
+        HIPCHK(hipMemcpyAsync(d_o + cap_n, t->qual1_offset, n * 8, hipMemcpyHostToDevice, s->q_copy));
+        HIPCHK(hipMemcpyAsync(d_q, t->qual1_length, n * 4, hipMemcpyHostToDevice, s->q_copy));
     }
-    if (paired) HIPCHK(hipMemcpyAsync(d_o + 2 * cap_n, t->seq2_offset, n * 8, hipMemcpyHostToDevice, cs));
+    if (paired) HIPCHK(hipMemcpyAsync(d_o + 2 * cap_n, t->seq2_offset, n * 8, hipMemcpyHostToDevice, s->q_copy));
     if (q2) {
-        HIPCHK(hipMemcpyAsync(d_o + 3 * cap_n, t->qual2_offset, n * 8, hipMemcpyHostToDevice, cs));
-        HIPCHK(hipMemcpyAsync(d_q + cap_n, t->qual2_length, n * 4, hipMemcpyHostToDevice, cs));
+        HIPCHK(hipMemcpyAsync(d_o + 3 * cap_n, t->qual2_offset, n * 8, hipMemcpyHostToDevice, s->q_copy));
+        HIPCHK(hipMemcpyAsync(d_q + cap_n, t->qual2_length, n * 4, hipMemcpyHostToDevice, s->q_copy));
     }
-    HIPCHK(hipMemsetAsync(sl.d_tctl.p, 0, 2 * 4, cs));
-    HIPCHK(hipMemsetAsync(sl.d_tctl.as<uint32_t>() + TXT_FIRST_BAD, 0xFF, 4, cs));
-    HIPCHK(hipMemsetAsync(sl.d_mq.p, 0, n * 4, cs));
+    HIPCHK(hipMemsetAsync(sl.d_tctl.p, 0, 2 * 4, s->q_copy));
+    HIPCHK(hipMemsetAsync(sl.d_tctl.as<uint32_t>() + TXT_FIRST_BAD, 0xFF, 4, s->q_copy));
+    HIPCHK(hipMemsetAsync(sl.d_mq.p, 0, n * 4, s->q_copy));
 
     TextPackArgs a;
     std::memset(&a, 0, sizeof a);
@@ -109,22 +108,22 @@ static int text_pack_run(chn_stream *s, Slot &sl, const chn_text_batch *t, const
     a.bases = sl.d_bases.as<uint32_t>(); a.nmask = sl.d_nmask.as<uint32_t>(); a.qsum = sl.d_mq.as<int>(); a.ctl = sl.d_tctl.as<uint32_t>();
     const uint64_t blocks = (n_bases / 16 + 255) / 256;
     if (blocks > 0x7FFFFFFFULL) return fail(CHN_E_CAPACITY, W + ": batch too large for one launch");
-    if (prof) HIPCHK(hipEventRecord(sl.tev[2], cs));
-    if (t->flags & CHN_TEXT_DNA5_RANKS) hipLaunchKernelGGL(k_text_pack<true>, dim3((uint32_t)blocks), dim3(256), 0, cs, a);
-    else hipLaunchKernelGGL(k_text_pack<false>, dim3((uint32_t)blocks), dim3(256), 0, cs, a);
+    if (prof) HIPCHK(hipEventRecord(sl.t_text_pack.begin, s->q_copy));
+    if (t->flags & CHN_TEXT_DNA5_RANKS) hipLaunchKernelGGL(k_text_pack<true>, dim3((uint32_t)blocks), dim3(256), 0, s->q_copy, a);
+    else hipLaunchKernelGGL(k_text_pack<false>, dim3((uint32_t)blocks), dim3(256), 0, s->q_copy, a);
     HIPCHK(hipGetLastError());
     if (q1 || q2) {
-        hipLaunchKernelGGL(k_text_mq, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, cs, sl.d_mq.as<int>(), a.ql1, a.ql2, (uint32_t)n);
+        hipLaunchKernelGGL(k_text_mq, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s->q_copy, sl.d_mq.as<int>(), a.ql1, a.ql2, (uint32_t)n);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(sl.h_text.as<char>() + TEXT_MQ_AT, sl.d_mq.p, n * 4, hipMemcpyDeviceToHost, cs));
+        HIPCHK(hipMemcpyAsync(sl.h_text.as<char>() + TEXT_MQ_AT, sl.d_mq.p, n * 4, hipMemcpyDeviceToHost, s->q_copy));
     }
-    if (prof) HIPCHK(hipEventRecord(sl.tev[3], cs));
-    HIPCHK(hipMemcpyAsync(sl.h_text.p, sl.d_tctl.p, TXT_CTL_WORDS * 4, hipMemcpyDeviceToHost, cs));
-    HIPCHK(hipStreamSynchronize(cs));
+    if (prof) HIPCHK(hipEventRecord(sl.t_text_pack.end, s->q_copy));
+    HIPCHK(hipMemcpyAsync(sl.h_text.p, sl.d_tctl.p, TXT_CTL_WORDS * 4, hipMemcpyDeviceToHost, s->q_copy));
+    HIPCHK(hipStreamSynchronize(s->q_copy));
     if (prof) {
         float up = 0, pk = 0;
-        HIPCHK(hipEventElapsedTime(&up, sl.tev[0], sl.tev[1]));
-        HIPCHK(hipEventElapsedTime(&pk, sl.tev[2], sl.tev[3]));
+        HIPCHK(hipEventElapsedTime(&up, sl.t_text_upload.begin, sl.t_text_upload.end));
+        HIPCHK(hipEventElapsedTime(&pk, sl.t_text_pack.begin, sl.t_text_pack.end));
         s->text_ms[0] += up; s->text_ms[1] += pk; s->text_n += 1;
     }
     const uint32_t *ctl = sl.h_text.as<uint32_t>();

@@ -40,18 +40,17 @@ extern "C" int chn_text_fetch(chn_stream *s, chn_text_fetch_job *j) {
     for (uint64_t i = 0; i < n; ++i) { h_src[i] = j->offset[i]; h_dst[i] = at; h_len[i] = j->length[i]; at += j->length[i]; }
     const uint64_t *d_src = x.d_desc.as<uint64_t>(), *d_dst = d_src + n;
     const uint32_t *d_len = reinterpret_cast<const uint32_t *>(d_dst + n);
-    hipStream_t cs = s->stream0;
     uint8_t *host_dst = direct ? j->out : x.h_out.as<uint8_t>();
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(n, (uint64_t)std::max<uint32_t>(1, s->n_cus) * 16);
-    hipError_t e = hipMemcpyAsync(x.d_desc.p, x.h_desc.p, n * 20, hipMemcpyHostToDevice, cs);
-    if (e == hipSuccess) e = x.timer.begin(prof, cs);
+    hipError_t e = hipMemcpyAsync(x.d_desc.p, x.h_desc.p, n * 20, hipMemcpyHostToDevice, s->q_copy);
+    if (e == hipSuccess) e = x.timer.begin(prof, s->q_copy);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_text_gather, dim3(blocks), dim3(WAVE), 0, cs, j->text, d_src, d_dst, d_len, n, x.d_out.as<uint8_t>());
+        hipLaunchKernelGGL(k_text_gather, dim3(blocks), dim3(WAVE), 0, s->q_copy, j->text, d_src, d_dst, d_len, n, x.d_out.as<uint8_t>());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = x.timer.end(prof, cs);
-    if (e == hipSuccess) e = hipMemcpyAsync(host_dst, x.d_out.p, total, hipMemcpyDeviceToHost, cs);
-    const hipError_t w = hipStreamSynchronize(cs);  // nothing stays queued into the caller's memory, whatever happened
+    if (e == hipSuccess) e = x.timer.end(prof, s->q_copy);
+    if (e == hipSuccess) e = hipMemcpyAsync(host_dst, x.d_out.p, total, hipMemcpyDeviceToHost, s->q_copy);
+    const hipError_t w = hipStreamSynchronize(s->q_copy);  // nothing stays queued into the caller's memory, whatever happened
     if (e == hipSuccess) e = w;
     if (e != hipSuccess) return fail(CHN_E_HIP, std::string("chn_text_fetch: ") + hipGetErrorString(e));
     HIPCHK(x.timer.collect(prof));

@@ -40,18 +40,17 @@ extern "C" int chn_text_pair_ids(chn_stream *s, chn_text_pair_job *j) {
     a.off1 = x.d_desc.as<uint64_t>(); a.off2 = a.off1 + n;
     a.len1 = reinterpret_cast<const uint32_t *>(a.off2 + n); a.len2 = a.len1 + n;
     a.n = n; a.first = x.d_first.as<unsigned long long>();
-    hipStream_t cs = s->stream0;
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)std::max<uint32_t>(1, s->n_cus) * 8);
-    hipError_t e = hipMemcpyAsync(x.d_desc.p, x.h_desc.p, n * 24, hipMemcpyHostToDevice, cs);
-    if (e == hipSuccess) e = hipMemsetAsync(x.d_first.p, 0xFF, 8, cs);
-    if (e == hipSuccess) e = x.timer.begin(prof, cs);
+    hipError_t e = hipMemcpyAsync(x.d_desc.p, x.h_desc.p, n * 24, hipMemcpyHostToDevice, s->q_copy);
+    if (e == hipSuccess) e = hipMemsetAsync(x.d_first.p, 0xFF, 8, s->q_copy);
+    if (e == hipSuccess) e = x.timer.begin(prof, s->q_copy);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_pair_ids, dim3(blocks), dim3(256), 0, cs, a);
+        hipLaunchKernelGGL(k_pair_ids, dim3(blocks), dim3(256), 0, s->q_copy, a);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = x.timer.end(prof, cs);
-    if (e == hipSuccess) e = hipMemcpyAsync(x.h_first.p, x.d_first.p, 8, hipMemcpyDeviceToHost, cs);
-    const hipError_t w = hipStreamSynchronize(cs);  // nothing stays queued, whatever happened
+    if (e == hipSuccess) e = x.timer.end(prof, s->q_copy);
+    if (e == hipSuccess) e = hipMemcpyAsync(x.h_first.p, x.d_first.p, 8, hipMemcpyDeviceToHost, s->q_copy);
+    const hipError_t w = hipStreamSynchronize(s->q_copy);  // nothing stays queued, whatever happened
     if (e == hipSuccess) e = w;
     if (e != hipSuccess) return fail(CHN_E_HIP, std::string("chn_text_pair_ids: ") + hipGetErrorString(e));
     HIPCHK(x.timer.collect(prof));

@@ -15,21 +15,20 @@ static int split_download(chn_stream *s, TextSplitScratch &x, J *j, uint64_t n, 
     std::string why;
     if (j->ids && ids_bytes > j->ids_capacity) return fail(ids_too_small(j, ids_bytes, who, why), why);
     if (!n) return CHN_OK;
-    hipStream_t cs = s->stream0;
     if (j->ids && ids_bytes) {
         const int rc = x.d_ids.ensure_grow((size_t)ids_bytes, (size_t)(ids_bytes / 4));
         if (rc) return rc;
-        hipLaunchKernelGGL(k_split_ids, dim3(std::min<uint32_t>((uint32_t)((n + 15) / 16), std::max<uint32_t>(1, s->n_cus) * 8)), dim3(256), 0, cs, j->text, id_off, id_len,
+        hipLaunchKernelGGL(k_split_ids, dim3(std::min<uint32_t>((uint32_t)((n + 15) / 16), std::max<uint32_t>(1, s->n_cus) * 8)), dim3(256), 0, s->q_copy, j->text, id_off, id_len,
                            x.d_idpos.as<uint32_t>(), (uint32_t)n, x.d_ids.as<uint8_t>());
         HIPCHK(hipGetLastError());
     }
-    hipError_t e = hipMemcpyAsync(j->id_offset, id_off, n * 8, hipMemcpyDeviceToHost, cs);
-    if (e == hipSuccess) e = hipMemcpyAsync(j->seq_offset, seq_off, n * 8, hipMemcpyDeviceToHost, cs);
-    if (e == hipSuccess && qual_off) e = hipMemcpyAsync(qual_offset, qual_off, n * 8, hipMemcpyDeviceToHost, cs);
-    if (e == hipSuccess) e = hipMemcpyAsync(j->id_length, id_len, n * 4, hipMemcpyDeviceToHost, cs);
-    if (e == hipSuccess) e = hipMemcpyAsync(j->seq_length, seq_len, n * 4, hipMemcpyDeviceToHost, cs);
-    if (e == hipSuccess && j->ids && ids_bytes) e = hipMemcpyAsync(j->ids, x.d_ids.p, ids_bytes, hipMemcpyDeviceToHost, cs);
-    const hipError_t w = hipStreamSynchronize(cs);  // nothing stays queued into the caller's arrays, whatever happened
+    hipError_t e = hipMemcpyAsync(j->id_offset, id_off, n * 8, hipMemcpyDeviceToHost, s->q_copy);
+    if (e == hipSuccess) e = hipMemcpyAsync(j->seq_offset, seq_off, n * 8, hipMemcpyDeviceToHost, s->q_copy);
+    if (e == hipSuccess && qual_off) e = hipMemcpyAsync(qual_offset, qual_off, n * 8, hipMemcpyDeviceToHost, s->q_copy);
+    if (e == hipSuccess) e = hipMemcpyAsync(j->id_length, id_len, n * 4, hipMemcpyDeviceToHost, s->q_copy);
+    if (e == hipSuccess) e = hipMemcpyAsync(j->seq_length, seq_len, n * 4, hipMemcpyDeviceToHost, s->q_copy);
+    if (e == hipSuccess && j->ids && ids_bytes) e = hipMemcpyAsync(j->ids, x.d_ids.p, ids_bytes, hipMemcpyDeviceToHost, s->q_copy);
+    const hipError_t w = hipStreamSynchronize(s->q_copy);  // nothing stays queued into the caller's arrays, whatever happened
     if (e == hipSuccess) e = w;
     if (e != hipSuccess) return fail(CHN_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
     return CHN_OK;
@@ -59,7 +58,6 @@ extern "C" int chn_text_split(chn_stream *s, chn_text_split_job *j) {
     const uint32_t n_tiles = (uint32_t)((end + TSP_TILE - 1) / TSP_TILE - tile0);  // >= 1, <= 2^19
     const uint32_t cap = 4 * bound;                                                   // <= 2^30 line starts behind the first
     TextSplitScratch &x = s->tsp;
-    hipStream_t cs = s->stream0;
     // descriptors in one block: id_off[bound] seq_off[bound] qual_off[bound] (64-bit), id_len[bound] seq_len[bound] (32-bit)
     if ((rc = x.d_tile.ensure((size_t)n_tiles * 8)) || (rc = x.d_line.ensure(((size_t)cap + 1) * 4)) || (rc = x.d_desc.ensure((size_t)bound * 32)) ||
         (rc = x.d_idpos.ensure((size_t)bound * 4)) || (rc = x.d_ctl.ensure(TSP_CTL_WORDS * 4)) || (rc = x.h_ctl.ensure(TSP_CTL_WORDS * 4)))
@@ -72,24 +70,24 @@ extern "C" int chn_text_split(chn_stream *s, chn_text_split_job *j) {
     const uint32_t cus = std::max<uint32_t>(1, s->n_cus);
     const uint32_t tile_blocks = std::min<uint32_t>((n_tiles + 3) / 4, cus * 8), rec_blocks = std::min<uint32_t>((bound + 255) / 256, cus * 8);
     const bool prof = (s->cfg.flags & CHN_STREAM_PROFILE) != 0;
-    HIPCHK(x.timer.begin(prof, cs));
-    HIPCHK(hipMemsetAsync(ctl, 0, TSP_CTL_WORDS * 4, cs));
-    HIPCHK(hipMemsetAsync(ctl + TSP_FIRST_BAD, 0xFF, 4, cs));
-    hipLaunchKernelGGL(k_split_count, dim3(tile_blocks), dim3(256), 0, cs, j->text, start, end, tile0, n_tiles, tile_count);
+    HIPCHK(x.timer.begin(prof, s->q_copy));
+    HIPCHK(hipMemsetAsync(ctl, 0, TSP_CTL_WORDS * 4, s->q_copy));
+    HIPCHK(hipMemsetAsync(ctl + TSP_FIRST_BAD, 0xFF, 4, s->q_copy));
+    hipLaunchKernelGGL(k_split_count, dim3(tile_blocks), dim3(256), 0, s->q_copy, j->text, start, end, tile0, n_tiles, tile_count);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, cs, tile_count, tile_off, (const uint32_t *)nullptr, n_tiles, ctl + TSP_LINES);
+    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, s->q_copy, tile_count, tile_off, (const uint32_t *)nullptr, n_tiles, ctl + TSP_LINES);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_split_lines, dim3(tile_blocks), dim3(256), 0, cs, j->text, start, end, tile0, n_tiles, tile_off, line_start, cap);
+    hipLaunchKernelGGL(k_split_lines, dim3(tile_blocks), dim3(256), 0, s->q_copy, j->text, start, end, tile0, n_tiles, tile_off, line_start, cap);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_split_records, dim3(rec_blocks), dim3(256), 0, cs, a);
+    hipLaunchKernelGGL(k_split_records, dim3(rec_blocks), dim3(256), 0, s->q_copy, a);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_split_close, dim3(1), dim3(64), 0, cs, line_start, ctl, bound);
+    hipLaunchKernelGGL(k_split_close, dim3(1), dim3(64), 0, s->q_copy, line_start, ctl, bound);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, cs, a.id_len, x.d_idpos.as<uint32_t>(), ctl + TSP_N, bound, ctl + TSP_IDS_BYTES);
+    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, s->q_copy, a.id_len, x.d_idpos.as<uint32_t>(), ctl + TSP_N, bound, ctl + TSP_IDS_BYTES);
     HIPCHK(hipGetLastError());
-    HIPCHK(x.timer.end(prof, cs));
-    HIPCHK(hipMemcpyAsync(x.h_ctl.p, ctl, TSP_CTL_WORDS * 4, hipMemcpyDeviceToHost, cs));
-    HIPCHK(hipStreamSynchronize(cs));
+    HIPCHK(x.timer.end(prof, s->q_copy));
+    HIPCHK(hipMemcpyAsync(x.h_ctl.p, ctl, TSP_CTL_WORDS * 4, hipMemcpyDeviceToHost, s->q_copy));
+    HIPCHK(hipStreamSynchronize(s->q_copy));
     HIPCHK(x.timer.collect(prof));
     const uint32_t *h = x.h_ctl.as<uint32_t>();
     const uint64_t n = h[TSP_N], ids_bytes = h[TSP_IDS_BYTES];

@@ -14,7 +14,8 @@ __device__ __forceinline__ uint32_t len_bucket(uint32_t len) {
 #define LEN_BLOCKS 256
 // Per-slot control words on the device (zeroed by k_len_hist at the head of every batch chain).  CTL_GATE: workgroups of the ordinary probe
 // launch that have started (the probe gate, k1_minimise_probe.inc); a re-run after a log overflow, which has no gate, sums lengths there.
-enum { CTL_BYTES = 0, CTL_MINIMISERS = 1, CTL_LOG_CURSOR = 2, CTL_ESC_CURSOR = 3, CTL_STATUS = 4, CTL_NLONG = 5, CTL_FETCHES = 6, CTL_GATE = 7, CTL_WORDS = 8 };
+enum { CTL_BYTES = 0, CTL_MINIMISERS = 1, CTL_LOG_CURSOR = 2, CTL_ESC_CURSOR = 3, CTL_STATUS = 4, CTL_NLONG = 5, CTL_FETCHES = 6, CTL_GATE = 7, CTL_WORDS = 8,
+       CTL_SUM_LEN = CTL_WORDS - 1 };  // k_sum_len's scratch word in such a re-run: the last word, which is the gate's
 // Reads of at least 2^15 bases (bucket 104 and up; the order lists them first) are split over the lanes of a wavefront by the SPLIT
 // launch of k_minimise_probe.  CHN_STREAM_SPLIT_BUCKET(b) overrides the bucket for testing (255: never split).
 #define LONG_BUCKET_DEFAULT 104u
