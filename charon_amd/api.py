@@ -167,6 +167,17 @@ class ExtractJob(C.Structure):
                 ("out_used", C.c_uint64)]
 
 
+class EfLayout(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("wl", C.c_uint32), ("m_size", C.c_uint64), ("ones", C.c_uint64), ("low_bits", C.c_uint64),
+                ("high_bits", C.c_uint64), ("n_low_words", C.c_uint64), ("n_high_words", C.c_uint64)]
+
+
+class EfEncodeJob(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("slice_rows", C.c_uint64), ("layout", C.POINTER(EfLayout)),
+                ("low", C.c_void_p), ("n_low_words", C.c_uint64), ("high", C.c_void_p), ("n_high_words", C.c_uint64),
+                ("ones_written", C.c_uint64), ("device_ms", C.c_double)]
+
+
 class SynthReadsOut(C.Structure):
     _fields_ = [("bases2", C.c_void_p), ("seg1_offset", C.c_void_p), ("seg1_length", C.c_void_p), ("mean_quality", C.c_void_p),
                 ("compression", C.c_void_p), ("n_bases", C.c_uint64)]
@@ -178,7 +189,7 @@ EXPORTS = ["chn_index_create", "chn_index_upload_rows", "chn_index_device_words"
            "chn_model_set", "chn_batch_submit", "chn_batch_wait", "chn_stream_sync", "chn_classify_counts", "chn_classify_counts_raw", "chn_stream_profile",
            "chn_stream_last_batch_bytes", "chn_synth_genomes", "chn_synth_fill_index", "chn_synth_plant", "chn_synth_reads",
            "chn_device_free", "chn_device_download", "chn_device_malloc", "chn_device_upload", "chn_host_alloc", "chn_host_free", "chn_shard_minimise",
-           "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_text_submit", "chn_text_wait", "chn_text_pack", "chn_text_split", "chn_text_split_host", "chn_fasta_split", "chn_fasta_split_host", "chn_text_fetch", "chn_text_fetch_host", "chn_text_pair_ids", "chn_text_pair_ids_host", "chn_device_copy", "chn_inflate_create", "chn_inflate_run",
+           "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_ef_layout_of", "chn_index_ef_layout", "chn_index_encode_ef", "chn_index_encode_ef_host", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_text_submit", "chn_text_wait", "chn_text_pack", "chn_text_split", "chn_text_split_host", "chn_fasta_split", "chn_fasta_split_host", "chn_text_fetch", "chn_text_fetch_host", "chn_text_pair_ids", "chn_text_pair_ids_host", "chn_device_copy", "chn_inflate_create", "chn_inflate_run",
            "chn_inflate_run_host", "chn_inflate_destroy", "chn_inflate_kernel_ms", "chn_inflate_run_crc", "chn_inflate_run_host_crc", "chn_inflate_stream_run", "chn_inflate_stream_run_host", "chn_inflate_stream_search_host", "chn_deflate_create", "chn_deflate_run", "chn_deflate_run_host",
            "chn_deflate_destroy", "chn_deflate_bound", "chn_deflate_kernel_ms", "chn_deflate_group_members", "chn_extract_create", "chn_extract_destroy",
            "chn_extract_bound", "chn_extract_append_records", "chn_extract_append_bytes", "chn_extract_finish", "chn_extract_records_host",
@@ -226,6 +237,10 @@ _L.chn_minimisers.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_uint
 _L.chn_index_emplace.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
 _L.chn_index_decode_ef.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64,
                                    C.POINTER(C.c_uint64)]
+_L.chn_ef_layout_of.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(EfLayout)]
+_L.chn_index_ef_layout.argtypes = [C.c_void_p, C.POINTER(EfLayout)]
+_L.chn_index_encode_ef.argtypes = [C.c_void_p, C.POINTER(EfEncodeJob)]
+_L.chn_index_encode_ef_host.argtypes = [C.POINTER(IndexDesc), C.c_void_p, C.POINTER(EfEncodeJob)]
 _L.chn_index_bin_popcounts.argtypes = [C.c_void_p, C.c_void_p]
 _L.chn_index_replicate.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
 _L.chn_device_count.argtypes = [C.POINTER(C.c_int)]
@@ -365,6 +380,20 @@ class Index:
         _chk(_L.chn_index_decode_ef(self.h, m_size, wl, high.ctypes.data if high.size else np.zeros(1, np.uint64).ctypes.data, 0, 0, 0, None, 0, 0, C.byref(bad)))
         return bad_total + bad.value
 
+    def ef_layout(self):
+        """chn_index_ef_layout: the sd_vector layout of this index (its set bits are counted on the device)"""
+        lay = EfLayout()
+        _chk(_L.chn_index_ef_layout(self.h, C.byref(lay)))
+        return lay
+
+    def encode_ef(self, slice_rows=0, layout=None):
+        """chn_index_encode_ef: (layout, low, high, device_ms) -- m_low and m_high of the whole index as numpy uint64 arrays, encoded on
+        the device in slices of `slice_rows` rows (0: 256 MiB of rows)"""
+        lay = self.ef_layout() if layout is None else layout
+        job, low, high = ef_encode_job(lay, slice_rows)
+        _chk(_L.chn_index_encode_ef(self.h, C.byref(job)))
+        return lay, low, high, job.device_ms
+
     def bin_popcounts(self):
         out = np.zeros(self.desc.technical_bins, np.uint64)
         _chk(_L.chn_index_bin_popcounts(self.h, out.ctypes.data))
@@ -401,6 +430,41 @@ class Index:
         if self.h:
             _L.chn_index_destroy(self.h)
             self.h = None
+
+
+_POP8 = np.array([bin(i).count("1") for i in range(256)], np.uint8)  # set bits of a byte
+
+
+def ef_layout_of(m_size, ones):
+    """chn_ef_layout_of: the sd_vector layout of m_size bits with `ones` set bits (the pure rule; no GPU)"""
+    lay = EfLayout()
+    _chk(_L.chn_ef_layout_of(m_size, ones, C.byref(lay)))
+    return lay
+
+
+def ef_encode_job(layout, slice_rows=0, low=None, high=None):
+    """a chn_ef_encode_job for `layout` with arrays of the layout's sizes (filled with ones where this makes them: the call writes every word)"""
+    low = np.full(layout.n_low_words, 2 ** 64 - 1, np.uint64) if low is None else low
+    high = np.full(layout.n_high_words, 2 ** 64 - 1, np.uint64) if high is None else high
+    job = EfEncodeJob()
+    job.struct_size = C.sizeof(EfEncodeJob)
+    job.slice_rows = slice_rows
+    job.layout = C.pointer(layout)
+    job.low, job.n_low_words = (low.ctypes.data if low.size else None), low.size
+    job.high, job.n_high_words = (high.ctypes.data if high.size else None), high.size
+    return job, low, high
+
+
+def encode_ef_host(desc, words, slice_rows=0, layout=None):
+    """chn_index_encode_ef_host: (layout, low, high, device_ms = 0) of the plain rows `words` of a whole index described by `desc`, on one
+    CPU thread (no GPU), in the slices chn_index_encode_ef walks"""
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    if words.size != desc.bin_size * desc.bin_words:
+        raise ValueError("encode_ef_host: %d words, the index has %d" % (words.size, desc.bin_size * desc.bin_words))
+    lay = ef_layout_of(desc.technical_bins * desc.bin_size, int(_POP8[words.view(np.uint8)].sum(dtype=np.uint64))) if layout is None else layout
+    job, low, high = ef_encode_job(lay, slice_rows)
+    _chk(_L.chn_index_encode_ef_host(C.byref(desc), words.ctypes.data, C.byref(job)))
+    return lay, low, high, job.device_ms
 
 
 DIST = {"kde": 0, "gamma": 1, "beta": 2}

@@ -73,10 +73,12 @@
 #include "parts/inflate_search.inc"
 #include "parts/deflate_members.inc"
 #include "parts/ef_decode.inc"
+#include "parts/ef_encode.inc"
 #include "parts/synth_kernels.inc"
 #include "parts/batch_plan.inc"
 #include "parts/abi_device_call.inc"
 #include "parts/abi_index_model.inc"
+#include "parts/abi_ef_encode.inc"
 #include "parts/abi_stream_batch.inc"
 #include "parts/abi_shard_wait.inc"
 #include "parts/abi_text_split.inc"

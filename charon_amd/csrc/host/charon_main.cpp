@@ -414,6 +414,13 @@ int main(int argc, char **argv) {
             std::cerr << e.what() << "\nRun with --help for more information.\n";
             return 105;
         }
+        if (const char *e = std::getenv("CHARON_GPU_INDEX_EF")) {
+            // CHARON_GPU_INDEX_EF: 1 = the index's Elias-Fano arrays are encoded on the device (chn_index_encode_ef), 0 or unset = by the -t
+            // threads from downloaded rows; anything else is an error.  Read by `charon index` alone.
+            const std::string v(e);
+            if (v != "0" && v != "1") { std::cerr << "charon: CHARON_GPU_INDEX_EF: '" << v << "' is neither 0 nor 1" << std::endl; return 1; }
+            iopt.gpu_ef = v == "1";
+        }
         try {
             index_main(iopt);
             return 0;

@@ -14,6 +14,7 @@ struct IndexArguments {
     uint8_t threads = 1, verbosity = 0;
     bool optimize = false;
     int device = 0;
+    bool gpu_ef = false;  // CHARON_GPU_INDEX_EF=1: the Elias-Fano arrays are encoded on the device (chn_index_encode_ef)
 };
 
 bool parse_index(int argc, char **argv, IndexArguments &opt) {
@@ -372,31 +373,50 @@ int index_main(IndexArguments &opt) {
 
     lap(t_emplace);
     // Index(...) compresses the IBF (include/index.hpp:43-50) and store_index writes it (include/store_index.hpp:12-17)
-    const uint64_t W = meta.bin_words, block_rows = std::max<uint64_t>(1, (256ULL << 20) / (8 * W));
-    std::vector<uint64_t> block(block_rows * W);
-    // both passes over the downloaded rows run on the -t threads: the second one cuts a block into one stretch per thread, counts the
-    // set bits of each stretch, and every thread then writes its bits at their final places (a set bit's place in the Elias-Fano arrays
-    // depends only on its position and on how many set bits precede it)
     const int nt_ef = std::max(1, (int)opt.threads);
-    uint64_t ones = 0;
-    for (uint64_t r0 = 0; r0 < S; r0 += block_rows) {
-        const uint64_t nr = std::min(block_rows, S - r0);
-        CHN_CHECK(chn_index_download_rows(index, r0, nr, block.data()));
-        uint64_t part = 0;
-#pragma omp parallel for num_threads(nt_ef) reduction(+ : part) schedule(static)
-        for (long i = 0; i < (long)(nr * W); ++i) part += (uint64_t)__builtin_popcountll(block[(size_t)i]);
-        ones += part;
-    }
     EliasFanoWriter ef;
-    ef.begin(meta.technical_bins * S, ones);
-    uint64_t before = 0;  // set bits in the blocks done
-    for (uint64_t r0 = 0; r0 < S; r0 += block_rows) {
-        const uint64_t nr = std::min(block_rows, S - r0), nwords = nr * W;
-        CHN_CHECK(chn_index_download_rows(index, r0, nr, block.data()));
-        before += ef_add_block(ef, block.data(), nwords, r0 * W * 64, before, nt_ef);
+    if (opt.gpu_ef) {
+        // CHARON_GPU_INDEX_EF=1: the set bits are counted and the two arrays written on the device, slice of rows by slice of rows; the plain
+        // index never comes to the host
+        chn_ef_layout lay;
+        CHN_CHECK(chn_index_ef_layout(index, &lay));
+        ef.begin(lay.m_size, lay.ones);
+        if (ef.wl != lay.wl || ef.high_bits != lay.high_bits || ef.high.size() != lay.n_high_words || ef.low.size() != lay.n_low_words + 1)
+            throw std::runtime_error("internal error: chn_index_ef_layout and the writer disagree about the Elias-Fano layout");
+        chn_ef_encode_job job;
+        std::memset(&job, 0, sizeof job);
+        job.struct_size = sizeof job; job.layout = &lay;
+        if (const char *e = std::getenv("CHARON_INDEX_EF_SLICE")) job.slice_rows = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));  // test hook
+        job.low = ef.low.data(); job.n_low_words = lay.n_low_words; job.high = ef.high.data(); job.n_high_words = lay.n_high_words;
+        CHN_CHECK(chn_index_encode_ef(index, &job));
+        ef.k = lay.ones;
+        g_log.info("CHARON_GPU_INDEX_EF=1: the Elias-Fano arrays were encoded on device " + std::to_string(opt.device) + " (" + std::to_string(lay.ones) +
+                   " set bits, kernels " + std::to_string(job.device_ms) + " ms)");
+    } else {
+        const uint64_t W = meta.bin_words, block_rows = std::max<uint64_t>(1, (256ULL << 20) / (8 * W));
+        std::vector<uint64_t> block(block_rows * W);
+        // both passes over the downloaded rows run on the -t threads: the second one cuts a block into one stretch per thread, counts the
+        // set bits of each stretch, and every thread then writes its bits at their final places (a set bit's place in the Elias-Fano arrays
+        // depends only on its position and on how many set bits precede it)
+        uint64_t ones = 0;
+        for (uint64_t r0 = 0; r0 < S; r0 += block_rows) {
+            const uint64_t nr = std::min(block_rows, S - r0);
+            CHN_CHECK(chn_index_download_rows(index, r0, nr, block.data()));
+            uint64_t part = 0;
+#pragma omp parallel for num_threads(nt_ef) reduction(+ : part) schedule(static)
+            for (long i = 0; i < (long)(nr * W); ++i) part += (uint64_t)__builtin_popcountll(block[(size_t)i]);
+            ones += part;
+        }
+        ef.begin(meta.technical_bins * S, ones);
+        uint64_t before = 0;  // set bits in the blocks done
+        for (uint64_t r0 = 0; r0 < S; r0 += block_rows) {
+            const uint64_t nr = std::min(block_rows, S - r0), nwords = nr * W;
+            CHN_CHECK(chn_index_download_rows(index, r0, nr, block.data()));
+            before += ef_add_block(ef, block.data(), nwords, r0 * W * 64, before, nt_ef);
+        }
+        if (before != ones) throw std::runtime_error("internal error: the index changed between the two Elias-Fano passes");
+        ef.k = ones;
     }
-    if (before != ones) throw std::runtime_error("internal error: the index changed between the two Elias-Fano passes");
-    ef.k = ones;
     chn_index_destroy(index);
     lap(t_ef);
     if (std::getenv("CHARON_TIMING"))

@@ -81,6 +81,47 @@ int chn_index_upload_rows(chn_index *idx, uint64_t row_begin, uint64_t n_rows, c
  * chn_index_bin_popcounts and chn_stream_create wait for the slices as well. */
 int chn_index_decode_ef(chn_index *idx, uint64_t m_size, uint32_t wl, const uint64_t *high, uint64_t high_bit0, uint64_t n_high_words,
                         uint64_t ones_before, const uint64_t *low, uint64_t low_elem0, uint64_t n_low_words, uint64_t *bad_bits);
+/* Elias-Fano (sdsl::sd_vector) ENCODE: the inverse of chn_index_decode_ef for the writer, replacing the compression of the IBF in
+ * Index(...) (include/index.hpp:43-50) whose result archive(ibf_) stores (include/index.hpp:130, store_index.hpp:12-17).
+ * The layout of a vector of m_size bits with `ones` set bits, with hi(x) = floor(log2 x) and hi(0) = 0: logm = hi(ones) + 1,
+ * logn = hi(m_size) + 1, logm one less where the two are equal; wl = logn - logm >= 1; low_bits = ones * wl; high_bits = ones + 2^logm;
+ * the word counts round up.  ones == 0 is legal (wl from logm = 1, no low words, two high bits).  The set bit of rank k at plain position
+ * pos = row * technical_bins + bin puts its low wl bits at bit k * wl of m_low and sets bit (pos >> wl) + k of m_high.
+ * chn_ef_layout_of is that rule alone and needs no GPU: CHN_E_INVALID for a null `out`, m_size == 0 or above 2^57, ones > m_size. */
+typedef struct chn_ef_layout {
+    uint32_t struct_size, wl;                 /* struct_size: set by the calls that fill the layout */
+    uint64_t m_size, ones;
+    uint64_t low_bits, high_bits;
+    uint64_t n_low_words, n_high_words;
+} chn_ef_layout;
+int chn_ef_layout_of(uint64_t m_size, uint64_t ones, chn_ef_layout *out);
+/* The layout of this index: its set bits are counted on the device, m_size = technical_bins * bin_size (include/index.hpp:43-50,130;
+ * store_index.hpp:12-17).  Waits for queued Elias-Fano slices and a queued replica copy; a row shard is refused with CHN_E_INVALID. */
+int chn_index_ef_layout(chn_index *idx, chn_ef_layout *out);
+/* m_low and m_high of the whole index into HOST memory (include/index.hpp:43-50,130; store_index.hpp:12-17: the two int_vectors the file
+ * holds).  Synchronous.  The call owns both arrays: every word of low[0, n_low_words) and high[0, n_high_words) is written, zeros included.
+ * The index is worked through in slices of `slice_rows` rows (0: 256 MiB of rows): a slice's set bits are counted, the words of m_low and
+ * m_high they can touch follow from the set bits in front of the slice and from its first and last position, device scratch of that size
+ * is zeroed, k_ef_encode fills it, and the host ORs the downloaded ranges into the arrays (neighbouring slices share the words at their
+ * seams).  The scratch is bounded by the slice, not by the index.
+ * CHN_E_INVALID, nothing having been written: a null job, a wrong struct_size (job or layout), a non-zero flag, a null layout or array, a
+ * layout that is not the one of this index's m_size and of its own `ones`, array sizes that are not the layout's, a slice of more than
+ * 2^31 words, a row shard, set bits in the index that number other than layout->ones (counted before anything is written).
+ * ones_written is the number of set bits encoded; device_ms the time of the kernels, from events, summed over the slices.
+ * Waits for queued Elias-Fano slices and a queued replica copy.
+ * chn_index_encode_ef_host is the same rule source on the calling thread over plain words in host memory (rows of `desc`, which must
+ * describe a whole index): the same checks, the same slices and seams; device_ms is 0. */
+typedef struct chn_ef_encode_job {
+    uint32_t struct_size, flags;              /* flags: 0 */
+    uint64_t slice_rows;                      /* 0: 256 MiB of rows */
+    const chn_ef_layout *layout;
+    uint64_t *low;  uint64_t n_low_words;     /* HOST; must equal the layout's */
+    uint64_t *high; uint64_t n_high_words;    /* HOST */
+    uint64_t ones_written;                    /* out */
+    double device_ms;                         /* out */
+} chn_ef_encode_job;
+int chn_index_encode_ef(chn_index *idx, chn_ef_encode_job *job);
+int chn_index_encode_ef_host(const chn_index_desc *desc, const uint64_t *host_words, chn_ef_encode_job *job);   /* one CPU thread; no GPU needed */
 /* set bits per technical bin over the rows this object holds (loader self-check iv); out[technical_bins] */
 int chn_index_bin_popcounts(chn_index *idx, uint64_t *out);
 /* Device pointer to the shard's words (for on-device index fabrication and for download in tests). */

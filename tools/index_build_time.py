@@ -1,11 +1,29 @@
 #!/usr/bin/env python3
 """How long does `charon index` take on references of some size?  Two synthetic genomes of N Mb each (one per category).
-usage: python tools/index_build_time.py [Mb per genome] [workdir] [threads]"""
-import os, subprocess, sys, time
+usage: python tools/index_build_time.py [Mb per genome] [workdir] [threads] [--legs NAME=EXE[@ef] ... [--rounds N]]
+
+Without --legs: one run of this tree's binary, as ever.
+With --legs: every leg is a binary (NAME=path of a `charon`), "@ef" behind the path runs it with CHARON_GPU_INDEX_EF=1 (the Elias-Fano arrays
+encoded on the device), without it the variable is unset.  `threads` may be a comma list.  The legs run `--rounds` times (default 3) for every
+thread count, the leg that goes first rotating from round to round; wall time and the last figure of the CHARON_TIMING line (the
+"download + Elias-Fano" stage, whichever path ran) are reported as min - median - max, and the sha256 of every file written."""
+import hashlib, os, re, statistics, subprocess, sys, time
 import numpy as np
-mb = int(sys.argv[1]) if len(sys.argv) > 1 else 200
-work = sys.argv[2] if len(sys.argv) > 2 else "/tmp/charon_idx"
-threads = sys.argv[3] if len(sys.argv) > 3 else "16"
+argv = sys.argv[1:]
+legs, rounds = [], 3
+if "--legs" in argv:
+    i = argv.index("--legs")
+    rest, argv = argv[i + 1:], argv[:i]
+    if "--rounds" in rest:
+        j = rest.index("--rounds")
+        rounds = int(rest[j + 1])
+        rest = rest[:j] + rest[j + 2:]
+    for spec in rest:
+        name, exe = spec.split("=", 1)
+        legs.append((name, exe[:-3] if exe.endswith("@ef") else exe, exe.endswith("@ef")))
+mb = int(argv[0]) if len(argv) > 0 else 200
+work = argv[1] if len(argv) > 1 else "/tmp/charon_idx"
+threads = argv[2] if len(argv) > 2 else "16"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.makedirs(work, exist_ok=True)
 r = np.random.default_rng(3)
@@ -19,13 +37,47 @@ with open(os.path.join(work, "refs.tsv"), "w") as tab:
                 f.write(b">%s_chr%d\n" % (name.encode(), c))
                 f.write(b"\n".join(s[i:i + 60].tobytes() for i in range(0, len(s), 60)) + b"\n")
         tab.write("%s\t%s\n" % (fa, name))
-for f in ("big.idx",):
-    if os.path.exists(os.path.join(work, f)):
-        os.remove(os.path.join(work, f))
-exe = os.path.join(ROOT, "charon_amd", "bin", "charon")
-t0 = time.time()
-p = subprocess.run([exe, "index", "-t", threads, "-p", os.path.join(work, "big"), "--log", os.path.join(work, "i.log"), os.path.join(work, "refs.tsv")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=dict(os.environ, CHARON_TIMING="1"))
-dt = time.time() - t0
-print("charon index -t %s: rc=%d, 2 x %d Mb in %.1f s (%.1f Mb/s), index file %.1f MB" % (threads, p.returncode, mb, dt, 2 * mb / dt, os.path.getsize(os.path.join(work, "big.idx")) / 1e6 if p.returncode == 0 else 0))
-print(p.stderr.decode()[-600:])
-print(open(os.path.join(work, "i.log")).read()[-600:])
+
+
+def run(exe, nthreads, ef=False):
+    """one `charon index` run: (return code, wall seconds, stderr, log tail); the file is <work>/big.idx"""
+    if os.path.exists(os.path.join(work, "big.idx")):
+        os.remove(os.path.join(work, "big.idx"))
+    env = {k: v for k, v in os.environ.items() if k != "CHARON_GPU_INDEX_EF"}
+    env["CHARON_TIMING"] = "1"
+    if ef:
+        env["CHARON_GPU_INDEX_EF"] = "1"
+    t0 = time.time()
+    p = subprocess.run([exe, "index", "-t", nthreads, "-p", os.path.join(work, "big"), "--log", os.path.join(work, "i.log"), os.path.join(work, "refs.tsv")],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
+    return p.returncode, time.time() - t0, p.stderr.decode(), open(os.path.join(work, "i.log")).read()[-600:]
+
+
+if not legs:
+    rc, dt, err, log = run(os.path.join(ROOT, "charon_amd", "bin", "charon"), threads)
+    print("charon index -t %s: rc=%d, 2 x %d Mb in %.1f s (%.1f Mb/s), index file %.1f MB" % (threads, rc, mb, dt, 2 * mb / dt, os.path.getsize(os.path.join(work, "big.idx")) / 1e6 if rc == 0 else 0))
+    print(err[-600:])
+    print(log)
+    sys.exit(0)
+
+spread = lambda v: "%.3f - %.3f - %.3f" % (min(v), statistics.median(v), max(v))
+hashes = set()
+for nt in threads.split(","):
+    wall = {name: [] for name, _, _ in legs}
+    stage = {name: [] for name, _, _ in legs}
+    for rd in range(rounds):
+        for name, exe, ef in legs[rd % len(legs):] + legs[:rd % len(legs)]:
+            rc, dt, err, _ = run(exe, nt, ef)
+            m = re.search(r"charon index: timing \(s\):.* ([0-9.]+)\s*$", err, re.M)
+            if rc != 0 or not m:
+                print("leg %s -t %s round %d: rc=%d\n%s" % (name, nt, rd, rc, err[-600:]))
+                sys.exit(1)
+            sha = hashlib.sha256(open(os.path.join(work, "big.idx"), "rb").read()).hexdigest()
+            hashes.add(sha)
+            wall[name].append(dt)
+            stage[name].append(float(m.group(1)))
+            print("  -t %s round %d %-8s wall %.3f s  stage %.3f s  sha256 %s  %.1f MB" % (nt, rd, name, dt, float(m.group(1)), sha[:16], os.path.getsize(os.path.join(work, "big.idx")) / 1e6), flush=True)
+    for name, _, _ in legs:
+        print("-t %-3s %-8s wall (s) %s   download + Elias-Fano stage (s) %s   [min - median - max of %d]" % (nt, name, spread(wall[name]), spread(stage[name]), rounds))
+print("sha256 of the files: %s" % ("one value, " + next(iter(hashes)) if len(hashes) == 1 else "%d DIFFERENT values" % len(hashes)))
+sys.exit(0 if len(hashes) == 1 else 1)
