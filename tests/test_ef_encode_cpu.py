@@ -26,6 +26,29 @@ def test_host_form_equals_the_reference_layout(name, slice_rows):
         assert lay.wl == 1 and lay.high_bits == 4096 + (1 << 12)  # logm == logn == 13: logm is decremented
 
 
+@pytest.mark.parametrize("name", [c[0] for c in cases.CASES] + [cases.SEAM[0]])
+def test_numpy_reference_equals_pyref(name):
+    """ef_encode_np is the reference of the large cases only as long as it is pyref.ef_encode on everything pyref can carry"""
+    case = cases.build(name)
+    wl, low_bits, low, high_bits, high = cases.ef_encode_np(case["pos"], case["universe"])
+    assert (wl, low_bits, high_bits) == (case["wl"], case["low_bits"], case["high_bits"])
+    assert low.dtype == np.uint64 and high.dtype == np.uint64
+    assert np.array_equal(low, case["low"]) and np.array_equal(high, case["high"])
+    if name == cases.SEAM[0]:
+        assert 64 % wl != 0 and case["pos"].size > 64 * 3
+
+
+@pytest.mark.parametrize("slice_rows", [0, cases.LARGE_SLICE_ROWS])
+@pytest.mark.parametrize("name", list(cases.LARGE))
+def test_host_form_on_slices_of_many_blocks(name, slice_rows):
+    """thousands of 256-word blocks a slice, as one slice and at 1025 blocks a slice (the builder asserts the shapes' conditions)"""
+    case = cases.build_large(name)
+    lay, low, high, _ = api.encode_ef_host(desc_of(case), case["words"], slice_rows)
+    cases.assert_is_expected(case, lay, low, high)
+    assert cases.prefix_chunks(case["high"].size) >= cases.LARGE[name]["decode_rounds"]
+    assert cases.prefix_chunks(case["words"].size) >= 3 and cases.prefix_chunks(cases.LARGE_SLICE_ROWS) == 2
+
+
 class _Counted:
     """a position list of `n` entries that are never looked at: pyref.ef_encode takes wl and the bit counts from its length alone"""
 
