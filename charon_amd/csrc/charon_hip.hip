@@ -49,6 +49,7 @@
 #include "default_kde.inc"
 
 #include "parts/common.inc"
+#include "parts/scan.inc"
 #include "parts/lds_budget.hpp"
 #include "parts/rowlog_entry.hpp"
 #include "parts/k1_minimise_probe.inc"

@@ -134,7 +134,7 @@ static int deflate_launch(chn_deflate *h, DeflateSet &st, const uint8_t *d_in, u
     HIPCHK(hipEventRecord(st.k0, h->s_run));
     hipLaunchKernelGGL(k_deflate_members, dim3(blocks), dim3(WAVE), 0, h->s_run, a);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_deflate_scan, dim3(1), dim3(WAVE), 0, h->s_run, a.out_len, d_off, (uint32_t)n);
+    hipLaunchKernelGGL(k_deflate_scan, dim3(1), dim3(SCAN_THREADS), 0, h->s_run, a.out_len, d_off, (uint32_t)n);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_deflate_gather, dim3((uint32_t)n), dim3(256), 0, h->s_run, a.slots, a.out_len, d_off, st.d_packed.as<uint8_t>(), (uint64_t)packed_bytes);
     HIPCHK(hipGetLastError());

@@ -146,7 +146,7 @@ static int ef_encode_device(chn_index *idx, chn_ef_encode_job *j, uint64_t slice
         HIPCHK(hipEventRecord(sc.ev[0], 0));
         hipLaunchKernelGGL(k_ef_block_counts, dim3((uint32_t)n_blocks), dim3(256), 0, 0, words, n, sc.counts.as<uint32_t>());
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_ef_block_prefix, dim3(1), dim3(1024), 0, 0, sc.counts.as<uint32_t>(), n_blocks + 1, sc.prefix.as<uint64_t>());
+        hipLaunchKernelGGL(k_ef_block_prefix, dim3(1), dim3(SCAN_THREADS), 0, 0, sc.counts.as<uint32_t>(), n_blocks + 1, sc.prefix.as<uint64_t>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(sc.ev[1], 0));
         uint64_t c = 0;

@@ -60,11 +60,11 @@ extern "C" int chn_fasta_split(chn_stream *s, chn_fasta_split_job *j) {
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_fasta_resolve, dim3(1), dim3(256), 0, s->q_copy, tiles, n_tiles, tile_state, tile_hdr, tile_feed, tile_kept);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, s->q_copy, tile_hdr, hdr_off, (const uint32_t *)nullptr, n_tiles, ctl + FSP_HDRS);
+    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(SCAN_THREADS), 0, s->q_copy, tile_hdr, hdr_off, (const uint32_t *)nullptr, n_tiles, ctl + FSP_HDRS);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, s->q_copy, tile_feed, feed_off, (const uint32_t *)nullptr, n_tiles, ctl + FSP_FEEDS);
+    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(SCAN_THREADS), 0, s->q_copy, tile_feed, feed_off, (const uint32_t *)nullptr, n_tiles, ctl + FSP_FEEDS);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, s->q_copy, tile_kept, kept_off, (const uint32_t *)nullptr, n_tiles, ctl + FSP_KEPT);
+    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(SCAN_THREADS), 0, s->q_copy, tile_kept, kept_off, (const uint32_t *)nullptr, n_tiles, ctl + FSP_KEPT);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_fasta_headers, dim3(tile_blocks), dim3(256), 0, s->q_copy, j->text, start, end, tile0, n_tiles, tile_state, hdr_off, feed_off, kept_off, ctl, hdr_pos,
                        feed_pos, kept_before, cap);
@@ -75,7 +75,7 @@ extern "C" int chn_fasta_split(chn_stream *s, chn_fasta_split_job *j) {
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_fasta_compact, dim3(tile_blocks), dim3(256), 0, s->q_copy, j->text, start, end, tile0, n_tiles, tile_state, kept_off, ctl, j->seq_text);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, s->q_copy, a.id_len, x.d_idpos.as<uint32_t>(), ctl + FSP_N, bound, ctl + FSP_IDS_BYTES);
+    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(SCAN_THREADS), 0, s->q_copy, a.id_len, x.d_idpos.as<uint32_t>(), ctl + FSP_N, bound, ctl + FSP_IDS_BYTES);
     HIPCHK(hipGetLastError());
     HIPCHK(x.timer.end(prof, s->q_copy));
     HIPCHK(hipMemcpyAsync(x.h_ctl.p, ctl, FSP_CTL_WORDS * 4, hipMemcpyDeviceToHost, s->q_copy));

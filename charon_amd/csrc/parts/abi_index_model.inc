@@ -331,7 +331,7 @@ extern "C" int chn_index_decode_ef(chn_index *idx, uint64_t m_size, uint32_t wl,
     HIPCHK(hipEventRecord(idx->ef_copied, st));
     hipLaunchKernelGGL(k_ef_block_counts, dim3((uint32_t)n_blocks), dim3(256), 0, st, d_high, n_high_words, d_counts);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_ef_block_prefix, dim3(1), dim3(1024), 0, st, d_counts, n_blocks, d_prefix);
+    hipLaunchKernelGGL(k_ef_block_prefix, dim3(1), dim3(SCAN_THREADS), 0, st, d_counts, n_blocks, d_prefix);
     HIPCHK(hipGetLastError());
     EfArgs a;
     a.high = d_high; a.low = d_low; a.n_high_words = n_high_words; a.high_bit0 = high_bit0; a.ones_before = ones_before; a.low_elem0 = low_elem0;

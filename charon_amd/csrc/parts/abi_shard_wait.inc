@@ -44,7 +44,7 @@ extern "C" int chn_shard_minimise(chn_stream *s, const chn_batch *b, uint64_t *n
     if ((rc = submit_impl(s, b, LIST_DENSE))) return rc;
     const uint32_t n_waves = (uint32_t)waves_of(b->n_reads);
     hipLaunchKernelGGL(k_counts_to_u64, dim3((n_waves + 1 + 255) / 256), dim3(256), 0, s->q_probe[0], s->big.wcount.as<uint32_t>(), n_waves, s->d_cbase.as<uint64_t>());
-    hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, s->q_probe[0], s->d_cbase.as<uint64_t>(), n_waves + 1);
+    hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(SCAN_THREADS), 0, s->q_probe[0], s->d_cbase.as<uint64_t>(), n_waves + 1);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s->q_probe[0]));
     uint64_t total = 0;

@@ -38,7 +38,7 @@ extern "C" int chn_shardx_counts(chn_stream *s, uint32_t n_ranks, const uint64_t
     a.rowlog = s->shx.log.as<uint32_t>(); a.rows = s->shx.rows.as<uint64_t>(); a.esc_capacity = s->shx.esc_cap;
     a.status = reinterpret_cast<uint32_t *>(sl.d_ctl.as<unsigned long long>() + CTL_STATUS); a.B = (uint32_t)d.bins;
     hipLaunchKernelGGL(k_shx_count, dim3(n_waves), dim3(SHX_THREADS), 0, s->q_probe[0], a);
-    hipLaunchKernelGGL(k_shx_scan, dim3(n_ranks), dim3(1024), 0, s->q_probe[0], a.cnt, n_waves);
+    hipLaunchKernelGGL(k_scan_u64, dim3(n_ranks), dim3(SCAN_THREADS), 0, s->q_probe[0], a.cnt, n_waves + 1);
     HIPCHK(hipGetLastError());
     std::vector<uint64_t> tot(n_ranks);
     for (uint32_t r = 0; r < n_ranks; ++r)

@@ -617,7 +617,7 @@ static int choose_log(chn_stream *s, Slot &sl, int list_kind, hipStream_t probe_
         a.rows = s->d_list.as<uint64_t>();
         hipLaunchKernelGGL(k_wave_caps, dim3((uint32_t)((sl.n_reads + 255) / 256)), dim3(256), 0, probe_q, sl.d_order.as<uint32_t>(), sl.len1, sl.len2,
                            (uint32_t)sl.n_reads, s->big.cap_num, s->big.esc_shift, s->big.meta.as<WaveMeta>());
-        hipLaunchKernelGGL(k_scan_meta, dim3(1), dim3(1024), 0, probe_q, s->big.meta.as<WaveMeta>(), (uint32_t)waves_of(sl.n_reads));
+        hipLaunchKernelGGL(k_scan_meta, dim3(1), dim3(SCAN_THREADS), 0, probe_q, s->big.meta.as<WaveMeta>(), (uint32_t)waves_of(sl.n_reads));
         HIPCHK(hipGetLastError());
     } else if (!sl.fused) {
         fill_k1_log(a, sl, sl.lb, true);

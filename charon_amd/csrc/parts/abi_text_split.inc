@@ -75,7 +75,7 @@ extern "C" int chn_text_split(chn_stream *s, chn_text_split_job *j) {
     HIPCHK(hipMemsetAsync(ctl + TSP_FIRST_BAD, 0xFF, 4, s->q_copy));
     hipLaunchKernelGGL(k_split_count, dim3(tile_blocks), dim3(256), 0, s->q_copy, j->text, start, end, tile0, n_tiles, tile_count);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, s->q_copy, tile_count, tile_off, (const uint32_t *)nullptr, n_tiles, ctl + TSP_LINES);
+    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(SCAN_THREADS), 0, s->q_copy, tile_count, tile_off, (const uint32_t *)nullptr, n_tiles, ctl + TSP_LINES);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_split_lines, dim3(tile_blocks), dim3(256), 0, s->q_copy, j->text, start, end, tile0, n_tiles, tile_off, line_start, cap);
     HIPCHK(hipGetLastError());
@@ -83,7 +83,7 @@ extern "C" int chn_text_split(chn_stream *s, chn_text_split_job *j) {
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_split_close, dim3(1), dim3(64), 0, s->q_copy, line_start, ctl, bound);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(256), 0, s->q_copy, a.id_len, x.d_idpos.as<uint32_t>(), ctl + TSP_N, bound, ctl + TSP_IDS_BYTES);
+    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(SCAN_THREADS), 0, s->q_copy, a.id_len, x.d_idpos.as<uint32_t>(), ctl + TSP_N, bound, ctl + TSP_IDS_BYTES);
     HIPCHK(hipGetLastError());
     HIPCHK(x.timer.end(prof, s->q_copy));
     HIPCHK(hipMemcpyAsync(x.h_ctl.p, ctl, TSP_CTL_WORDS * 4, hipMemcpyDeviceToHost, s->q_copy));

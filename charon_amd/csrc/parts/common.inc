@@ -36,20 +36,6 @@ __device__ __constant__ uint64_t c_ibf_seeds[5] = {13572355802537770549ULL, 1304
 
 __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & (WAVE - 1); }
 
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
-    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        uint64_t t = (uint64_t)__shfl_xor((long long)v, o);
-        v = t > v ? t : v;
-    }
-    return v;
-}
-
 // Loads whose completion the KERNEL tracks instead of the compiler (cdna_hip_programming.md 5.7): hipcc does not see a
 // load inside an asm statement, so it inserts no s_waitcnt for it -- the caller must wait before touching the result.
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));

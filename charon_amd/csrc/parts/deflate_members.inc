@@ -116,10 +116,7 @@ struct DflWavePolicy {
     __device__ void add32(uint32_t *p, uint32_t v) const { atomicAdd(p, v); }
     __device__ void or32(uint32_t *p, uint32_t v) const { atomicOr(p, v); }
     __device__ uint32_t excl_scan(uint32_t *a) const {
-        const uint32_t own = a[0];
-        uint32_t s = own;
-#pragma unroll
-        for (int o = 1; o < WAVE; o <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)s, o); if (lane_id() >= (uint32_t)o) s += t; }
+        const uint32_t own = a[0], s = wave_scan(own);
         a[0] = s - own;
         return (uint32_t)__builtin_amdgcn_readlane((int)s, WAVE - 1);
     }
@@ -414,19 +411,12 @@ __global__ void __launch_bounds__(WAVE) k_deflate_members(DeflateArgs a) {
     }
 }
 
-// out_off[i] = the sizes in front of member i, out_off[n] = their sum; one wavefront
-__global__ void __launch_bounds__(WAVE) k_deflate_scan(const uint32_t *out_len, uint64_t *out_off, uint32_t n) {
-    uint64_t carry = 0;
-    for (uint32_t b = 0; b < n; b += WAVE) {
-        const uint32_t i = b + lane_id();
-        const uint32_t own = i < n && out_len[i] <= DFL_SLOT ? out_len[i] : 0;  // (a member that failed its size check takes no room)
-        uint32_t s = own;
-#pragma unroll
-        for (int o = 1; o < WAVE; o <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)s, o); if (lane_id() >= (uint32_t)o) s += t; }
-        if (i < n) out_off[i] = carry + s - own;
-        carry += (uint32_t)__builtin_amdgcn_readlane((int)s, WAVE - 1);
-    }
-    if (lane_id() == 0) out_off[n] = carry;
+// out_off[i] = the sizes in front of member i, out_off[n] = their sum; one workgroup (array_scan, scan.inc)
+__global__ void __launch_bounds__(SCAN_THREADS) k_deflate_scan(const uint32_t *out_len, uint64_t *out_off, uint32_t n) {
+    const uint64_t sum = array_scan<SCAN_THREADS, uint64_t>(
+        n, [&](uint32_t i) { const uint32_t len = out_len[i]; return len <= DFL_SLOT ? len : 0u; },  // (a member that failed its size check takes no room)
+        [&](uint32_t i, uint64_t at) { out_off[i] = at; });
+    if (threadIdx.x == 0) out_off[n] = sum;
 }
 
 // the members back to back: member blockIdx.x from its slot to packed + out_off; whole destination words where it can

@@ -12,51 +12,21 @@ struct EfArgs {
     uint32_t wl, W, B, TB;
 };
 __global__ __launch_bounds__(256) void k_ef_block_counts(const uint64_t *high, uint64_t n, uint32_t *block_ones) {
-    __shared__ uint32_t s[256];
     const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
-    s[threadIdx.x] = i < n ? (uint32_t)__popcll(high[i]) : 0u;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o]; __syncthreads(); }
-    if (threadIdx.x == 0) block_ones[blockIdx.x] = s[0];
+    uint32_t ones;
+    block_scan<256>(i < n ? (uint32_t)__popcll(high[i]) : 0u, ones);
+    if (threadIdx.x == 0) block_ones[blockIdx.x] = ones;
 }
-// exclusive prefix of the per-block counts, by one workgroup (a slice has some 10^4 blocks): keeps a slice's whole chain on the device
-__global__ __launch_bounds__(1024) void k_ef_block_prefix(const uint32_t *counts, uint64_t n, uint64_t *prefix) {
-    __shared__ uint64_t s[1024];
-    __shared__ uint64_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (uint64_t base = 0; base < n; base += 1024) {
-        const uint64_t i = base + threadIdx.x;
-        const uint64_t v = i < n ? counts[i] : 0;
-        s[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 1; o < 1024; o <<= 1) {
-            const uint64_t add = (int)threadIdx.x >= o ? s[threadIdx.x - o] : 0;
-            __syncthreads();
-            s[threadIdx.x] += add;
-            __syncthreads();
-        }
-        if (i < n) prefix[i] = carry + s[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += s[1023];
-        __syncthreads();
-    }
+// exclusive prefix of the per-block counts, by one workgroup (a slice has some 10^4 blocks: n < 2^32): keeps a slice's whole chain on the device
+__global__ __launch_bounds__(SCAN_THREADS) void k_ef_block_prefix(const uint32_t *counts, uint64_t n, uint64_t *prefix) {
+    array_scan<SCAN_THREADS, uint64_t>((uint32_t)n, [&](uint32_t i) { return counts[i]; }, [&](uint32_t i, uint64_t at) { prefix[i] = at; });
 }
 __global__ __launch_bounds__(256) void k_ef_decode(const EfArgs a, const uint64_t *block_prefix /* exclusive, per 256-word block */) {
-    __shared__ uint32_t s[256];
     const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
     const uint64_t word = i < a.n_high_words ? a.high[i] : 0ULL;
-    const uint32_t pc = (uint32_t)__popcll(word);
-    s[threadIdx.x] = pc;
-    __syncthreads();
-    // exclusive scan of the 256 popcounts (Hillis-Steele)
-    for (int o = 1; o < 256; o <<= 1) {
-        const uint32_t v = (int)threadIdx.x >= o ? s[threadIdx.x - o] : 0u;
-        __syncthreads();
-        s[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint64_t k = a.ones_before + block_prefix[blockIdx.x] + (s[threadIdx.x] - pc);  // rank of this word's first one
+    uint32_t block_ones;
+    const uint32_t before = block_scan<256>((uint32_t)__popcll(word), block_ones);  // ones of the block's words in front of this one
+    uint64_t k = a.ones_before + block_prefix[blockIdx.x] + before;  // rank of this word's first one
     uint64_t x = word;
     const uint64_t bit0 = a.high_bit0 + i * 64;
     const uint64_t lowmask = a.wl >= 64 ? ~0ULL : ((1ULL << a.wl) - 1);

@@ -114,21 +114,12 @@ struct EfEncArgs {
     uint32_t wl;
 };
 __global__ __launch_bounds__(256) void k_ef_encode(const EfEncArgs a, const uint64_t *block_prefix /* exclusive, per 256-word block */) {
-    __shared__ uint32_t s[256];
     const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
     const uint64_t word = i < a.n_words ? a.words[i] : 0ULL;
-    const uint32_t pc = (uint32_t)__popcll(word);
-    s[threadIdx.x] = pc;
-    __syncthreads();
-    // exclusive scan of the 256 popcounts (Hillis-Steele), as in k_ef_decode
-    for (int o = 1; o < 256; o <<= 1) {
-        const uint32_t v = (int)threadIdx.x >= o ? s[threadIdx.x - o] : 0u;
-        __syncthreads();
-        s[threadIdx.x] += v;
-        __syncthreads();
-    }
+    uint32_t block_ones;
+    const uint32_t before = block_scan<256>((uint32_t)__popcll(word), block_ones);  // ones of the block's words in front of this one
     if (!word) return;
-    const uint64_t k = a.ones_before + block_prefix[blockIdx.x] + (s[threadIdx.x] - pc);  // 64-bit: the high ranks of a large index pass 2^32
+    const uint64_t k = a.ones_before + block_prefix[blockIdx.x] + before;  // 64-bit: the high ranks of a large index pass 2^32
     const uint32_t bad = ef_encode_word(word, a.pos0 + i * 64, k, a.wl, a.out, EfOrAtomic());
     if (bad) atomicAdd(a.bad, (unsigned long long)bad);
 }

@@ -245,8 +245,8 @@ __global__ void __launch_bounds__(256) k_fasta_tiles(const uint8_t *text, uint64
             kept_in += (uint32_t)__popc(x.kept());
             feed_in += (uint32_t)__popc(x.header_feeds());
         }
-        n_hdr = tsp_wave_sum(n_hdr); kept_pre = tsp_wave_sum(kept_pre); feed_pre = tsp_wave_sum(feed_pre);
-        kept_in = tsp_wave_sum(kept_in); feed_in = tsp_wave_sum(feed_in);
+        n_hdr = wave_sum(n_hdr); kept_pre = wave_sum(kept_pre); feed_pre = wave_sum(feed_pre);
+        kept_in = wave_sum(kept_in); feed_in = wave_sum(feed_in);
         if (lane_id() == 0) {
             FspTile o;
             o.state = x.state; o.n_hdr = n_hdr; o.kept_pre = kept_pre; o.feed_pre = feed_pre; o.kept_in = kept_in; o.feed_in = feed_in;
@@ -322,7 +322,7 @@ __global__ void __launch_bounds__(256) k_fasta_headers(const uint8_t *text, uint
             x.step(text, p, start, end);
             const uint32_t kept = x.kept(), hf = x.header_feeds();
             const uint32_t c2 = (uint32_t)__popc(x.hs) | ((uint32_t)__popc(hf) << 16), ck = (uint32_t)__popc(kept);  // (at most 1024 each a round)
-            const uint32_t i2 = tsp_wave_scan(c2), ik = tsp_wave_scan(ck);
+            const uint32_t i2 = wave_scan(c2), ik = wave_scan(ck);
             uint32_t rank_h = hr + ((i2 - c2) & 0xFFFFu), rank_f = fr + ((i2 - c2) >> 16);
             const uint32_t kb = kr + ik - ck;
             for (uint32_t b = 0; b < 16; ++b) {  // (sixteen rounds whatever the bytes are)
@@ -405,7 +405,7 @@ __global__ void __launch_bounds__(256) k_fasta_compact(const uint8_t *text, uint
 #pragma unroll
         for (uint32_t k = 0; k < TSP_TILE / (WAVE * 16); ++k) {
             x.step(text, tile_base + k * WAVE * 16 + lane_id() * 16, start, end);
-            const uint32_t kept = x.kept(), c = (uint32_t)__popc(kept), incl = tsp_wave_scan(c);
+            const uint32_t kept = x.kept(), c = (uint32_t)__popc(kept), incl = wave_scan(c);
             uint32_t pos = at + incl - c;
 #pragma unroll
             for (uint32_t b = 0; b < 16; ++b)

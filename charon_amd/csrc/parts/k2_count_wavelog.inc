@@ -228,35 +228,19 @@ __global__ void k_wave_caps(const uint32_t *order, const uint32_t *len1, const u
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t v = 0;
     if (i < n) { const uint32_t r = order[i]; v = len1[r] + (len2 ? len2[r] : 0u); }
-    uint64_t sum = v;
-    for (int o = 32; o > 0; o >>= 1) sum += (uint64_t)__shfl_xor((long long)sum, o);
+    const uint64_t sum = wave_sum((uint64_t)v);
     if (lane_id() == 0 && i < n) {
         const uint64_t cap = wave_log_cap(sum, cap_num);
         meta[i / WAVE].base = cap;
         meta[i / WAVE].esc_base = wave_esc_cap(cap, esc_shift);
     }
 }
-__global__ __launch_bounds__(1024) void k_scan_meta(WaveMeta *v, uint32_t n) {  // in place exclusive scan of both fields, single workgroup
-    __shared__ uint64_t part[1024][2];
-    const uint32_t per = (n + 1023) / 1024, lo = threadIdx.x * per, hi = min(n, lo + per);
-    uint64_t s0 = 0, s1 = 0;
-    for (uint32_t i = lo; i < hi; ++i) { s0 += v[i].base; s1 += v[i].esc_base; }
-    part[threadIdx.x][0] = s0; part[threadIdx.x][1] = s1;
-    __syncthreads();
-    if (threadIdx.x < 2) { uint64_t run = 0; for (int i = 0; i < 1024; ++i) { const uint64_t t = part[i][threadIdx.x]; part[i][threadIdx.x] = run; run += t; } }
-    __syncthreads();
-    uint64_t r0 = part[threadIdx.x][0], r1 = part[threadIdx.x][1];
-    for (uint32_t i = lo; i < hi; ++i) { const uint64_t t0 = v[i].base, t1 = v[i].esc_base; v[i].base = r0; v[i].esc_base = r1; r0 += t0; r1 += t1; }
+__global__ __launch_bounds__(SCAN_THREADS) void k_scan_meta(WaveMeta *v, uint32_t n) {  // in place exclusive scan of both fields, single workgroup
+    array_scan<SCAN_THREADS, uint64_t>(n, [&](uint32_t i) { return v[i].base; }, [&](uint32_t i, uint64_t at) { v[i].base = at; });
+    array_scan<SCAN_THREADS, uint64_t>(n, [&](uint32_t i) { return v[i].esc_base; }, [&](uint32_t i, uint64_t at) { v[i].esc_base = at; });
 }
-__global__ __launch_bounds__(1024) void k_scan_u64(uint64_t *v, uint32_t n) {  // in place exclusive scan, single workgroup
-    __shared__ uint64_t part[1024];
-    const uint32_t per = (n + 1023) / 1024, lo = threadIdx.x * per, hi = min(n, lo + per);
-    uint64_t s = 0;
-    for (uint32_t i = lo; i < hi; ++i) s += v[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) { uint64_t run = 0; for (int i = 0; i < 1024; ++i) { const uint64_t t = part[i]; part[i] = run; run += t; } }
-    __syncthreads();
-    uint64_t run = part[threadIdx.x];
-    for (uint32_t i = lo; i < hi; ++i) { const uint64_t t = v[i]; v[i] = run; run += t; }
+// in place exclusive scan of the rows of n values at v, one workgroup a row
+__global__ __launch_bounds__(SCAN_THREADS) void k_scan_u64(uint64_t *v, uint32_t n) {
+    uint64_t *row = v + (size_t)blockIdx.x * n;
+    array_scan<SCAN_THREADS, uint64_t>(n, [&](uint32_t i) { return row[i]; }, [&](uint32_t i, uint64_t at) { row[i] = at; });
 }

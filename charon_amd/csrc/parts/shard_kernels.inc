@@ -37,6 +37,24 @@ __global__ __launch_bounds__(256) void k_probe_partial(const ShardArgs a) {
         }
     }
 }
+// The AND of a minimiser's h rows becomes entry e of the wavefront's log (k_and_partial, k_shx_and): an escaped row claims a slot of the
+// wavefront's region `rows` (ecap rows) from the workgroup's counter s_esc, or raises status bit 0 when the region is full.
+template <int W>
+__device__ __forceinline__ void store_row_entry(const uint64_t *row, uint32_t B, uint32_t *log, uint32_t e, uint64_t *rows, uint32_t ecap, uint32_t *s_esc, uint32_t *status) {
+    bool esc;
+    uint32_t entry = encode_row<W>(row, B, log[e] >> 26, esc);
+    if (esc) {
+        const uint32_t slot = atomicAdd(s_esc, 1u);
+        if (slot < ecap) {
+#pragma unroll
+            for (int w = 0; w < W; ++w) rows[(size_t)slot * W + w] = row[w];
+            entry |= (slot + 1) << 2;
+        } else {
+            atomicOr(status, 1u);
+        }
+    }
+    log[e] = entry;
+}
 template <int W>
 __global__ __launch_bounds__(256) void k_and_partial(const ShardArgs a) {
     __shared__ uint32_t s_esc;
@@ -55,19 +73,7 @@ __global__ __launch_bounds__(256) void k_and_partial(const ShardArgs a) {
             acc[w] = ~0ULL;
             for (uint32_t i = 0; i < a.h; ++i) acc[w] &= in[((size_t)e * a.h + i) * W + w];
         }
-        bool esc;
-        uint32_t entry = encode_row<W>(acc, a.B, log[e] >> 26, esc);
-        if (esc) {
-            const uint32_t slot = atomicAdd(&s_esc, 1u);
-            if (slot < ecap) {
-#pragma unroll
-                for (int w = 0; w < W; ++w) rows[(size_t)slot * W + w] = acc[w];
-                entry |= (slot + 1) << 2;
-            } else {
-                atomicOr(a.status, 1u);
-            }
-        }
-        log[e] = entry;
+        store_row_entry<W>(acc, a.B, log, e, rows, ecap, &s_esc, a.status);
     }
 }
 __global__ __launch_bounds__(256) void k_compact_list(const ShardArgs a, uint64_t *out) {

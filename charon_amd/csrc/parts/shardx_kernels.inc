@@ -65,20 +65,7 @@ __global__ __launch_bounds__(SHX_THREADS) void k_shx_count(const ShxArgs a) {
         if (g == 0) a.cnt[(size_t)threadIdx.x * (a.n_waves + 1) + a.n_waves] = 0;
     }
 }
-// one workgroup per rank: exclusive scan of that rank's per-wavefront counts (the total lands in element n_waves)
-__global__ __launch_bounds__(1024) void k_shx_scan(uint64_t *cnt, uint32_t n_waves) {
-    __shared__ uint64_t part[1024];
-    uint64_t *v = cnt + (size_t)blockIdx.x * (n_waves + 1);
-    const uint32_t n = n_waves + 1, per = (n + 1023) / 1024, lo = threadIdx.x * per, hi = min(n, lo + per);
-    uint64_t s = 0;
-    for (uint32_t i = lo; i < hi; ++i) s += v[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) { uint64_t run = 0; for (int i = 0; i < 1024; ++i) { const uint64_t t = part[i]; part[i] = run; run += t; } }
-    __syncthreads();
-    uint64_t run = part[threadIdx.x];
-    for (uint32_t i = lo; i < hi; ++i) { const uint64_t t = v[i]; v[i] = run; run += t; }
-}
+// (k_scan_u64 with one workgroup per rank then scans that rank's n_waves + 1 counts in place: the total lands in element n_waves)
 
 // Walk wavefront log g in the canonical probe order and hand every probe to `f(e, i, k, valid, row, owner, gpos)`, gpos = its
 // position in the query / response buffers (send_base[owner] + offset of (owner, g) + rank inside (owner, g)).  A chunk is
@@ -213,21 +200,7 @@ __global__ __launch_bounds__(SHX_THREADS) void k_shx_and(const ShxArgs a) {
 #pragma unroll
                     for (int w = 0; w < W; ++w) { acc[kk][w] = (i == 0 ? ~0ULL : acc[kk][w]) & v[w]; v[w] = acc[kk][w]; }
                 }
-            if (i + 1 == a.h) {
-                bool esc;
-                uint32_t entry = encode_row<W>(v, a.B, log[e] >> 26, esc);
-                if (esc) {
-                    const uint32_t slot = atomicAdd(&s_esc, 1u);
-                    if (slot < ecap) {
-#pragma unroll
-                        for (int w = 0; w < W; ++w) rows[(size_t)slot * W + w] = v[w];
-                        entry |= (slot + 1) << 2;
-                    } else {
-                        atomicOr(a.status, 1u);
-                    }
-                }
-                log[e] = entry;
-            }
+            if (i + 1 == a.h) store_row_entry<W>(v, a.B, log, e, rows, ecap, &s_esc, a.status);
         }
     });
 }

@@ -134,18 +134,6 @@ __device__ __forceinline__ uint32_t tsp_piece_feeds(const uint8_t *text, uint64_
     return m & ((1u << hi) - 1u) & ~((1u << lo) - 1u);
 }
 
-__device__ __forceinline__ uint32_t tsp_wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
-}
-// inclusive scan over the lanes of a wavefront
-__device__ __forceinline__ uint32_t tsp_wave_scan(uint32_t v) {
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)v, o); if (lane_id() >= (uint32_t)o) v += t; }
-    return v;
-}
-
 // 1. count: tile t is bytes [(tile0 + t) * TSP_TILE, + TSP_TILE) of the text; one wavefront a tile, a looping grid
 __global__ void __launch_bounds__(256) k_split_count(const uint8_t *text, uint64_t start, uint64_t end, uint64_t tile0, uint32_t n_tiles, uint32_t *tile_count) {
     const uint32_t wave = (blockIdx.x * 256 + threadIdx.x) / WAVE, n_waves = gridDim.x * (256 / WAVE);
@@ -154,37 +142,18 @@ __global__ void __launch_bounds__(256) k_split_count(const uint8_t *text, uint64
         uint32_t c = 0;
 #pragma unroll
         for (uint32_t k = 0; k < TSP_TILE / (WAVE * 16); ++k) c += (uint32_t)__popc(tsp_piece_feeds(text, base + k * WAVE * 16, start, end));
-        c = tsp_wave_sum(c);
+        c = wave_sum(c);
         if (lane_id() == 0) tile_count[t] = c;
     }
 }
 
-// 2. exclusive scan of in[0 .. n) into out, the sum into *total; ONE workgroup of 256 threads, four values a thread and round.
+// 2. exclusive scan of in[0 .. n) into out, the sum into *total; ONE workgroup (array_scan, scan.inc).
 // n is min(*n_dev, n_max) where n_dev is given (the number of records is known on the device only).  The sum stays below 2^32: it
 // counts bytes of a text of at most 2^31.
-__global__ void __launch_bounds__(256) k_split_scan(const uint32_t *in, uint32_t *out, const uint32_t *n_dev, uint32_t n_max, uint32_t *total) {
-    __shared__ uint32_t part[256 / WAVE];
+__global__ void __launch_bounds__(SCAN_THREADS) k_split_scan(const uint32_t *in, uint32_t *out, const uint32_t *n_dev, uint32_t n_max, uint32_t *total) {
     const uint32_t n = n_dev ? min(*n_dev, n_max) : n_max;
-    const uint32_t wv = threadIdx.x / WAVE;
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < n; base += 1024) {
-        const uint32_t i = base + threadIdx.x * 4;
-        uint32_t v[4];
-#pragma unroll
-        for (uint32_t k = 0; k < 4; ++k) v[k] = i + k < n ? in[i + k] : 0u;
-        const uint32_t mine = v[0] + v[1] + v[2] + v[3], incl = tsp_wave_scan(mine);
-        if (lane_id() == WAVE - 1) part[wv] = incl;
-        __syncthreads();
-        uint32_t before = carry, all = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < 256 / WAVE; ++k) { if (k < wv) before += part[k]; all += part[k]; }
-        uint32_t at = before + incl - mine;
-#pragma unroll
-        for (uint32_t k = 0; k < 4; ++k) { if (i + k < n) out[i + k] = at; at += v[k]; }
-        carry += all;
-        __syncthreads();  // part[] is the next round's
-    }
-    if (threadIdx.x == 0) *total = carry;
+    const uint32_t sum = array_scan<SCAN_THREADS, uint32_t>(n, [&](uint32_t i) { return in[i]; }, [&](uint32_t i, uint32_t at) { out[i] = at; });
+    if (threadIdx.x == 0) *total = sum;
 }
 
 // 3. line starts: line feed number `rank` of [start, end) ends line `rank`; line rank + 1 starts behind it.  Only the first `cap` line
@@ -201,7 +170,7 @@ __global__ void __launch_bounds__(256) k_split_lines(const uint8_t *text, uint64
         for (uint32_t k = 0; k < TSP_TILE / (WAVE * 16); ++k) {
             const uint64_t p = base + k * WAVE * 16;
             uint32_t m = tsp_piece_feeds(text, p, start, end);
-            const uint32_t c = (uint32_t)__popc(m), incl = tsp_wave_scan(c);
+            const uint32_t c = (uint32_t)__popc(m), incl = wave_scan(c);
             uint32_t rank = rank0 + incl - c;
             for (uint32_t b = 0; b < 16; ++b)  // (sixteen rounds whatever the bytes are)
                 if (m & (1u << b)) {

@@ -149,7 +149,7 @@ def positions_of(words):
 
 
 _POP8 = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(axis=1).astype(np.uint8)  # set bits of a byte
-PREFIX_CHUNK = 1024  # block counts k_ef_block_prefix takes at a time, with a carry from one chunk to the next
+PREFIX_CHUNK = 1024  # block counts k_ef_block_prefix takes a round (array_scan, parts/scan.inc: 256 threads, four counts each); the sum so far is carried in a register
 BLOCK_WORDS = 256    # words whose ones k_ef_block_counts adds up into one count
 
 
@@ -160,7 +160,7 @@ def block_counts(words):
 
 
 def prefix_chunks(n_words):
-    """rounds of k_ef_block_prefix's loop for the blocks of n_words words"""
+    """rounds of 1024 counts that k_ef_block_prefix's scan takes for the blocks of n_words words"""
     n_blocks = (n_words + BLOCK_WORDS - 1) // BLOCK_WORDS
     return (n_blocks + PREFIX_CHUNK - 1) // PREFIX_CHUNK
 
@@ -190,7 +190,7 @@ def _random_words(rng, n, ands, ors=0):
     return w
 
 
-# Shapes whose slices have thousands of 256-word blocks, so that k_ef_block_prefix goes round its loop and carries.  64 bins, one word a
+# Shapes whose slices have thousands of 256-word blocks, so that k_ef_block_prefix's scan takes several rounds of 1024 counts and carries from one to the next.  64 bins, one word a
 # row.  They are kept apart from CASES: oracle.pyref is never asked for them; the expected arrays are ef_encode_np's.
 #
 # many_blocks: one bit in eight, ~2^24 + 2.6e5 ones in 2^27.02 bits: logm = 25, logn = 28, wl = 3.  m_high has ~790 000 words = ~3090

@@ -1,5 +1,5 @@
-"""GPU tests of the Elias-Fano kernels where the small cases do not reach: slices of thousands of 256-word blocks (k_ef_block_prefix
-goes round its loop and carries) through chn_index_encode_ef and chn_index_decode_ef; decode slices that begin in the middle of a word of
+"""GPU tests of the Elias-Fano kernels where the small cases do not reach: slices of thousands of 256-word blocks (k_ef_block_prefix's
+scan takes several rounds of 1024 counts and carries the sum in a register) through chn_index_encode_ef and chn_index_decode_ef; decode slices that begin in the middle of a word of
 m_low at every wl the cases have; decodes of the whole vector into row shards; and vectors sdsl does not write (positions beyond m_size,
 wl = 0).  Every comparison is word for word: with oracle.pyref.ef_encode for the small cases, with its numpy restatement ef_encode_np
 (pinned to pyref in test_ef_encode_cpu.py) for the large ones, with the positions' own words for what a decode leaves."""
