@@ -178,6 +178,10 @@ class EfEncodeJob(C.Structure):
                 ("ones_written", C.c_uint64), ("device_ms", C.c_double)]
 
 
+class HashSetCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("tile_keys", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class SynthReadsOut(C.Structure):
     _fields_ = [("bases2", C.c_void_p), ("seg1_offset", C.c_void_p), ("seg1_length", C.c_void_p), ("mean_quality", C.c_void_p),
                 ("compression", C.c_void_p), ("n_bases", C.c_uint64)]
@@ -189,7 +193,7 @@ EXPORTS = ["chn_index_create", "chn_index_upload_rows", "chn_index_device_words"
            "chn_model_set", "chn_batch_submit", "chn_batch_wait", "chn_stream_sync", "chn_classify_counts", "chn_classify_counts_raw", "chn_stream_profile",
            "chn_stream_last_batch_bytes", "chn_synth_genomes", "chn_synth_fill_index", "chn_synth_plant", "chn_synth_reads",
            "chn_device_free", "chn_device_download", "chn_device_malloc", "chn_device_upload", "chn_host_alloc", "chn_host_free", "chn_shard_minimise",
-           "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_index_decode_ef", "chn_ef_layout_of", "chn_index_ef_layout", "chn_index_encode_ef", "chn_index_encode_ef_host", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_text_submit", "chn_text_wait", "chn_text_pack", "chn_text_split", "chn_text_split_host", "chn_fasta_split", "chn_fasta_split_host", "chn_text_fetch", "chn_text_fetch_host", "chn_text_pair_ids", "chn_text_pair_ids_host", "chn_device_copy", "chn_inflate_create", "chn_inflate_run",
+           "chn_shard_probe", "chn_shard_finish", "chn_shardx_minimise", "chn_shardx_counts", "chn_shardx_queries", "chn_shardx_serve", "chn_shardx_finish", "chn_minimisers", "chn_index_emplace", "chn_hashset_create", "chn_hashset_destroy", "chn_hashset_append", "chn_minimisers_into", "chn_hashset_unique", "chn_hashset_size", "chn_hashset_download", "chn_index_emplace_set", "chn_device_memory", "chn_index_decode_ef", "chn_ef_layout_of", "chn_index_ef_layout", "chn_index_encode_ef", "chn_index_encode_ef_host", "chn_index_bin_popcounts", "chn_index_replicate", "chn_device_count", "chn_index_gather_roof", "chn_text_submit", "chn_text_wait", "chn_text_pack", "chn_text_split", "chn_text_split_host", "chn_fasta_split", "chn_fasta_split_host", "chn_text_fetch", "chn_text_fetch_host", "chn_text_pair_ids", "chn_text_pair_ids_host", "chn_device_copy", "chn_inflate_create", "chn_inflate_run",
            "chn_inflate_run_host", "chn_inflate_destroy", "chn_inflate_kernel_ms", "chn_inflate_run_crc", "chn_inflate_run_host_crc", "chn_inflate_stream_run", "chn_inflate_stream_run_host", "chn_inflate_stream_search_host", "chn_deflate_create", "chn_deflate_run", "chn_deflate_run_host",
            "chn_deflate_destroy", "chn_deflate_bound", "chn_deflate_kernel_ms", "chn_deflate_group_members", "chn_extract_create", "chn_extract_destroy",
            "chn_extract_bound", "chn_extract_append_records", "chn_extract_append_bytes", "chn_extract_finish", "chn_extract_records_host",
@@ -235,6 +239,15 @@ _L.chn_shardx_serve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, 
 _L.chn_shardx_finish.argtypes = [C.c_void_p, C.c_void_p]
 _L.chn_minimisers.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
 _L.chn_index_emplace.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
+_L.chn_hashset_create.argtypes = [C.POINTER(HashSetCfg), C.POINTER(C.c_void_p)]
+_L.chn_hashset_destroy.argtypes = [C.c_void_p]
+_L.chn_hashset_append.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+_L.chn_minimisers_into.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.POINTER(C.c_uint64)]
+_L.chn_hashset_unique.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+_L.chn_hashset_size.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+_L.chn_hashset_download.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+_L.chn_index_emplace_set.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+_L.chn_device_memory.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
 _L.chn_index_decode_ef.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64,
                                    C.POINTER(C.c_uint64)]
 _L.chn_ef_layout_of.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(EfLayout)]
@@ -414,6 +427,10 @@ class Index:
         values = np.ascontiguousarray(values, dtype=np.uint64)
         _chk(_L.chn_index_emplace(self.h, values.ctypes.data, values.size, bin_index))
 
+    def emplace_set(self, hashset, bin_index):
+        """chn_index_emplace_set: emplace every value of the device-resident set, read in place"""
+        _chk(_L.chn_index_emplace_set(self.h, hashset.h, bin_index))
+
     def gather_roof(self, nt=True):
         """row fetches per second this device sustains for nothing but random probes of this index (measurement aid)"""
         r = C.c_double()
@@ -430,6 +447,49 @@ class Index:
         if self.h:
             _L.chn_index_destroy(self.h)
             self.h = None
+
+
+class HashSet:
+    """chn_hashset: 64-bit values in device memory (tile_keys: test hook, 0 = default)"""
+
+    def __init__(self, device=0, tile_keys=0):
+        cfg = HashSetCfg(C.sizeof(HashSetCfg), device, tile_keys, 0)
+        self.h = C.c_void_p()
+        _chk(_L.chn_hashset_create(C.byref(cfg), C.byref(self.h)))
+
+    def append(self, values):
+        values = np.ascontiguousarray(values, dtype=np.uint64)
+        _chk(_L.chn_hashset_append(self.h, values.ctypes.data if values.size else None, values.size))
+
+    def unique(self):
+        """sort ascending and drop repeats; returns the number of distinct values"""
+        n = C.c_uint64()
+        _chk(_L.chn_hashset_unique(self.h, C.byref(n)))
+        return n.value
+
+    def size(self):
+        """(values held, device bytes held)"""
+        n, b = C.c_uint64(), C.c_uint64()
+        _chk(_L.chn_hashset_size(self.h, C.byref(n), C.byref(b)))
+        return n.value, b.value
+
+    def download(self, first=0, n=None):
+        n = self.size()[0] - first if n is None else n
+        out = np.zeros(max(n, 0), np.uint64)
+        _chk(_L.chn_hashset_download(self.h, first, n, out.ctypes.data if out.size else None))
+        return out
+
+    def destroy(self):
+        if self.h:
+            _L.chn_hashset_destroy(self.h)
+            self.h = None
+
+
+def device_memory(device=0):
+    """chn_device_memory: (free bytes, total bytes) of a device"""
+    f, t = C.c_uint64(), C.c_uint64()
+    _chk(_L.chn_device_memory(device, C.byref(f), C.byref(t)))
+    return f.value, t.value
 
 
 _POP8 = np.array([bin(i).count("1") for i in range(256)], np.uint8)  # set bits of a byte
@@ -546,6 +606,13 @@ class Stream:
         e = C.c_uint64()
         _chk(_L.chn_minimisers(self.h, C.byref(b), out.ctypes.data, cap, C.byref(e)))
         return out[:e.value]
+
+    def minimisers_into(self, packed, hashset):
+        """chn_minimisers_into: the batch's minimisers (with repeats) appended to the device-resident set; returns how many"""
+        b, keep, n = self._host_batch(packed, None, None)
+        e = C.c_uint64()
+        _chk(_L.chn_minimisers_into(self.h, C.byref(b), hashset.h, C.byref(e)))
+        return e.value
 
     # ---- row-sharded mode (see include/charon_hip.h) ----
     def shard_minimise_host(self, packed, mean_quality=None, compression=None):

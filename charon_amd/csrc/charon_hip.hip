@@ -52,6 +52,7 @@
 #include "parts/scan.inc"
 #include "parts/lds_budget.hpp"
 #include "parts/rowlog_entry.hpp"
+#include "parts/radix_plan.hpp"
 #include "parts/k1_minimise_probe.inc"
 #include "parts/k2_count_wavelog.inc"
 #include "parts/shard_kernels.inc"
@@ -75,6 +76,7 @@
 #include "parts/deflate_members.inc"
 #include "parts/ef_decode.inc"
 #include "parts/ef_encode.inc"
+#include "parts/radix_sort.inc"
 #include "parts/synth_kernels.inc"
 #include "parts/batch_plan.inc"
 #include "parts/abi_device_call.inc"
@@ -82,6 +84,7 @@
 #include "parts/abi_ef_encode.inc"
 #include "parts/abi_stream_batch.inc"
 #include "parts/abi_shard_wait.inc"
+#include "parts/abi_hashset.inc"
 #include "parts/abi_text_split.inc"
 #include "parts/abi_fasta_split.inc"
 #include "parts/abi_text_fetch.inc"

@@ -61,6 +61,7 @@
 
 #include "charon_hip.h"
 #include "gzip_size.hpp"
+#include "../parts/radix_plan.hpp"  // what a chn_hashset_unique call takes in scratch: the index builder weighs it against its budget
 
 #ifndef CHARON_VERSION
 #define CHARON_VERSION "charon-mi355x 0.1.0 (reference behaviour: rmcolq/charon @ 2025-07-04)"
@@ -420,6 +421,14 @@ int main(int argc, char **argv) {
             const std::string v(e);
             if (v != "0" && v != "1") { std::cerr << "charon: CHARON_GPU_INDEX_EF: '" << v << "' is neither 0 nor 1" << std::endl; return 1; }
             iopt.gpu_ef = v == "1";
+        }
+        if (const char *e = std::getenv("CHARON_GPU_INDEX_SETS")) {
+            // CHARON_GPU_INDEX_SETS: 1 = every bin's minimisers stay in device memory, are sorted and made distinct there and emplaced in place
+            // (chn_hashset), 0 or unset = they come to the host, are sorted by the -t threads and uploaded again; anything else is an
+            // error.  Read by `charon index` alone.
+            const std::string v(e);
+            if (v != "0" && v != "1") { std::cerr << "charon: CHARON_GPU_INDEX_SETS: '" << v << "' is neither 0 nor 1" << std::endl; return 1; }
+            iopt.gpu_sets = v == "1";
         }
         try {
             index_main(iopt);

@@ -15,6 +15,7 @@ struct IndexArguments {
     bool optimize = false;
     int device = 0;
     bool gpu_ef = false;  // CHARON_GPU_INDEX_EF=1: the Elias-Fano arrays are encoded on the device (chn_index_encode_ef)
+    bool gpu_sets = false;  // CHARON_GPU_INDEX_SETS=1: the bins' minimisers stay in device memory (chn_hashset), sorted and made distinct there
 };
 
 bool parse_index(int argc, char **argv, IndexArguments &opt) {
@@ -168,6 +169,49 @@ void sort_unique(std::vector<uint64_t> &v, int threads) {
     v.erase(std::unique(v.begin(), v.end()), v.end());
 }
 
+// CHARON_GPU_INDEX_SETS=1: the bins' minimiser sets in device memory and the budget of bytes they share.  The sets must not end a run
+// that the host path would have finished: when the set being filled would pass the budget, cannot get its memory or reaches 2^32
+// values, it comes down into the bin's host vector and that bin and every later one take the host path (spill); the sets of the
+// bins done stay where they are.
+struct DeviceSets {
+    bool on = false;                    // the bin being read, and those behind it, still go to the device
+    uint64_t budget = 0;                // bytes; default: half of what the device had free at the start (a guess, not a tuned value)
+    uint64_t compact_at = 1ULL << 26;   // values appended to a set before it is made distinct inside the loop, as on the host path
+    uint64_t held_done = 0;             // bytes the sets of the bins done hold
+    std::vector<chn_hashset *> set;     // per bin; null: the bin's minimisers are in its host vector
+    std::vector<uint64_t> appended;     // per bin: values that went from the minimiser kernel's log into the set
+    uint64_t held_with(const chn_hashset *h, uint64_t *n = nullptr) const {
+        uint64_t nn = 0, bytes = 0;
+        CHN_CHECK(chn_hashset_size(h, &nn, &bytes));
+        if (n) *n = nn;
+        return held_done + bytes;
+    }
+    // chn_hashset_unique if its scratch fits the budget and the device has it; false: it did not run, the set is as it was
+    bool unique(chn_hashset *h, uint64_t &distinct) const {
+        uint64_t n = 0;
+        const uint64_t held = held_with(h, &n);
+        if (held + radix_scratch_bytes(n, RADIX_TILE_DEFAULT) > budget) return false;
+        const int rc = chn_hashset_unique(h, &distinct);
+        if (rc == CHN_E_NOMEM) return false;
+        if (rc != CHN_OK) throw std::runtime_error(std::string("chn_hashset_unique failed: ") + chn_last_error());
+        return true;
+    }
+    // the set of `bin` comes down behind the values `host` holds; from here on every bin takes the host path
+    void spill(uint8_t bin, std::vector<uint64_t> &host, const std::string &why) {
+        chn_hashset *h = set[bin];
+        uint64_t n = 0;
+        (void)unique(h, n);  // fewer values to bring down, if it can be done
+        (void)held_with(h, &n);
+        const size_t old = host.size();
+        host.resize(old + n);
+        CHN_CHECK(chn_hashset_download(h, 0, n, host.data() + old));
+        chn_hashset_destroy(h);
+        set[bin] = nullptr; appended[bin] = 0; on = false;
+        g_log.info("CHARON_GPU_INDEX_SETS=1: bin " + std::to_string(bin) + " and the bins behind it take the host path (" + why + "); " + std::to_string(n) +
+                   " values of its set came down");
+    }
+};
+
 int index_main(IndexArguments &opt) {
     g_log.open(opt.log_file, opt.verbosity);
     g_reader_threads = reader_threads_for(opt.threads);
@@ -215,6 +259,16 @@ int index_main(IndexArguments &opt) {
     d0.struct_size = sizeof d0; d0.device = opt.device; d0.kmer_size = opt.kmer_size; d0.window_size = opt.window_size; d0.hash_funs = opt.num_hash;
     d0.num_categories = 1; d0.host_index = 255; d0.minimiser_seed = 0x8F3F73B5CF1C9ADEULL;
     d0.bins = 1; d0.technical_bins = 64; d0.bin_size = 64; d0.hash_shift = (uint64_t)__builtin_clzll(64ULL); d0.bin_words = 1;
+    DeviceSets sets;
+    sets.set.assign(meta.num_bins, nullptr); sets.appended.assign(meta.num_bins, 0);
+    if (opt.gpu_sets) {
+        sets.on = true;
+        uint64_t free_bytes = 0, total_bytes = 0;
+        CHN_CHECK(chn_device_memory(opt.device, &free_bytes, &total_bytes));
+        sets.budget = free_bytes / 2;
+        if (const char *e = std::getenv("CHARON_INDEX_SETS_BUDGET")) sets.budget = std::strtoull(e, nullptr, 10);  // test hook
+        if (const char *e = std::getenv("CHARON_INDEX_SETS_COMPACT")) sets.compact_at = std::strtoull(e, nullptr, 10);  // test hook
+    }
     chn_index *probe_index = nullptr;
     CHN_CHECK(chn_index_create(&d0, &probe_index));
     const uint64_t max_bases = 1ULL << 28;
@@ -235,6 +289,13 @@ int index_main(IndexArguments &opt) {
         std::vector<uint64_t> &set = hashes[bin];
         uint64_t record_count = 0;
         std::vector<uint64_t> values;
+        uint64_t since_unique = 0, distinct = 0;  // of the bin's device set
+        if (sets.on) {
+            chn_hashset_cfg hc;
+            std::memset(&hc, 0, sizeof hc);
+            hc.struct_size = sizeof hc; hc.device = opt.device;
+            CHN_CHECK(chn_hashset_create(&hc, &sets.set[bin]));
+        }
         // two blocks: while the device minimises block i (and the host packs, sorts), a helper thread reads and unwraps block i + 1
         RawBlock blks[2];
         int cur = 0;
@@ -291,8 +352,26 @@ int index_main(IndexArguments &opt) {
                 std::memset(&bt, 0, sizeof bt);
                 bt.struct_size = sizeof bt; bt.n_reads = coff.size(); bt.n_bases = sub.n_bases; bt.bases2 = sub.bases.data();
                 bt.nmask = sub.any_n ? sub.nmask.data() : nullptr; bt.seg1_offset = coff.data(); bt.seg1_length = clen.data();
-                values.resize(sub.n_bases + (uint64_t)opt.window_size * coff.size());
                 uint64_t nv = 0;
+                if (chn_hashset *hs = sets.set[bin]) {
+                    // the batch's minimisers go from the kernel's log into the set, device to device; only their number comes back
+                    const int rc = chn_minimisers_into(stream, &bt, hs, &nv);
+                    if (rc == CHN_OK) {
+                        sets.appended[bin] += nv; since_unique += nv;
+                        lap(t_min);
+                        if (sets.held_with(hs) > sets.budget) sets.spill(bin, set, "the sets would hold more than the budget of " + std::to_string(sets.budget) + " bytes");
+                        else if (since_unique > sets.compact_at) {
+                            if (sets.unique(hs, distinct)) { since_unique = 0; lap(t_sort); }
+                            else sets.spill(bin, set, "no room to sort its set within the budget of " + std::to_string(sets.budget) + " bytes");
+                        }
+                        if (!sets.set[bin]) lap(t_min);  // (the download of a spilled set)
+                        continue;
+                    }
+                    if (rc != CHN_E_NOMEM && rc != CHN_E_CAPACITY) throw std::runtime_error(std::string("chn_minimisers_into failed: ") + chn_last_error());
+                    // the set is as it was; this batch, too, goes the host's way
+                    sets.spill(bin, set, rc == CHN_E_NOMEM ? "the device has no memory for its set" : "its set is full");
+                }
+                values.resize(sub.n_bases + (uint64_t)opt.window_size * coff.size());
                 CHN_CHECK(chn_minimisers(stream, &bt, values.data(), values.size(), &nv));
                 set.insert(set.end(), values.begin(), values.begin() + (long)nv);
                 lap(t_min);
@@ -302,11 +381,15 @@ int index_main(IndexArguments &opt) {
             cur ^= 1;
         }
         lap(t_read);
-        sort_unique(set, opt.threads);
+        if (chn_hashset *hs = sets.set[bin]) {
+            if (sets.unique(hs, distinct)) sets.held_done = sets.held_with(hs);
+            else { sets.spill(bin, set, "no room to sort its set within the budget of " + std::to_string(sets.budget) + " bytes"); lap(t_min); }
+        }
+        if (!sets.set[bin]) { sort_unique(set, opt.threads); distinct = set.size(); }
         lap(t_sort);
         meta.records_per_bin[bin] += record_count;
-        meta.hashes_per_bin[bin] += set.size();
-        g_log.info("Added file " + fb.first + " with " + std::to_string(record_count) + " records and " + std::to_string(set.size()) + " hashes to bin " + std::to_string(bin));
+        meta.hashes_per_bin[bin] += distinct;
+        g_log.info("Added file " + fb.first + " with " + std::to_string(record_count) + " records and " + std::to_string(distinct) + " hashes to bin " + std::to_string(bin));
     }
     chn_stream_destroy(stream);
     chn_index_destroy(probe_index);
@@ -365,11 +448,25 @@ int index_main(IndexArguments &opt) {
     for (uint64_t b = 0; b < meta.bins; ++b) d.bin_to_category[b] = meta.category_index(meta.bin_to_category.at((uint8_t)b));
     chn_index *index = nullptr;
     CHN_CHECK(chn_index_create(&d, &index));
+    uint64_t bins_on_device = 0;
     for (const auto &kv : bucket_to_bins)
         for (uint8_t bin : kv.second) {
+            if (chn_hashset *hs = sets.set[bin]) {
+                bins_on_device += 1;
+                CHN_CHECK(chn_index_emplace_set(index, hs, kv.first));
+                chn_hashset_destroy(hs);
+                sets.set[bin] = nullptr;
+                continue;
+            }
             CHN_CHECK(chn_index_emplace(index, hashes[bin].data(), hashes[bin].size(), kv.first));
             std::vector<uint64_t>().swap(hashes[bin]);
         }
+    if (opt.gpu_sets) {
+        uint64_t values_on_device = 0;
+        for (uint64_t a : sets.appended) values_on_device += a;
+        g_log.info("CHARON_GPU_INDEX_SETS=1: the minimiser sets of " + std::to_string(bins_on_device) + " of " + std::to_string(sets.appended.size()) +
+                   " bins stayed on device " + std::to_string(opt.device) + " (" + std::to_string(values_on_device) + " values never crossed to the host)");
+    }
 
     lap(t_emplace);
     // Index(...) compresses the IBF (include/index.hpp:43-50) and store_index writes it (include/store_index.hpp:12-17)

@@ -7,8 +7,8 @@
 //                                     the carry from round to round in a register
 // Every thread of the workgroup calls block_scan / array_scan, with the same n: both hold barriers.  The sums are unsigned and wrap; a
 // caller that wants 64-bit sums of 32-bit values asks for T = uint64_t and converts in its load.
-// Callers: k_split_scan, k_deflate_scan, k_ef_block_prefix, k_scan_u64, k_scan_meta (array_scan); k_ef_block_counts, k_ef_decode,
-// k_ef_encode (block_scan); k_wave_caps, the text / FASTA splitters, DflWavePolicy (the wave forms).  tools/scan_check.hip checks all of it.
+// Callers: k_split_scan, k_deflate_scan, k_ef_block_prefix, k_scan_u64, k_scan_meta, k_radix_offsets, k_unique_offsets (array_scan);
+// k_ef_block_counts, k_ef_decode, k_ef_encode, k_radix_offsets, k_unique_count, k_unique_compact (block_scan); k_wave_caps, the text / FASTA splitters, DflWavePolicy (the wave forms).  tools/scan_check.hip checks all of it.
 
 // sum over the lanes, to every lane
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {

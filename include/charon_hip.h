@@ -626,6 +626,47 @@ int chn_shardx_finish(chn_stream *s, const uint64_t *dev_rows_back);
 int chn_minimisers(chn_stream *s, const chn_batch *b, uint64_t *host_values, uint64_t capacity, uint64_t *n_values);
 int chn_index_emplace(chn_index *idx, const uint64_t *host_values, uint64_t n_values, uint32_t bin);
 
+/* ---- minimiser sets in device memory (`charon index`, src/index_main.cpp:141-149,247-255) ----------------------------------
+ * The reference collects the minimisers of a file in an std::unordered_set (:141-149) and re-inserts every one of them into the
+ * bucket's bin (:247-255).  A chn_hashset is that set kept in HBM: 64-bit values in one device buffer, appended to device to device,
+ * made distinct by a radix sort and a unique pass on the device, and read in place by the emplace.  Only counts cross to the host.
+ * A set is used by ONE thread at a time; every call is synchronous.  Every call checks its arguments before its first HIP call
+ * (CHN_E_INVALID: a null pointer, a wrong struct_size, a tile_keys that is neither 0 nor a multiple of 256 up to 65 536, a non-zero
+ * `reserved`), and every refusal, a failed allocation included, leaves the set holding the values it held and the caller's memory as it was.
+ * Memory rule: the set owns one buffer, bytes_held bytes of it; an append that does not fit allocates max(need, twice the size),
+ * copies device to device and frees the old buffer.  chn_hashset_unique takes scratch of its own (a second key buffer of n values,
+ * 1 KiB of counters per tile of 4 096 keys, 18 KiB of histograms), frees it before it returns, and leaves the set in a buffer of
+ * exactly n_distinct values.  A failed hipMalloc is CHN_E_NOMEM and the set stays valid (chn_hashset_download still gives every value).
+ * A set holds fewer than 2^32 values: an append beyond that is CHN_E_CAPACITY.
+ *   chn_hashset_append     n values from HOST memory (tests, and callers whose values are on the host)
+ *   chn_minimisers_into    the values chn_minimisers returns for the same batch, as a multiset, appended in device memory; nothing
+ *                          comes down but *n_values.  The overflow and misalignment statuses of chn_minimisers; CHN_E_INVALID, before
+ *                          anything runs, where the stream's index and the set are on different devices
+ *   chn_hashset_unique     sorts ascending and drops repeats; *n_distinct = values left.  Idempotent; after later appends it gives the
+ *                          distinct values of everything appended so far (the whole buffer is sorted again)
+ *   chn_hashset_size       *n = values held (repeats included until the next unique call), *bytes_held = device bytes of the buffer
+ *   chn_hashset_download   values [first, first + n) to HOST memory; CHN_E_INVALID, nothing written, where that is not inside the set
+ *   chn_index_emplace_set  ibf.emplace(value, bin) for every value of the set (:252-255), read in place: chn_index_emplace without the
+ *                          upload, with its waits and refusals (a bin out of range, row shards emplace the rows they hold);
+ *                          CHN_E_INVALID where index and set are on different devices
+ *   chn_device_memory      free and total bytes of a device (hipMemGetInfo): what a caller sizes a budget for its sets from */
+typedef struct chn_hashset chn_hashset;
+typedef struct chn_hashset_cfg {
+    uint32_t struct_size;      /* sizeof(chn_hashset_cfg) */
+    int32_t device;            /* HIP device ordinal */
+    uint32_t tile_keys;        /* 0: 4 096.  Test hook: a smaller multiple of 256 lets a small array span many tiles and scan rounds */
+    uint32_t reserved;         /* 0 */
+} chn_hashset_cfg;
+int chn_hashset_create(const chn_hashset_cfg *cfg, chn_hashset **out);
+int chn_hashset_destroy(chn_hashset *set);
+int chn_hashset_append(chn_hashset *set, const uint64_t *host_values, uint64_t n);
+int chn_minimisers_into(chn_stream *s, const chn_batch *b, chn_hashset *set, uint64_t *n_values);
+int chn_hashset_unique(chn_hashset *set, uint64_t *n_distinct);
+int chn_hashset_size(const chn_hashset *set, uint64_t *n, uint64_t *bytes_held);
+int chn_hashset_download(const chn_hashset *set, uint64_t first, uint64_t n, uint64_t *host_values);
+int chn_index_emplace_set(chn_index *idx, const chn_hashset *set, uint32_t bin);
+int chn_device_memory(int device, uint64_t *free_bytes, uint64_t *total_bytes);
+
 /* Per-kernel device time accumulated since the last reset (CHN_STREAM_PROFILE streams only), added up as the batches are waited for.
  * which: 0 = minimise+probe kernel, 1 = count kernel, 2 = model+call kernel, 3 = whole batch chain;
  *   0 is the device time ATTRIBUTABLE to each batch's minimise+probe kernel (both its launches): the probe kernels of consecutive

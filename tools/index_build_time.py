@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """How long does `charon index` take on references of some size?  Two synthetic genomes of N Mb each (one per category).
-usage: python tools/index_build_time.py [Mb per genome] [workdir] [threads] [--legs NAME=EXE[@ef] ... [--rounds N]]
+usage: python tools/index_build_time.py [Mb per genome] [workdir] [threads] [--legs NAME=EXE[@sets][@ef] ... [--rounds N]]
 
 Without --legs: one run of this tree's binary, as ever.
 With --legs: every leg is a binary (NAME=path of a `charon`), "@ef" behind the path runs it with CHARON_GPU_INDEX_EF=1 (the Elias-Fano arrays
-encoded on the device), without it the variable is unset.  `threads` may be a comma list.  The legs run `--rounds` times (default 3) for every
+encoded on the device), "@sets" with CHARON_GPU_INDEX_SETS=1 (the minimiser sets kept, sorted and made distinct in device memory); the two
+combine ("@sets@ef"); without a suffix the variable is unset.  `threads` may be a comma list.  The legs run `--rounds` times (default 3) for every
 thread count, the leg that goes first rotating from round to round; wall time and the last figure of the CHARON_TIMING line (the
-"download + Elias-Fano" stage, whichever path ran) are reported as min - median - max, and the sha256 of every file written."""
+"download + Elias-Fano" stage, whichever path ran), its "sort+unique" and its "minimisers" figures are reported as min - median - max, and
+the sha256 of every file written."""
 import hashlib, os, re, statistics, subprocess, sys, time
 import numpy as np
 argv = sys.argv[1:]
@@ -20,7 +22,10 @@ if "--legs" in argv:
         rest = rest[:j] + rest[j + 2:]
     for spec in rest:
         name, exe = spec.split("=", 1)
-        legs.append((name, exe[:-3] if exe.endswith("@ef") else exe, exe.endswith("@ef")))
+        exe, *suffixes = exe.split("@")
+        if set(suffixes) - {"ef", "sets"}:
+            sys.exit("unknown suffix in " + spec)
+        legs.append((name, exe, tuple(sorted(suffixes))))  # (what a leg switches on: "ef", "sets")
 mb = int(argv[0]) if len(argv) > 0 else 200
 work = argv[1] if len(argv) > 1 else "/tmp/charon_idx"
 threads = argv[2] if len(argv) > 2 else "16"
@@ -39,14 +44,17 @@ with open(os.path.join(work, "refs.tsv"), "w") as tab:
         tab.write("%s\t%s\n" % (fa, name))
 
 
-def run(exe, nthreads, ef=False):
+SWITCHES = {"ef": "CHARON_GPU_INDEX_EF", "sets": "CHARON_GPU_INDEX_SETS"}
+
+
+def run(exe, nthreads, on=()):
     """one `charon index` run: (return code, wall seconds, stderr, log tail); the file is <work>/big.idx"""
     if os.path.exists(os.path.join(work, "big.idx")):
         os.remove(os.path.join(work, "big.idx"))
-    env = {k: v for k, v in os.environ.items() if k != "CHARON_GPU_INDEX_EF"}
+    env = {k: v for k, v in os.environ.items() if k not in SWITCHES.values()}
     env["CHARON_TIMING"] = "1"
-    if ef:
-        env["CHARON_GPU_INDEX_EF"] = "1"
+    for sw in on:
+        env[SWITCHES[sw]] = "1"
     t0 = time.time()
     p = subprocess.run([exe, "index", "-t", nthreads, "-p", os.path.join(work, "big"), "--log", os.path.join(work, "i.log"), os.path.join(work, "refs.tsv")],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
@@ -65,19 +73,25 @@ hashes = set()
 for nt in threads.split(","):
     wall = {name: [] for name, _, _ in legs}
     stage = {name: [] for name, _, _ in legs}
+    sort_stage = {name: [] for name, _, _ in legs}
+    min_stage = {name: [] for name, _, _ in legs}
     for rd in range(rounds):
-        for name, exe, ef in legs[rd % len(legs):] + legs[:rd % len(legs)]:
-            rc, dt, err, _ = run(exe, nt, ef)
-            m = re.search(r"charon index: timing \(s\):.* ([0-9.]+)\s*$", err, re.M)
+        for name, exe, on in legs[rd % len(legs):] + legs[:rd % len(legs)]:
+            rc, dt, err, _ = run(exe, nt, on)
+            m = re.search(r"charon index: timing \(s\):.*minimisers \(device \+ download\) ([0-9.]+)  sort\+unique ([0-9.]+) .* ([0-9.]+)\s*$", err, re.M)
             if rc != 0 or not m:
                 print("leg %s -t %s round %d: rc=%d\n%s" % (name, nt, rd, rc, err[-600:]))
                 sys.exit(1)
             sha = hashlib.sha256(open(os.path.join(work, "big.idx"), "rb").read()).hexdigest()
             hashes.add(sha)
             wall[name].append(dt)
-            stage[name].append(float(m.group(1)))
-            print("  -t %s round %d %-8s wall %.3f s  stage %.3f s  sha256 %s  %.1f MB" % (nt, rd, name, dt, float(m.group(1)), sha[:16], os.path.getsize(os.path.join(work, "big.idx")) / 1e6), flush=True)
+            stage[name].append(float(m.group(3)))
+            sort_stage[name].append(float(m.group(2)))
+            min_stage[name].append(float(m.group(1)))
+            print("  -t %s round %d %-8s wall %.3f s  minimisers %.3f s  sort+unique %.3f s  Elias-Fano %.3f s  sha256 %s  %.1f MB" %
+                  (nt, rd, name, dt, float(m.group(1)), float(m.group(2)), float(m.group(3)), sha[:16], os.path.getsize(os.path.join(work, "big.idx")) / 1e6), flush=True)
     for name, _, _ in legs:
-        print("-t %-3s %-8s wall (s) %s   download + Elias-Fano stage (s) %s   [min - median - max of %d]" % (nt, name, spread(wall[name]), spread(stage[name]), rounds))
+        print("-t %-3s %-8s wall (s) %s   minimisers (s) %s   sort+unique (s) %s   download + Elias-Fano stage (s) %s   [min - median - max of %d]" %
+              (nt, name, spread(wall[name]), spread(min_stage[name]), spread(sort_stage[name]), spread(stage[name]), rounds))
 print("sha256 of the files: %s" % ("one value, " + next(iter(hashes)) if len(hashes) == 1 else "%d DIFFERENT values" % len(hashes)))
 sys.exit(0 if len(hashes) == 1 else 1)
